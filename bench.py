@@ -40,6 +40,10 @@ TRAFFIC_FILE = "hbm_traffic.json"
 PMC_FILE = "pmc_sq.txt"
 CALIB_FILE = "profiles/r04/issue_calibration.txt"      # (the in-situ cost per extra instruction was measured once, in round 4)
 UBENCH_FILE = "profiles/r03/ubench_issue_rates.txt"
+# --dump-outputs: at most this many bytes of .npy payload, and a fixed seeded sample of this many reads when the batch is larger
+DUMP_BYTES_MAX = 64 << 20
+DUMP_READS_MAX = 1 << 18
+RUN_FIELDS = ("abs_loc_first", "len_first", "len_last", "mismatches", "flags", "chr_id")
 
 
 def cpu_baseline(chroms, batch, params_kw, budget_s=10.0, bd=None, bd_off=None, thread_points=True):
@@ -167,6 +171,39 @@ def pack_roofline(batch, pack_ms):
             "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": nbytes, "traffic": None,
             "note": "as a launch of its own, measured outside the timed region; inside the step "
                     "and more the same code runs in pg_search_kernel, claim by claim"}
+
+
+def dump_outputs(out_dir, results, seed):
+    """--dump-outputs: what the caller of the timed path receives for its batch (the CSR of UP_Close / UP_Far runs and the
+    rc flags of every read, `results` = the downloaded result of each launch of one step, in read order) as float arrays,
+    one DIR/<name>.npy each.  A batch of more than DUMP_READS_MAX reads is represented by a sample of reads drawn from
+    `seed` alone, so two builds given the same arguments dump the same reads.  Per sampled read: read_index, rc_flag,
+    close_count, far_count; per run of those reads, in read order: close_<field> / far_<field> for every field of
+    binding.RUN_DTYPE.  abs_loc_first and read_index are float64 (exact below 2**53), the rest float32 (exact below
+    2**24).  Reads past the point where the files would exceed DUMP_BYTES_MAX are dropped from the end of the sample."""
+    import numpy as np
+    from pindel_amd import shard
+    a = shard.concat_results([shard.result_arrays(r) for r in results])
+    n = len(a["rc_flag"])
+    reads = np.arange(n, dtype=np.int64)
+    if n > DUMP_READS_MAX:
+        reads = np.sort(np.random.default_rng(seed).choice(n, DUMP_READS_MAX, replace=False))
+    off = {k: a[k + "_off"].astype(np.int64) for k in ("close", "far")}
+    cnt = {k: off[k][reads + 1] - off[k][reads] for k in off}
+    per_read = 8 + 3 * 4 + (8 + 5 * 4) * (cnt["close"] + cnt["far"])
+    reads = reads[np.cumsum(per_read) <= DUMP_BYTES_MAX - (1 << 16)]       # (room for the .npy headers)
+    out = {"read_index": reads.astype(np.float64), "rc_flag": a["rc_flag"][reads].astype(np.float32)}
+    for k in ("close", "far"):
+        c = cnt[k][:len(reads)]
+        out[k + "_count"] = c.astype(np.float32)
+        first = np.cumsum(c) - c                                   # where each read's runs start in the dump
+        idx = np.repeat(off[k][reads] - first, c) + np.arange(int(c.sum()), dtype=np.int64)
+        runs = a[k + "_runs"][idx]
+        for f in RUN_FIELDS:
+            out[f"{k}_{f}"] = runs[f].astype(np.float64 if f == "abs_loc_first" else np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def self_spawn(args):
@@ -319,7 +356,12 @@ def main():
                          "0.65 M reads per bin = 30x WGS with 400 M one-end-anchored reads), as main()'s loop does; wgs-real = the "
                          "read mix INTEGRATION.md expects of a real WGS run: three reads in four find no close end and walk all "
                          "four attempts (150 bp, coordinate order, chr20-shaped reference)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's reads) as DIR/<name>.npy, float32/float64, "
+                         f"at most {DUMP_BYTES_MAX >> 20} MB: a seeded sample of {DUMP_READS_MAX} reads when the batch is larger (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_spawn(args)
@@ -407,6 +449,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if os.environ.get("PG_BENCH_SHARE_GPU") else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # downloaded before the standalone launches below run on the same device batches again
+        dump_outputs(args.dump_outputs, [eng.download(h) for h in ([dbatch] if bins is None else bins)], args.seed)
 
     # ---- outside the timed region: accounting, result digests, the host-buffer seam, the CPU baseline
     # The pack (ASCII bases as src/reader.cpp:852-856 hands them over -> the bit planes + packed records the search reads) is
