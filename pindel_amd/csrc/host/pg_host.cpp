@@ -157,10 +157,17 @@ Caller::Caller(const Settings &s, const std::vector<Chromosome> *g, const std::s
     if (truncate_outputs) {
         const char *suffixes[] = { "_D", "_SI", "_TD", "_INV" };
         for (const char *sf : suffixes) std::ofstream((prefix + sf).c_str(), std::ios::trunc);
+        if (S.Analyze_LI) std::ofstream((prefix + "_LI").c_str(), std::ios::trunc);
+        if (S.close_mapped_output()) std::ofstream((prefix + "_CloseEndMapped").c_str(), std::ios::trunc);
     }
 }
 
-Caller::~Caller() { flush_reports(); }
+Caller::~Caller()
+{
+    flush_reports();
+    if (li_out_.is_open()) li_out_.flush();
+    if (cem_out_.is_open()) cem_out_.flush();
+}
 
 void Caller::update_ref_coverage(const std::vector<RefReadSpan> &reads, const std::vector<std::string> &tags,
                                  unsigned start, unsigned end)
@@ -200,6 +207,20 @@ void Caller::update_ref_coverage(const std::vector<RefReadSpan> &reads, const st
 struct EvMark { size_t at; int kind; };
 static thread_local std::ostringstream *tl_box_out = nullptr;
 static thread_local std::vector<EvMark> *tl_box_marks = nullptr;
+// ... and the CurrentChrMask positions (absolute) its reporters marked
+static thread_local std::vector<unsigned> *tl_mask_marks = nullptr;
+
+void Caller::mark(unsigned bp)
+{
+    const unsigned pos = bp + S.spacer;
+    if (tl_mask_marks) tl_mask_marks->push_back(pos);
+    else apply_marks(std::vector<unsigned>(1, pos));
+}
+
+void Caller::apply_marks(const std::vector<unsigned> &abs_positions)
+{
+    chr_marks_.insert(abs_positions.begin(), abs_positions.end());
+}
 
 std::ostream &operator<<(std::ostream &out, Caller::EvNo e)
 {
@@ -240,12 +261,14 @@ void Caller::for_boxes(unsigned n_boxes, const std::function<void(unsigned)> &bo
     };
     std::vector<BoxText> texts(n_boxes);
     const unsigned nt = std::max(1u, std::min(host_threads(), n_boxes / 64u + 1u));
+    std::vector<std::vector<unsigned>> mask_marks(nt);
     std::atomic<unsigned> next(0);
-    auto work = [&]() {
+    auto work = [&](unsigned t) {
         std::ostringstream os[REP_N];
         std::vector<EvMark> marks[REP_N];
         tl_box_out = os;
         tl_box_marks = marks;
+        tl_mask_marks = &mask_marks[t];
         for (unsigned b = next.fetch_add(1); b < n_boxes; b = next.fetch_add(1)) {
             body(b);
             for (int k = 0; k < REP_N; k++)
@@ -259,13 +282,15 @@ void Caller::for_boxes(unsigned n_boxes, const std::function<void(unsigned)> &bo
         }
         tl_box_out = nullptr;
         tl_box_marks = nullptr;
+        tl_mask_marks = nullptr;
     };
-    if (nt == 1) work();
+    if (nt == 1) work(0);
     else {
         std::vector<std::thread> th;
-        for (unsigned t = 0; t < nt; t++) th.emplace_back(work);
+        for (unsigned t = 0; t < nt; t++) th.emplace_back(work, t);
         for (std::thread &x : th) x.join();
     }
+    for (const std::vector<unsigned> &m : mask_marks) apply_marks(m);
     for (unsigned b = 0; b < n_boxes; b++)
         for (int k = 0; k < REP_N; k++) {
             const std::string &t = texts[b].text[k];
@@ -429,6 +454,10 @@ void Caller::output_deletion(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsi
     unsigned n_reads = 0;
     std::string sup = support_columns(g, s, e, f.BPLeft, f.BPRight, n_reads);
     short gap = f.IndelSize < 14 ? (short)f.IndelSize : (short)(13 + (int)log10((double)(f.IndelSize - 10)));
+    mark(f.BPLeft);                      // reporter.cpp:330-336
+    mark(f.BPRight);
+    mark(rs);
+    mark(re);
     out << HASHES << '\n';
     out << ev_no(EV_D) << "\tD " << f.IndelSize << "\tNT " << f.NT_size << " \"" << f.NT_str
         << "\"\tChrID " << f.FragName << "\tBP " << f.BPLeft + 1 << "\t" << f.BPRight + 1 << "\tBP_range "
@@ -462,6 +491,8 @@ void Caller::output_di(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsigned e
     const SplitRead &f = g[s];
     unsigned n_reads = 0;
     std::string sup = support_columns(g, s, e, f.BPLeft, f.BPRight, n_reads);
+    mark(f.BPLeft);                      // reporter.cpp:802-803
+    mark(f.BPRight);
     out << HASHES << '\n';
     out << ev_no(EV_D_NT) << "\tD " << f.IndelSize << "\tNT " << f.NT_size << " \"" << f.NT_str
         << "\"\tChrID " << f.FragName << "\tBP " << f.BPLeft + 1 << "\t" << f.BPRight + 1 << "\tBP_range "
@@ -501,6 +532,10 @@ void Caller::output_si(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsigned e
     const SplitRead &f = g[s];
     unsigned n_reads = 0;
     std::string sup = support_columns(g, s, e, f.BPLeft, f.BPRight, n_reads);
+    mark(f.BPLeft);                      // reporter.cpp:676-679
+    mark(f.BPRight);
+    mark(rs);
+    mark(re);
     out << HASHES << '\n';
     out << ev_no(EV_SI) << "\tI " << f.IndelSize << "\tNT " << f.IndelSize << " \"" << consensus_inserted(g, s, e)
         << "\"\tChrID " << f.FragName << "\tBP " << f.BPLeft + 1 << "\t" << f.BPRight + 1 << "\tBP_range "
@@ -885,11 +920,16 @@ void Caller::process_window(const Chromosome &chrom, std::vector<SplitRead> &rea
     BoxSize = (unsigned)(chrom.seq.size() / 30000);
     if (BoxSize == 0) BoxSize = 1;
     c.NumBoxes = (unsigned)(chrom.seq.size() * 2 / BoxSize) + 1;
+    c.win_start = win_start;
     c.win_end = win_end;
     c.region_start = region_start;
     c.region_end = region_end;
     g_RegionStart = win_start;
     g_RegionEnd = win_end;
+    if (mask_chr_ != &chrom) {           // a new chromosome: CurrentChrMask all 'N' (pindel.cpp:1801-1804)
+        chr_marks_.clear();
+        mask_chr_ = &chrom;
+    }
     for (SplitRead &r : reads) {
         if (!r.UP_Far.empty()) {
             int fc = r.UP_Far[0].chr;        // UpdateFarFragName, pindel.cpp:1262-1270
@@ -927,6 +967,12 @@ void Caller::process_window(const Chromosome &chrom, std::vector<SplitRead> &rea
     lap("short insertions");
     flush_reports();
     lap("flush");
+    if (S.Analyze_LI) {                  // SearchSVs, pindel.cpp:1167-1169: after the four reporters
+        const double t_li = now();
+        sort_output_li(c, win_start, win_end);
+        li_seconds += now() - t_li;
+        lap("long insertions");
+    }
 }
 
 }  // namespace pgh

@@ -10,7 +10,8 @@
 //   classifiers  SearchVariant::Search src/search_variant.cpp:48-266 (+ searchdeletions.cpp,
 //                searchshortinsertions.cpp), searchIndels src/search_deletions_nt.cpp:26-140
 //   reporters    SortOutputD / OutputDeletions, SortOutputDI / OutputDI, SortOutputSI /
-//                OutputSIs  src/reporter.cpp
+//                OutputSIs  src/reporter.cpp; SortOutputLI src/reporter.cpp:1853-2141 and
+//                ReportCloseMappedReads src/pindel.cpp:1076-1092 (pg_host_li.cpp)
 // The search itself is NOT here: UP_Close / UP_Far come from the GPU through the C ABI
 // (include/pindel_pg.h).  No HIP dependency in this file; plain g++.
 #ifndef PG_HOST_HPP
@@ -72,6 +73,10 @@ struct Settings {                 // the flags the downstream steps read (src/fn
     double window_mbp = 5.0;             // -w
     unsigned max_mismatch[500] = {0};    // g_maxMismatch
     bool log_counts = false;             // print the reference's cross-check lines (far-end counts and checksum)
+    bool Analyze_LI = false;             // -l: <prefix>_LI (SortOutputLI)
+    bool report_close_mapped = false;    // -s: <prefix>_CloseEndMapped (ReportCloseMappedReads)
+    bool only_close_mapped = false;      // -S: close end + _CloseEndMapped only, no far end, no SV search
+    bool close_mapped_output() const { return report_close_mapped || only_close_mapped; }
 };
 
 int load_fasta(const std::string &path, std::vector<Chromosome> &out, unsigned spacer, std::string &err);
@@ -99,7 +104,17 @@ public:
     void note_close_mapped(SplitRead &r);
     // ... for every read of `reads` that has a close end, on a few threads
     void note_close_mapped_all(std::vector<SplitRead> &reads);
+    // g_maxInsertSize (GetCloseEndInner, pindel.cpp:2257): the largest InsertSize of any read that entered the close-end
+    // search, with or without a close end; never reset.  LI's border buffer is four times it.
+    void note_insert_size(int insert_size)
+    {
+        if (insert_size > g_maxInsertSize) g_maxInsertSize = insert_size;
+    }
+    // ReportCloseMappedReads (pindel.cpp:1076-1092): the reads of a window that kept a close end, in their order, as
+    // Pindel-text records (UnmatchedSeq as GetCloseEnd left it), appended to <prefix>_CloseEndMapped
+    void report_close_mapped(const std::vector<SplitRead> &reads);
     unsigned long far_end_checksum = 0;
+    double li_seconds = 0.0;             // host time spent in SortOutputLI, all windows so far
     // UpdateRefReadCoverage (pindel.cpp:1272-1330), BAM input: per sample (in the order of the sample-name set as
     // it stands now) the number of reference-supporting reads over every position of the window [start, end];
     // a read counts from its second to its last-but-one base and only if it lies inside the window.  The two
@@ -117,6 +132,20 @@ private:
     std::vector<char> rep_buf_[REP_N];
     std::ostream &report(int which);        // the file -- or, inside for_boxes, the calling worker's buffer
     void flush_reports();
+    // _LI and _CloseEndMapped: written outside for_boxes, so plain files (append, large buffer)
+    std::ofstream li_out_, cem_out_;
+    std::vector<char> li_buf_, cem_buf_;
+    std::ofstream &open_append(std::ofstream &f, std::vector<char> &buf, const char *suffix);
+    // CurrentChrMask (pindel.cpp:1801-1804): the positions of this chromosome where an event has been reported so far
+    // ('B'), kept as a set; reset when the chromosome changes.  The reporters call mark() with the breakpoints they print; inside for_boxes the marks
+    // are collected per worker and applied when the boxes are done (setting a mark commutes, so the order of the boxes
+    // and workers does not matter).
+    std::set<unsigned> chr_marks_;
+    const Chromosome *mask_chr_ = nullptr;
+    void mark(unsigned bp);
+    void apply_marks(const std::vector<unsigned> &abs_positions);
+    int count_li_ = 0;                   // Count_LI: function-static in the reference, runs across windows and chromosomes
+    int g_maxInsertSize = 0;
     // The event number at the head of a report entry.  Entries are formatted box by box in parallel (for_boxes),
     // so `out << ev_no(kind)` writes nothing and only marks the place; the number -- the running count of that kind
     // (D entries print template + non-template deletions so far) -- is put in when the boxes' texts are written in
@@ -160,6 +189,7 @@ private:
     void output_td(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsigned e, unsigned rs, unsigned re);
     void output_inv(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsigned e, unsigned rs, unsigned re);
     void output_short_inv(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsigned e);
+    void sort_output_li(Ctx &c, unsigned win_start, unsigned win_end);
 };
 
 }  // namespace pgh

@@ -34,13 +34,16 @@ struct pgh_settings {
     int32_t analyze_td, analyze_inv;
     double window_mbp;           /* -w */
     uint32_t max_mismatch[500];  /* g_maxMismatch (pg_get_max_mismatch) */
+    int32_t analyze_li;          /* -l: also write <prefix>_LI */
+    int32_t report_close_mapped; /* -s: also write <prefix>_CloseEndMapped */
 };
 
 /*
  * Pindel's post-search pipeline for a Pindel-text read file: attaches the given UP_Close /
  * UP_Far (CSR over ALL reads of the file, in file order; reads without close end have an
  * empty range) and the rc flags, then walks chromosomes and 5-Mbp bins like main()
- * (pindel.cpp:1778-1989) and appends <prefix>_D, _SI, _TD, _INV.
+ * (pindel.cpp:1778-1989) and appends <prefix>_D, _SI, _TD, _INV -- and _LI / _CloseEndMapped when
+ * analyze_li / report_close_mapped are set.
  */
 int pgh_call_from_points(const char *fasta_path, const char *reads_path, const char *out_prefix,
                          const pgh_settings *st, uint32_t n_reads,
@@ -65,6 +68,8 @@ int pgh_call_from_points(const char *fasta_path, const char *reads_path, const c
     S.Analyze_TD = st->analyze_td != 0;
     S.Analyze_INV = st->analyze_inv != 0;
     S.window_mbp = st->window_mbp;
+    S.Analyze_LI = st->analyze_li != 0;
+    S.report_close_mapped = st->report_close_mapped != 0;
     memcpy(S.max_mismatch, st->max_mismatch, sizeof S.max_mismatch);
     std::vector<unsigned> fai = read_fai(fasta_path, genome);
     auto to_up = [](const pg_point &p) {

@@ -21,7 +21,7 @@ struct Caller::Ctx {
     const Chromosome *chrom;
     std::vector<SplitRead> *reads;
     unsigned NumBoxes;
-    unsigned win_end;
+    unsigned win_start, win_end;
     unsigned region_start, region_end;
 };
 

@@ -173,6 +173,8 @@ void Caller::output_td(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsigned e
     const SplitRead &f = g[s];
     unsigned n_reads = 0;
     std::string sup = support_columns(g, s, e, f.BPLeft - 1, f.BPRight + 1, n_reads);
+    mark(f.BPLeft);                      // reporter.cpp:194-195
+    mark(f.BPRight);
     out << HASHES << '\n';
     out << ev_no(EV_TD) << "\tTD " << f.IndelSize << "\tNT " << f.NT_size << " \"" << f.NT_str << "\"\tChrID "
         << f.FragName << "\tBP " << f.BPLeft << "\t" << f.BPRight + 2 << "\tBP_range " << f.BPLeft << "\t"
@@ -441,6 +443,8 @@ void Caller::output_inv(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsigned 
         }
     unsigned n_reads = 0;
     std::string sup = support_columns(g, s, e, f.BPLeft - 1, f.BPRight + 1, n_reads);
+    mark(f.BPLeft);                      // reporter.cpp:517-518
+    mark(f.BPRight);
     out << HASHES << '\n';
     out << ev_no(EV_INV) << "\tINV " << f.IndelSize << "\tNT " << lnt << ":" << rnt << " \"" << lstr << "\":\"" << rstr
         << "\"\tChrID " << f.FragName << "\tBP " << f.BPLeft + 1 - 1 << "\t" << f.BPRight + 1 + 1 << "\tBP_range "
@@ -483,6 +487,8 @@ void Caller::output_short_inv(Ctx &c, std::vector<SplitRead> &g, unsigned s, uns
     const SplitRead &f = g[s];
     unsigned n_reads = 0;
     std::string sup = support_columns(g, s, e, f.BPLeft, f.BPRight, n_reads);
+    mark(f.BPLeft);                      // reporter.cpp:1625-1626
+    mark(f.BPRight);
     out << HASHES << '\n';
     out << ev_no(EV_INV) << "\tINV " << f.IndelSize << "\tNT " << f.NT_size << " \"" << f.NT_str << "\"\tChrID "
         << f.FragName << "\tBP " << f.BPLeft + 1 << "\t" << f.BPRight + 1 << "\tBP_range " << f.BPLeft + 1 << "\t"

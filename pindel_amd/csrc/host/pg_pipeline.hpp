@@ -59,6 +59,9 @@ inline void release_reads(std::vector<SplitRead> &v)
 //                                                (SearchFarEnds, src/pindel.cpp:1115-1138, called at :1888); [ws, we) =
 //                                                the window being processed, biological coordinates (currentWindow,
 //                                                src/pindel.cpp:1828: what g_bdData.loadRegion is given at :1853)
+// With S.close_mapped_output() the reads that kept a close end are written to <prefix>_CloseEndMapped before the far end
+// (src/pindel.cpp:1880-1883); with S.only_close_mapped (-S) that is all: no far end, no classifiers, no reports.
+// li_seconds (nullable) receives the host time of the _LI reporter over all windows.
 struct NoFarSearch {
     int operator()(const Chromosome &, int, std::vector<SplitRead> &, unsigned, unsigned) const { return 0; }
 };
@@ -66,7 +69,7 @@ struct NoFarSearch {
 template <class Search, class FarSearch>
 int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<unsigned> &fai,
                  const std::vector<SplitRead> &all, const Settings &S, const std::string &prefix,
-                 Search search, FarSearch far_search, std::string &err)
+                 Search search, FarSearch far_search, std::string &err, double *li_seconds = nullptr)
 {
     Caller caller(S, &genome, prefix, true);
     const unsigned WINDOW = (unsigned)(S.window_mbp * 1000000);
@@ -129,6 +132,7 @@ int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<unsign
                 return rc;
             }
             t_search += now() - t0; t0 = now();
+            for (const SplitRead &r : reads) caller.note_insert_size(r.InsertSize);
             caller.note_close_mapped_all(reads);                        // reader.cpp:258-291
             std::vector<SplitRead> kept;
             {
@@ -138,13 +142,14 @@ int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<unsign
             }
             for (SplitRead &r : reads)
                 if (!r.UP_Close.empty()) kept.push_back(std::move(r));      // `reads` is not used after this loop
+            if (S.close_mapped_output() && !kept.empty()) caller.report_close_mapped(kept);
             t_keep += now() - t0; t0 = now();
-            if (!kept.empty() && (rc = far_search(chrom, (int)c, kept, ws, we))) {
+            if (!S.only_close_mapped && !kept.empty() && (rc = far_search(chrom, (int)c, kept, ws, we))) {
                 err = "far-end search step failed";
                 return rc;
             }
             t_search += now() - t0; t0 = now();
-            if (!kept.empty()) caller.process_window(chrom, kept, ws, we, bed_start, bed_end);
+            if (!S.only_close_mapped && !kept.empty()) caller.process_window(chrom, kept, ws, we, bed_start, bed_end);
             t_call += now() - t0; t0 = now();
             release_reads(kept);
             release_reads(reads);
@@ -154,6 +159,7 @@ int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<unsign
     if (timing)
         fprintf(stderr, "pgh timing: pipeline: copy reads %.3f s, search step %.3f s, keep %.3f s, classify + report %.3f s, free %.3f s\n",
                 t_copy, t_search, t_keep, t_call, t_free);
+    if (li_seconds) *li_seconds = caller.li_seconds;
     return 0;
 }
 
@@ -195,7 +201,8 @@ template <class CloseSoa, class FarSearch>
 int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<unsigned> &fai,
                      const std::vector<BamSource> &bams, const BamIngestSettings &ingest, const Settings &S,
                      const std::string &prefix, CloseSoa close_soa, FarSearch far_search, std::string &err, size_t *n_reads_total = nullptr,
-                     BDHints *bd = nullptr, bool search_rp = false, size_t *n_rp_events = nullptr)
+                     BDHints *bd = nullptr, bool search_rp = false, size_t *n_rp_events = nullptr,
+                     double *li_seconds = nullptr)
 {
     Caller caller(S, &genome, prefix, true);
     std::ofstream rp_out;
@@ -286,6 +293,7 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<un
         IngestedReads &in = d->in;
         if (n_reads_total) *n_reads_total += in.size();
         if (in.size() == 0) continue;
+        for (size_t i = 0; i < in.size(); i++) caller.note_insert_size(in.batch.isz[i]);
         CloseView view;
         int rc = close_soa(chrom, (int)c, in.batch, view);
         if (rc) {
@@ -336,14 +344,15 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<un
         });
         if (view.release) view.release();
         caller.note_close_mapped_all(kept);
+        if (S.close_mapped_output() && !kept.empty()) caller.report_close_mapped(kept);
         t_keep += now() - t0; t0 = now();
-        if (!kept.empty() && (rc = far_search(chrom, (int)c, kept, win.ws, win.we))) {
+        if (!S.only_close_mapped && !kept.empty() && (rc = far_search(chrom, (int)c, kept, win.ws, win.we))) {
             err = "far-end search step failed";
             status = rc;
             break;
         }
         t_far += now() - t0; t0 = now();
-        {   // UpdateRefReadCoverage, after the close ends (sample names) and before the classifiers
+        if (!S.only_close_mapped) {   // UpdateRefReadCoverage, after the close ends (sample names) and before the classifiers
             std::vector<Caller::RefReadSpan> spans(in.ref_reads.size());
             for (size_t i = 0; i < spans.size(); i++) {
                 spans[i].pos = in.ref_reads[i].pos;
@@ -353,7 +362,7 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<un
             caller.update_ref_coverage(spans, in.ref_tags, win.ws, win.we);
         }
         t_cov += now() - t0; t0 = now();
-        if (!kept.empty()) caller.process_window(chrom, kept, win.ws, win.we, bed_start, bed_end);
+        if (!S.only_close_mapped && !kept.empty()) caller.process_window(chrom, kept, win.ws, win.we, bed_start, bed_end);
         t_call += now() - t0; t0 = now();
         // the window's reads are freed behind the next window's work (one disposal in flight)
         if (trash.valid()) trash.wait();
@@ -376,6 +385,7 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<un
                         "discovery %.3f s, ingest %.3f s (inflate + decode on threads %.3f, selection rules on threads %.3f, layout %.3f)\n",
                 now() - t_begin, t_wait, t_close, t_keep, t_far, t_cov, t_call, t_free, t_rp, t_ingest,
                 ingest_timing().inflate_decode, ingest_timing().select, ingest_timing().layout);
+    if (li_seconds) *li_seconds = caller.li_seconds;
     return status;
 }
 

@@ -1,8 +1,12 @@
 // pindel_pg -- command line with Pindel's flags for the path this repository implements:
 //   pindel_pg -f ref.fa -p reads.txt -o prefix [-x 2 -a 1 -m 3 -u 0.02 -e 0.01 -E 0.95 -H 8
-//                                               -M 1 -B 100 -d 30 -v 50 -w 5 -G device]
+//                                               -M 1 -B 100 -d 30 -v 50 -w 5 -G device -l -s -S]
 // FASTA + Pindel-text reads -> close/far-end search on the MI355X (C ABI, libpindel_pg.so)
-// -> SV classification and <prefix>_D/_SI/_TD/_INV reports (host code in this directory).
+// -> SV classification and <prefix>_D/_SI/_TD/_INV reports (host code in this directory);
+// -l adds <prefix>_LI (long insertions), -s <prefix>_CloseEndMapped (the reads with a close end),
+// -S writes <prefix>_CloseEndMapped only (no far end, no SV search).  Like the reference, every run
+// creates all seven files (_D _SI _TD _INV _LI _BP _CloseEndMapped); _BP stays empty, as the
+// reference's breakpoint report is not called.
 // Flags and their defaults follow src/fn_parameters.cpp; BAM input (-i) needs htslib and is
 // not built here.
 #include <cstdio>
@@ -45,8 +49,8 @@ int main(int argc, char **argv)
     Settings S;
     // Flags as src/fn_parameters.cpp defines them: value flags need an argument that does not start with
     // '-'; unary switches take an optional true/false word (readParameters, fn_parameters.cpp:366-406).
-    // Switches of report families this program does not write are accepted and ignored, like the reference
-    // accepts them; anything else is an error, and so is a value that is not a number.
+    // The switches -k (beyond the empty _BP file), -I, -q and -C select searches and reports this program does not
+    // run; they are accepted and ignored; anything else is an error, and so is a value that is not a number.
     struct Flag { const char *sh, *lg; char kind; };      // kind: i int, f float, s string, u unary
     static const Flag flags[] = {
         { "-f", "--fasta", 's' }, { "-p", "--pindel-file", 's' }, { "-i", "--config-file", 's' }, { "-o", "--output-prefix", 's' },
@@ -85,7 +89,10 @@ int main(int argc, char **argv)
             if (key == "-R") search_rp = on;
             else if (key == "-r") S.Analyze_INV = on;
             else if (key == "-t") S.Analyze_TD = on;
-            // the other switches select reports (LI, BP, CloseEndMapped, INT ...) outside this program's scope
+            else if (key == "-l") S.Analyze_LI = on;
+            else if (key == "-s") S.report_close_mapped = on;
+            else if (key == "-S") S.only_close_mapped = on;
+            // -k, -I, -q, -C (and -N): reports / searches outside this program's scope, accepted and ignored
             continue;
         }
         if (i + 1 >= argc) {
@@ -173,6 +180,14 @@ int main(int argc, char **argv)
     if (fasta.empty() || (reads_path.empty() == bam_config.empty()) || prefix.empty()) {
         fprintf(stderr, "usage: pindel_pg -f ref.fa (-p reads.txt | -i bam_config.txt) -o prefix [options]\n");
         return 2;
+    }
+    // TestFileForOutput (pindel.cpp:932-938): every output file exists, empty, from the start
+    for (const char *sf : { "_D", "_SI", "_TD", "_INV", "_LI", "_BP", "_CloseEndMapped" }) {
+        std::ofstream f((prefix + sf).c_str(), std::ios::trunc);
+        if (!f) {
+            fprintf(stderr, "pindel_pg: cannot write %s%s\n", prefix.c_str(), sf);
+            return 1;
+        }
     }
     std::string err;
     std::vector<Chromosome> genome;
@@ -270,6 +285,7 @@ int main(int argc, char **argv)
         printf("pindel_pg: BD events: %zu%s\n", bd.n_events(), use_bd ? "" : " (not used for Pindel-text input; --bd-hints on to use them)");
     }
     size_t n_close = 0, n_far = 0;
+    double li_seconds = 0.0;
     // fn(ctx, part) on contiguous shards of `reads`, one host thread and one ctx per device; the parts are moved out
     // and back, so the order is kept (reads are independent: identical results for any device count)
     auto on_devices = [&](std::vector<SplitRead> &reads, const std::function<int(pg_ctx *, std::vector<SplitRead> &)> &fn) {
@@ -315,6 +331,8 @@ int main(int argc, char **argv)
             }
             return 0;
         });
+        if (S.only_close_mapped)          // (otherwise the far-end step counts the reads that kept a close end)
+            for (const SplitRead &x : reads) n_close += !x.UP_Close.empty();
         t_search += now_s() - t0;
         return r;
     };
@@ -407,6 +425,8 @@ int main(int argc, char **argv)
             for (size_t d = 0; d < np; d++) {
                 pg_result_view rv;
                 pg_result_view_get(res[d], &rv);
+                if (S.only_close_mapped)
+                    for (size_t i = 0; i < rv.n_reads; i++) n_close += rv.close_off[i + 1] > rv.close_off[i];
                 ClosePart p;
                 p.first = n * d / np;
                 p.n = rv.n_reads;
@@ -418,16 +438,23 @@ int main(int argc, char **argv)
             t_search += now_s() - t0;
             return 0;
         };
-        rc = run_bam_pipeline(genome, fai, bams, ing, S, prefix, close_soa, far_search, err, &n_bam_reads, &bd, search_rp, &n_rp_events);
+        rc = run_bam_pipeline(genome, fai, bams, ing, S, prefix, close_soa, far_search, err, &n_bam_reads, &bd, search_rp, &n_rp_events,
+                              &li_seconds);
         if (search_rp) printf("pindel_pg: read-pair events added as window hints: %zu\n", n_rp_events);
     } else
-        rc = run_pipeline(genome, fai, all, S, prefix, close_search, far_search, err);
+        rc = run_pipeline(genome, fai, all, S, prefix, close_search, far_search, err, &li_seconds);
     if (rc) fprintf(stderr, "pindel_pg: %s (%s)\n", err.c_str(), pg_last_error(ctx));
     else {
-        printf("pindel_pg: %zu reads, close end %zu, far end %zu\n", bams.empty() ? all.size() : n_bam_reads, n_close, n_far);
+        const size_t n_reads = bams.empty() ? all.size() : n_bam_reads;
+        if (S.only_close_mapped)
+            printf("pindel_pg: %zu reads, close end %zu (-S: close-end-mapped reads only, no far-end search)\n", n_reads, n_close);
+        else
+            printf("pindel_pg: %zu reads, close end %zu, far end %zu\n", n_reads, n_close, n_far);
         // the phases the reference's Timer reports (pindel.cpp:1990-1996), wall-clock seconds
         printf("pindel_pg: loading %.2f s, split-read search (GPU, incl. adapters) %.2f s, classification + reports %.2f s\n",
                t_loaded - t_start, t_search, now_s() - t_loaded - t_search);
+        if (S.Analyze_LI && !S.only_close_mapped)
+            printf("pindel_pg: long insertions (_LI, host, part of classification + reports) %.3f s\n", li_seconds);
     }
     for (pg_ctx *c : ctxs) pg_destroy(c);
     return rc ? 1 : 0;

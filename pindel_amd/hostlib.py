@@ -17,7 +17,8 @@ class HostSettings(C.Structure):
         ("spacer", C.c_uint32), ("min_support", C.c_uint32), ("balance_cutoff", C.c_uint32),
         ("seq_error_rate", C.c_double), ("min_num_matched_bases", C.c_int32),
         ("min_inversion_size", C.c_int32), ("analyze_td", C.c_int32), ("analyze_inv", C.c_int32),
-        ("window_mbp", C.c_double), ("max_mismatch", C.c_uint32 * 500)]
+        ("window_mbp", C.c_double), ("max_mismatch", C.c_uint32 * 500),
+        ("analyze_li", C.c_int32), ("report_close_mapped", C.c_int32)]
 
 
 def build(force=False):
@@ -59,6 +60,8 @@ def default_settings(max_mismatch) -> HostSettings:
     s.analyze_td = 1
     s.analyze_inv = 1
     s.window_mbp = 5.0
+    s.analyze_li = 0           # -l (default false): <prefix>_LI
+    s.report_close_mapped = 0  # -s (default false): <prefix>_CloseEndMapped
     for i in range(500):
         s.max_mismatch[i] = int(max_mismatch[i])
     return s
@@ -67,7 +70,8 @@ def default_settings(max_mismatch) -> HostSettings:
 def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pts, far_off, far_pts,
                      rc_flag):
     """Classify + report (_D, _SI, _TD, _INV) from per-read UP_Close / UP_Far points (CSR over
-    all reads of the file, 12-byte pg_point records)."""
+    all reads of the file, 12-byte pg_point records).  settings.analyze_li / settings.report_close_mapped
+    add <out_prefix>_LI / <out_prefix>_CloseEndMapped."""
     L = lib()
     close_off = np.ascontiguousarray(close_off, dtype=np.uint64)
     far_off = np.ascontiguousarray(far_off, dtype=np.uint64)
