@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from collections import namedtuple
 
 import numpy as np
 
@@ -58,6 +59,10 @@ POINT_DTYPE = np.dtype([("abs_loc", "<u4"), ("length", "<i2"), ("mismatches", "<
                         ("chr_id", "<i2"), ("direction", "S1"), ("strand", "S1")], align=True)
 WINDOW_DTYPE = np.dtype([("chr_id", "<i4"), ("start", "<i4"), ("end", "<i4")], align=True)
 assert RUN_DTYPE.itemsize == 12 and POINT_DTYPE.itemsize == 12 and WINDOW_DTYPE.itemsize == 12
+
+# one record of the library's launch log (PgLaunchRec, pg_device.h); it keeps the first LAUNCH_LOG_CAP (pg_ctx::PG_LAUNCH_LOG_CAP)
+LaunchRec = namedtuple("LaunchRec", "kernel blocks ns id_bits mode default in_place")
+LAUNCH_LOG_CAP = 256
 
 # every symbol include/pindel_pg.h declares
 EXPORTS = [
@@ -375,6 +380,25 @@ class Engine:
         """tests: did the last pack_search_device build its records inside the search kernel (one launch)?"""
         self._L.pg_debug_last_pack_in_place.argtypes = [C.c_void_p]
         return bool(self._L.pg_debug_last_pack_in_place(self._h))
+
+    def launch_log(self):
+        """tests: the kernels the search path launched since the last clear_launch_log, in launch order -- LaunchRec tuples
+        (kernel 1 search / 2 exact / 3 pack, blocks = NB or PB, ns, id_bits, mode, default, in_place)."""
+        L = self._L
+        L.pg_debug_launch_log.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.pg_debug_launch_log.restype = C.c_int32
+        n = L.pg_debug_launch_log(self._h, None, 0)
+        self._check(min(n, 0))
+        if n > LAUNCH_LOG_CAP:
+            raise PgError(PG_E_DEVICE, f"launch log overflowed: {n} launches, room for {LAUNCH_LOG_CAP}")
+        out = np.zeros((max(n, 1), 7), dtype=np.int32)
+        L.pg_debug_launch_log(self._h, out.ctypes.data, n)
+        return [LaunchRec(*map(int, r)) for r in out[:n]]
+
+    def clear_launch_log(self):
+        self._L.pg_debug_clear_launch_log.argtypes = [C.c_void_p]
+        self._L.pg_debug_clear_launch_log.restype = None
+        self._L.pg_debug_clear_launch_log(self._h)
 
     def scribble_records(self, dbatch):
         """tests: overwrite the packed records and planes of the batch"""

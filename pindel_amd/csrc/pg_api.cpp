@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -228,7 +229,20 @@ struct pg_ctx {
     uint32_t ref_epoch = 0;            // counts reference (re)loads: a device batch's records hold chromosome offsets and sizes
     bool kargs_checked = false;        // the kernels' view of the kernarg segment was checked on this device (pg_debug_kargs_check)
     bool last_in_place = false;        // the last launch asked to pack did so inside the search kernel (pg_debug_last_pack_in_place)
+    // The launch log (pg_debug_launch_log): every kernel launch on the search path in launch order, the first PG_LAUNCH_LOG_CAP
+    // since the last pg_debug_clear_launch_log; launch_n counts them all.  A slot is claimed atomically (launches of one context
+    // may come from more than one host thread) and costs a few host stores, no device work.
+    static constexpr uint32_t PG_LAUNCH_LOG_CAP = 256;
+    PgLaunchRec launch_log[PG_LAUNCH_LOG_CAP]{};
+    std::atomic<uint32_t> launch_n{0};
 };
+
+void log_launch(pg_ctx *ctx, const PgLaunchRec &r)
+{
+    if (!r.kernel) return;
+    const uint32_t i = ctx->launch_n.fetch_add(1u, std::memory_order_relaxed);
+    if (i < pg_ctx::PG_LAUNCH_LOG_CAP) ctx->launch_log[i] = r;
+}
 
 struct pg_device_batch {
     uint32_t n = 0;
@@ -838,8 +852,10 @@ int pack_reads(pg_ctx *ctx, pg_device_batch *b, uint32_t lo, uint32_t cnt, hipSt
         HIP_TRY(ctx, hipMemsetAsync(b->exact_count, 0, sizeof(uint32_t), st ? st : ctx->stream));
         b->exact_n = -1;
     }
-    int rc = pg_pack_reads(&a, b->in_rec, lo, cnt, st ? st : ctx->stream);
+    PgLaunchRec rec;
+    int rc = pg_pack_reads(&a, b->in_rec, lo, cnt, st ? st : ctx->stream, &rec);
     if (rc) return fail(ctx, PG_E_DEVICE, std::string("pack kernel: ") + hipGetErrorString((hipError_t)rc));
+    log_launch(ctx, rec);
     return PG_OK;
 }
 
@@ -950,14 +966,18 @@ int launch_range(pg_ctx *ctx, pg_device_batch *b, int mode, uint32_t lo, uint32_
             return rc;
         ctx->last_in_place = d.soa != nullptr;
     }
-    int lrc = pg_launch_search(&ref, &prm, &d, mode, b->max_len, b->levels, small_ids(ctx, b) ? 1 : 0, st);
+    PgLaunchRec recs[PG_LAUNCH_RECS_MAX];
+    int n_recs = 0;
+    int lrc = pg_launch_search(&ref, &prm, &d, mode, b->max_len, b->levels, small_ids(ctx, b) ? 1 : 0, st, recs, &n_recs);
     if (lrc != 0) return fail(ctx, PG_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString((hipError_t)lrc));
+    for (int k = 0; k < n_recs; k++) log_launch(ctx, recs[k]);
     // ... then, behind it on the same stream, the reads of this range that hold a character outside ACGTN, with the reference's
     // read-shortening semantics (setUnmatchedSeq, pindel.cpp:142-169, 2545): a 64-workgroup launch that finds its list empty for
     // every batch a sequencer produced -- skipped when the host has read the list's length and it is zero
     if (b->exact_n != 0) {
-        lrc = pg_launch_search_exact(&ref, &prm, &d, mode, b->max_len, b->levels, st);
+        lrc = pg_launch_search_exact(&ref, &prm, &d, mode, b->max_len, b->levels, st, &recs[0]);
         if (lrc != 0) return fail(ctx, PG_E_DEVICE, std::string("exact kernel launch: ") + hipGetErrorString((hipError_t)lrc));
+        log_launch(ctx, recs[0]);
     }
     return PG_OK;
 }
@@ -1550,6 +1570,25 @@ void pg_device_batch_free(pg_ctx *ctx, pg_device_batch *b)
 
 // Diagnostics (not in the public header): did the last launch that was asked to pack build its records inside the search kernel ?
 int pg_debug_last_pack_in_place(const pg_ctx *ctx) { return ctx && ctx->last_in_place ? 1 : 0; }
+
+// Diagnostics (not in the public header): the launch log -- the kernels the search path launched since the last
+// pg_debug_clear_launch_log, seven int32 per launch (PgLaunchRec: kernel, NB / PB, NS, id bits, mode, DEF, packed in place).
+// Writes the first min(count, cap, PG_LAUNCH_LOG_CAP) records to out (may be null) and returns the count of launches logged.
+// Like every debug hook: not while a pg_* call is in flight on the context.
+int32_t pg_debug_launch_log(const pg_ctx *ctx, int32_t *out, int32_t cap)
+{
+    if (!ctx) return PG_E_INVALID;
+    const uint32_t n = ctx->launch_n.load(std::memory_order_relaxed);
+    const uint32_t k = std::min<uint32_t>(std::min<uint32_t>(n, pg_ctx::PG_LAUNCH_LOG_CAP), cap > 0 ? (uint32_t)cap : 0u);
+    static_assert(sizeof(PgLaunchRec) == 7 * sizeof(int32_t), "seven int32 per record");
+    if (out && k) std::memcpy(out, ctx->launch_log, (size_t)k * sizeof(PgLaunchRec));
+    return (int32_t)std::min<uint32_t>(n, 0x7fffffffu);
+}
+
+void pg_debug_clear_launch_log(pg_ctx *ctx)
+{
+    if (ctx) ctx->launch_n.store(0u, std::memory_order_relaxed);
+}
 
 // Diagnostics (not in the public header): overwrites the batch's packed records and bit planes (tests: what a search that packs in
 // place finds afterwards is what it packed itself).

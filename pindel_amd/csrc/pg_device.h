@@ -284,20 +284,36 @@ void pg_debug_reload_env(void);
 // number of kernel arguments whose value fetched from the kernarg segment at PgKArgs' offsets differs from the by-value one (0)
 int pg_debug_kargs_check(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch, uint32_t max_len, uint32_t levels,
                          uint32_t *scratch_dev, void *stream);
+// What one kernel launch on the search path ran (the launch log of pg_api.cpp, pg_debug_launch_log): the kernel and its
+// template arguments.  The launch functions below fill these when given somewhere to put them (null: nothing is recorded).
+enum PgKernelKind { PG_KERNEL_SEARCH = 1, PG_KERNEL_EXACT = 2, PG_KERNEL_PACK = 3 };
+struct PgLaunchRec {
+    int32_t kernel;                // PgKernelKind
+    int32_t blocks;                // NB of pg_search_kernel, PB of pg_pack_kernel (0: pg_search_exact_kernel)
+    int32_t ns;                    // counter slices of pg_search_kernel (0 otherwise)
+    int32_t id_bits;               // 32 / 64: candidate ids of pg_search_kernel (0 otherwise)
+    int32_t mode;                  // PgMode of the search and exact kernels (0: the pack)
+    int32_t def;                   // pg_search_kernel of the default-parameter family
+    int32_t in_place;              // the search launch built its reads' records itself (PgDevBatch::soa)
+};
+#define PG_LAUNCH_RECS_MAX 2       // records one pg_launch_search writes at most (PG_SPLIT_LAUNCH: close kernel, far kernel)
 // Launches the search kernel for the reads of the batch on `stream`.  small_ids selects the
-// 32-bit candidate ids (see above for when that is valid).
+// 32-bit candidate ids (see above for when that is valid).  rec (may be null): room for PG_LAUNCH_RECS_MAX records of the
+// kernels launched, *n_rec their number.
 int pg_launch_search(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch,
-                     int mode, uint32_t max_len, uint32_t levels, int small_ids, void *stream);
+                     int mode, uint32_t max_len, uint32_t levels, int small_ids, void *stream,
+                     struct PgLaunchRec *rec, int *n_rec);
 // may that launch build the records of its reads itself (PgDevBatch::soa) ?
 int pg_pack_in_place_ok(int mode, uint32_t max_len, int small_ids, uint32_t n_reads, uint32_t plane_blocks);
 // ... then the reads on the batch's exact list that lie in the launch's range, with the reference's read-shortening semantics
+// (rec may be null; rec->kernel stays 0 when nothing was launched)
 int pg_launch_search_exact(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch, int mode,
-                           uint32_t max_len, uint32_t levels, void *stream);
+                           uint32_t max_len, uint32_t levels, void *stream, struct PgLaunchRec *rec);
 // Device-side CSR of a result list: first the scan (gather = 0: csr[0..n] = exclusive sums of cnt, cnt has
 // n + 1 readable entries), then the gather (gather = 1: out[csr[i] + k] = pool[off[i] + k]).
 size_t pg_scan_tmp_bytes(uint32_t n);
-// in[lo .. lo + cnt) from the SoA input arrays; cnt = 0 is allowed
-int pg_pack_reads(const PgSoaIn *soa, PgInRec *in, uint32_t lo, uint32_t cnt, void *stream);
+// in[lo .. lo + cnt) from the SoA input arrays; cnt = 0 is allowed (rec may be null; rec->kernel stays 0 when nothing was launched)
+int pg_pack_reads(const PgSoaIn *soa, PgInRec *in, uint32_t lo, uint32_t cnt, void *stream, struct PgLaunchRec *rec);
 // close-end summary (rc flag, last AbsLoc, max length) of a host result into the output records
 int pg_pack_close_summary(const PgSoaOut *soa, PgOutRec *out, uint32_t n, void *stream);
 int pg_unpack_results(const PgOutRec *out, const PgSoaOut *soa, uint32_t n, void *stream);

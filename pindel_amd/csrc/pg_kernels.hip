@@ -2637,9 +2637,11 @@ __global__ __launch_bounds__(WAVE, PG_WAVES(8, u64)) void pg_search_exact_kernel
     }
 }
 extern "C" int pg_launch_search_exact(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch, int mode,
-                                      uint32_t max_len, uint32_t levels, void *stream)
+                                      uint32_t max_len, uint32_t levels, void *stream, PgLaunchRec *rec)
 {
+    if (rec) *rec = PgLaunchRec{};
     if (batch->n_reads == 0 || !batch->exact_list) return 0;
+    if (rec) *rec = PgLaunchRec{PG_KERNEL_EXACT, 0, 0, 0, mode == PG_MODE_BOTH || mode == PG_MODE_CLOSE ? mode : PG_MODE_FAR, 0, 0};
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(64), block(WAVE);
     if (mode == PG_MODE_BOTH)
@@ -2690,34 +2692,47 @@ extern "C" int pg_debug_kargs_check(const PgDevRef *ref, const PgDevParams *prm,
 }
 
 // ---------------------------------------------------------------------------------
+// (the launch log: one record per kernel launched, when the caller gave room for them)
+template <int NB, int NS, typename Id, bool DEF>
+static void note_search(PgLaunchRec *rec, int *n_rec, int mode, const PgDevBatch *batch)
+{
+    if (rec && *n_rec < PG_LAUNCH_RECS_MAX)
+        rec[(*n_rec)++] = PgLaunchRec{PG_KERNEL_SEARCH, NB, NS, (int32_t)(8 * sizeof(Id)), mode, DEF ? 1 : 0, batch->soa ? 1 : 0};
+}
+
 template <int NB, int NS, typename Id, bool DEF>
 static void launch_modes(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch, int mode,
-                         uint32_t max_len, uint32_t levels, hipStream_t st, unsigned lds_pad, dim3 grid, dim3 block)
+                         uint32_t max_len, uint32_t levels, hipStream_t st, unsigned lds_pad, dim3 grid, dim3 block,
+                         PgLaunchRec *rec, int *n_rec)
 {
     // close end + far end in one launch; PG_SPLIT_LAUNCH=1 runs the two seams as separate launches
     const bool fused = !pg_env_switches()->split_launch;
     if (mode == PG_MODE_BOTH && fused) {
         hipLaunchKernelGGL((pg_search_kernel<NB, NS, Id, PG_MODE_BOTH, DEF>), grid, block, lds_pad, st,
                            *ref, *prm, *batch, max_len, levels);
+        note_search<NB, NS, Id, DEF>(rec, n_rec, PG_MODE_BOTH, batch);
         return;
     }
 #ifdef PG_ONLY_BENCH
     abort();          // experiment builds (scripts/build_variant.sh -DPG_ONLY_BENCH): only the fused kernel exists
 #else
-    if (mode & PG_MODE_CLOSE)
+    if (mode & PG_MODE_CLOSE) {
         hipLaunchKernelGGL((pg_search_kernel<NB, NS, Id, PG_MODE_CLOSE, DEF>), grid, block, lds_pad, st,
                            *ref, *prm, *batch, max_len, levels);
+        note_search<NB, NS, Id, DEF>(rec, n_rec, PG_MODE_CLOSE, batch);
+    }
     if (mode & PG_MODE_FAR) {
         if (mode & PG_MODE_CLOSE) (void)hipMemsetAsync(batch->work_ctr, 0, PG_N_XCD * 16u * sizeof(uint32_t), st);
         hipLaunchKernelGGL((pg_search_kernel<NB, NS, Id, PG_MODE_FAR, DEF>), grid, block, lds_pad, st,
                            *ref, *prm, *batch, max_len, levels);
+        note_search<NB, NS, Id, DEF>(rec, n_rec, PG_MODE_FAR, batch);
     }
 #endif
 }
 
 template <int NB, int NS, typename Id>
 static void launch_ns(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch, int mode,
-                   uint32_t max_len, uint32_t levels, hipStream_t st, unsigned lds_pad)
+                   uint32_t max_len, uint32_t levels, hipStream_t st, unsigned lds_pad, PgLaunchRec *rec, int *n_rec)
 {
     // a few resident workgroups per CU (the launch is persistent); more than fit simply queue up and find
     // the remaining chunks
@@ -2763,24 +2778,24 @@ static void launch_ns(const PgDevRef *ref, const PgDevParams *prm, const PgDevBa
                      prm->spacer == PG_DEF_SPACER;
     if constexpr (HAS_DEF) {
         if (def) {
-            launch_modes<NB, NS, Id, true>(ref, prm, batch, mode, max_len, levels, st, lds_pad, grid, block);
+            launch_modes<NB, NS, Id, true>(ref, prm, batch, mode, max_len, levels, st, lds_pad, grid, block, rec, n_rec);
             return;
         }
     }
-    launch_modes<NB, NS, Id, false>(ref, prm, batch, mode, max_len, levels, st, lds_pad, grid, block);
+    launch_modes<NB, NS, Id, false>(ref, prm, batch, mode, max_len, levels, st, lds_pad, grid, block, rec, n_rec);
 }
 
 // the seed filter's counter width follows the batch's largest number of mismatch levels (validate_and_measure)
 template <int NB, typename Id>
 static void launch(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch, int mode,
-                   uint32_t max_len, uint32_t levels, hipStream_t st, unsigned lds_pad)
+                   uint32_t max_len, uint32_t levels, hipStream_t st, unsigned lds_pad, PgLaunchRec *rec, int *n_rec)
 {
-    if (levels <= 8) launch_ns<NB, 3, Id>(ref, prm, batch, mode, max_len, levels, st, lds_pad);
+    if (levels <= 8) launch_ns<NB, 3, Id>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
 #ifdef PG_ONLY_BENCH
     else abort();     // experiment builds: default parameters only
 #else
-    else if (levels <= 16) launch_ns<NB, 4, Id>(ref, prm, batch, mode, max_len, levels, st, lds_pad);
-    else launch_ns<NB, 5, Id>(ref, prm, batch, mode, max_len, levels, st, lds_pad);
+    else if (levels <= 16) launch_ns<NB, 4, Id>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
+    else launch_ns<NB, 5, Id>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
 #endif
 }
 
@@ -3079,9 +3094,11 @@ static void launch_pack(const PgSoaIn *soa, PgInRec *in, uint32_t lo, uint32_t c
     const uint32_t want = (cnt + 255u) / 256u, cap = PG_PACK_GRID;       // 64 reads per wave and loop iteration, 4 waves per workgroup
     pg_pack_kernel<PB><<<want < cap ? want : cap, 256, 0, st>>>(*soa, in, lo, cnt);
 }
-extern "C" int pg_pack_reads(const PgSoaIn *soa, PgInRec *in, uint32_t lo, uint32_t cnt, void *stream)
+extern "C" int pg_pack_reads(const PgSoaIn *soa, PgInRec *in, uint32_t lo, uint32_t cnt, void *stream, PgLaunchRec *rec)
 {
+    if (rec) *rec = PgLaunchRec{};
     if (cnt) {
+        if (rec) *rec = PgLaunchRec{PG_KERNEL_PACK, (int32_t)soa->plane_blocks, 0, 0, 0, 0, 0};
         hipStream_t st = (hipStream_t)stream;
         switch (soa->plane_blocks) {
         case 1: launch_pack<1>(soa, in, lo, cnt, st); break;
@@ -3204,8 +3221,12 @@ extern "C" int pg_pack_in_place_ok(int mode, uint32_t max_len, int small_ids, ui
 }
 
 extern "C" int pg_launch_search(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch,
-                                int mode, uint32_t max_len, uint32_t levels, int small_ids, void *stream)
+                                int mode, uint32_t max_len, uint32_t levels, int small_ids, void *stream,
+                                PgLaunchRec *rec, int *n_rec)
 {
+    int n_local = 0;
+    if (!n_rec) n_rec = &n_local;
+    *n_rec = 0;
     if (batch->n_reads == 0) return 0;
     // a launch that packs in place must be one pg_pack_in_place_ok admits (the kernels run the pack of THEIR class on the batch's planes)
     if (batch->soa && !pg_pack_in_place_ok(mode, max_len, small_ids, batch->n_reads, batch->plane_blocks)) return (int)hipErrorInvalidValue;
@@ -3218,20 +3239,20 @@ extern "C" int pg_launch_search(const PgDevRef *ref, const PgDevParams *prm, con
     // experiment builds: only the instantiations of the bench workloads (100 / 150-base reads, 32-bit ids), compiled in a
     // fraction of the time
     if (!small_ids || max_len > 192) abort();
-    if (nb == 2 && max_len > 64) launch<2, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad);
-    else launch<3, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad);
+    if (nb == 2 && max_len > 64) launch<2, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
+    else launch<3, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
     return (int)hipGetLastError();
 #else
     if (small_ids) {
-        if (max_len <= 64) launch<1, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad);
-        else if (nb == 2) launch<2, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad);
-        else if (max_len <= 192) launch<3, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad);
-        else if (nb == 4) launch<4, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad);
-        else launch<8, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad);
+        if (max_len <= 64) launch<1, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
+        else if (nb == 2) launch<2, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
+        else if (max_len <= 192) launch<3, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
+        else if (nb == 4) launch<4, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
+        else launch<8, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
     } else {
-        if (nb == 2) launch<2, u64>(ref, prm, batch, mode, max_len, levels, st, lds_pad);
-        else if (nb == 4) launch<4, u64>(ref, prm, batch, mode, max_len, levels, st, lds_pad);
-        else launch<8, u64>(ref, prm, batch, mode, max_len, levels, st, lds_pad);
+        if (nb == 2) launch<2, u64>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
+        else if (nb == 4) launch<4, u64>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
+        else launch<8, u64>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
     }
     return (int)hipGetLastError();
 #endif

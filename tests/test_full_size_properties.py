@@ -39,6 +39,15 @@ def test_bench_workload_properties(engine_factory):
     db = eng.upload(batch)
     eng.search_device(db)
     res = eng.download(db)
+    assert int(res.close_off[-1]) + int(res.far_off[-1]) == 21235377
+    assert int((res.far_off[1:] > res.far_off[:-1]).sum()) == 6290009
+    assert shard.digest_hex(shard.read_digests(res)) == "ec6c3a18d3adc53802a769355a3129f4668632c3072f87679b6c1b245b94c19f"
+    # ... and through the step bench.py times: one launch that packs the batch in place over scribbled records
+    del res
+    eng.scribble_records(db)
+    eng.pack_search_device(db)
+    assert eng.last_step_in_place()
+    res = eng.download(db)
     eng.free_device_batch(db)
     assert int(res.close_off[-1]) + int(res.far_off[-1]) == 21235377
     assert int((res.far_off[1:] > res.far_off[:-1]).sum()) == 6290009
