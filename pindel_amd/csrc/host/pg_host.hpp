@@ -113,6 +113,12 @@ public:
     // ReportCloseMappedReads (pindel.cpp:1076-1092): the reads of a window that kept a close end, in their order, as
     // Pindel-text records (UnmatchedSeq as GetCloseEnd left it), appended to <prefix>_CloseEndMapped
     void report_close_mapped(const std::vector<SplitRead> &reads);
+    // The start of a region-plan record (pindel.cpp:1801-1804 sits inside the record loop): CurrentChrMask all 'N'
+    void begin_region()
+    {
+        chr_marks_.clear();
+        mask_chr_ = nullptr;
+    }
     unsigned long far_end_checksum = 0;
     double li_seconds = 0.0;             // host time spent in SortOutputLI, all windows so far
     // UpdateRefReadCoverage (pindel.cpp:1272-1330), BAM input: per sample (in the order of the sample-name set as
@@ -137,7 +143,7 @@ private:
     std::vector<char> li_buf_, cem_buf_;
     std::ofstream &open_append(std::ofstream &f, std::vector<char> &buf, const char *suffix);
     // CurrentChrMask (pindel.cpp:1801-1804): the positions of this chromosome where an event has been reported so far
-    // ('B'), kept as a set; reset when the chromosome changes.  The reporters call mark() with the breakpoints they print; inside for_boxes the marks
+    // ('B'), kept as a set; reset at every region record (begin_region) and when the chromosome changes.  The reporters call mark() with the breakpoints they print; inside for_boxes the marks
     // are collected per worker and applied when the boxes are done (setting a mark commutes, so the order of the boxes
     // and workers does not matter).
     std::set<unsigned> chr_marks_;

@@ -36,14 +36,19 @@ struct pgh_settings {
     uint32_t max_mismatch[500];  /* g_maxMismatch (pg_get_max_mismatch) */
     int32_t analyze_li;          /* -l: also write <prefix>_LI */
     int32_t report_close_mapped; /* -s: also write <prefix>_CloseEndMapped */
+    const char *region;          /* -c: NULL or "" = ALL */
+    const char *include_bed;     /* -j: NULL or "" = none */
+    const char *exclude_bed;     /* -J: NULL or "" = none */
 };
+
+static std::string str_or_empty(const char *s) { return s ? s : ""; }
 
 /*
  * Pindel's post-search pipeline for a Pindel-text read file: attaches the given UP_Close /
  * UP_Far (CSR over ALL reads of the file, in file order; reads without close end have an
  * empty range) and the rc flags, then walks chromosomes and 5-Mbp bins like main()
  * (pindel.cpp:1778-1989) and appends <prefix>_D, _SI, _TD, _INV -- and _LI / _CloseEndMapped when
- * analyze_li / report_close_mapped are set.
+ * analyze_li / report_close_mapped are set.  region / include_bed / exclude_bed: the region plan (pg_region.hpp).
  */
 int pgh_call_from_points(const char *fasta_path, const char *reads_path, const char *out_prefix,
                          const pgh_settings *st, uint32_t n_reads,
@@ -71,7 +76,10 @@ int pgh_call_from_points(const char *fasta_path, const char *reads_path, const c
     S.Analyze_LI = st->analyze_li != 0;
     S.report_close_mapped = st->report_close_mapped != 0;
     memcpy(S.max_mismatch, st->max_mismatch, sizeof S.max_mismatch);
-    std::vector<unsigned> fai = read_fai(fasta_path, genome);
+    std::vector<RegionRecord> plan;
+    if (region_plan(chromosome_names(genome), chromosome_sizes(genome, read_fai(fasta_path, genome), S.spacer), str_or_empty(st->region),
+                    str_or_empty(st->include_bed), str_or_empty(st->exclude_bed), plan, g_err))
+        return -1;
     auto to_up = [](const pg_point &p) {
         UniquePoint u;
         u.chr = p.chr_id;
@@ -95,7 +103,30 @@ int pgh_call_from_points(const char *fasta_path, const char *reads_path, const c
         }
         return 0;
     };
-    return run_pipeline(genome, fai, all, S, out_prefix, attach, pgh::NoFarSearch(), g_err);
+    return run_pipeline(genome, plan, all, S, out_prefix, attach, pgh::NoFarSearch(), g_err);
+}
+
+/*
+ * The region plan of -c region -j include_bed -J exclude_bed (any may be NULL or "") on the reference fasta_path (its
+ * .fai sizes when present): 3 values per record (chromosome index in the FASTA, start, end), in plan order.  Returns the
+ * number of records (also when it exceeds cap; only cap are written), -1 = unreadable input, unknown chromosome, start
+ * beyond the chromosome or a malformed BED line, -2 = -c syntax (pgh_last_error says which).
+ */
+int64_t pgh_region_plan(const char *fasta_path, const char *region, const char *include_bed, const char *exclude_bed,
+                        uint32_t *out, uint64_t cap)
+{
+    std::vector<Chromosome> genome;
+    if (load_fasta(fasta_path, genome, 0, g_err)) return -1;
+    std::vector<RegionRecord> plan;
+    const int rc = region_plan(chromosome_names(genome), chromosome_sizes(genome, read_fai(fasta_path, genome), 0), str_or_empty(region),
+                               str_or_empty(include_bed), str_or_empty(exclude_bed), plan, g_err);
+    if (rc) return rc == REGION_BAD_SYNTAX ? -2 : -1;
+    for (size_t k = 0; k < plan.size() && k < cap; k++) {
+        out[3 * k] = (uint32_t)plan[k].chr;
+        out[3 * k + 1] = plan[k].start;
+        out[3 * k + 2] = plan[k].end;
+    }
+    return (int64_t)plan.size();
 }
 
 // BreakDancer hints (pg_bdhints.hpp) for one bin: clusters of the reads whose last close-end point is at

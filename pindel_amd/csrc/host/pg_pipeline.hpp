@@ -19,6 +19,7 @@
 #include "pg_bam.hpp"
 #include "pg_bdhints.hpp"
 #include "pg_host.hpp"
+#include "pg_region.hpp"
 #include "pg_rp.hpp"
 
 namespace pgh {
@@ -36,6 +37,21 @@ inline std::vector<unsigned> read_fai(const std::string &fasta_path, const std::
             if (genome[c].name == name) fai[c] = size;
     }
     return fai;
+}
+
+// The chromosome sizes of the region plan: the .fai length, or the FASTA length without one
+inline std::vector<unsigned> chromosome_sizes(const std::vector<Chromosome> &genome, const std::vector<unsigned> &fai, unsigned spacer)
+{
+    std::vector<unsigned> sizes(genome.size());
+    for (size_t c = 0; c < genome.size(); c++) sizes[c] = fai[c] ? fai[c] : (unsigned)(genome[c].seq.size() - 2 * spacer);
+    return sizes;
+}
+
+inline std::vector<std::string> chromosome_names(const std::vector<Chromosome> &genome)
+{
+    std::vector<std::string> names;
+    for (const Chromosome &c : genome) names.push_back(c.name);
+    return names;
 }
 
 // Frees the strings and point lists of a window's reads on several threads (the destructors of ~10^7 reads are
@@ -66,8 +82,16 @@ struct NoFarSearch {
     int operator()(const Chromosome &, int, std::vector<SplitRead> &, unsigned, unsigned) const { return 0; }
 };
 
+// Both pipelines walk a region plan (pg_region.hpp) record by record, in plan order (main's IncludeBed loop,
+// src/pindel.cpp:1777-1987): record [S, E] on chromosome c is searched in windows from S - 10 kbp in steps of -w, each
+// ending at min(start + W, biological size, E + 10 kbp), and its calls are restricted to [S, E] (readInSpecifiedRegion).
+// A read in the windows of two records is searched and reported in both, as in the reference.  CurrentChrMask starts
+// empty at every record; Count_LI, g_maxInsertSize, the event numbers and the _RP stream run on across records.
+// Under -j the reference also calls ControlState::CleanUPReads at every record.  That has no effect here: the reference
+// clears the same vectors at the end of every window (pindel.cpp:1962-1968), and so do these loops (reads, kept reads,
+// read-pair events and reference-supporting reads all live for one window only).
 template <class Search, class FarSearch>
-int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<unsigned> &fai,
+int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<RegionRecord> &plan,
                  const std::vector<SplitRead> &all, const Settings &S, const std::string &prefix,
                  Search search, FarSearch far_search, std::string &err, double *li_seconds = nullptr)
 {
@@ -82,39 +106,53 @@ int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<unsign
     double t_copy = 0, t_search = 0, t_keep = 0, t_call = 0, t_free = 0;
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     // The Pindel-text reader rescans the whole file for every window and raises g_maxPos for EVERY read it
-    // passes (reader.cpp:224-226), so after the first window of a chromosome g_maxPos is the largest position
-    // in the file; the windows then run until they pass it.  Here the reads are bucketed once: per chromosome
-    // the indices of its reads by window, in input order (a stable counting sort), instead of one pass over
-    // all reads per window.
+    // passes (reader.cpp:224-226), so after the first window of a record g_maxPos is the largest position
+    // in the file; the windows then run until they pass it.  Here the reads are sorted once: per chromosome
+    // the indices of its reads by position (input order among equal positions); a record takes the range of
+    // its windows from that list and bins it by window, in input order, instead of one pass over all reads
+    // per window.
     unsigned file_max_pos = 0;
     std::vector<std::vector<uint32_t>> by_chr(genome.size());
     for (uint32_t i = 0; i < all.size(); i++) {
         file_max_pos = std::max(file_max_pos, all[i].MatchedRelPos);
         if (all[i].chr_id >= 0 && all[i].chr_id < (int)genome.size()) by_chr[all[i].chr_id].push_back(i);
     }
-    for (size_t c = 0; c < genome.size(); c++) {
+    for (std::vector<uint32_t> &v : by_chr)
+        if (!std::is_sorted(v.begin(), v.end(), [&](uint32_t a, uint32_t b) { return all[a].MatchedRelPos < all[b].MatchedRelPos; }))
+            std::stable_sort(v.begin(), v.end(), [&](uint32_t a, uint32_t b) { return all[a].MatchedRelPos < all[b].MatchedRelPos; });
+    for (const RegionRecord &rec : plan) {
+        const size_t c = (size_t)rec.chr;
         const Chromosome &chrom = genome[c];
         const unsigned biol = (unsigned)(chrom.seq.size() - 2 * S.spacer);
-        const unsigned bed_start = 1, bed_end = fai[c] ? fai[c] : biol;   // "-c ALL": one BED record per chromosome
-        const unsigned global_end = std::min(biol, bed_end + 10000u);      // AROUND_REGION_BUFFER
-        // windows that will be visited: ws = 0, W, 2W, ... while !(ws >= g_maxPos || ws > global_end), at least one
+        const unsigned bed_start = rec.start, bed_end = rec.end;
+        const unsigned global_start = region_global_start(rec), global_end = region_global_end(rec, biol);
+        caller.begin_region();
+        // windows that will be visited: ws = G, G + W, ... while !(ws >= g_maxPos || ws > global_end), at least one
         std::vector<unsigned> starts;
         {
-            unsigned ws = 0;
+            uint64_t ws = global_start;
             do {
-                starts.push_back(ws);
+                starts.push_back((unsigned)ws);
                 ws += WINDOW;
             } while (!(ws >= file_max_pos || ws > global_end));
         }
         std::vector<std::vector<uint32_t>> bins(starts.size());
-        for (uint32_t i : by_chr[c]) {
-            const size_t w = all[i].MatchedRelPos / WINDOW;
-            // a read is picked up by window w iff ws <= pos < min(ws + W, global_end)
-            if (w < starts.size() && all[i].MatchedRelPos < std::min(starts[w] + WINDOW, global_end)) bins[w].push_back(i);
+        {
+            const std::vector<uint32_t> &v = by_chr[c];
+            auto first = std::lower_bound(v.begin(), v.end(), global_start,
+                                          [&](uint32_t i, unsigned p) { return all[i].MatchedRelPos < p; });
+            for (auto it = first; it != v.end() && all[*it].MatchedRelPos < global_end; ++it) {
+                const unsigned pos = all[*it].MatchedRelPos;
+                const size_t w = (pos - global_start) / WINDOW;
+                // a read is picked up by window w iff ws <= pos < min(ws + W, global_end)
+                if (w < starts.size() && (uint64_t)pos < std::min<uint64_t>((uint64_t)starts[w] + WINDOW, global_end)) bins[w].push_back(*it);
+            }
+            for (std::vector<uint32_t> &b : bins)                                      // input order
+                if (!std::is_sorted(b.begin(), b.end())) std::sort(b.begin(), b.end());
         }
         for (size_t w = 0; w < starts.size(); w++) {
             if (bins[w].empty()) continue;
-            const unsigned ws = starts[w], we = std::min(ws + WINDOW, global_end);
+            const unsigned ws = starts[w], we = (unsigned)std::min<uint64_t>((uint64_t)ws + WINDOW, global_end);
             double t0 = now();
             std::vector<SplitRead> reads(bins[w].size());
             pg_adapter::parallel_ranges(reads.size(), [&](size_t lo, size_t hi) {
@@ -164,8 +202,9 @@ int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<unsign
 }
 
 // BAM input (`-i config`): main()'s loop with get_SR_Reads per window (src/pindel.cpp:1816-1982,
-// src/reader.cpp:1427-1470).  Windows run from 0 in steps of the bin size while the start does not pass the
-// end of the chromosome (LoopingSearchWindow::finished without the Pindel-text shortcut); every window reads
+// src/reader.cpp:1427-1470).  The windows of each plan record run from its global start in steps of the bin size
+// while the start does not pass the record's global end (LoopingSearchWindow::finished without the Pindel-text
+// shortcut); every window reads
 // its candidates from every BAM of the configuration through pg_bam.hpp, so only one window's reads are in
 // memory at a time (a coordinate-sorted BAM delivers them bin by bin).
 struct BamSource {
@@ -198,7 +237,7 @@ struct CloseView {
 // The windows are a three-stage pipeline on the host: while window k is searched and classified, a second thread
 // already reads window k + 1 from the BAMs (read-pair discovery + ingest, the stage that dominates a BAM-fed run).
 template <class CloseSoa, class FarSearch>
-int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<unsigned> &fai,
+int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<RegionRecord> &plan,
                      const std::vector<BamSource> &bams, const BamIngestSettings &ingest, const Settings &S,
                      const std::string &prefix, CloseSoa close_soa, FarSearch far_search, std::string &err, size_t *n_reads_total = nullptr,
                      BDHints *bd = nullptr, bool search_rp = false, size_t *n_rp_events = nullptr,
@@ -222,13 +261,16 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<un
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_begin = now();
 
-    struct Win { size_t c; unsigned ws, we; };
+    // the windows of every plan record, in plan order (LoopingSearchWindow::finished without the Pindel-text shortcut);
+    // rec: the record's index in the plan, first: the record's first window
+    struct Win { size_t c, rec; unsigned ws, we; bool first; };
     std::vector<Win> wins;
-    for (size_t c = 0; c < genome.size(); c++) {
+    for (size_t k = 0; k < plan.size(); k++) {
+        const size_t c = (size_t)plan[k].chr;
         const unsigned biol = (unsigned)(genome[c].seq.size() - 2 * S.spacer);
-        const unsigned bed_end = fai[c] ? fai[c] : biol;
-        const unsigned global_end = std::min(biol, bed_end + 10000u);
-        for (unsigned ws = 0; !(ws > global_end); ws += WINDOW) wins.push_back({ c, ws, std::min(ws + WINDOW, global_end) });
+        const unsigned global_end = region_global_end(plan[k], biol);
+        for (uint64_t ws = region_global_start(plan[k]); !(ws > global_end); ws += WINDOW)
+            wins.push_back({ c, k, (unsigned)ws, (unsigned)std::min<uint64_t>(ws + WINDOW, global_end), ws == region_global_start(plan[k]) });
     }
     // what the reader thread hands over for one window
     struct WinData {
@@ -284,8 +326,8 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<un
         const Win &win = wins[w];
         const size_t c = win.c;
         const Chromosome &chrom = genome[c];
-        const unsigned biol = (unsigned)(chrom.seq.size() - 2 * S.spacer);
-        const unsigned bed_start = 1, bed_end = fai[c] ? fai[c] : biol;
+        const unsigned bed_start = plan[win.rec].start, bed_end = plan[win.rec].end;
+        if (win.first) caller.begin_region();
         if (bd && search_rp) {
             bd->update_with_rp(d->sides);
             if (n_rp_events) *n_rp_events += d->n_events;

@@ -1,12 +1,14 @@
 // pindel_pg -- command line with Pindel's flags for the path this repository implements:
 //   pindel_pg -f ref.fa -p reads.txt -o prefix [-x 2 -a 1 -m 3 -u 0.02 -e 0.01 -E 0.95 -H 8
-//                                               -M 1 -B 100 -d 30 -v 50 -w 5 -G device -l -s -S]
+//                                               -M 1 -B 100 -d 30 -v 50 -w 5 -G device -l -s -S
+//                                               -c ALL|chr[:start[-end]] -j include.bed -J exclude.bed]
 // FASTA + Pindel-text reads -> close/far-end search on the MI355X (C ABI, libpindel_pg.so)
 // -> SV classification and <prefix>_D/_SI/_TD/_INV reports (host code in this directory);
 // -l adds <prefix>_LI (long insertions), -s <prefix>_CloseEndMapped (the reads with a close end),
 // -S writes <prefix>_CloseEndMapped only (no far end, no SV search).  Like the reference, every run
 // creates all seven files (_D _SI _TD _INV _LI _BP _CloseEndMapped); _BP stays empty, as the
-// reference's breakpoint report is not called.
+// reference's breakpoint report is not called.  -c, -j and -J select the regions searched (pg_region.hpp); they are
+// checked before the first device call (exit status 2 for -c syntax, 1 for an unreadable file or an unknown chromosome).
 // Flags and their defaults follow src/fn_parameters.cpp; BAM input (-i) needs htslib and is
 // not built here.
 #include <cstdio>
@@ -25,6 +27,7 @@
 #include "pg_bdhints.hpp"
 #include "pg_host.hpp"
 #include "pg_pipeline.hpp"
+#include "pg_region.hpp"
 #include "pindel_pg.h"
 
 using namespace pgh;
@@ -39,6 +42,7 @@ int main(int argc, char **argv)
     const double t_start = now_s();
     double t_search = 0.0;
     std::string fasta, reads_path, prefix, bd_path, bam_config;
+    std::string region, include_bed, exclude_bed;           // -c, -j, -J
     unsigned min_anchor_quality = 0;
     int ref_read_nm = 2;                    // -n / --NM (isRefRead)
     bool search_rp = true;                 // -R: discordant read pairs as window hints (BAM input only; default true)
@@ -61,6 +65,7 @@ int main(int argc, char **argv)
         { "-d", "--min_num_matched_bases", 'i' }, { "-v", "--min_inversion_size", 'i' },
         { "-w", "--window_size", 'f' }, { "-T", "--number_of_threads", 'i' }, { "-b", "--breakdancer", 's' },
         { "-G", "--gpus", 's' }, { "", "--bd-hints", 's' }, { "", "--flush-reads", 'i' }, { "-c", "--chromosome", 's' },
+        { "-j", "--include", 's' }, { "-J", "--exclude", 's' },
         { "-n", "--NM", 'i' }, { "", "--min_NT_size", 'i' }, { "-A", "--anchor_quality", 'i' }, { "-L", "--logfilename", 's' },
         { "-r", "--report_inversions", 'u' }, { "-t", "--report_duplications", 'u' },
         { "-l", "--report_long_insertions", 'u' }, { "-k", "--report_breakpoints", 'u' },
@@ -144,11 +149,16 @@ int main(int argc, char **argv)
         else if (key == "-b") bd_path = v;                                     // --breakdancer
         else if (key == "--bd-hints") use_bd = std::string(v) == "on";         // see below: off = what 0.2.5b9 does
         else if (key == "-c") {
-            if (std::string(v) != "ALL") {
-                fprintf(stderr, "pindel_pg: only -c ALL is supported\n");
+            RegionSpec spec;
+            std::string rerr;
+            if (parse_region(v, spec, rerr)) {
+                fprintf(stderr, "pindel_pg: %s\n", rerr.c_str());
                 return 2;
             }
+            region = v;
         }
+        else if (key == "-j") include_bed = v;
+        else if (key == "-J") exclude_bed = v;
         else if (key == "-T") {
             // host threads of the classifiers / reporters (the search itself runs on the GPU); PGH_THREADS wins
             if (iv >= 1) setenv("PGH_THREADS", std::to_string(iv).c_str(), 0);
@@ -195,6 +205,22 @@ int main(int argc, char **argv)
         fprintf(stderr, "pindel_pg: %s\n", err.c_str());
         return 1;
     }
+    // the region plan (main's IncludeBed, src/pindel.cpp:1605-1720), complete before any device is touched
+    std::vector<unsigned> fai = read_fai(fasta, genome);
+    std::vector<RegionRecord> plan;
+    {
+        const int prc = region_plan(chromosome_names(genome), chromosome_sizes(genome, fai, prm.spacer), region, include_bed, exclude_bed,
+                                    plan, err);
+        if (prc) {
+            fprintf(stderr, "pindel_pg: %s\n", err.c_str());
+            return prc;
+        }
+    }
+    if (plan.empty()) {
+        printf("pindel_pg: no region left to search (every record of the include list is excluded); the reports are empty\n");
+        return 0;
+    }
+    for (const RegionRecord &r : plan) printf("Processing region: %s\t%u\t%u\n", genome[r.chr].name.c_str(), r.start, r.end);
     std::vector<SplitRead> all;
     if (!reads_path.empty() && load_pindel_text(reads_path, genome, all, err)) {
         fprintf(stderr, "pindel_pg: %s\n", err.c_str());
@@ -255,7 +281,6 @@ int main(int argc, char **argv)
     S.spacer = prm.spacer;
     S.log_counts = true;
     pg_get_max_mismatch(ctx, S.max_mismatch);
-    std::vector<unsigned> fai = read_fai(fasta, genome);
     const double t_loaded = now_s();
     auto chr_of = [](const SplitRead &r) { return r.chr_id; };
     auto make_point = [](const pg_point &p) {
@@ -438,11 +463,11 @@ int main(int argc, char **argv)
             t_search += now_s() - t0;
             return 0;
         };
-        rc = run_bam_pipeline(genome, fai, bams, ing, S, prefix, close_soa, far_search, err, &n_bam_reads, &bd, search_rp, &n_rp_events,
+        rc = run_bam_pipeline(genome, plan, bams, ing, S, prefix, close_soa, far_search, err, &n_bam_reads, &bd, search_rp, &n_rp_events,
                               &li_seconds);
         if (search_rp) printf("pindel_pg: read-pair events added as window hints: %zu\n", n_rp_events);
     } else
-        rc = run_pipeline(genome, fai, all, S, prefix, close_search, far_search, err, &li_seconds);
+        rc = run_pipeline(genome, plan, all, S, prefix, close_search, far_search, err, &li_seconds);
     if (rc) fprintf(stderr, "pindel_pg: %s (%s)\n", err.c_str(), pg_last_error(ctx));
     else {
         const size_t n_reads = bams.empty() ? all.size() : n_bam_reads;

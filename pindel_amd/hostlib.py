@@ -18,7 +18,8 @@ class HostSettings(C.Structure):
         ("seq_error_rate", C.c_double), ("min_num_matched_bases", C.c_int32),
         ("min_inversion_size", C.c_int32), ("analyze_td", C.c_int32), ("analyze_inv", C.c_int32),
         ("window_mbp", C.c_double), ("max_mismatch", C.c_uint32 * 500),
-        ("analyze_li", C.c_int32), ("report_close_mapped", C.c_int32)]
+        ("analyze_li", C.c_int32), ("report_close_mapped", C.c_int32),
+        ("region", C.c_char_p), ("include_bed", C.c_char_p), ("exclude_bed", C.c_char_p)]
 
 
 def build(force=False):
@@ -44,6 +45,8 @@ def lib():
         L.pgh_call_from_points.argtypes = [
             C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(HostSettings), C.c_uint32,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pgh_region_plan.restype = C.c_int64
+        L.pgh_region_plan.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64]
         _lib = L
     return _lib
 
@@ -62,17 +65,60 @@ def default_settings(max_mismatch) -> HostSettings:
     s.window_mbp = 5.0
     s.analyze_li = 0           # -l (default false): <prefix>_LI
     s.report_close_mapped = 0  # -s (default false): <prefix>_CloseEndMapped
+    s.region = None            # -c (None = ALL)
+    s.include_bed = None       # -j (None = no include list)
+    s.exclude_bed = None       # -J (None = no exclude list)
     for i in range(500):
         s.max_mismatch[i] = int(max_mismatch[i])
     return s
 
 
+def _enc(x):
+    return None if x is None else str(x).encode()
+
+
+def region_plan(fasta, region=None, include_bed=None, exclude_bed=None):
+    """The records a run with -c region -j include_bed -J exclude_bed searches, in order: a list of
+    (chromosome name, start, end), Pindel coordinates, both ends included (pindel_amd/csrc/host/pg_region.hpp).
+    Raises ValueError for a malformed region, an unknown chromosome, a start beyond the chromosome, an
+    unreadable or malformed BED file."""
+    L = lib()
+    names = _fasta_names(fasta)
+    cap = 64
+    while True:
+        out = np.zeros(3 * cap, dtype=np.uint32)
+        n = L.pgh_region_plan(_enc(fasta), _enc(region), _enc(include_bed), _enc(exclude_bed), out.ctypes.data, cap)
+        if n < 0:
+            raise ValueError("region plan: " + (L.pgh_last_error() or b"").decode())
+        if n <= cap:
+            return [(names[int(out[3 * k])], int(out[3 * k + 1]), int(out[3 * k + 2])) for k in range(n)]
+        cap = int(n)
+
+
+def _fasta_names(fasta):
+    """the FASTA's record names in file order (the chromosome indices of the host library)"""
+    out = []
+    with open(fasta, "rb") as f:
+        for line in f:
+            if line.startswith(b">"):
+                nm = line[1:].split()
+                out.append(nm[0].decode() if nm else "")
+    return out
+
+
 def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pts, far_off, far_pts,
-                     rc_flag):
+                     rc_flag, region=None, include_bed=None, exclude_bed=None):
     """Classify + report (_D, _SI, _TD, _INV) from per-read UP_Close / UP_Far points (CSR over
     all reads of the file, 12-byte pg_point records).  settings.analyze_li / settings.report_close_mapped
-    add <out_prefix>_LI / <out_prefix>_CloseEndMapped."""
+    add <out_prefix>_LI / <out_prefix>_CloseEndMapped.  region / include_bed / exclude_bed (-c, -j, -J)
+    override the settings' fields of the same names when given; by default the whole genome is searched."""
     L = lib()
+    keep = [_enc(region), _enc(include_bed), _enc(exclude_bed)]     # (alive until the call returns)
+    if any(k is not None for k in keep):
+        settings = HostSettings.from_buffer_copy(settings)
+        for field, v in zip(("region", "include_bed", "exclude_bed"), keep):
+            if v is not None:
+                setattr(settings, field, v)
     close_off = np.ascontiguousarray(close_off, dtype=np.uint64)
     far_off = np.ascontiguousarray(far_off, dtype=np.uint64)
     close_pts = np.ascontiguousarray(close_pts)
