@@ -14,6 +14,7 @@
 #include "pg_host_priv.hpp"
 #include "pg_pipeline.hpp"
 #include "pg_rp.hpp"
+#include "pg_vcf.hpp"
 #include "pindel_pg.h"
 
 using namespace pgh;
@@ -127,6 +128,82 @@ int64_t pgh_region_plan(const char *fasta_path, const char *region, const char *
         out[3 * k + 2] = plan[k].end;
     }
     return (int64_t)plan.size();
+}
+
+/* pindel2vcf's flags (pg_vcf.hpp VcfOptions); pgh_vcf_default_options fills in the reference's defaults. */
+struct pgh_vcf_options {
+    const char *reference;       /* -r */
+    const char *reference_name;  /* -R */
+    const char *reference_date;  /* -d */
+    const char *report;          /* -p: NULL or "" = none */
+    const char *prefix;          /* -P: NULL or "" = none */
+    const char *vcf;             /* -v: NULL or "" = <report>.vcf / <prefix>.vcf */
+    const char *chromosome;      /* -c: NULL or "" = all */
+    int32_t window_size, min_coverage;
+    double het_cutoff, hom_cutoff;
+    int32_t min_size, max_size, both_strands, min_supporting_samples, min_supporting_reads, max_supporting_reads;
+    int32_t region_start, region_end, max_internal_repeats, max_internal_repeatlength, max_postindel_repeats;
+    int32_t max_postindel_repeatlength, compact_output_limit, only_balanced_samples, minimum_strand_support, gatk_compatible;
+};
+
+void pgh_vcf_default_options(pgh_vcf_options *o)
+{
+    const VcfOptions d;
+    *o = pgh_vcf_options{};
+    o->window_size = d.window_size;
+    o->min_coverage = d.min_coverage;
+    o->het_cutoff = d.het_cutoff;
+    o->hom_cutoff = d.hom_cutoff;
+    o->min_size = d.min_size;
+    o->max_size = d.max_size;
+    o->both_strands = d.both_strands;
+    o->min_supporting_samples = d.min_supporting_samples;
+    o->min_supporting_reads = d.min_supporting_reads;
+    o->max_supporting_reads = d.max_supporting_reads;
+    o->region_start = d.region_start;
+    o->region_end = d.region_end;
+    o->max_internal_repeats = d.max_internal_repeats;
+    o->max_internal_repeatlength = d.max_internal_repeatlength;
+    o->max_postindel_repeats = d.max_postindel_repeats;
+    o->max_postindel_repeatlength = d.max_postindel_repeatlength;
+    o->compact_output_limit = d.compact_output_limit;
+    o->only_balanced_samples = d.only_balanced_samples;
+    o->minimum_strand_support = d.minimum_strand_support;
+    o->gatk_compatible = d.gatk_compatible;
+}
+
+/* Pindel reports -> VCF (pg_vcf.hpp).  0 = written, 1 = error (pgh_last_error says which; no output file is left). */
+int pgh_reports_to_vcf(const pgh_vcf_options *o)
+{
+    VcfOptions v;
+    v.reference = str_or_empty(o->reference);
+    v.reference_name = str_or_empty(o->reference_name);
+    v.reference_date = str_or_empty(o->reference_date);
+    v.report = str_or_empty(o->report);
+    v.prefix = str_or_empty(o->prefix);
+    v.vcf = str_or_empty(o->vcf);
+    v.chromosome = str_or_empty(o->chromosome);
+    v.window_size = o->window_size;
+    v.min_coverage = o->min_coverage;
+    v.het_cutoff = o->het_cutoff;
+    v.hom_cutoff = o->hom_cutoff;
+    v.min_size = o->min_size;
+    v.max_size = o->max_size;
+    v.both_strands = o->both_strands != 0;
+    v.min_supporting_samples = o->min_supporting_samples;
+    v.min_supporting_reads = o->min_supporting_reads;
+    v.max_supporting_reads = o->max_supporting_reads;
+    v.region_start = o->region_start;
+    v.region_end = o->region_end;
+    v.max_internal_repeats = o->max_internal_repeats;
+    v.max_internal_repeatlength = o->max_internal_repeatlength;
+    v.max_postindel_repeats = o->max_postindel_repeats;
+    v.max_postindel_repeatlength = o->max_postindel_repeatlength;
+    v.compact_output_limit = o->compact_output_limit;
+    v.only_balanced_samples = o->only_balanced_samples != 0;
+    v.minimum_strand_support = o->minimum_strand_support;
+    v.gatk_compatible = o->gatk_compatible != 0;
+    return reports_to_vcf(v, g_err) ? 1 : 0;
 }
 
 // BreakDancer hints (pg_bdhints.hpp) for one bin: clusters of the reads whose last close-end point is at

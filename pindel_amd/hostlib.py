@@ -22,6 +22,32 @@ class HostSettings(C.Structure):
         ("region", C.c_char_p), ("include_bed", C.c_char_p), ("exclude_bed", C.c_char_p)]
 
 
+class VcfOptions(C.Structure):
+    """pgh_vcf_options: pindel2vcf's flags (pindel_amd/csrc/host/pg_vcf.hpp)"""
+    _fields_ = [(n, C.c_char_p) for n in ("reference", "reference_name", "reference_date", "report", "prefix", "vcf",
+                                          "chromosome")] + [
+        ("window_size", C.c_int32), ("min_coverage", C.c_int32), ("het_cutoff", C.c_double), ("hom_cutoff", C.c_double)] + [
+        (n, C.c_int32) for n in ("min_size", "max_size", "both_strands", "min_supporting_samples", "min_supporting_reads",
+                                 "max_supporting_reads", "region_start", "region_end", "max_internal_repeats",
+                                 "max_internal_repeatlength", "max_postindel_repeats", "max_postindel_repeatlength",
+                                 "compact_output_limit", "only_balanced_samples", "minimum_strand_support", "gatk_compatible")]
+
+
+# reports_to_vcf keyword -> (VcfOptions field, pindel2vcf flag)
+VCF_FLAGS = {
+    "chromosome": ("chromosome", "-c"), "window_size": ("window_size", "-w"), "min_coverage": ("min_coverage", "-mc"),
+    "het_cutoff": ("het_cutoff", "-he"), "hom_cutoff": ("hom_cutoff", "-ho"), "min_size": ("min_size", "-is"),
+    "max_size": ("max_size", "-as"), "both_strands_supported": ("both_strands", "-b"),
+    "min_supporting_samples": ("min_supporting_samples", "-m"), "min_supporting_reads": ("min_supporting_reads", "-e"),
+    "max_supporting_reads": ("max_supporting_reads", "-f"), "region_start": ("region_start", "-sr"),
+    "region_end": ("region_end", "-er"), "max_internal_repeats": ("max_internal_repeats", "-ir"),
+    "max_internal_repeatlength": ("max_internal_repeatlength", "-il"), "max_postindel_repeats": ("max_postindel_repeats", "-pr"),
+    "max_postindel_repeatlength": ("max_postindel_repeatlength", "-pl"), "compact_output_limit": ("compact_output_limit", "-co"),
+    "only_balanced_samples": ("only_balanced_samples", "-sb"), "minimum_strand_support": ("minimum_strand_support", "-ss"),
+    "gatk_compatible": ("gatk_compatible", "-G"),
+}
+
+
 def build(force=False):
     src_dir = os.path.join(_HERE, "csrc")
     host_dir = os.path.join(src_dir, "host")
@@ -47,6 +73,8 @@ def lib():
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pgh_region_plan.restype = C.c_int64
         L.pgh_region_plan.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64]
+        L.pgh_vcf_default_options.argtypes = [C.POINTER(VcfOptions)]
+        L.pgh_reports_to_vcf.argtypes = [C.POINTER(VcfOptions)]
         _lib = L
     return _lib
 
@@ -131,3 +159,40 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
                                 rc_flag.ctypes.data)
     if rc:
         raise RuntimeError("pgh_call_from_points: " + (L.pgh_last_error() or b"").decode())
+
+
+def vcf_cli():
+    """Path of the pindel_pg2vcf command line (built by `make all`; `make vcf` builds it alone)."""
+    exe = os.path.join(_HERE, "pindel_pg2vcf")
+    host_dir = os.path.join(_HERE, "csrc", "host")
+    srcs = [os.path.join(host_dir, f) for f in ("pindel_pg2vcf_main.cpp", "pg_vcf.cpp", "pg_vcf.hpp")]
+    if not os.path.exists(exe) or any(os.path.getmtime(s) > os.path.getmtime(exe) for s in srcs):
+        subprocess.check_call(["make", "-C", os.path.join(_HERE, "csrc"), "vcf"], stdout=subprocess.DEVNULL)
+    return exe
+
+
+def reports_to_vcf(fasta, out_vcf, prefix=None, report=None, *, reference_name, reference_date, **flags):
+    """pindel2vcf: Pindel reports -> out_vcf (pindel_amd/csrc/host/pg_vcf.hpp).  prefix reads <prefix>_D, _SI, _LI, _INV
+    and _TD (-P), report one file (-p); exactly one of them.  reference_name / reference_date are -R / -d.  flags are the
+    converter's other options by long name (VCF_FLAGS: window_size=1 is -w 1, gatk_compatible=True is -G, ...), with the
+    reference's defaults.  Raises ValueError for an unknown flag and RuntimeError when the conversion fails."""
+    L = lib()
+    o = VcfOptions()
+    L.pgh_vcf_default_options(C.byref(o))
+    keep = {"reference": _enc(fasta), "reference_name": _enc(reference_name), "reference_date": _enc(reference_date),
+            "report": _enc(report), "prefix": _enc(prefix), "vcf": _enc(out_vcf)}
+    for k, v in flags.items():
+        if k not in VCF_FLAGS:
+            raise ValueError(f"reports_to_vcf: unknown flag {k!r}")
+        field = VCF_FLAGS[k][0]
+        if field == "chromosome":
+            keep[field] = _enc(v)
+        elif field in ("het_cutoff", "hom_cutoff"):
+            setattr(o, field, float(v))
+        else:
+            setattr(o, field, int(v))
+    for field, v in keep.items():   # (alive until the call returns)
+        setattr(o, field, v)
+    if L.pgh_reports_to_vcf(C.byref(o)):
+        raise RuntimeError("pgh_reports_to_vcf: " + (L.pgh_last_error() or b"").decode())
+    return str(out_vcf)
