@@ -11,10 +11,15 @@ one-end-anchored reads on a chr20-shaped reference, all SV types, Pindel default
 Multi-GPU: reads shard by index, reference replicated per GPU, no collective on the data
 path (torch.distributed only for the barrier and the max-over-ranks time).
   --scaling weak    (default) every rank generates its own --reads reads
-  --scaling strong  ONE seeded batch of --reads reads, rank r searches shard.shard_bounds(...)[r]; rank 0
+  --scaling strong  ONE seeded batch of --reads reads, rank r searches shard.shard_bounds(...)[r]; with --full rank 0
                     gathers the per-read digests in rank order: config.result_sha256 must equal the N=1 value
 `python bench.py --gpus N` without a launcher re-executes itself under torch.distributed.run with N ranks.
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, the JSON line
+(metric, value, unit, ms_per_step, ... and config: the workload, the set-up's seconds, device_ms_per_step).  --full adds
+what is measured or checked after the timed region: the stages as launches of their own, run counts and candidates,
+config.result_sha256 (the strong-scaling check), the roofline, the host-buffer seam and the CPU baseline.
 """
 import argparse
 import json
@@ -341,17 +346,22 @@ def main():
     ap.add_argument("--chr-len", type=int, default=CHR20_LEN)
     ap.add_argument("--max-range-index", type=int, default=2, help="Pindel -x")
     ap.add_argument("--seed", type=int, default=20260927)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the PCIe-inclusive pg_search_batch sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need: the pack and the "
+                         "search as launches of their own, the accounting of the last step (run counts, candidates, "
+                         "config.result_sha256, roofline), the host-buffer seam and the CPU baseline.  Without it a run sets up, "
+                         "warms up, times the steps, dumps (--dump-outputs) and prints the headline fields and the set-up")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-host-path", action="store_true", help="--full: skip the PCIe-inclusive pg_search_batch sample")
     ap.add_argument("--no-standalone", action="store_true",
-                    help="skip the launches that time the pack and the search as kernels of their own after the timed region "
-                         "(config.pack_ms_standalone / search_ms_standalone / value_search_only): a traced run then holds the steps' launches only")
+                    help="--full: skip the launches that time the pack and the search as kernels of their own after the timed region "
+                         "(config.pack_ms_standalone / search_ms_standalone / value_search_only)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     ap.add_argument("--genome-scale", type=float, default=1.0, help="grch38-150: scale every chromosome (tests)")
     ap.add_argument("--workload", choices=["sv10m", "colo-bd", "grch38-150", "repeat-rich", "wgs-bins", "wgs-real"], default="sv10m",
                     help="sv10m = BASELINE configs[2] (default); colo-bd = configs[1]-shaped; grch38-150 = configs[3]-shaped "
                          "(one rank's 12.5 M x 150 bp on a 3.1 Gbp 24-chromosome reference); repeat-rich = configs[2] on a "
-                         "reference that is 45 % diverged repeat copies; wgs-bins = configs[4]-shaped: 150-bp reads in "
+                         "reference that is 45 %% diverged repeat copies; wgs-bins = configs[4]-shaped: 150-bp reads in "
                          "coordinate order on the GRCh38-shaped reference, searched 5-Mbp bin by bin (one launch per bin, "
                          "0.65 M reads per bin = 30x WGS with 400 M one-end-anchored reads), as main()'s loop does; wgs-real = the "
                          "read mix INTEGRATION.md expects of a real WGS run: three reads in four find no close end and walk all "
@@ -450,67 +460,48 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     if args.dump_outputs and rank == 0:
-        # downloaded before the standalone launches below run on the same device batches again
+        # downloaded before the standalone launches of --full run on the same device batches again
         dump_outputs(args.dump_outputs, [eng.download(h) for h in ([dbatch] if bins is None else bins)], args.seed)
+    units = total_reads if args.scaling == "strong" else world * args.reads
 
-    # ---- outside the timed region: accounting, result digests, the host-buffer seam, the CPU baseline
+    # ---- --full only, outside the timed region: accounting, result digests, the host-buffer seam, the CPU baseline
     # The pack (ASCII bases as src/reader.cpp:852-856 hands them over -> the bit planes + packed records the search reads) is
     # part of every timed step.  Bytes per read: len + 8 (offset) + 11 (strand, position, insert size, chromosome) in, 64 x
     # blocks (planes) + 128 (record + symbol programs) out (roofline.pack).
     # The two stages on their own, OUTSIDE the timed region (three launches each, HIP events): pg_pack_kernel as a launch of its
     # own and pg_search_kernel on records already packed -- the latter is what rounds 1-5 reported as `value`
     # (config.value_search_only), kept for comparison.
-    pack_ms = search_only_ms = None
-    if not args.no_standalone:
-        units_of_step = [dbatch] if bins is None else bins          # (wgs-bins: a launch per bin, as in the timed steps)
-        pack_ms = min(sum(eng.repack(h) for h in units_of_step) for _ in range(3))
-        search_only_ms = []
-        for _ in range(3):
-            ms = 0.0
-            for h in units_of_step:
-                eng.search_device(h)
-                ms += eng.last_stats()[0]
-            search_only_ms.append(ms)
-        search_only_ms = min(search_only_ms)
-    if bins is not None or not args.no_standalone:
-        eng.pack_search_device(dbatch)            # the step once more on the whole batch, for the accounting below
-    alg_bytes = eng.algorithmic_bytes(dbatch)     # per launch
-    n_cand = eng.candidates(dbatch)
-    res = eng.download(dbatch)
-    n_runs = int(res.close_off[-1]) + int(res.far_off[-1])
-    n_close = int((res.close_off[1:] > res.close_off[:-1]).sum())
-    n_far = int((res.far_off[1:] > res.far_off[:-1]).sum())
-    digests = shard.read_digests(res)
-    if dist is not None and args.scaling == "strong":
-        gathered = [None] * world if rank == 0 else None
-        dist.gather_object(digests, gathered, dst=0)
-        if rank == 0:
-            import numpy as np
-            digests = np.concatenate(gathered)      # rank order == input order
-    units = total_reads if args.scaling == "strong" else world * args.reads
+    if args.full:
+        pack_ms = search_only_ms = None
+        if not args.no_standalone:
+            units_of_step = [dbatch] if bins is None else bins          # (wgs-bins: a launch per bin, as in the timed steps)
+            pack_ms = min(sum(eng.repack(h) for h in units_of_step) for _ in range(3))
+            search_only_ms = []
+            for _ in range(3):
+                ms = 0.0
+                for h in units_of_step:
+                    eng.search_device(h)
+                    ms += eng.last_stats()[0]
+                search_only_ms.append(ms)
+            search_only_ms = min(search_only_ms)
+        if bins is not None or not args.no_standalone:
+            eng.pack_search_device(dbatch)            # the step once more on the whole batch, for the accounting below
+        alg_bytes = eng.algorithmic_bytes(dbatch)     # per launch
+        n_cand = eng.candidates(dbatch)
+        res = eng.download(dbatch)
+        n_runs = int(res.close_off[-1]) + int(res.far_off[-1])
+        n_close = int((res.close_off[1:] > res.close_off[:-1]).sum())
+        n_far = int((res.far_off[1:] > res.far_off[:-1]).sum())
+        digests = shard.read_digests(res)
+        if dist is not None and args.scaling == "strong":
+            gathered = [None] * world if rank == 0 else None
+            dist.gather_object(digests, gathered, dst=0)
+            if rank == 0:
+                import numpy as np
+                digests = np.concatenate(gathered)      # rank order == input order
 
     if rank == 0:
         avg_ms = sum(kernel_ms) / max(len(kernel_ms), 1)
-        achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        traffic, traffic_src = measured_traffic(args, batch.n)
-        host_path = None
-        if world == 1 and not args.no_host_path:
-            # the seam a Pindel maintainer calls: host buffers in, host CSR out (PCIe both ways) -- never `value`
-            import ctypes as C
-            nb = min(batch.n, 4_000_000)
-            st, keep = binding._batch_struct(batch.slice(0, nb))
-            L = binding.lib()
-            best_t = None
-            for _ in range(5):                        # the first calls pin the result buffers / grow the device arena
-                h = C.c_void_p()
-                th = time.perf_counter()
-                rc = L.pg_search_batch(eng._h, C.byref(st), C.byref(h))
-                dt = time.perf_counter() - th
-                if rc:
-                    raise SystemExit(f"pg_search_batch failed: {rc}")
-                L.pg_result_free(h)
-                best_t = dt if best_t is None else min(best_t, dt)
-            host_path = nb / best_t
         out = {
             "metric": "one-end-anchored reads/sec through split-read search (close end + far end)",
             "value": units * args.steps / elapsed,
@@ -529,11 +520,6 @@ def main():
                 "reads_per_gpu": batch.n, "reads_total": units, "read_len": args.read_len, "insert_size": 500,
                 "parallelism": f"reads sharded over {world} GPU(s) ({args.scaling} scaling), reference replicated, no collective",
                 "launches_per_step": 1 if bins is None else len(bins),
-                "reads_with_close_end": n_close, "reads_with_far_end": n_far, "runs_out": int(n_runs),
-                "candidates_per_read": n_cand / max(batch.n, 1),    # seed-filter survivors that went through the full comparison
-                "result_sha256": shard.digest_hex(digests),
-                "host_path_reads_per_s": host_path,
-                # `value` covers pack + search; the search alone (rounds 1-5's `value`: inputs already packed) for comparison
                 "step": ("pack + search on raw inputs resident in HBM (pg_device_batch_pack_search): " +
                          ("ONE launch, pg_search_kernel packs the reads of each claim before it searches them" if in_place and all(in_place)
                           else "pg_pack_kernel + pg_search_kernel" if not any(in_place)
@@ -541,12 +527,41 @@ def main():
                 "setup_seconds": {"synthetic_inputs": t_setup[1] - t_setup[0], "reference_to_hbm": t_setup[2] - t_setup[1],
                                   "reads_to_hbm": t_setup[3] - t_setup[2]},
                 "device_ms_per_step": avg_ms,
+            },
+        }
+        if args.full:
+            achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            traffic, traffic_src = measured_traffic(args, batch.n)
+            host_path = None
+            if world == 1 and not args.no_host_path:
+                # the seam a Pindel maintainer calls: host buffers in, host CSR out (PCIe both ways) -- never `value`
+                import ctypes as C
+                nb = min(batch.n, 4_000_000)
+                st, keep = binding._batch_struct(batch.slice(0, nb))
+                L = binding.lib()
+                best_t = None
+                for _ in range(5):                        # the first calls pin the result buffers / grow the device arena
+                    h = C.c_void_p()
+                    th = time.perf_counter()
+                    rc = L.pg_search_batch(eng._h, C.byref(st), C.byref(h))
+                    dt = time.perf_counter() - th
+                    if rc:
+                        raise SystemExit(f"pg_search_batch failed: {rc}")
+                    L.pg_result_free(h)
+                    best_t = dt if best_t is None else min(best_t, dt)
+                host_path = nb / best_t
+            out["config"].update({
+                "reads_with_close_end": n_close, "reads_with_far_end": n_far, "runs_out": int(n_runs),
+                "candidates_per_read": n_cand / max(batch.n, 1),    # seed-filter survivors that went through the full comparison
+                "result_sha256": shard.digest_hex(digests),
+                "host_path_reads_per_s": host_path,
+                # `value` covers pack + search; the search alone (rounds 1-5's `value`: inputs already packed) for comparison --
                 # outside the timed region, three launches each: the stages as launches of their own
                 "pack_ms_standalone": pack_ms,
                 "search_ms_standalone": search_only_ms,
                 "value_search_only": batch.n * world / (search_only_ms * 1e-3) if search_only_ms else None,
-            },
-            "roofline": {
+            })
+            out["roofline"] = {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                 # what the memory system actually moved per second (counter traffic / kernel time) and how much of it the
@@ -565,10 +580,9 @@ def main():
                 "actual_bound": "instruction issue (VALU + scalar), see DESIGN.md section 4",
                 "issue": issue_model(args, avg_ms, batch.n),
                 "pack": pack_roofline(batch, pack_ms) if pack_ms else None,
-            },
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(chroms, batch, params_kw, bd=bd, bd_off=bd_off)
+            }
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(chroms, batch, params_kw, bd=bd, bd_off=bd_off)
         print(json.dumps(out), flush=True)
     for h in bins or []:
         eng.free_device_batch(h)

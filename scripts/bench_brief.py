@@ -1,10 +1,10 @@
 #!/usr/bin/env python
-"""Run bench.py with the given args and print a one-line summary (dev helper)."""
+"""Run bench.py --full with the given args and print a one-line summary (dev helper)."""
 import json
 import subprocess
 import sys
 
-out = subprocess.run([sys.executable, "bench.py"] + sys.argv[1:], capture_output=True, text=True)
+out = subprocess.run([sys.executable, "bench.py", "--full"] + sys.argv[1:], capture_output=True, text=True)
 line = [l for l in out.stdout.splitlines() if l.startswith("{")]
 if not line:
     print(out.stdout[-2000:], out.stderr[-2000:])

@@ -35,8 +35,8 @@ print(f"same run, 10 M reads, a step = ONE launch (pg_search_kernel packs its cl
       f"(pg_pack_kernel launches in the run: {pcalls} = the upload's) | HIP-event device_ms_per_step {ev:.3f} | wall ms_per_step {d['ms_per_step']:.3f} | "
       f"value {d['value'] / 1e6:.1f} M reads/s | spread of the three step times {100 * (max(ev, avg, d['ms_per_step']) / min(ev, avg, d['ms_per_step']) - 1):.2f} %")
 PY
-# ... and the judged command as the driver runs it (no tracer; with the stages as launches of their own measured after the timed region)
-python "$root/bench.py" --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > "$out/bench_default.json"
+# ... and the judged command untraced with --full (the stages as launches of their own, measured after the timed region)
+python "$root/bench.py" --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > "$out/bench_default.json"
 python - "$out/bench_default.json" <<'PY' | tee -a "$out/reconciliation.txt"
 import json, sys
 d = json.loads(open(sys.argv[1]).read())
@@ -68,7 +68,7 @@ pmc_set "$out/pmc_sq_wgsreal.txt" PG_LEN=150 PG_SORT=1 PG_MIX=0.02,0.01,0.01,0.0
 # 3. HBM traffic of the search kernel: FETCH_SIZE / WRITE_SIZE in passes of their own + the calibration stream
 rm -rf /tmp/rp_fetch /tmp/rp_write /tmp/rp_calib /tmp/rp_stats
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_stats -- \
-    python "$root/bench.py" --reads "$reads" --steps 3 --warmup 1 --no-cpu-baseline --no-host-path > "$out/bench_under_rocprof.json" 2> /tmp/rp_stats.err
+    python "$root/bench.py" --reads "$reads" --steps 3 --warmup 1 --full --no-cpu-baseline --no-host-path > "$out/bench_under_rocprof.json" 2> /tmp/rp_stats.err
 f=$(find /tmp/rp_stats -name '*kernel_stats.csv' | head -1)
 [ -n "$f" ] && head -8 "$f" > "$out/kernel_stats.csv"
 PG_STEP=1 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/rp_fetch -- python "$root/scripts/run_variant.py" "$LIBSO" "$reads" > /tmp/rp_fetch.log 2>&1
@@ -83,7 +83,7 @@ for v in "x5 --max-range-index 5" "150bp --read-len 150"; do
     tag2=$1; shift
     rm -rf /tmp/rp_stats2
     rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_stats2 -- \
-        python "$root/bench.py" --reads "$reads" --steps 3 --warmup 1 --no-cpu-baseline --no-host-path "$@" > "$out/bench_under_rocprof_$tag2.json" 2> /tmp/rp_stats2.err
+        python "$root/bench.py" --reads "$reads" --steps 3 --warmup 1 --full --no-cpu-baseline --no-host-path "$@" > "$out/bench_under_rocprof_$tag2.json" 2> /tmp/rp_stats2.err
     f=$(find /tmp/rp_stats2 -name '*kernel_stats.csv' | head -1)
     [ -n "$f" ] && head -8 "$f" > "$out/kernel_stats_$tag2.csv"
 done
@@ -95,12 +95,12 @@ PG_LEN=150 python scripts/pack_rate.py pindel_amd/libpindel_pg.so 10000000 2>/de
 cat "$out/pack_rate.txt"
 {
     for w in colo-bd repeat-rich wgs-bins grch38-150 wgs-real; do
-        python bench.py --workload $w --steps 3 --warmup 1 --no-cpu-baseline --no-host-path 2>/dev/null | tail -1
+        python bench.py --workload $w --steps 3 --warmup 1 --full --no-cpu-baseline --no-host-path 2>/dev/null | tail -1
     done
-    python bench.py --steps 3 --warmup 1 --max-range-index 5 --reads 2000000 --no-cpu-baseline --no-host-path 2>/dev/null | tail -1
-    python bench.py --steps 3 --warmup 1 --read-len 150 --no-cpu-baseline --no-host-path 2>/dev/null | tail -1
-    python bench.py --steps 3 --warmup 1 --read-len 250 --reads 4000000 --no-cpu-baseline --no-host-path 2>/dev/null | tail -1
-    python bench.py --steps 3 --warmup 1 --read-len 400 --reads 2000000 --no-cpu-baseline --no-host-path 2>/dev/null | tail -1
+    python bench.py --steps 3 --warmup 1 --max-range-index 5 --reads 2000000 --full --no-cpu-baseline --no-host-path 2>/dev/null | tail -1
+    python bench.py --steps 3 --warmup 1 --read-len 150 --full --no-cpu-baseline --no-host-path 2>/dev/null | tail -1
+    python bench.py --steps 3 --warmup 1 --read-len 250 --reads 4000000 --full --no-cpu-baseline --no-host-path 2>/dev/null | tail -1
+    python bench.py --steps 3 --warmup 1 --read-len 400 --reads 2000000 --full --no-cpu-baseline --no-host-path 2>/dev/null | tail -1
 } > "$out/bench_workloads.jsonl"
 python - "$out/bench_workloads.jsonl" <<'PY'
 import json, sys

@@ -5,7 +5,8 @@ torch.distributed, shards the ONE seeded batch (--scaling strong), and rank 0 ga
 order: config.result_sha256 must not depend on N.  A 1-GPU box cannot give two ranks a GPU each, so
 PG_BENCH_SHARE_GPU=1 lets both ranks use device 0 (gloo for the rendezvous, the data path is unchanged: there is no
 collective on it).  PG_BENCH_FORCE_DIST=1 runs the N = 1 line through the RCCL path the 8-GPU run takes:
-init_process_group(backend="nccl", device_id=...), barrier, all_reduce(MAX) of the step time."""
+init_process_group(backend="nccl", device_id=...), barrier, all_reduce(MAX) of the step time.  The digests, the roofline and
+the stages as launches of their own are --full's: a plain run prints the headline figure and its set-up only."""
 import json
 import os
 import socket
@@ -16,7 +17,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--scaling", "strong", "--reads", "400000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-host-path"]
+COMMON = ["--scaling", "strong", "--reads", "400000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-host-path"]
 
 
 def _run(cmd, **env):
@@ -116,7 +117,7 @@ def test_dump_outputs_are_the_steps_result_and_reproducible(one_gpu_line, one_gp
     # --dump-outputs: float arrays of the last timed step's result, the same from run to run; --steps sets the timed steps
     import numpy as np
     again = _run([sys.executable, "bench.py", "--gpus", "1", "--scaling", "strong", "--reads", "400000", "--steps", "3", "--warmup", "0",
-                  "--no-cpu-baseline", "--no-host-path", "--dump-outputs", str(tmp_path)])
+                  "--full", "--no-cpu-baseline", "--no-host-path", "--dump-outputs", str(tmp_path)])
     assert one_gpu_line["steps"] == 2 and again["steps"] == 3 and again["ms_per_step"] > 0
     assert again["config"]["result_sha256"] == one_gpu_line["config"]["result_sha256"]
     names = sorted(os.listdir(one_gpu_dump))
@@ -130,3 +131,23 @@ def test_dump_outputs_are_the_steps_result_and_reproducible(one_gpu_line, one_gp
     assert len(reads) == 262144 and reads[-1] < 400000 and (np.diff(reads) > 0).all()
     assert a["close_count.npy"].sum() == len(a["close_abs_loc_first.npy"]) > 0
     assert a["far_count.npy"].sum() == len(a["far_abs_loc_first.npy"]) > 0
+
+
+def test_a_plain_run_is_the_headline_only(one_gpu_line, one_gpu_dump, tmp_path):
+    # without --full: set-up, warm-up, the timed steps, the dump and the headline fields -- nothing measured or checked after
+    # the timed region -- and the same result as the --full run's last step
+    import numpy as np
+    plain = _run([sys.executable, "bench.py", "--gpus", "1", "--scaling", "strong", "--reads", "400000", "--steps", "2", "--warmup", "1",
+                  "--dump-outputs", str(tmp_path)])
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling", "data"):
+        assert plain[k] == one_gpu_line[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert "roofline" not in plain and "cpu_baseline" not in plain
+    c = plain["config"]
+    assert c["reads_total"] == 400000 and c["device_ms_per_step"] > 0 and plain["ms_per_step"] >= c["device_ms_per_step"] * 0.98
+    for k in ("result_sha256", "candidates_per_read", "host_path_reads_per_s", "pack_ms_standalone", "search_ms_standalone"):
+        assert k not in c and k in one_gpu_line["config"], k
+    names = sorted(os.listdir(one_gpu_dump))
+    assert sorted(os.listdir(tmp_path)) == names
+    for f in names:
+        np.testing.assert_array_equal(np.load(os.path.join(tmp_path, f)), np.load(os.path.join(one_gpu_dump, f)), err_msg=f)

@@ -32,7 +32,7 @@ def test_bench_workload_properties(engine_factory):
     eng.load_reference(chroms)
     n_close, n_far = check_workload(eng, chroms, batch)
     assert n_close > 0.7 * N_READS and n_far > 0.5 * N_READS
-    # The workload is seeded: the checksum of checksums bench.py prints as config.result_sha256 (one 64-bit digest per
+    # The workload is seeded: the checksum of checksums bench.py --full prints as config.result_sha256 (one 64-bit digest per
     # read over its rc flag and run lists, sha256 over the digests) is a constant of the repository.  It has been
     # ec6c3a18... since the round-1 kernel; a kernel change that alters ANY read's result alters it.
     from pindel_amd import shard
