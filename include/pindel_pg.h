@@ -233,6 +233,14 @@ int  pg_device_batch_algorithmic_bytes(pg_ctx *ctx, pg_device_batch *b, double *
  * comparison in the last search of this batch -- what a repeat-rich reference drives up. */
 int  pg_device_batch_candidates(pg_ctx *ctx, pg_device_batch *b, double *n_candidates);
 
+/* -q (dispersed duplications): per item i, contains_subseq_any_strand(query_i, window_i, 15) of Pindel's MEI search
+ * (src/search_MEI_util.cpp:188-351, bit-exact), where query_i = query[query_off[i] .. query_off[i+1]) (at most
+ * PG_MAX_READ_LEN bases) and window_i = the loaded chromosome chr_id[i] at padded (AbsLoc) positions
+ * [win_start[i], win_start[i] + win_len[i]), read from the planes on the device.  out[i] = 0 / 1.  Synchronous;
+ * pg_last_search_stats then reports the kernel's HIP-event time. */
+int  pg_dd_contains_batch(pg_ctx *ctx, uint32_t n, const uint8_t *query, const uint64_t *query_off, const int32_t *chr_id,
+                          const uint64_t *win_start, const uint32_t *win_len, uint8_t *out);
+
 #ifdef __cplusplus
 }
 #endif

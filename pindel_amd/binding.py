@@ -73,7 +73,7 @@ EXPORTS = [
     "pg_search_batch", "pg_search_batch_multi", "pg_result_view_get", "pg_result_free", "pg_expand_runs",
     "pg_device_batch_upload", "pg_device_batch_set_windows", "pg_device_batch_search", "pg_device_batch_download",
     "pg_device_batch_free", "pg_last_search_stats", "pg_device_batch_algorithmic_bytes",
-    "pg_device_batch_candidates", "pg_device_batch_repack", "pg_device_batch_pack_search"]
+    "pg_device_batch_candidates", "pg_device_batch_repack", "pg_device_batch_pack_search", "pg_dd_contains_batch"]
 
 
 def build(force: bool = False) -> str:
@@ -127,6 +127,7 @@ def lib():
     L.pg_get_max_mismatch.argtypes = [vp, vp]
     L.pg_load_reference.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(u64)]
     L.pg_load_fasta.argtypes = [vp, C.c_char_p]
+    L.pg_dd_contains_batch.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
     L.pg_reference_save_packed.argtypes = [vp, C.c_char_p]
     L.pg_reference_load_packed.argtypes = [vp, C.c_char_p]
     L.pg_reference_n_chr.argtypes = [vp]
@@ -301,6 +302,24 @@ class Engine:
         out = np.zeros(n, dtype=np.uint8)
         self._check(self._L.pg_reference_fetch(self._h, chr_id, start, n, out.ctypes.data))
         return out.tobytes()
+
+    def dd_contains(self, queries, chr_id, win_start, win_len):
+        """-q's containment test (pg_dd_contains_batch): per item, contains_subseq_any_strand(queries[i], the loaded chromosome
+        chr_id[i] at padded positions [win_start[i], win_start[i] + win_len[i]), 15).  Returns (uint8 array, kernel ms)."""
+        n = len(queries)
+        qb = [bytes(q) if not isinstance(q, str) else q.encode() for q in queries]
+        q = np.frombuffer(b"".join(qb) or b"\0", dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(x) for x in qb]) if n else []
+        cid = np.ascontiguousarray(chr_id, dtype=np.int32)
+        ws = np.ascontiguousarray(win_start, dtype=np.uint64)
+        wl = np.ascontiguousarray(win_len, dtype=np.uint32)
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        self._check(self._L.pg_dd_contains_batch(self._h, n, q.ctypes.data, off.ctypes.data, cid.ctypes.data, ws.ctypes.data,
+                                                 wl.ctypes.data, out.ctypes.data))
+        ms = C.c_double()
+        self._L.pg_last_search_stats(self._h, C.byref(ms), None)
+        return out[:n], ms.value
 
     # ---- host in / host out
     def close_end_batch(self, batch) -> Result:

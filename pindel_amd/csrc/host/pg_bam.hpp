@@ -205,6 +205,40 @@ struct BamRecord {
         }
         return pos + (l ? l : 1);
     }
+    // a Z-typed aux field (bam_aux_get + bam_aux2Z); "" when absent or of another type
+    std::string aux_str(const char *tag) const
+    {
+        size_t i = 0;
+        const size_t n = aux.size();
+        while (i + 3 <= n) {
+            const char t0 = (char)aux[i], t1 = (char)aux[i + 1], ty = (char)aux[i + 2];
+            i += 3;
+            size_t sz = 0;
+            switch (ty) {
+            case 'A': case 'c': case 'C': sz = 1; break;
+            case 's': case 'S': sz = 2; break;
+            case 'i': case 'I': case 'f': sz = 4; break;
+            case 'd': sz = 8; break;
+            case 'Z': case 'H': {
+                size_t e = i;
+                while (e < n && aux[e]) e++;
+                if (t0 == tag[0] && t1 == tag[1] && ty == 'Z') return std::string((const char *)aux.data() + i, e - i);
+                i = e + 1;
+                continue;
+            }
+            case 'B': {
+                if (i + 5 > n) return "";
+                const char st = (char)aux[i];
+                const uint32_t cnt = aux[i + 1] | (aux[i + 2] << 8) | (aux[i + 3] << 16) | ((uint32_t)aux[i + 4] << 24);
+                i += 5 + ((st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4) * (size_t)cnt;
+                continue;
+            }
+            default: return "";
+            }
+            i += sz;
+        }
+        return "";
+    }
     // integer value of an aux tag (types cCsSiI); false if absent or not an integer
     bool aux_int(const char *tag, int64_t &v) const
     {
@@ -253,6 +287,7 @@ struct BamRecord {
 };
 
 struct BamHeader {
+    std::string text;                 // the SAM header text (@RG lines: -q's sample names)
     std::vector<std::string> names;
     std::vector<uint32_t> lengths;
     int id_of(const std::string &name) const
@@ -281,6 +316,7 @@ public:
         std::string text((size_t)l_text, ' ');
         if (l_text && !z_.read(&text[0], (size_t)l_text)) return bad(err);
         if (!z_.read(&n_ref, 4) || n_ref < 0) return bad(err);
+        hdr_.text = text.c_str();
         for (int i = 0; i < n_ref; i++) {
             int32_t l_name = 0;
             uint32_t l_ref = 0;
@@ -539,6 +575,7 @@ struct BamIngestSettings {
     unsigned spacer = 100000;
     int nm = 2;                        // -n  NM (isRefRead)
     double max_mismatch_rate = 0.02;   // -u  MaximumAllowedMismatchRate (isRefRead)
+    bool read_groups = false;          // keep the RG of each read's anchor (SPLIT_READ::read_group, reader.cpp:822; -q's sample names)
 };
 
 // A read that supports the reference allele (REF_READ, pindel.h:199-212): what UpdateRefReadCoverage needs of it
@@ -554,6 +591,7 @@ struct IngestedReads {
     std::vector<std::string> names;    // "@qname/1"
     std::vector<int16_t> ms;           // mapping quality of the anchor
     std::vector<std::string> tags;     // sample tag of the BAM
+    std::vector<std::string> read_groups;  // RG of the anchor (BamIngestSettings::read_groups; empty otherwise)
     std::vector<RefRead> ref_reads;    // RefSupportingReads of the window
     std::vector<std::string> ref_tags; // their sample tags (RefRead::tag indexes this)
     size_t size() const { return names.size(); }
@@ -564,6 +602,7 @@ struct IngestedReads {
         names.clear();
         ms.clear();
         tags.clear();
+        read_groups.clear();
         ref_reads.clear();
         ref_tags.clear();
     }
@@ -739,6 +778,7 @@ public:
             out.names.resize(base + M);
             out.ms.resize(base + M);
             out.tags.resize(base + M);
+            if (S.read_groups) out.read_groups.resize(base + M);
             out.batch.strand.resize(base + M);
             out.batch.pos.resize(base + M);
             out.batch.isz.resize(base + M);
@@ -758,6 +798,7 @@ public:
                         out.names[base + g].swap(e.out.names[k]);
                         out.ms[base + g] = e.out.ms[k];
                         out.tags[base + g].swap(e.out.tags[k]);
+                        if (S.read_groups) out.read_groups[base + g].swap(e.out.read_groups[k]);
                         out.batch.strand[base + g] = e.out.batch.strand[k];
                         out.batch.pos[base + g] = e.out.batch.pos[k];
                         out.batch.isz[base + g] = e.out.batch.isz[k];
@@ -920,6 +961,7 @@ private:
         out.names.push_back(name);
         out.ms.push_back((int16_t)mapped.mapq);
         out.tags.push_back(tag);
+        if (S.read_groups) out.read_groups.push_back(mapped.aux_str("RG"));   // get_read_group(mapped_read, ...)
         return true;
     }
 };

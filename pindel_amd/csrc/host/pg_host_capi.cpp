@@ -6,10 +6,12 @@
 #include <fstream>
 #include <sstream>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "pg_bam.hpp"
 #include "pg_bdhints.hpp"
+#include "pg_dd.hpp"
 #include "pg_host.hpp"
 #include "pg_host_priv.hpp"
 #include "pg_pipeline.hpp"
@@ -403,6 +405,116 @@ void pgh_test_exchange_sort(const int32_t *keys, uint32_t n, uint32_t *out_refer
         out_reference[i] = a[i];
         out_fast[i] = b[i];
     }
+}
+
+// -q's containment test on the host (src/search_MEI_util.cpp:188-351): out[i] = contains_subseq_any_strand(query_i, db_i, 15) with
+// query_i = q[q_off[i] .. q_off[i+1]), db_i = db[db_off[i] .. db_off[i+1]) and g_maxMismatch = mm500; items on up to n_threads threads.
+int pgh_dd_contains_cpu(uint32_t n, const uint8_t *q, const uint64_t *q_off, const uint8_t *db, const uint64_t *db_off, const uint32_t *mm500,
+                        uint8_t *out, int n_threads)
+{
+    const unsigned nt = (unsigned)std::max(1, std::min(n_threads > 0 ? n_threads : 1, 64));
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < nt; t++)
+        th.emplace_back([=]() {
+            for (uint32_t i = t; i < n; i += nt) {
+                const std::string query((const char *)q + q_off[i], (size_t)(q_off[i + 1] - q_off[i]));
+                out[i] = dd_contains_any_strand(query, (const char *)db + db_off[i], (size_t)(db_off[i + 1] - db_off[i]), mm500) ? 1 : 0;
+            }
+        });
+    for (std::thread &x : th) x.join();
+    return 0;
+}
+
+// The close end of one batch for pgh_dd_run, supplied by the caller: per read has / rc_flag / UP_Close.back() AbsLoc, LengthStr.
+typedef int (*pgh_dd_close_cb)(uint32_t n, const uint8_t *seq, const uint64_t *off, const uint8_t *strand, const int32_t *pos,
+                               const int16_t *isz, const int32_t *chr, uint8_t *has, uint8_t *rc_flag, uint32_t *last_abs,
+                               uint16_t *last_len);
+
+// The -q pipeline (pg_dd.hpp) of `pindel_pg -f fasta -i config -o prefix -q [flags]` with the close ends from `close_cb` (null: no read
+// has one) and the containment test on the host.  opts: MAX_DD_BREAKPOINT_DISTANCE, MAX_DISTANCE_CLUSTER_READS, MIN_DD_CLUSTER_SIZE,
+// MIN_DD_BREAKPOINT_SUPPORT, MIN_DD_MAP_DISTANCE, DD_REPORT_DUPLICATION_READS, -A, -n; mm_rate = -u; region / include_bed /
+// exclude_bed (nullable) = -c / -j / -J.  The configuration file, the region plan and the read selection are the command line's own
+// (read_bam_config, region_plan, BamIngestSettings).  stats6 (nullable): discordant reads, clusters, breakpoints, containment tests,
+// breakpoints kept by them, events; bp5 (nullable, cap breakpoints): tid, pos, strand, #reads, #split reads per breakpoint; tested
+// (nullable, tested_cap bytes): per containment test a line "tid pos strand #split-reads consensus contained" (tab-separated).
+// Returns the number of breakpoints, or -1 (pgh_last_error).
+int64_t pgh_dd_run(const char *fasta, const char *bam_config, const char *prefix, const int32_t *opts, double mm_rate, const char *region,
+                   const char *include_bed, const char *exclude_bed, double window_mbp, uint32_t spacer, const uint32_t *mm500,
+                   pgh_dd_close_cb close_cb, uint64_t *stats6, int32_t *bp5, uint64_t cap, char *tested, uint64_t tested_cap)
+{
+    std::string err;
+    std::vector<Chromosome> genome;
+    if (load_fasta(fasta, genome, spacer, err)) {
+        g_err = err;
+        return -1;
+    }
+    std::vector<BamSource> bams;
+    if (!read_bam_config(bam_config, bams, err)) {
+        g_err = err;
+        return -1;
+    }
+    const std::vector<unsigned> sizes = chromosome_sizes(genome, read_fai(fasta, genome), spacer);
+    std::vector<RegionRecord> plan;
+    if (region_plan(chromosome_names(genome), sizes, region ? region : "", include_bed ? include_bed : "", exclude_bed ? exclude_bed : "",
+                    plan, err)) {
+        g_err = err;
+        return -1;
+    }
+    BamIngestSettings ing;
+    ing.min_anchor_quality = (unsigned)opts[6];
+    ing.spacer = spacer;
+    ing.nm = opts[7];
+    ing.max_mismatch_rate = mm_rate;
+    DDSettings dd;
+    dd.max_bp_distance = opts[0];
+    dd.max_distance_cluster = opts[1];
+    dd.min_cluster_size = opts[2];
+    dd.min_bp_support = opts[3];
+    dd.min_map_distance = opts[4];
+    dd.report_dup_reads = opts[5] != 0;
+    std::vector<uint32_t> mm(mm500, mm500 + 500);
+    auto close_fn = [&](int, const pg_adapter::Batch &b, std::vector<DDClose> &out) {
+        const size_t n = b.strand.size();
+        out.assign(n, DDClose());
+        if (!close_cb || !n) return 0;
+        std::vector<uint8_t> has(n), rcf(n);
+        std::vector<uint32_t> la(n);
+        std::vector<uint16_t> ll(n);
+        const int rc = close_cb((uint32_t)n, b.seq.data(), b.off.data(), b.strand.data(), b.pos.data(), b.isz.data(), b.chr.data(), has.data(),
+                                rcf.data(), la.data(), ll.data());
+        for (size_t i = 0; i < n; i++) {
+            out[i].has = has[i];
+            out[i].rc_flag = rcf[i];
+            out[i].last_abs = la[i];
+            out[i].last_len = ll[i];
+        }
+        return rc;
+    };
+    auto contains_fn = [&](const std::vector<std::string> &q, const std::vector<int32_t> &chr, const std::vector<uint64_t> &st,
+                           const std::vector<uint32_t> &len, std::vector<uint8_t> &found) {
+        found.assign(q.size(), 0);
+        for (size_t i = 0; i < q.size(); i++)
+            found[i] = dd_contains_any_strand(q[i], genome[(size_t)chr[i]].seq.data() + st[i], len[i], mm.data()) ? 1 : 0;
+        return 0;
+    };
+    DDStats stats;
+    if (run_dd(genome, sizes, plan, bams, ing, window_mbp, dd, prefix, close_fn, contains_fn, err, &stats)) {
+        g_err = err;
+        return -1;
+    }
+    if (stats6) {
+        const size_t v[6] = { stats.discordant, stats.clusters, stats.breakpoints, stats.candidates, stats.kept_by_containment, stats.events };
+        for (int k = 0; k < 6; k++) stats6[k] = v[k];
+    }
+    const size_t n_bp = stats.bp_list.size() / 5;
+    if (bp5)
+        for (size_t k = 0; k < std::min<size_t>(n_bp, cap) * 5; k++) bp5[k] = stats.bp_list[k];
+    if (tested && tested_cap) {
+        const size_t m = std::min<size_t>(stats.tested.size(), tested_cap - 1);
+        memcpy(tested, stats.tested.data(), m);
+        tested[m] = 0;
+    }
+    return (int64_t)n_bp;
 }
 
 }  // extern "C"

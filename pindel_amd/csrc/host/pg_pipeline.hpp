@@ -212,6 +212,30 @@ struct BamSource {
     int insert_size = 0;
 };
 
+// -i: one line per BAM: file, insert size, sample tag (readBamConfigFile, src/pindel.cpp); a relative file name is relative to
+// the configuration file.  false: the file cannot be read or lists no BAM (err says which).
+inline bool read_bam_config(const std::string &config, std::vector<BamSource> &bams, std::string &err)
+{
+    std::ifstream cf(config.c_str());
+    if (!cf) {
+        err = "cannot open " + config;
+        return false;
+    }
+    BamSource b;
+    while (cf >> b.path >> b.insert_size >> b.tag) {
+        if (b.path[0] != '/') {
+            const size_t sl = config.rfind('/');
+            if (sl != std::string::npos) b.path = config.substr(0, sl + 1) + b.path;
+        }
+        bams.push_back(b);
+    }
+    if (bams.empty()) {
+        err = "no BAM files in " + config;
+        return false;
+    }
+    return true;
+}
+
 // The close end of one window of the BAM path, straight on the ingested structure-of-arrays batch (no SplitRead per
 // candidate): what comes back per contiguous part of the batch (one part per device).
 struct ClosePart {

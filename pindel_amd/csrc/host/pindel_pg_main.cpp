@@ -5,7 +5,8 @@
 // FASTA + Pindel-text reads -> close/far-end search on the MI355X (C ABI, libpindel_pg.so)
 // -> SV classification and <prefix>_D/_SI/_TD/_INV reports (host code in this directory);
 // -l adds <prefix>_LI (long insertions), -s <prefix>_CloseEndMapped (the reads with a close end),
-// -S writes <prefix>_CloseEndMapped only (no far end, no SV search).  Like the reference, every run
+// -S writes <prefix>_CloseEndMapped only (no far end, no SV search); -q adds <prefix>_DD (dispersed duplications, BAM input,
+// pg_dd.hpp).  Like the reference, every run
 // creates all seven files (_D _SI _TD _INV _LI _BP _CloseEndMapped); _BP stays empty, as the
 // reference's breakpoint report is not called.  -c, -j and -J select the regions searched (pg_region.hpp); they are
 // checked before the first device call (exit status 2 for -c syntax, 1 for an unreadable file or an unknown chromosome).
@@ -25,6 +26,7 @@
 
 #include "pg_adapter.hpp"
 #include "pg_bdhints.hpp"
+#include "pg_dd.hpp"
 #include "pg_host.hpp"
 #include "pg_pipeline.hpp"
 #include "pg_region.hpp"
@@ -48,12 +50,14 @@ int main(int argc, char **argv)
     bool search_rp = true;                 // -R: discordant read pairs as window hints (BAM input only; default true)
     bool use_bd = false;
     size_t flush_reads = 0;                // --flush-reads: reads per close-end call (0 = a whole bin)
+    bool detect_dd = false;               // -q: set by the flag whatever its word (the reference tests isSet(), pindel.cpp:1992)
+    DDSettings dd;
     pg_params prm;
     pg_default_params(&prm);
     Settings S;
     // Flags as src/fn_parameters.cpp defines them: value flags need an argument that does not start with
     // '-'; unary switches take an optional true/false word (readParameters, fn_parameters.cpp:366-406).
-    // The switches -k (beyond the empty _BP file), -I, -q and -C select searches and reports this program does not
+    // The switches -k (beyond the empty _BP file), -I and -C select searches and reports this program does not
     // run; they are accepted and ignored; anything else is an error, and so is a value that is not a number.
     struct Flag { const char *sh, *lg; char kind; };      // kind: i int, f float, s string, u unary
     static const Flag flags[] = {
@@ -72,6 +76,8 @@ int main(int argc, char **argv)
         { "-s", "--report_close_mapped_reads", 'u' }, { "-S", "--report_only_close_mapped_reads", 'u' },
         { "-I", "--report_interchromosomal_events", 'u' }, { "-C", "--IndelCorrection", 'u' },
         { "-N", "--NormalSamples", 'u' }, { "-R", "--RP", 'u' }, { "-q", "--detect_DD", 'u' },
+        { "", "--MAX_DD_BREAKPOINT_DISTANCE", 'i' }, { "", "--MAX_DISTANCE_CLUSTER_READS", 'i' }, { "", "--MIN_DD_CLUSTER_SIZE", 'i' },
+        { "", "--MIN_DD_BREAKPOINT_SUPPORT", 'i' }, { "", "--MIN_DD_MAP_DISTANCE", 'i' }, { "", "--DD_REPORT_DUPLICATION_READS", 'u' },
     };
     std::string gpu_list;
     for (int i = 1; i < argc; i++) {
@@ -97,7 +103,9 @@ int main(int argc, char **argv)
             else if (key == "-l") S.Analyze_LI = on;
             else if (key == "-s") S.report_close_mapped = on;
             else if (key == "-S") S.only_close_mapped = on;
-            // -k, -I, -q, -C (and -N): reports / searches outside this program's scope, accepted and ignored
+            else if (key == "-q") detect_dd = true;
+            else if (key == "--DD_REPORT_DUPLICATION_READS") dd.report_dup_reads = on;
+            // -k, -I, -C (and -N): reports / searches outside this program's scope, accepted and ignored
             continue;
         }
         if (i + 1 >= argc) {
@@ -157,6 +165,11 @@ int main(int argc, char **argv)
             }
             region = v;
         }
+        else if (key == "--MAX_DD_BREAKPOINT_DISTANCE") dd.max_bp_distance = (int)iv;
+        else if (key == "--MAX_DISTANCE_CLUSTER_READS") dd.max_distance_cluster = (int)iv;
+        else if (key == "--MIN_DD_CLUSTER_SIZE") dd.min_cluster_size = (int)iv;
+        else if (key == "--MIN_DD_BREAKPOINT_SUPPORT") dd.min_bp_support = (int)iv;
+        else if (key == "--MIN_DD_MAP_DISTANCE") dd.min_map_distance = (int)iv;
         else if (key == "-j") include_bed = v;
         else if (key == "-J") exclude_bed = v;
         else if (key == "-T") {
@@ -228,24 +241,9 @@ int main(int argc, char **argv)
     }
     // -i: one line per BAM: file, insert size, sample tag (readBamConfigFile, src/pindel.cpp)
     std::vector<BamSource> bams;
-    if (!bam_config.empty()) {
-        std::ifstream cf(bam_config.c_str());
-        if (!cf) {
-            fprintf(stderr, "pindel_pg: cannot open %s\n", bam_config.c_str());
-            return 1;
-        }
-        BamSource b;
-        while (cf >> b.path >> b.insert_size >> b.tag) {
-            if (b.path[0] != '/') {                       // relative to the configuration file
-                const size_t sl = bam_config.rfind('/');
-                if (sl != std::string::npos) b.path = bam_config.substr(0, sl + 1) + b.path;
-            }
-            bams.push_back(b);
-        }
-        if (bams.empty()) {
-            fprintf(stderr, "pindel_pg: no BAM files in %s\n", bam_config.c_str());
-            return 1;
-        }
+    if (!bam_config.empty() && !read_bam_config(bam_config, bams, err)) {
+        fprintf(stderr, "pindel_pg: %s\n", err.c_str());
+        return 1;
     }
     std::vector<pg_ctx *> ctxs;
     int rc = 0;
@@ -405,12 +403,12 @@ int main(int argc, char **argv)
         return r;
     };
     size_t n_bam_reads = 0, n_rp_events = 0;
+    BamIngestSettings ing;                 // -A, -n, -u: the split-read selection of the main search and of -q
+    ing.min_anchor_quality = min_anchor_quality;
+    ing.spacer = prm.spacer;
+    ing.nm = ref_read_nm;
+    ing.max_mismatch_rate = prm.max_allowed_mismatch_rate;
     if (!bams.empty()) {
-        BamIngestSettings ing;
-        ing.min_anchor_quality = min_anchor_quality;
-        ing.spacer = prm.spacer;
-        ing.nm = ref_read_nm;
-        ing.max_mismatch_rate = prm.max_allowed_mismatch_rate;
         // BAM input: with -R (default) the window hints are live -- the events of a -b file plus the read-pair events of
         // every window; without -R the reference never hands any event to the search (UpdateBD is not called)
         use_bd = search_rp;
@@ -468,6 +466,57 @@ int main(int argc, char **argv)
         if (search_rp) printf("pindel_pg: read-pair events added as window hints: %zu\n", n_rp_events);
     } else
         rc = run_pipeline(genome, plan, all, S, prefix, close_search, far_search, err, &li_seconds);
+    // -q: searchMEImain (src/search_MEI.cpp:963-1024) over the same plan and windows, after the split-read search.  The reference
+    // runs it INSTEAD of that search and exits (`exit(searchMEImain(...))`, src/pindel.cpp:1745-1746, its other reports left
+    // empty); here both run, and _DD does not depend on the order (difference 3).
+    if (!rc && detect_dd) {
+        DDStats dst;
+        auto dd_close = [&](int, const pg_adapter::Batch &batch, std::vector<DDClose> &outc) {
+            pg_read_batch v = batch.view();
+            pg_result *res = nullptr;
+            const int r = pg_close_end_batch(ctx, &v, &res);
+            if (r) return r;
+            pg_result_view rv;
+            pg_result_view_get(res, &rv);
+            outc.assign(rv.n_reads, DDClose());
+            for (size_t i = 0; i < rv.n_reads; i++) {
+                if (rv.close_off[i + 1] == rv.close_off[i]) continue;
+                std::vector<UniquePoint> pts;
+                pg_adapter::fill_points(pts, rv.close_runs, rv.close_off[i], rv.close_off[i + 1], make_point);
+                outc[i].has = 1;
+                outc[i].rc_flag = rv.rc_flag[i];
+                outc[i].last_abs = pts.back().AbsLoc;
+                outc[i].last_len = (uint16_t)pts.back().LengthStr;
+            }
+            pg_result_free(res);
+            return 0;
+        };
+        auto dd_contains = [&](const std::vector<std::string> &q, const std::vector<int32_t> &chr, const std::vector<uint64_t> &st,
+                               const std::vector<uint32_t> &len, std::vector<uint8_t> &found) {
+            std::vector<uint8_t> qs;
+            std::vector<uint64_t> qo(1, 0);
+            for (const std::string &x : q) {
+                qs.insert(qs.end(), x.begin(), x.end());
+                qo.push_back(qs.size());
+            }
+            found.assign(q.size(), 0);
+            return pg_dd_contains_batch(ctx, (uint32_t)q.size(), qs.data(), qo.data(), chr.data(), st.data(), len.data(), found.data());
+        };
+        if (bams.empty()) {
+            // Pindel-text input has no discordant reads: no breakpoint, where the reference ends with std::out_of_range
+            std::ofstream((prefix + "_DD").c_str(), std::ios::trunc);
+            printf("pindel_pg: -q needs BAM input (-i) for discordant read pairs; no dispersed-duplication breakpoint, %s_DD is empty\n", prefix.c_str());
+        } else {
+            rc = run_dd(genome, chromosome_sizes(genome, fai, prm.spacer), plan, bams, ing, S.window_mbp, dd, prefix, dd_close, dd_contains,
+                        err, &dst);
+            if (!rc) {
+                printf("pindel_pg: dispersed duplications: %zu discordant reads, %zu clusters, %zu breakpoints, %zu consensus tests "
+                       "(GPU %.3f s, %zu kept), %zu events\n", dst.discordant, dst.clusters, dst.breakpoints, dst.candidates,
+                       dst.contains_seconds, dst.kept_by_containment, dst.events);
+                if (!dst.note.empty()) printf("pindel_pg: %s\n", dst.note.c_str());
+            }
+        }
+    }
     if (rc) fprintf(stderr, "pindel_pg: %s (%s)\n", err.c_str(), pg_last_error(ctx));
     else {
         const size_t n_reads = bams.empty() ? all.size() : n_bam_reads;

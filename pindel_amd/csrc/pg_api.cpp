@@ -2210,4 +2210,76 @@ uint64_t pg_expand_runs(const pg_run *runs, uint64_t n_runs, pg_point *out)
     return k;
 }
 
+// -q (dispersed duplications): contains_subseq_any_strand(query, window, 15) per item on the device (pg_dd.hip).  The windows
+// are read from the reference planes already in HBM; only the queries and five numbers per item are uploaded.  Not on the
+// search path: no launch-log record.
+int pg_dd_contains_batch(pg_ctx *ctx, uint32_t n, const uint8_t *query, const uint64_t *query_off, const int32_t *chr_id,
+                         const uint64_t *win_start, const uint32_t *win_len, uint8_t *out)
+{
+    use_device(ctx);
+    if (!ctx || (n && (!query_off || !chr_id || !win_start || !win_len || !out))) return fail(ctx, PG_E_INVALID, "bad containment arguments");
+    if (!ctx->d_lo) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
+    ctx->last_ms = 0.0;
+    if (n == 0) return PG_OK;
+    uint64_t max_win = 0, max_query = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        max_query = std::max<uint64_t>(max_query, query_off[i + 1] - query_off[i]);
+        if (query_off[i + 1] < query_off[i]) return fail(ctx, PG_E_INVALID, "query offsets decrease");
+        if (query_off[i + 1] - query_off[i] > PG_MAX_READ_LEN) return fail(ctx, PG_E_READ_TOO_LONG, "containment query longer than 499 bases");
+        if (chr_id[i] < 0 || chr_id[i] >= (int32_t)ctx->names.size()) return fail(ctx, PG_E_INVALID, "containment window on an unknown chromosome");
+        if (win_start[i] > ctx->comp_size[chr_id[i]] || win_len[i] > ctx->comp_size[chr_id[i]] - win_start[i])
+            return fail(ctx, PG_E_INVALID, "containment window outside its chromosome");
+        max_win = std::max<uint64_t>(max_win, win_len[i]);
+    }
+    if (query_off[n] && !query) return fail(ctx, PG_E_INVALID, "bad containment arguments");
+    // one wave per (item, strand), at most 8192 resident waves (256 CUs x 4 SIMDs x occupancy 8: each systolic step is a chain of
+    // lane exchanges, hidden only by other waves); with queries of more than 64 bases each wave keeps one boundary row of its
+    // window, capped at 512 MB in all
+    const uint64_t n_tasks = 2ull * n;
+    const uint64_t stride = max_query > 64 ? (max_win + 63) / 64 * 64 : 0;
+    uint64_t waves = std::min<uint64_t>(n_tasks, 8192);
+    if (stride) waves = std::min<uint64_t>(waves, std::max<uint64_t>(4, (512ull << 20) / (stride * 4)));
+    const uint64_t blocks = (waves + 3) / 4;
+    uint8_t *d_q = nullptr, *d_out = nullptr;
+    uint64_t *d_qo = nullptr, *d_ws = nullptr;
+    int32_t *d_c = nullptr;
+    uint32_t *d_wl = nullptr, *d_scr = nullptr;
+    auto release = [&]() {
+        for (void *p : { (void *)d_q, (void *)d_out, (void *)d_qo, (void *)d_ws, (void *)d_c, (void *)d_wl, (void *)d_scr })
+            if (p) (void)hipFree(p);
+    };
+    int rc = dev_upload(ctx, &d_q, query ? query : (const uint8_t *)"", (size_t)query_off[n]);
+    if (!rc) rc = dev_upload(ctx, &d_qo, query_off, (size_t)n + 1);
+    if (!rc) rc = dev_upload(ctx, &d_c, chr_id, n);
+    if (!rc) rc = dev_upload(ctx, &d_ws, win_start, n);
+    if (!rc) rc = dev_upload(ctx, &d_wl, win_len, n);
+    if (!rc) rc = dev_alloc(ctx, &d_out, (size_t)n_tasks);
+    if (!rc) rc = dev_alloc(ctx, &d_scr, (size_t)(stride ? blocks * 4 * stride : 1));
+    if (rc) {
+        release();
+        return rc;
+    }
+    const PgDevRef ref = dev_ref(ctx);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t he = hipEventCreate(&e0);
+    if (he == hipSuccess) he = hipEventCreate(&e1);
+    if (he == hipSuccess) he = hipEventRecord(e0, ctx->stream);
+    if (he == hipSuccess && pg_dd_launch(&ref, ctx->d_mm, d_q, d_qo, d_c, d_ws, d_wl, d_out, d_scr, std::max<uint64_t>(stride, 1),
+                                         (uint32_t)n_tasks, (uint32_t)blocks, ctx->stream))
+        he = hipErrorLaunchFailure;
+    if (he == hipSuccess) he = hipEventRecord(e1, ctx->stream);
+    if (he == hipSuccess) he = hipEventSynchronize(e1);
+    float ms = 0.f;
+    if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
+    std::vector<uint8_t> two((size_t)n_tasks);
+    if (he == hipSuccess) he = hipMemcpy(two.data(), d_out, (size_t)n_tasks, hipMemcpyDeviceToHost);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    release();
+    if (he != hipSuccess) return fail(ctx, PG_E_DEVICE, std::string("containment kernel: ") + hipGetErrorString(he));
+    for (uint32_t i = 0; i < n; i++) out[i] = (uint8_t)(two[2 * (size_t)i] | two[2 * (size_t)i + 1]);
+    ctx->last_ms = ms;
+    return PG_OK;
+}
+
 }  // extern "C"

@@ -304,6 +304,11 @@ int pg_launch_search(const PgDevRef *ref, const PgDevParams *prm, const PgDevBat
                      int mode, uint32_t max_len, uint32_t levels, int small_ids, void *stream,
                      struct PgLaunchRec *rec, int *n_rec);
 // may that launch build the records of its reads itself (PgDevBatch::soa) ?
+// -q: contains_subseq_any_strand per item (pg_dd.hip); n_tasks = 2 x items (strand = task & 1), out2[task]; workgroups of four
+// waves, each wave with scratch_stride words of d_scratch (the boundary row between its 64-row blocks).
+int pg_dd_launch(const PgDevRef *ref, const uint32_t *d_mm, const uint8_t *d_query, const uint64_t *d_query_off, const int32_t *d_chr,
+                 const uint64_t *d_ws, const uint32_t *d_wl, uint8_t *d_out2, uint32_t *d_scratch, uint64_t scratch_stride, uint32_t n_tasks,
+                 uint32_t n_blocks, void *stream);
 int pg_pack_in_place_ok(int mode, uint32_t max_len, int small_ids, uint32_t n_reads, uint32_t plane_blocks);
 // ... then the reads on the batch's exact list that lie in the launch's range, with the reference's read-shortening semantics
 // (rec may be null; rec->kernel stays 0 when nothing was launched)
