@@ -159,6 +159,7 @@ Caller::Caller(const Settings &s, const std::vector<Chromosome> *g, const std::s
         for (const char *sf : suffixes) std::ofstream((prefix + sf).c_str(), std::ios::trunc);
         if (S.Analyze_LI) std::ofstream((prefix + "_LI").c_str(), std::ios::trunc);
         if (S.close_mapped_output()) std::ofstream((prefix + "_CloseEndMapped").c_str(), std::ios::trunc);
+        if (S.report_interchromosomal) std::ofstream((prefix + "_INT").c_str(), std::ios::trunc);
     }
 }
 
@@ -167,6 +168,10 @@ Caller::~Caller()
     flush_reports();
     if (li_out_.is_open()) li_out_.flush();
     if (cem_out_.is_open()) cem_out_.flush();
+    if (S.report_interchromosomal) {     // MergeInterChr, the last step of main (pindel.cpp:1999)
+        if (int_out_.is_open()) int_out_.close();
+        write_int_final(prefix + "_INT", prefix + "_INT_final");
+    }
 }
 
 void Caller::update_ref_coverage(const std::vector<RefReadSpan> &reads, const std::vector<std::string> &tags,
@@ -937,6 +942,7 @@ void Caller::process_window(const Chromosome &chrom, std::vector<SplitRead> &rea
             r.MatchedFarD = r.UP_Far[0].Strand;
         }
     }
+    if (S.report_interchromosomal) collect_interchr(reads);
     // PGH_TIMING=1: wall-clock seconds per classifier on stderr (diagnostics)
     static const bool timing = getenv("PGH_TIMING") != nullptr;
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -972,6 +978,10 @@ void Caller::process_window(const Chromosome &chrom, std::vector<SplitRead> &rea
         sort_output_li(c, win_start, win_end);
         li_seconds += now() - t_li;
         lap("long insertions");
+    }
+    if (S.report_interchromosomal) {
+        report_interchr();
+        lap("interchromosomal");
     }
 }
 

@@ -11,7 +11,9 @@
 //                searchshortinsertions.cpp), searchIndels src/search_deletions_nt.cpp:26-140
 //   reporters    SortOutputD / OutputDeletions, SortOutputDI / OutputDI, SortOutputSI /
 //                OutputSIs  src/reporter.cpp; SortOutputLI src/reporter.cpp:1853-2141 and
-//                ReportCloseMappedReads src/pindel.cpp:1076-1092 (pg_host_li.cpp)
+//                ReportCloseMappedReads src/pindel.cpp:1076-1092 (pg_host_li.cpp);
+//                SortAndReportInterChromosomalEvents src/reporter.cpp:2428-2665 and MergeInterChr
+//                src/pindel.cpp:1514-1579 (pg_host_int.cpp)
 // The search itself is NOT here: UP_Close / UP_Far come from the GPU through the C ABI
 // (include/pindel_pg.h).  No HIP dependency in this file; plain g++.
 #ifndef PG_HOST_HPP
@@ -77,6 +79,7 @@ struct Settings {                 // the flags the downstream steps read (src/fn
     bool report_close_mapped = false;    // -s: <prefix>_CloseEndMapped (ReportCloseMappedReads)
     bool only_close_mapped = false;      // -S: close end + _CloseEndMapped only, no far end, no SV search
     bool close_mapped_output() const { return report_close_mapped || only_close_mapped; }
+    bool report_interchromosomal = false; // -I: <prefix>_INT per window and <prefix>_INT_final at the end of the run
 };
 
 int load_fasta(const std::string &path, std::vector<Chromosome> &out, unsigned spacer, std::string &err);
@@ -87,6 +90,10 @@ int load_pindel_text(const std::string &path, const std::vector<Chromosome> &gen
                      std::vector<SplitRead> &out, std::string &err);
 
 std::string reverse_complement(const std::string &s);
+
+// MergeInterChr (src/pindel.cpp:1514-1579): the calls of int_path (the lines of <prefix>_INT) paired within 10 bp on
+// both sides, or alone with support >= 4, written to final_path (created empty when there is no call)
+void write_int_final(const std::string &int_path, const std::string &final_path);
 
 // Everything that happens to the reads of ONE chromosome after the close-end stage, with the
 // reference's global counters (SV indices, g_reportLength, g_sampleNames) kept across calls.
@@ -139,8 +146,8 @@ private:
     std::ostream &report(int which);        // the file -- or, inside for_boxes, the calling worker's buffer
     void flush_reports();
     // _LI and _CloseEndMapped: written outside for_boxes, so plain files (append, large buffer)
-    std::ofstream li_out_, cem_out_;
-    std::vector<char> li_buf_, cem_buf_;
+    std::ofstream li_out_, cem_out_, int_out_;
+    std::vector<char> li_buf_, cem_buf_, int_buf_;
     std::ofstream &open_append(std::ofstream &f, std::vector<char> &buf, const char *suffix);
     // CurrentChrMask (pindel.cpp:1801-1804): the positions of this chromosome where an event has been reported so far
     // ('B'), kept as a set; reset at every region record (begin_region) and when the chromosome changes.  The reporters call mark() with the breakpoints they print; inside for_boxes the marks
@@ -196,6 +203,12 @@ private:
     void output_inv(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsigned e, unsigned rs, unsigned re);
     void output_short_inv(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsigned e);
     void sort_output_li(Ctx &c, unsigned win_start, unsigned win_end);
+    // -I (pg_host_int.cpp): the window's reads whose far end lies on another chromosome, copied before the classifiers
+    // touch them (InterChromosome_SR, pindel.cpp:1905-1917), and their calls, appended to <prefix>_INT after the window's
+    // other reports (pindel.cpp:1940-1942)
+    std::vector<SplitRead> interchr_;
+    void collect_interchr(const std::vector<SplitRead> &reads);
+    void report_interchr();
 };
 
 }  // namespace pgh

@@ -2,6 +2,7 @@
 // before and after the hot path (loaders, classifiers, reporters), callable from tests and
 // from the pindel_pg command line.  No search code here.
 #include <cctype>
+#include <chrono>
 #include <cstring>
 #include <fstream>
 #include <sstream>
@@ -42,6 +43,7 @@ struct pgh_settings {
     const char *region;          /* -c: NULL or "" = ALL */
     const char *include_bed;     /* -j: NULL or "" = none */
     const char *exclude_bed;     /* -J: NULL or "" = none */
+    int32_t report_interchromosomal; /* -I: also write <prefix>_INT and <prefix>_INT_final */
 };
 
 static std::string str_or_empty(const char *s) { return s ? s : ""; }
@@ -51,7 +53,7 @@ static std::string str_or_empty(const char *s) { return s ? s : ""; }
  * UP_Far (CSR over ALL reads of the file, in file order; reads without close end have an
  * empty range) and the rc flags, then walks chromosomes and 5-Mbp bins like main()
  * (pindel.cpp:1778-1989) and appends <prefix>_D, _SI, _TD, _INV -- and _LI / _CloseEndMapped when
- * analyze_li / report_close_mapped are set.  region / include_bed / exclude_bed: the region plan (pg_region.hpp).
+ * analyze_li / report_close_mapped are set, _INT and _INT_final when report_interchromosomal is.  region / include_bed / exclude_bed: the region plan (pg_region.hpp).
  */
 int pgh_call_from_points(const char *fasta_path, const char *reads_path, const char *out_prefix,
                          const pgh_settings *st, uint32_t n_reads,
@@ -78,6 +80,7 @@ int pgh_call_from_points(const char *fasta_path, const char *reads_path, const c
     S.window_mbp = st->window_mbp;
     S.Analyze_LI = st->analyze_li != 0;
     S.report_close_mapped = st->report_close_mapped != 0;
+    S.report_interchromosomal = st->report_interchromosomal != 0;
     memcpy(S.max_mismatch, st->max_mismatch, sizeof S.max_mismatch);
     std::vector<RegionRecord> plan;
     if (region_plan(chromosome_names(genome), chromosome_sizes(genome, read_fai(fasta_path, genome), S.spacer), str_or_empty(st->region),
@@ -390,6 +393,135 @@ int64_t pgh_window_hints(const char *bd_path, const char *bam_path, int32_t n_ch
         out_off[i + 1] = k;
     }
     return (int64_t)ev.size();
+}
+
+// The events of `ev` as 6 values each: chromosome index of the first side (in `names`; -1 = unknown), pos1, pos1b, then the same for
+// the second side
+static void events_with_chromosomes(const std::vector<pgh::RpEvent> &ev, const std::vector<std::string> &names, int64_t *out, uint64_t cap)
+{
+    auto id_of = [&](const std::string &n) {
+        for (size_t c = 0; c < names.size(); c++)
+            if (names[c] == n) return (int64_t)c;
+        return (int64_t)-1;
+    };
+    for (size_t i = 0; i < ev.size() && i < cap; i++) {
+        const int64_t v[6] = { id_of(ev[i].chr1), ev[i].pos1, ev[i].pos1b, id_of(ev[i].chr2), ev[i].pos2, ev[i].pos2b };
+        for (int k = 0; k < 6; k++) out[6 * i + k] = v[k];
+    }
+}
+
+// pgh_rp_events with the interchromosomal pairs of the window (interchr != 0: what -I adds; their events and _RP lines follow the
+// same-chromosome ones) and with the chromosomes of both sides: out receives 6 values per event (events_with_chromosomes; the
+// chromosome index is the one of the BAM header).  Returns the number of events, -1 on a file error.
+int64_t pgh_rp_events_chr(const char *bam_path, const char *chr_name, int64_t win_start, int64_t win_end, int32_t insert_size,
+                          const char *tag, uint32_t min_anchor_quality, uint32_t spacer, int32_t interchr, const char *rp_path, int64_t *out,
+                          uint64_t cap)
+{
+    pgh::BamFile bam;
+    if (!bam.open(bam_path, g_err)) return -1;
+    std::vector<pgh::RpRead> rp, rp_inter;
+    if (!pgh::rp_discover(bam, chr_name, win_start, win_end, insert_size, tag ? tag : "", min_anchor_quality, rp, interchr ? &rp_inter : nullptr))
+        return -1;
+    std::ofstream f;
+    if (rp_path) f.open(rp_path, std::ios::trunc);
+    std::vector<pgh::RpEvent> ev = pgh::rp_events(rp, spacer, rp_path ? &f : nullptr);
+    if (interchr) {
+        const std::vector<pgh::RpEvent> inter = pgh::rp_events_interchr(rp_inter, spacer, rp_path ? &f : nullptr);
+        ev.insert(ev.end(), inter.begin(), inter.end());
+    }
+    events_with_chromosomes(ev, bam.header().names, out, cap);
+    return (int64_t)ev.size();
+}
+
+// The interchromosomal clustering alone (rp_events_interchr) on pairs given as arrays, as build_record_RP_Discovery would have left
+// them: chromosome indices (into names) and strands ('+' / '-') of both sides, positions, insert size, read length, sample tag index
+// (into tags).  out / rp_path as for pgh_rp_events_chr; seconds (nullable) receives the time of the clustering.
+int64_t pgh_rp_interchr_pairs(uint32_t n, const int32_t *chr_a, const int32_t *chr_b, const uint8_t *d_a, const uint8_t *d_b,
+                              const uint32_t *pos_a, const uint32_t *pos_b, const int32_t *insert_size, const int16_t *read_length,
+                              const int32_t *tag, int32_t n_names, const char *const *names, int32_t n_tags, const char *const *tags,
+                              uint32_t spacer, const char *rp_path, int64_t *out, uint64_t cap, double *seconds)
+{
+    std::vector<std::string> nm(names, names + n_names), tg(tags, tags + n_tags);
+    std::vector<pgh::RpRead> rp(n);
+    for (uint32_t i = 0; i < n; i++) {
+        pgh::RpRead &t = rp[i];
+        if (chr_a[i] < 0 || chr_a[i] >= n_names || chr_b[i] < 0 || chr_b[i] >= n_names || tag[i] < 0 || tag[i] >= n_tags) {
+            g_err = "pgh_rp_interchr_pairs: index out of range";
+            return -1;
+        }
+        t.ChrA = chr_a[i];
+        t.ChrB = chr_b[i];
+        t.ChrNameA = nm[(size_t)chr_a[i]];
+        t.ChrNameB = nm[(size_t)chr_b[i]];
+        t.DA = (char)d_a[i];
+        t.DB = (char)d_b[i];
+        t.PosA = t.OriginalPosA = pos_a[i];
+        t.PosB = t.OriginalPosB = pos_b[i];
+        t.InsertSize = insert_size[i];
+        t.ReadLength = read_length[i];
+        t.Tags.push_back(tg[(size_t)tag[i]]);
+    }
+    std::ofstream f;
+    if (rp_path) f.open(rp_path, std::ios::trunc);
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::vector<pgh::RpEvent> ev = pgh::rp_events_interchr(rp, spacer, rp_path ? &f : nullptr);
+    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    events_with_chromosomes(ev, nm, out, cap);
+    return (int64_t)ev.size();
+}
+
+// pgh_window_hints with -I's interchromosomal pairs when interchr != 0 (UpdateBD hands both kinds to the event list), and with the
+// read-pair events themselves: ev_out (nullable) receives 6 values per event (events_with_chromosomes, indices into names).
+int64_t pgh_window_hints_chr(const char *bd_path, const char *bam_path, int32_t n_chr, const char *const *names, int32_t chr_id,
+                             int64_t win_start, int64_t win_end, int64_t region_end, int32_t insert_size, const char *tag,
+                             uint32_t min_anchor_quality, uint32_t spacer, int32_t interchr, uint32_t n_q, const uint32_t *q, uint64_t *out_off,
+                             int32_t *out_win, uint64_t cap, int64_t *ev_out, uint64_t ev_cap)
+{
+    pgh::BDHints h;
+    std::string note;
+    if (bd_path && bd_path[0] && h.load_file(bd_path, spacer, note) < 0) {
+        g_err = note;
+        return -1;
+    }
+    std::vector<std::string> nm(names, names + n_chr);
+    pgh::BamFile bam;
+    if (!bam.open(bam_path, g_err)) return -1;
+    std::vector<pgh::RpRead> rp, rp_inter;
+    if (!pgh::rp_discover(bam, nm[chr_id], win_start, win_end, insert_size, tag ? tag : "", min_anchor_quality, rp, interchr ? &rp_inter : nullptr))
+        return -1;
+    std::vector<pgh::RpEvent> ev = pgh::rp_events(rp, spacer, nullptr);
+    if (interchr) {
+        const std::vector<pgh::RpEvent> inter = pgh::rp_events_interchr(rp_inter, spacer, nullptr);
+        ev.insert(ev.end(), inter.begin(), inter.end());
+    }
+    if (ev_out) events_with_chromosomes(ev, nm, ev_out, ev_cap);
+    std::vector<std::pair<pgh::BDHints::RpSide, pgh::BDHints::RpSide>> sides;
+    for (const pgh::RpEvent &e : ev) {
+        pgh::BDHints::RpSide a = { e.chr1, e.pos1, e.pos1b }, b = { e.chr2, e.pos2, e.pos2b };
+        sides.push_back(std::make_pair(a, b));
+    }
+    h.update_with_rp(sides);
+    if (!h.load_region(nm, chr_id, (unsigned)win_start + spacer, (unsigned)region_end + spacer, g_err)) return -2;
+    uint64_t k = 0;
+    out_off[0] = 0;
+    for (uint32_t i = 0; i < n_q; i++) {
+        for (const pgh::BDWindow &w : h.cluster(q[i])) {
+            if (k >= cap) return -3;
+            out_win[3 * k] = w.chr_id;
+            out_win[3 * k + 1] = (int32_t)w.start;
+            out_win[3 * k + 2] = (int32_t)w.end;
+            k++;
+        }
+        out_off[i + 1] = k;
+    }
+    return (int64_t)ev.size();
+}
+
+// MergeInterChr alone: the _INT_final text of an _INT file (write_int_final, pg_host_int.cpp)
+int pgh_int_final(const char *int_path, const char *final_path)
+{
+    pgh::write_int_final(int_path, final_path);
+    return 0;
 }
 
 // Test hook (tests/test_cpu_suite.py): sorts indices 0..n-1 by keys[] with the reference's O(n^2)

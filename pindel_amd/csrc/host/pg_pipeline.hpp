@@ -252,6 +252,8 @@ struct CloseView {
 // bd != null && search_rp: before the reads of a window are taken, its discordant read pairs become BreakDancer-like
 // events (get_RP_Reads_Discovery + BDData::UpdateBD, src/pindel.cpp:1838-1848; -R, default on) next to the events of
 // a -b file; the search step then looks their windows up per read (loadRegion / getCorrespondingSearchWindowCluster).
+// With S.report_interchromosomal (-I) the pairs whose mates lie on different chromosomes are kept and clustered as
+// well (rp_events_interchr): their events and _RP lines follow the window's same-chromosome ones, as in UpdateBD.
 //
 //   close_soa(chrom, chr_id, batch, view)   ReadBuffer::flush on the window's candidates as ingested (SoA): the close
 //                                           ends as run lists + rc flags; only the reads that have one become SplitReads
@@ -281,7 +283,7 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<Re
     // PGH_TIMING=1: wall-clock seconds per stage of this loop on stderr (diagnostics)
     const bool timing = getenv("PGH_TIMING") != nullptr;
     double t_wait = 0, t_close = 0, t_keep = 0, t_far = 0, t_cov = 0, t_call = 0, t_free = 0;
-    double t_rp = 0, t_ingest = 0;                         // (on the reader thread)
+    double t_rp = 0, t_rp_inter = 0, t_ingest = 0;         // (on the reader thread; t_rp_inter: the -I clustering, part of t_rp)
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_begin = now();
 
@@ -310,13 +312,20 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<Re
         const Chromosome &chrom = genome[win.c];
         double t0 = now();
         if (bd && search_rp) {
-            std::vector<RpRead> rp;
+            std::vector<RpRead> rp, rp_inter;
             for (size_t k = 0; k < bams.size(); k++)
-                if (!rp_discover(files[k], chrom.name, win.ws, win.we, bams[k].insert_size, bams[k].tag, ingest.min_anchor_quality, rp)) {
+                if (!rp_discover(files[k], chrom.name, win.ws, win.we, bams[k].insert_size, bams[k].tag, ingest.min_anchor_quality, rp,
+                                 S.report_interchromosomal ? &rp_inter : nullptr)) {
                     d->error = bams[k].path + ": BAM read failed";
                     return d;
                 }
-            const std::vector<RpEvent> ev = rp_events(rp, S.spacer, &rp_out);
+            std::vector<RpEvent> ev = rp_events(rp, S.spacer, &rp_out);
+            if (S.report_interchromosomal) {
+                const double t1 = now();
+                const std::vector<RpEvent> inter = rp_events_interchr(rp_inter, S.spacer, &rp_out);
+                ev.insert(ev.end(), inter.begin(), inter.end());
+                t_rp_inter += now() - t1;
+            }
             for (const RpEvent &e : ev) {
                 BDHints::RpSide a = { e.chr1, e.pos1, e.pos1b }, b = { e.chr2, e.pos2, e.pos2b };
                 d->sides.push_back(std::make_pair(a, b));
@@ -448,8 +457,9 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<Re
     if (timing)
         fprintf(stderr, "pgh timing: BAM pipeline %.3f s wall: waiting for the reader %.3f s, close end %.3f s, keep + SplitReads %.3f s, "
                         "far end %.3f s, reference coverage %.3f s, classify + report %.3f s, free %.3f s | reader thread: read-pair "
-                        "discovery %.3f s, ingest %.3f s (inflate + decode on threads %.3f, selection rules on threads %.3f, layout %.3f)\n",
-                now() - t_begin, t_wait, t_close, t_keep, t_far, t_cov, t_call, t_free, t_rp, t_ingest,
+                        "discovery %.3f s (of which interchromosomal clustering %.3f s), ingest %.3f s (inflate + decode on threads %.3f, "
+                        "selection rules on threads %.3f, layout %.3f)\n",
+                now() - t_begin, t_wait, t_close, t_keep, t_far, t_cov, t_call, t_free, t_rp, t_rp_inter, t_ingest,
                 ingest_timing().inflate_decode, ingest_timing().select, ingest_timing().layout);
     if (li_seconds) *li_seconds = caller.li_seconds;
     return status;

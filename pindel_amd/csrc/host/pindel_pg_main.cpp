@@ -1,12 +1,13 @@
 // pindel_pg -- command line with Pindel's flags for the path this repository implements:
 //   pindel_pg -f ref.fa -p reads.txt -o prefix [-x 2 -a 1 -m 3 -u 0.02 -e 0.01 -E 0.95 -H 8
-//                                               -M 1 -B 100 -d 30 -v 50 -w 5 -G device -l -s -S
+//                                               -M 1 -B 100 -d 30 -v 50 -w 5 -G device -l -s -S -I
 //                                               -c ALL|chr[:start[-end]] -j include.bed -J exclude.bed]
 // FASTA + Pindel-text reads -> close/far-end search on the MI355X (C ABI, libpindel_pg.so)
 // -> SV classification and <prefix>_D/_SI/_TD/_INV reports (host code in this directory);
 // -l adds <prefix>_LI (long insertions), -s <prefix>_CloseEndMapped (the reads with a close end),
 // -S writes <prefix>_CloseEndMapped only (no far end, no SV search); -q adds <prefix>_DD (dispersed duplications, BAM input,
-// pg_dd.hpp).  Like the reference, every run
+// pg_dd.hpp); -I adds <prefix>_INT and <prefix>_INT_final (interchromosomal events, pg_host_int.cpp: far ends on other chromosomes
+// need window hints, i.e. BAM input with -R or `-b file --bd-hints on`).  Like the reference, every run
 // creates all seven files (_D _SI _TD _INV _LI _BP _CloseEndMapped); _BP stays empty, as the
 // reference's breakpoint report is not called.  -c, -j and -J select the regions searched (pg_region.hpp); they are
 // checked before the first device call (exit status 2 for -c syntax, 1 for an unreadable file or an unknown chromosome).
@@ -57,7 +58,7 @@ int main(int argc, char **argv)
     Settings S;
     // Flags as src/fn_parameters.cpp defines them: value flags need an argument that does not start with
     // '-'; unary switches take an optional true/false word (readParameters, fn_parameters.cpp:366-406).
-    // The switches -k (beyond the empty _BP file), -I and -C select searches and reports this program does not
+    // The switches -k (beyond the empty _BP file) and -C select searches and reports this program does not
     // run; they are accepted and ignored; anything else is an error, and so is a value that is not a number.
     struct Flag { const char *sh, *lg; char kind; };      // kind: i int, f float, s string, u unary
     static const Flag flags[] = {
@@ -103,9 +104,10 @@ int main(int argc, char **argv)
             else if (key == "-l") S.Analyze_LI = on;
             else if (key == "-s") S.report_close_mapped = on;
             else if (key == "-S") S.only_close_mapped = on;
+            else if (key == "-I") S.report_interchromosomal = on;
             else if (key == "-q") detect_dd = true;
             else if (key == "--DD_REPORT_DUPLICATION_READS") dd.report_dup_reads = on;
-            // -k, -I, -C (and -N): reports / searches outside this program's scope, accepted and ignored
+            // -k, -C (and -N): reports / searches outside this program's scope, accepted and ignored
             continue;
         }
         if (i + 1 >= argc) {
@@ -205,7 +207,10 @@ int main(int argc, char **argv)
         return 2;
     }
     // TestFileForOutput (pindel.cpp:932-938): every output file exists, empty, from the start
-    for (const char *sf : { "_D", "_SI", "_TD", "_INV", "_LI", "_BP", "_CloseEndMapped" }) {
+    // (... and with -I its two files: <prefix>_INT is truncated here, where the reference only ever appends to it)
+    std::vector<const char *> suffixes = { "_D", "_SI", "_TD", "_INV", "_LI", "_BP", "_CloseEndMapped" };
+    if (S.report_interchromosomal) suffixes.insert(suffixes.end(), { "_INT", "_INT_final" });
+    for (const char *sf : suffixes) {
         std::ofstream f((prefix + sf).c_str(), std::ios::trunc);
         if (!f) {
             fprintf(stderr, "pindel_pg: cannot write %s%s\n", prefix.c_str(), sf);
@@ -307,6 +312,9 @@ int main(int argc, char **argv)
         if (brc > 0) printf("pindel_pg: %s\n", note.c_str());
         printf("pindel_pg: BD events: %zu%s\n", bd.n_events(), use_bd ? "" : " (not used for Pindel-text input; --bd-hints on to use them)");
     }
+    if (S.report_interchromosomal && bam_config.empty() && !(use_bd && bd.n_events()))
+        printf("pindel_pg: -I without window hints (BAM input, or -b file --bd-hints on): no far end is searched on another chromosome, "
+               "%s_INT and %s_INT_final stay empty\n", prefix.c_str(), prefix.c_str());
     size_t n_close = 0, n_far = 0;
     double li_seconds = 0.0;
     // fn(ctx, part) on contiguous shards of `reads`, one host thread and one ctx per device; the parts are moved out

@@ -19,7 +19,8 @@ class HostSettings(C.Structure):
         ("min_inversion_size", C.c_int32), ("analyze_td", C.c_int32), ("analyze_inv", C.c_int32),
         ("window_mbp", C.c_double), ("max_mismatch", C.c_uint32 * 500),
         ("analyze_li", C.c_int32), ("report_close_mapped", C.c_int32),
-        ("region", C.c_char_p), ("include_bed", C.c_char_p), ("exclude_bed", C.c_char_p)]
+        ("region", C.c_char_p), ("include_bed", C.c_char_p), ("exclude_bed", C.c_char_p),
+        ("report_interchromosomal", C.c_int32)]
 
 
 class VcfOptions(C.Structure):
@@ -96,6 +97,7 @@ def default_settings(max_mismatch) -> HostSettings:
     s.region = None            # -c (None = ALL)
     s.include_bed = None       # -j (None = no include list)
     s.exclude_bed = None       # -J (None = no exclude list)
+    s.report_interchromosomal = 0  # -I (default false): <prefix>_INT and <prefix>_INT_final
     for i in range(500):
         s.max_mismatch[i] = int(max_mismatch[i])
     return s
@@ -138,7 +140,8 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
                      rc_flag, region=None, include_bed=None, exclude_bed=None):
     """Classify + report (_D, _SI, _TD, _INV) from per-read UP_Close / UP_Far points (CSR over
     all reads of the file, 12-byte pg_point records).  settings.analyze_li / settings.report_close_mapped
-    add <out_prefix>_LI / <out_prefix>_CloseEndMapped.  region / include_bed / exclude_bed (-c, -j, -J)
+    add <out_prefix>_LI / <out_prefix>_CloseEndMapped, settings.report_interchromosomal <out_prefix>_INT and
+    <out_prefix>_INT_final (reads whose far points lie on another chromosome than their anchor).  region / include_bed / exclude_bed (-c, -j, -J)
     override the settings' fields of the same names when given; by default the whole genome is searched."""
     L = lib()
     keep = [_enc(region), _enc(include_bed), _enc(exclude_bed)]     # (alive until the call returns)
