@@ -170,8 +170,18 @@ int  pg_reference_fetch(const pg_ctx *ctx, int32_t chr_id, uint64_t start, uint6
 
 /* ---- the path, host buffers in / host results out ---------------------- */
 int  pg_close_end_batch(pg_ctx *ctx, const pg_read_batch *reads, pg_result **out);
-/* Both seams on ONE read vector: `close` must be the result of pg_close_end_batch on the same reads, given here in
- * their ORIGINAL orientation (the result carries UP_Close and the rc flags); it is extended in place with UP_Far.
+/* Both seams on ONE read vector: `close` must be the result of pg_close_end_batch on the same reads (it carries UP_Close
+ * and the rc flags) and is extended in place with UP_Far; its close lists and rc flags are left as they are.  The reads
+ * are given in their ORIGINAL orientation, which admits exactly two forms per read, with i's flag f = rc_flag[i]:
+ *   (a) the read as it was first handed to pg_close_end_batch: the library applies the f
+ *       "setUnmatchedSeq(ReverseComplement())" steps itself, shortening included; or
+ *   (b) the read as the close end left it (the post-state, f steps applied: what pg_adapter::CloseEndBatch puts into
+ *       UnmatchedSeq), reverse-complemented back where f & 1 -- every byte outside ACGTN becoming NUL, nothing stripped --
+ *       and unchanged where f is 0 or 2 (what pg_adapter::make_batch(reads, chr_of, rc_flag) uploads).
+ * Either way the far end runs on the post-state: on the reverse complement of what is given where f & 1, on the read
+ * as given otherwise.  f = 2 means "in hand as is": two reverse complements, the ORIGINAL orientation again -- for form
+ * (b) a read whose only characters outside ACGTN were at its ends is then a clean, shorter read that still carries 2.
+ * For a read without such characters (a) and (b) are the same bytes.
  * The reference's own call site has a different vector by then -- see pg_far_end_batch_from_close. */
 int  pg_far_end_batch(pg_ctx *ctx, const pg_read_batch *reads, pg_result *close,
                       const pg_windows *bd_hints /* nullable */);

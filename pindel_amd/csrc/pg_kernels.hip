@@ -2162,8 +2162,12 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
         alg = (u32)uni((int)o1.z) << 3;
         if (EXACT) ex_apply(flipped);                          // the read as the close end left it (rc_flag 1 / 2)
     }
-    const int rc_out = flipped;                                // PgOutRec::rc_flag
-    if (EXACT) flipped &= 1;                                   // (orientation in hand for the far end: 2 = the original orientation)
+    const int rc_out = flipped;                                // PgOutRec::rc_flag (a 2 stays a 2)
+    // orientation in hand for the far end: 2 = two reverse complements = the original orientation.  A far-only launch can meet a 2 in
+    // every instantiation: a read whose only characters outside ACGTN were at its ends comes back from the close end clean, shorter
+    // and flagged 2 (pg_far_end_batch's post-state form), and is no read of the exact list any more.  The close end of the ordinary
+    // kernels never yields a 2 itself, so the fused kernels do not need the mask.
+    if (EXACT || !do_close) flipped &= 1;
 
     // ------------------------------------------------------------------------------- far end
 #ifdef PG_TIMING

@@ -6,7 +6,8 @@
 //   * built and linked with libpindel_pg.so it is the GPU test's driver (tests/test_gpu_parity.py::
 //     test_adapter_on_reference_shapes): FASTA + a plain read table in, the flow of the reference out --
 //     ReadBuffer::flush in `flush`-sized batches (seam 1), keep the reads with a close end, SearchFarEnds on their
-//     union (seam 2, both overloads) -- one line per read with the sequence as it was left and every UniquePoint.
+//     union (seam 2, both overloads) -- one line per read with the sequence as it was left (as hex: it can hold NUL where the
+//     read had a character outside ACGTN) and every UniquePoint.
 //
 // read table: one read per line  "<name> <chr name> <strand> <MatchedRelPos> <InsertSize> <sequence>"
 #include <cstdio>
@@ -33,6 +34,17 @@ static int pg_chr_of(const SPLIT_READ &r)
    for (size_t i = 0; i < g_chr.size(); i++)
       if (g_chr[i]->getName() == r.FragName) return (int)i;
    return -1;
+}
+
+static std::string hex_of(const std::string &s)
+{
+   static const char d[] = "0123456789abcdef";
+   std::string o;
+   for (size_t i = 0; i < s.size(); i++) {
+      o.push_back(d[(unsigned char)s[i] >> 4]);
+      o.push_back(d[(unsigned char)s[i] & 15]);
+   }
+   return o.empty() ? "-" : o;
 }
 
 static void print_points(std::ostream &os, const SortedUniquePoints &pts)
@@ -114,7 +126,7 @@ int main(int argc, char **argv)
    size_t k = 0;
    for (size_t i = 0; i < raw.size(); i++) {
       const SPLIT_READ &r = raw[i].hasCloseEnd() ? kept[k++] : raw[i];
-      out << r.Name << ' ' << r.getUnmatchedSeq() << " C ";
+      out << r.Name << ' ' << hex_of(r.getUnmatchedSeq()) << " C ";
       print_points(out, r.UP_Close);
       out << " F ";
       print_points(out, r.UP_Far);

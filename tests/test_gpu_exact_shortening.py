@@ -2,11 +2,9 @@
 BEGINS (first reverse complement) or ENDS (second) with such characters (setUnmatchedSeq, pindel.cpp:142-169, 2545; the derivation
 and the hand-written expectations: tests/shortening_cases.py, tests/test_oracle_shortening.py).  The pack kernel lists these reads,
 pg_search_exact_kernel searches them again with the shortening; every entry of the ABI goes through it."""
-import numpy as np
 import pytest
 
 from pindel_amd import synth
-from pindel_amd.synth import ReadBatch
 from tests import shortening_cases as sc
 from tests.parity import compare_result, run_oracle
 
@@ -18,17 +16,7 @@ def ref():
     return [("chrS", synth.make_reference(600_000, seed=31))]
 
 
-def _concat(batches):
-    off = [np.zeros(1, dtype=np.uint64)]
-    base = 0
-    for b in batches:
-        off.append(b.seq_off[1:].astype(np.uint64) + np.uint64(base))
-        base += len(b.seq)
-    return ReadBatch(seq=np.concatenate([b.seq for b in batches]), seq_off=np.concatenate(off),
-                     anchor_strand=np.concatenate([b.anchor_strand for b in batches]),
-                     anchor_pos=np.concatenate([b.anchor_pos for b in batches]),
-                     insert_size=np.concatenate([b.insert_size for b in batches]),
-                     chr_id=np.concatenate([b.chr_id for b in batches]))
+_concat = sc.concat
 
 
 def _cases(ref):

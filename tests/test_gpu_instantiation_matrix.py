@@ -12,6 +12,7 @@ import pytest
 
 from pindel_amd import binding, hostio
 from tests import instantiations as I
+from tests import shortening_cases as sc
 from tests.parity import compare_result, oracle_points, points_per_read, run_oracle
 
 pytestmark = pytest.mark.gpu
@@ -42,12 +43,8 @@ def _max_mm(orc, which, idx):
 def _kept_for_far(batch, close, orc, bd, bd_off):
     """the reads with a close end as GetCloseEnd left them (the oracle's sequences: reverse-complemented and shortened where it
     did so -- (d) equals the oracle, so these are what (d) left), UP_Close.back() from (d), and their windows"""
-    has = np.diff(close.close_off.astype(np.int64)) > 0
+    has, close_last, close_max = sc.close_back(close)
     kept = np.nonzero(has)[0]
-    last_run = close.close_runs[close.close_off[1:][has].astype(np.int64) - 1]
-    d = last_run["len_last"].astype(np.int64) - last_run["len_first"]
-    back = (last_run["flags"] & 1) != 0
-    close_last = np.where(back, last_run["abs_loc_first"].astype(np.int64) - d, last_run["abs_loc_first"].astype(np.int64) + d)
     off = batch.seq_off.astype(np.int64)
     seqs = [orc["seq"][off[i]:off[i] + int(orc["len_out"][i])].tobytes() for i in kept]
     kb = hostio.batch_from_lists(seqs, [bytes([c]) for c in batch.anchor_strand[kept]], batch.anchor_pos[kept],
@@ -57,7 +54,7 @@ def _kept_for_far(batch, close, orc, bd, bd_off):
         bo = bd_off.astype(np.int64)
         kbd = np.concatenate([bd[bo[i]:bo[i + 1]] for i in kept])
         kbd_off = np.concatenate([[0], np.cumsum(bo[kept + 1] - bo[kept])]).astype(np.uint64)
-    return kept, kb, close_last.astype(np.uint32), last_run["len_last"].astype(np.int16), kbd, kbd_off
+    return kept, kb, close_last[kept], close_max[kept], kbd, kbd_off
 
 
 @pytest.mark.parametrize("case", I.CASES, ids=[c.id for c in I.CASES])
