@@ -15,6 +15,8 @@
 #include <sstream>
 #include <thread>
 
+#include <zlib.h>
+
 namespace pgh {
 
 using namespace detail;
@@ -67,19 +69,117 @@ int load_fasta(const std::string &path, std::vector<Chromosome> &out, unsigned s
     return 0;
 }
 
+// A gzip file, every member of it, inflated into `out`.  Anything that does not inflate to a clean end of the last
+// member -- a file that is not gzip, a damaged or truncated stream, trailing bytes -- is an error: a short read
+// list must never pass for the file's content.
+static int read_gzip_file(const std::string &path, std::string &out, std::string &err)
+{
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) {
+        err = "cannot open " + path;
+        return -1;
+    }
+    z_stream zs;
+    memset(&zs, 0, sizeof zs);
+    if (inflateInit2(&zs, 15 + 16) != Z_OK) {                  // gzip wrapper
+        fclose(f);
+        err = "zlib: inflateInit2 failed";
+        return -1;
+    }
+    std::vector<unsigned char> in(1 << 16), tmp(1 << 18);
+    bool ok = true, at_member_end = false, any_member = false;
+    while (ok) {
+        const size_t k = fread(in.data(), 1, in.size(), f);
+        if (k == 0) break;
+        zs.next_in = in.data();
+        zs.avail_in = (uInt)k;
+        while (ok && zs.avail_in > 0) {
+            if (at_member_end) {                               // the next member of a concatenated file
+                ok = inflateReset(&zs) == Z_OK;
+                at_member_end = false;
+                if (!ok) break;
+            }
+            zs.next_out = tmp.data();
+            zs.avail_out = (uInt)tmp.size();
+            const int zr = inflate(&zs, Z_NO_FLUSH);
+            if (zr != Z_OK && zr != Z_STREAM_END) {
+                ok = false;
+                break;
+            }
+            out.append((const char *)tmp.data(), tmp.size() - zs.avail_out);
+            if (zr == Z_STREAM_END) {
+                at_member_end = true;
+                any_member = true;
+            }
+        }
+    }
+    if (ferror(f)) ok = false;
+    inflateEnd(&zs);
+    fclose(f);
+    if (!ok || !any_member || !at_member_end) {
+        err = path + ": not a complete gzip file (it does not inflate)";
+        return -1;
+    }
+    return 0;
+}
+
+int read_pindel_config(const std::string &config, std::vector<std::string> &files, std::string &err)
+{
+    std::ifstream cf(config.c_str());
+    if (!cf) {
+        err = "Pindel configuration file '" + config + "' cannot be read";
+        return -1;
+    }
+    const size_t sl = config.rfind('/');
+    std::string line;
+    while (std::getline(cf, line)) {
+        std::istringstream iss(line);
+        std::string name;
+        if (!(iss >> name)) continue;
+        auto exists = [](const std::string &p) { return (bool)std::ifstream(p.c_str()); };
+        if (!exists(name)) {
+            const std::string beside = sl == std::string::npos ? name : config.substr(0, sl + 1) + name;
+            if (name[0] == '/' || !exists(beside)) {
+                err = "cannot find the file '" + name + "' referred to in configuration file '" + config + "'";
+                return -1;
+            }
+            name = beside;
+        }
+        files.push_back(name);
+    }
+    if (files.empty()) {
+        err = "could not find any samples in the Pindel configuration file '" + config + "'";
+        return -1;
+    }
+    return 0;
+}
+
+int load_pindel_inputs(const std::string &config, const std::string &reads_path, const std::vector<Chromosome> &genome,
+                       std::vector<SplitRead> &out, std::string &err)
+{
+    std::vector<std::string> files;
+    if (!config.empty() && read_pindel_config(config, files, err)) return -1;
+    if (!reads_path.empty()) files.push_back(reads_path);
+    for (const std::string &f : files)
+        if (load_pindel_text(f, genome, out, err)) return -1;
+    return 0;
+}
+
 int load_pindel_text(const std::string &path, const std::vector<Chromosome> &genome,
                      std::vector<SplitRead> &out, std::string &err)
 {
     // Three lines per record, taken in order from the top whatever they contain (PindelReadReader: getline x 3); the
     // list ends at an empty name line or at an incomplete record.  The file is read in one piece, cut into lines,
     // and the records are parsed on several threads; the first malformed record (in file order) is the error.
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) {
-        err = "cannot open " + path;
-        return -1;
-    }
     std::string buf;
-    {
+    if (path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0) {
+        if (read_gzip_file(path, buf, err)) return -1;
+    } else {
+        FILE *f = fopen(path.c_str(), "rb");
+        if (!f) {
+            err = "cannot open " + path;
+            return -1;
+        }
         char tmp[1 << 16];
         size_t k;
         fseeko(f, 0, SEEK_END);

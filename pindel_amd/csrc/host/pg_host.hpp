@@ -21,6 +21,7 @@
 
 #include <cstdint>
 #include <map>
+#include <memory>
 #include <set>
 #include <fstream>
 #include <functional>
@@ -64,6 +65,8 @@ struct Chromosome {
     std::string seq;              // spacer + sequence + spacer
 };
 
+class GermlineDepth;              // pg_depth.hpp: the BAMs a -N run measures read depth in
+
 struct Settings {                 // the flags the downstream steps read (src/fn_parameters.cpp)
     unsigned spacer = 100000;
     unsigned NumRead2ReportCutOff = 1;   // -M
@@ -80,14 +83,31 @@ struct Settings {                 // the flags the downstream steps read (src/fn
     bool only_close_mapped = false;      // -S: close end + _CloseEndMapped only, no far end, no SV search
     bool close_mapped_output() const { return report_close_mapped || only_close_mapped; }
     bool report_interchromosomal = false; // -I: <prefix>_INT per window and <prefix>_INT_final at the end of the run
+    // -N (--NormalSamples): IsGoodTD / IsGoodINV's germline filter.  It only acts on reads that come from BAMs
+    // (the reference returns true early for -p and -P): `germline` holds those BAMs and is null for text input.
+    bool NormalSamples = false;
+    std::shared_ptr<const GermlineDepth> germline;
+    bool germline_filter() const { return NormalSamples && germline; }
 };
 
 int load_fasta(const std::string &path, std::vector<Chromosome> &out, unsigned spacer, std::string &err);
 
-// Pindel-text reads (3 lines per read).  Trailing non-alphanumerics of SEQ are stripped
-// (setUnmatchedSeq).  Reads on unknown chromosomes are kept with chr_id = -1.
+// Pindel-text reads (3 lines per read), appended to `out`.  Trailing non-alphanumerics of SEQ are stripped
+// (setUnmatchedSeq).  Reads on unknown chromosomes are kept with chr_id = -1.  A name longer than three
+// characters that ends in ".gz" is read through zlib (getLineReaderByFilename, src/pindel.cpp:740-751), all
+// members of the file; one that does not inflate is an error.
 int load_pindel_text(const std::string &path, const std::vector<Chromosome> &genome,
                      std::vector<SplitRead> &out, std::string &err);
+
+// -P (readPindelConfigFile, src/pindel.cpp:705-737): the first token of every line of `config` is a Pindel-text
+// file, the rest of the line is ignored; a last line without a newline counts (the reference drops it).  A relative
+// name is tried as given and then relative to the configuration's directory.  Non-zero: the configuration cannot
+// be read, lists no file, or lists one that does not exist (err names both).
+int read_pindel_config(const std::string &config, std::vector<std::string> &files, std::string &err);
+// The reads of a run: the files of the -P configuration in order, then the -p file (src/reader.cpp:1469-1483);
+// either may be empty.
+int load_pindel_inputs(const std::string &config, const std::string &reads_path, const std::vector<Chromosome> &genome,
+                       std::vector<SplitRead> &out, std::string &err);
 
 std::string reverse_complement(const std::string &s);
 

@@ -13,6 +13,7 @@
 #include "pg_bam.hpp"
 #include "pg_bdhints.hpp"
 #include "pg_dd.hpp"
+#include "pg_depth.hpp"
 #include "pg_host.hpp"
 #include "pg_host_priv.hpp"
 #include "pg_pipeline.hpp"
@@ -44,6 +45,9 @@ struct pgh_settings {
     const char *include_bed;     /* -j: NULL or "" = none */
     const char *exclude_bed;     /* -J: NULL or "" = none */
     int32_t report_interchromosomal; /* -I: also write <prefix>_INT and <prefix>_INT_final */
+    int32_t normal_samples;      /* -N: the germline filter of _TD and _INV (acts with bam_config only) */
+    const char *bam_config;      /* NULL or "" = the reads are text input; else the -i configuration they were derived from */
+    const char *pindel_config;   /* -P: NULL or "" = none; else its files are read before reads_path */
 };
 
 static std::string str_or_empty(const char *s) { return s ? s : ""; }
@@ -54,6 +58,10 @@ static std::string str_or_empty(const char *s) { return s ? s : ""; }
  * empty range) and the rc flags, then walks chromosomes and 5-Mbp bins like main()
  * (pindel.cpp:1778-1989) and appends <prefix>_D, _SI, _TD, _INV -- and _LI / _CloseEndMapped when
  * analyze_li / report_close_mapped are set, _INT and _INT_final when report_interchromosomal is.  region / include_bed / exclude_bed: the region plan (pg_region.hpp).
+ * pindel_config (-P): its files are read first, then reads_path (which may then be NULL or ""); the point arrays cover
+ * the concatenated reads in load order.  normal_samples with bam_config: the reads are taken as derived from the BAMs
+ * of that -i configuration, so IsGoodTD / IsGoodINV filter as they do for BAM input and read depth comes from those
+ * BAMs (pg_depth.hpp); without bam_config the reads are text input and -N changes nothing, as in the reference.
  */
 int pgh_call_from_points(const char *fasta_path, const char *reads_path, const char *out_prefix,
                          const pgh_settings *st, uint32_t n_reads,
@@ -63,7 +71,7 @@ int pgh_call_from_points(const char *fasta_path, const char *reads_path, const c
     std::vector<Chromosome> genome;
     if (load_fasta(fasta_path, genome, st->spacer, g_err)) return -1;
     std::vector<SplitRead> all;
-    if (load_pindel_text(reads_path, genome, all, g_err)) return -1;
+    if (load_pindel_inputs(str_or_empty(st->pindel_config), str_or_empty(reads_path), genome, all, g_err)) return -1;
     if (all.size() != n_reads) {
         g_err = "read count mismatch between the read file and the point arrays";
         return -1;
@@ -82,6 +90,11 @@ int pgh_call_from_points(const char *fasta_path, const char *reads_path, const c
     S.report_close_mapped = st->report_close_mapped != 0;
     S.report_interchromosomal = st->report_interchromosomal != 0;
     memcpy(S.max_mismatch, st->max_mismatch, sizeof S.max_mismatch);
+    S.NormalSamples = st->normal_samples != 0;
+    if (S.NormalSamples && st->bam_config && st->bam_config[0]) {
+        std::vector<BamSource> bams;
+        if (!read_bam_config(st->bam_config, bams, g_err) || !(S.germline = open_germline(bams, g_err))) return -1;
+    }
     std::vector<RegionRecord> plan;
     if (region_plan(chromosome_names(genome), chromosome_sizes(genome, read_fai(fasta_path, genome), S.spacer), str_or_empty(st->region),
                     str_or_empty(st->include_bed), str_or_empty(st->exclude_bed), plan, g_err))
@@ -111,6 +124,46 @@ int pgh_call_from_points(const char *fasta_path, const char *reads_path, const c
     };
     return run_pipeline(genome, plan, all, S, out_prefix, attach, pgh::NoFarSearch(), g_err);
 }
+
+/*
+ * Average read depth of [beg, end) (0-based) of chromosome chr_name in one BAM, as the reference's bam2depth counts it
+ * (pg_depth.hpp): 0 when the BAM's header lacks the chromosome, NaN for an empty region.  0 = done, -1 = the file
+ * cannot be read (pgh_last_error).
+ */
+int pgh_region_depth(const char *bam_path, const char *chr_name, int64_t beg, int64_t end, double *avg)
+{
+    BamFile bam;
+    if (!bam.open(bam_path, g_err)) return -1;
+    DepthSums d;
+    d.add(beg, end);
+    if (!depth_sums(bam, chr_name, d)) {
+        g_err = std::string(bam_path) + ": BAM read failed";
+        return -1;
+    }
+    *avg = d.avg(0);
+    return 0;
+}
+
+/*
+ * getRelativeCoverageInternal: per BAM the depth of the event [start, end) against its two flanks of the same length,
+ * clipped to [0, chr_size): 2 * (2 * sv) / (before + after), -1 when before + after == 0, NaN when a flank has no length.
+ */
+int pgh_depth_ratio(int32_t n_bams, const char *const *bam_paths, const char *chr_name, int64_t chr_size, int64_t start, int64_t end,
+                    double *ratio)
+{
+    for (int32_t k = 0; k < n_bams; k++) {
+        BamFile bam;
+        if (!bam.open(bam_paths[k], g_err)) return -1;
+        if (!depth_ratio(bam, chr_name, chr_size, start, end, ratio[k])) {
+            g_err = std::string(bam_paths[k]) + ": BAM read failed";
+            return -1;
+        }
+    }
+    return 0;
+}
+
+/* IsGoodTD's rule on the ratios of the measured BAMs (reporter.cpp:1141-1152): 1 = the event is kept */
+int pgh_depth_rule_td(int32_t n, const double *ratio) { return depth_rule_td(ratio, n > 0 ? (size_t)n : 0) ? 1 : 0; }
 
 /*
  * The region plan of -c region -j include_bed -J exclude_bed (any may be NULL or "") on the reference fasta_path (its

@@ -8,6 +8,7 @@
 #include <fstream>
 #include <sstream>
 
+#include "pg_depth.hpp"
 #include "pg_host_priv.hpp"
 
 namespace pgh {
@@ -226,8 +227,14 @@ void Caller::sort_output_td(Ctx &c, std::vector<std::vector<unsigned>> &boxes, b
         close_event();
         for (const Ev &ev : evs) {
             if (ev.e - ev.s + 1 < S.NumRead2ReportCutOff) continue;
-            // IsGoodTD (reporter.cpp:1093-1155) for Pindel-text / points input
+            // IsGoodTD (reporter.cpp:1093-1155); beyond its first two tests it only acts under -N on BAM-derived reads
             if (ev.re < ev.rs || ev.rs == 0) continue;
+            if (S.germline_filter() && ev.re - ev.rs >= (unsigned)(good[0].getReadLength() * 2)) {
+                // (good[0]: the first read of the box's list, not of the event -- GoodIndels[0], reporter.cpp:1113)
+                std::set<std::string> tags;                  // UpdateSampleID: the samples among the event's reads
+                for (unsigned i = ev.s; i <= ev.e; i++) tags.insert(good[i].Tag);
+                if (!S.germline->good_td(c.chrom->name, (int64_t)c.chrom->seq.size() - 2 * (int64_t)S.spacer, ev.rs, ev.re, tags)) continue;
+            }
             if (good[ev.s].IndelSize < S.BalanceCutoff || report_event(good, ev.s, ev.e)) {
                 output_td(c, good, ev.s, ev.e, ev.rs, ev.re);
             }
@@ -587,7 +594,11 @@ void Caller::sort_output_inv(Ctx &c, std::vector<std::vector<unsigned>> &boxes, 
         if (whether) evs.push_back({ cs, ce, cbl, cbr });
         for (const Ev &ev : evs) {
             if (ev.e - ev.s + 1 < S.NumRead2ReportCutOff) continue;
-            if (ev.re < ev.rs || ev.rs == 0) continue;          // IsGoodINV, text/points input
+            if (ev.re < ev.rs || ev.rs == 0) continue;          // IsGoodINV (output_sorter.cpp:264-369)
+            // ... under -N on BAM-derived reads: an event of two read lengths or more needs >= 5 supporting pairs on each
+            // side among Reads_RP_Discovery -- a list UpdateBD has emptied by then (bddata.cpp:733; never filled with
+            // -R false), so none is ever counted and the event is dropped
+            if (S.germline_filter() && ev.re - ev.rs >= (unsigned)good[ev.s].getReadLength() * 2) continue;
             if (good[ev.s].IndelSize < S.BalanceCutoff || report_event(good, ev.s, ev.e))
                 output_inv(c, good, ev.s, ev.e, ev.rs, ev.re);
         }

@@ -18,6 +18,7 @@
 
 #include "pg_bam.hpp"
 #include "pg_bdhints.hpp"
+#include "pg_depth.hpp"
 #include "pg_host.hpp"
 #include "pg_region.hpp"
 #include "pg_rp.hpp"
@@ -65,6 +66,20 @@ inline void release_reads(std::vector<SplitRead> &v)
         }
     });
     std::vector<SplitRead>().swap(v);
+}
+
+// The end of a run with the germline filter: its PGH_TIMING figure, and a BAM it could not read is the run's error
+inline int germline_done(const Settings &S, bool timing, std::string &err)
+{
+    if (!S.germline_filter()) return 0;
+    if (timing)
+        fprintf(stderr, "pgh timing: germline filter %.3f s (read depth of %zu BAM regions, summed over the reporter threads)\n",
+                S.germline->seconds(), S.germline->queries());
+    if (!S.germline->error().empty()) {
+        err = "germline filter: " + S.germline->error();
+        return -1;
+    }
+    return 0;
 }
 
 // The two seams, in the reference's order (src/pindel.cpp:1816-1888):
@@ -198,7 +213,7 @@ int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<Region
         fprintf(stderr, "pgh timing: pipeline: copy reads %.3f s, search step %.3f s, keep %.3f s, classify + report %.3f s, free %.3f s\n",
                 t_copy, t_search, t_keep, t_call, t_free);
     if (li_seconds) *li_seconds = caller.li_seconds;
-    return 0;
+    return germline_done(S, timing, err);
 }
 
 // BAM input (`-i config`): main()'s loop with get_SR_Reads per window (src/pindel.cpp:1816-1982,
@@ -234,6 +249,20 @@ inline bool read_bam_config(const std::string &config, std::vector<BamSource> &b
         return false;
     }
     return true;
+}
+
+// -N: the BAMs of the configuration as the germline filter measures them (pg_depth.hpp); null with err set when one
+// cannot be opened
+inline std::shared_ptr<const GermlineDepth> open_germline(const std::vector<BamSource> &bams, std::string &err)
+{
+    std::vector<std::string> paths, tags;
+    for (const BamSource &b : bams) {
+        paths.push_back(b.path);
+        tags.push_back(b.tag);
+    }
+    std::shared_ptr<GermlineDepth> g(new GermlineDepth());
+    if (!g->open(paths, tags, err)) return nullptr;
+    return g;
 }
 
 // The close end of one window of the BAM path, straight on the ingested structure-of-arrays batch (no SplitRead per
@@ -462,7 +491,8 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<Re
                 now() - t_begin, t_wait, t_close, t_keep, t_far, t_cov, t_call, t_free, t_rp, t_rp_inter, t_ingest,
                 ingest_timing().inflate_decode, ingest_timing().select, ingest_timing().layout);
     if (li_seconds) *li_seconds = caller.li_seconds;
-    return status;
+    const int grc = germline_done(S, timing, err);
+    return status ? status : grc;
 }
 
 }  // namespace pgh

@@ -1,18 +1,21 @@
 // pindel_pg -- command line with Pindel's flags for the path this repository implements:
-//   pindel_pg -f ref.fa -p reads.txt -o prefix [-x 2 -a 1 -m 3 -u 0.02 -e 0.01 -E 0.95 -H 8
+//   pindel_pg -f ref.fa (-p reads.txt[.gz] | -P text_config | -i bam_config) -o prefix
+//                                              [-x 2 -a 1 -m 3 -u 0.02 -e 0.01 -E 0.95 -H 8
 //                                               -M 1 -B 100 -d 30 -v 50 -w 5 -G device -l -s -S -I
-//                                               -c ALL|chr[:start[-end]] -j include.bed -J exclude.bed]
+//                                               -c ALL|chr[:start[-end]] -j include.bed -J exclude.bed -N]
 // FASTA + Pindel-text reads -> close/far-end search on the MI355X (C ABI, libpindel_pg.so)
 // -> SV classification and <prefix>_D/_SI/_TD/_INV reports (host code in this directory);
 // -l adds <prefix>_LI (long insertions), -s <prefix>_CloseEndMapped (the reads with a close end),
 // -S writes <prefix>_CloseEndMapped only (no far end, no SV search); -q adds <prefix>_DD (dispersed duplications, BAM input,
 // pg_dd.hpp); -I adds <prefix>_INT and <prefix>_INT_final (interchromosomal events, pg_host_int.cpp: far ends on other chromosomes
-// need window hints, i.e. BAM input with -R or `-b file --bd-hints on`).  Like the reference, every run
+// need window hints, i.e. BAM input with -R or `-b file --bd-hints on`).  -P lists Pindel-text files, one per line (read before a
+// -p file when both are given); a text file whose name ends in .gz is read through zlib.  -N (--NormalSamples) turns on the
+// germline filter of _TD and _INV for BAM input (pg_depth.hpp); for text input it changes nothing.
+// Like the reference, every run
 // creates all seven files (_D _SI _TD _INV _LI _BP _CloseEndMapped); _BP stays empty, as the
 // reference's breakpoint report is not called.  -c, -j and -J select the regions searched (pg_region.hpp); they are
 // checked before the first device call (exit status 2 for -c syntax, 1 for an unreadable file or an unknown chromosome).
-// Flags and their defaults follow src/fn_parameters.cpp; BAM input (-i) needs htslib and is
-// not built here.
+// Flags and their defaults follow src/fn_parameters.cpp; BAM input (-i) is read without htslib (pg_bam.hpp).
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
@@ -44,7 +47,7 @@ int main(int argc, char **argv)
 {
     const double t_start = now_s();
     double t_search = 0.0;
-    std::string fasta, reads_path, prefix, bd_path, bam_config;
+    std::string fasta, reads_path, prefix, bd_path, bam_config, pindel_config;
     std::string region, include_bed, exclude_bed;           // -c, -j, -J
     unsigned min_anchor_quality = 0;
     int ref_read_nm = 2;                    // -n / --NM (isRefRead)
@@ -62,7 +65,8 @@ int main(int argc, char **argv)
     // run; they are accepted and ignored; anything else is an error, and so is a value that is not a number.
     struct Flag { const char *sh, *lg; char kind; };      // kind: i int, f float, s string, u unary
     static const Flag flags[] = {
-        { "-f", "--fasta", 's' }, { "-p", "--pindel-file", 's' }, { "-i", "--config-file", 's' }, { "-o", "--output-prefix", 's' },
+        { "-f", "--fasta", 's' }, { "-p", "--pindel-file", 's' }, { "-P", "--pindel-config-file", 's' },
+        { "-i", "--config-file", 's' }, { "-o", "--output-prefix", 's' },
         { "-x", "--max_range_index", 'i' }, { "-a", "--additional_mismatch", 'i' },
         { "-m", "--min_perfect_match_around_BP", 'i' }, { "-u", "--maximum_allowed_mismatch_rate", 'f' },
         { "-e", "--sequencing_error_rate", 'f' }, { "-E", "--sensitivity", 'f' }, { "-H", "--min_close", 'i' },
@@ -106,8 +110,9 @@ int main(int argc, char **argv)
             else if (key == "-S") S.only_close_mapped = on;
             else if (key == "-I") S.report_interchromosomal = on;
             else if (key == "-q") detect_dd = true;
+            else if (key == "-N") S.NormalSamples = on;
             else if (key == "--DD_REPORT_DUPLICATION_READS") dd.report_dup_reads = on;
-            // -k, -C (and -N): reports / searches outside this program's scope, accepted and ignored
+            // -k, -C: reports / searches outside this program's scope, accepted and ignored
             continue;
         }
         if (i + 1 >= argc) {
@@ -132,6 +137,7 @@ int main(int argc, char **argv)
         }
         if (key == "-f") fasta = v;
         else if (key == "-p") reads_path = v;
+        else if (key == "-P") pindel_config = v;
         else if (key == "-i") bam_config = v;
         else if (key == "-A") min_anchor_quality = (unsigned)iv;
         else if (key == "-n") ref_read_nm = (int)iv;       // "-n" is registered twice in the reference; --NM comes first
@@ -202,9 +208,23 @@ int main(int argc, char **argv)
             return 2;
         }
     }
-    if (fasta.empty() || (reads_path.empty() == bam_config.empty()) || prefix.empty()) {
-        fprintf(stderr, "usage: pindel_pg -f ref.fa (-p reads.txt | -i bam_config.txt) -o prefix [options]\n");
+    const bool text_input = !reads_path.empty() || !pindel_config.empty();
+    if (text_input && !bam_config.empty()) {
+        fprintf(stderr, "pindel_pg: mixed input is not supported: give either BAM input (-i) or Pindel-text input (-p, -P), not both\n");
         return 2;
+    }
+    if (fasta.empty() || (!text_input && bam_config.empty()) || prefix.empty()) {
+        fprintf(stderr, "usage: pindel_pg -f ref.fa (-p reads.txt[.gz] | -P text_config.txt | -i bam_config.txt) -o prefix [options]\n");
+        return 2;
+    }
+    // -P: the list of text files is checked before anything is written and before any device is touched
+    if (!pindel_config.empty()) {
+        std::vector<std::string> listed;
+        std::string perr;
+        if (read_pindel_config(pindel_config, listed, perr)) {
+            fprintf(stderr, "pindel_pg: %s\n", perr.c_str());
+            return 1;
+        }
     }
     // TestFileForOutput (pindel.cpp:932-938): every output file exists, empty, from the start
     // (... and with -I its two files: <prefix>_INT is truncated here, where the reference only ever appends to it)
@@ -240,7 +260,7 @@ int main(int argc, char **argv)
     }
     for (const RegionRecord &r : plan) printf("Processing region: %s\t%u\t%u\n", genome[r.chr].name.c_str(), r.start, r.end);
     std::vector<SplitRead> all;
-    if (!reads_path.empty() && load_pindel_text(reads_path, genome, all, err)) {
+    if (text_input && load_pindel_inputs(pindel_config, reads_path, genome, all, err)) {
         fprintf(stderr, "pindel_pg: %s\n", err.c_str());
         return 1;
     }
@@ -250,6 +270,12 @@ int main(int argc, char **argv)
         fprintf(stderr, "pindel_pg: %s\n", err.c_str());
         return 1;
     }
+    // -N: IsGoodTD / IsGoodINV filter only when the reads come from BAMs (they return true early for -p and -P)
+    if (S.NormalSamples && !bams.empty() && !(S.germline = open_germline(bams, err))) {
+        fprintf(stderr, "pindel_pg: %s\n", err.c_str());
+        return 1;
+    }
+    if (S.NormalSamples && bams.empty()) printf("pindel_pg: -N has no effect on Pindel-text input (as in Pindel)\n");
     std::vector<pg_ctx *> ctxs;
     int rc = 0;
     for (int d : devices) {

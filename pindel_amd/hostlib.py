@@ -5,6 +5,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -20,7 +21,8 @@ class HostSettings(C.Structure):
         ("window_mbp", C.c_double), ("max_mismatch", C.c_uint32 * 500),
         ("analyze_li", C.c_int32), ("report_close_mapped", C.c_int32),
         ("region", C.c_char_p), ("include_bed", C.c_char_p), ("exclude_bed", C.c_char_p),
-        ("report_interchromosomal", C.c_int32)]
+        ("report_interchromosomal", C.c_int32),
+        ("normal_samples", C.c_int32), ("bam_config", C.c_char_p), ("pindel_config", C.c_char_p)]
 
 
 class VcfOptions(C.Structure):
@@ -72,6 +74,10 @@ def lib():
         L.pgh_call_from_points.argtypes = [
             C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(HostSettings), C.c_uint32,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pgh_region_depth.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.POINTER(C.c_double)]
+        L.pgh_depth_ratio.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.c_char_p, C.c_int64, C.c_int64, C.c_int64,
+                                      C.POINTER(C.c_double)]
+        L.pgh_depth_rule_td.argtypes = [C.c_int32, C.POINTER(C.c_double)]
         L.pgh_region_plan.restype = C.c_int64
         L.pgh_region_plan.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64]
         L.pgh_vcf_default_options.argtypes = [C.POINTER(VcfOptions)]
@@ -98,6 +104,9 @@ def default_settings(max_mismatch) -> HostSettings:
     s.include_bed = None       # -j (None = no include list)
     s.exclude_bed = None       # -J (None = no exclude list)
     s.report_interchromosomal = 0  # -I (default false): <prefix>_INT and <prefix>_INT_final
+    s.normal_samples = 0       # -N (default false): the germline filter of _TD and _INV; acts with bam_config only
+    s.bam_config = None        # the -i configuration the reads were derived from (None = text input)
+    s.pindel_config = None     # -P (None = no list of Pindel-text files)
     for i in range(500):
         s.max_mismatch[i] = int(max_mismatch[i])
     return s
@@ -136,30 +145,76 @@ def _fasta_names(fasta):
     return out
 
 
+def region_depth(bam, chrom, beg, end):
+    """Average read depth of [beg, end) (0-based) of chromosome `chrom` in one BAM, counted as Pindel's bam2depth does
+    (pindel_amd/csrc/host/pg_depth.hpp): M/=/X bases of the reads that are not unmapped, secondary, QC-fail or duplicate,
+    MAPQ ignored, over end - beg.  0.0 when the BAM's header lacks the chromosome, NaN for an empty region."""
+    L = lib()
+    out = C.c_double(0.0)
+    if L.pgh_region_depth(_enc(bam), _enc(chrom), int(beg), int(end), C.byref(out)):
+        raise RuntimeError("pgh_region_depth: " + (L.pgh_last_error() or b"").decode())
+    return out.value
+
+
+def depth_ratio(bams, chrom, chrom_size, start, end):
+    """Per BAM the standardised depth of the event [start, end) against its two flanks of the same length, clipped to
+    [0, chrom_size): 2 * (2 * sv) / (before + after); -1.0 when before + after == 0, NaN when a flank has no length
+    (getRelativeCoverageInternal).  Returns a list of floats in the order of `bams`."""
+    L = lib()
+    paths = (C.c_char_p * len(bams))(*[_enc(b) for b in bams])
+    out = (C.c_double * len(bams))()
+    if L.pgh_depth_ratio(len(bams), paths, _enc(chrom), int(chrom_size), int(start), int(end), out):
+        raise RuntimeError("pgh_depth_ratio: " + (L.pgh_last_error() or b"").decode())
+    return list(out)
+
+
+def depth_rule_td(ratios):
+    """-N's decision on a tandem duplication from the ratios of the BAMs measured for it (IsGoodTD): True = kept."""
+    arr = (C.c_double * len(ratios))(*[float(r) for r in ratios])
+    return bool(lib().pgh_depth_rule_td(len(ratios), arr))
+
+
 def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pts, far_off, far_pts,
-                     rc_flag, region=None, include_bed=None, exclude_bed=None):
+                     rc_flag, region=None, include_bed=None, exclude_bed=None, reads_config=None, normal_samples=None,
+                     bam_config=None):
     """Classify + report (_D, _SI, _TD, _INV) from per-read UP_Close / UP_Far points (CSR over
     all reads of the file, 12-byte pg_point records).  settings.analyze_li / settings.report_close_mapped
     add <out_prefix>_LI / <out_prefix>_CloseEndMapped, settings.report_interchromosomal <out_prefix>_INT and
     <out_prefix>_INT_final (reads whose far points lie on another chromosome than their anchor).  region / include_bed / exclude_bed (-c, -j, -J)
-    override the settings' fields of the same names when given; by default the whole genome is searched."""
+    override the settings' fields of the same names when given; by default the whole genome is searched.
+    reads_config (-P): a file that lists Pindel-text files, one per line, or a list of such files; they are read in order
+    before reads_txt (which may then be None), and the point arrays cover the concatenated reads in load order.  A text file
+    whose name ends in .gz is read through zlib.  normal_samples (-N) with bam_config (an -i configuration): the reads are
+    taken as derived from those BAMs, and _TD / _INV pass the germline filter with read depth from them; without bam_config
+    -N changes nothing (text input).  Both override the settings' fields when given."""
     L = lib()
-    keep = [_enc(region), _enc(include_bed), _enc(exclude_bed)]     # (alive until the call returns)
-    if any(k is not None for k in keep):
+    tmp_cfg = None
+    if reads_config is not None and not isinstance(reads_config, (str, bytes, os.PathLike)):
+        with tempfile.NamedTemporaryFile("w", suffix=".pindel_config", delete=False) as f:
+            f.write("".join(f"{os.path.abspath(str(x))}\n" for x in reads_config))
+            tmp_cfg = reads_config = f.name
+    keep = [_enc(region), _enc(include_bed), _enc(exclude_bed), _enc(reads_config), _enc(bam_config)]     # (alive until the call returns)
+    if any(k is not None for k in keep) or normal_samples is not None:
         settings = HostSettings.from_buffer_copy(settings)
-        for field, v in zip(("region", "include_bed", "exclude_bed"), keep):
+        for field, v in zip(("region", "include_bed", "exclude_bed", "pindel_config", "bam_config"), keep):
             if v is not None:
                 setattr(settings, field, v)
+        if normal_samples is not None:
+            settings.normal_samples = int(bool(normal_samples))
     close_off = np.ascontiguousarray(close_off, dtype=np.uint64)
     far_off = np.ascontiguousarray(far_off, dtype=np.uint64)
     close_pts = np.ascontiguousarray(close_pts)
     far_pts = np.ascontiguousarray(far_pts)
     rc_flag = np.ascontiguousarray(rc_flag, dtype=np.uint8)
     assert close_pts.dtype.itemsize == 12 and far_pts.dtype.itemsize == 12
-    rc = L.pgh_call_from_points(str(fasta).encode(), str(reads_txt).encode(), str(out_prefix).encode(),
-                                C.byref(settings), len(close_off) - 1, close_off.ctypes.data,
-                                close_pts.ctypes.data, far_off.ctypes.data, far_pts.ctypes.data,
-                                rc_flag.ctypes.data)
+    try:
+        rc = L.pgh_call_from_points(str(fasta).encode(), _enc(reads_txt), str(out_prefix).encode(),
+                                    C.byref(settings), len(close_off) - 1, close_off.ctypes.data,
+                                    close_pts.ctypes.data, far_off.ctypes.data, far_pts.ctypes.data,
+                                    rc_flag.ctypes.data)
+    finally:
+        if tmp_cfg:
+            os.unlink(tmp_cfg)
     if rc:
         raise RuntimeError("pgh_call_from_points: " + (L.pgh_last_error() or b"").decode())
 
