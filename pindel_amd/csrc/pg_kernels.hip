@@ -40,10 +40,10 @@
 //     counters (every XCD works through a contiguous eighth of the batch: neighbouring reads share cache
 //     lines and reference windows in ONE L2).
 //
-// The kernel is bound by instruction issue, not by HBM -- vector and scalar together, the CU's one scalar unit first: in situ a
-// scalar instruction costs 1.65 ns of SIMD time, a vector one 0.8-1.1 (profiles/r03/ubench_issue_rates.txt,
-// profiles/r04/issue_calibration.txt, profiles/r04/component_instruction_counts.txt).  No MFMA: this is bit/byte comparison
-// work, not a contraction.
+// The kernel is bound by instruction issue, not by HBM.  What a read's time follows is the vector pipe (about 1500 instructions at
+// 2.0 to 3.2 cycles, seven waves per SIMD: 56-89 % busy); scalar work that sits between vector instructions of the same wave
+// lengthens that wave's chain, scalar work the other waves can overlap is close to free -- no fixed price per scalar instruction
+// holds (profiles/r06/).  No MFMA: this is bit/byte comparison work, not a contraction.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -1472,6 +1472,7 @@ __device__ __forceinline__ void scan_impl(const PgDevRef &ref, Search &S,
                                           u32 use_cache, u32 &cacheF, u32 &cacheB, u32 &cache_valid)
 {
     if (!Q.first_ok() || s >= e) return;
+    PG_STOP_AT(S, 33);
     const int k0 = (s - g0) >> PG_CHUNK_SHIFT, k1 = (e - 1 - g0) >> PG_CHUNK_SHIFT;   // floor
     for (int k = k0; k <= k1; k++) {
         const int cs = g0 + (k << PG_CHUNK_SHIFT);
@@ -1563,6 +1564,7 @@ __device__ __forceinline__ void scan_impl(const PgDevRef &ref, Search &S,
         // innermost far-end chunk are computed once for all nested ranges, and an earlier fill with the same
         // base (a close-end window that happens to start where this chunk starts) may be shorter.
         const int se = e_max < cs + (int)PG_CHUNK ? e_max : cs + (int)PG_CHUNK;
+        PG_STOP_AT(S, 34);
         if (!(wo == S.win_wo && S.wbase == wb && se + 64 * NB <= S.win_hi))
         {
             stage_window<NB>(ref, S, wo, wb, se + 64 * NB, lane);
@@ -1575,6 +1577,7 @@ __device__ __forceinline__ void scan_impl(const PgDevRef &ref, Search &S,
         const u32 rmask = (low32_lane(ne - pbase) & ~low32_lane(ns - pbase)) & ~(low32_lane(xe - pbase) & ~low32_lane(xs - pbase));
         const bool cached = use_cache && k == 0 && cache_valid != 0u;
         u32 mF = 0u, mB = 0u;
+        PG_STOP_AT(S, 37);
         if (cached) {
             mF = cacheF;
             mB = cacheB;
@@ -1656,6 +1659,56 @@ __device__ __forceinline__ void scan_range(const PgDevRef &ref, Search &S,
     else
         scan_impl<NB, NS, Id, false, false>(ref, S, Q, A, wo, g0, s, e, e_max, xs, xe, origin, region, lane,
                                         use_cache, cacheF, cacheB, cache_valid);
+}
+
+// ATTEMPT 0 OF THE CLOSE END ON THE WINDOW STAGED AT THE START OF THE READ: what scan_range does for it, as straight-line code.
+// Four reads in five stop at this attempt, and for it everything scan_range works out is known beforehand: the range [s, e) lies
+// in ONE chunk whose grid base is g0 (the pack kernel staged exactly that chunk: pack_block, "the first window fill"), so there is
+// no chunk loop and no residency test; nothing has been scanned yet, so there is no exclusion interval and no cached mask to
+// find; the anchor's strand -- one candidate kind -- is a constant of the caller's instance.  What is left: the one filter run,
+// the range mask, the prefix sum, the queue and the candidate pass.  keep: the masks are left for the retries exactly as
+// scan_impl leaves them (the read runs on the grid of the R = 1 window).  The caller checks the conditions (search_read).
+template <int NB, int NS, typename Id>
+__device__ __forceinline__ void scan_staged(Search &S, const Query<NB> &Q, Acc<NB, Id> &A, int g0, int s, int e, int origin,
+                                            int lane, u32 keep, u32 &cacheF, u32 &cacheB, u32 &cache_valid)
+{
+    const int wb = g0 - 64 * NB;
+    PG_STOP_AT(S, 33);
+    PG_STOP_AT(S, 34);
+    PG_STOP_AT(S, 13);
+    PG_STOP_AT(S, 37);
+    u32 mF = 0u, mB = 0u, unused;
+    if (Q.allowB()) seed_filter<NB, NS, false>(S, Q, true, false, lane, mB, unused);
+    else seed_filter<NB, NS, false>(S, Q, false, false, lane, mF, unused);
+    if (keep) { cacheF = mF; cacheB = mB; cache_valid = 1u; }
+    PG_STOP_AT(S, 14);
+    const u32 kb = Q.allowB() ? 1u : 0u;
+    const int pbase = g0 + 32 * lane;
+    u32 m = (mF | mB) & low32_lane(e - pbase) & ~low32_lane(s - pbase);       // (one kind: the other mask is 0)
+    const u32 cnt = (u32)__popc(m);
+    const u32 incl = wave_scan(cnt);
+    const int total = (int)read_lane(incl, 63);
+    int slot = (int)(incl - cnt);
+    PG_STOP_AT(S, 15);
+    for (int base = 0; base < total; base += PG_PASS(NB)) {
+        PG_SYNC();
+        const int top = base + PG_PASS(NB);
+        while (m != 0u && slot < top) {
+            const int bit = __ffs((int)m) - 1;
+            m &= m - 1u;
+            S.queue[slot - base] = (uint16_t)(((u32)(64 * NB + 32 * lane + bit) << 1) | kb);
+            slot++;
+        }
+        const int n = total - base < PG_PASS(NB) ? total - base : PG_PASS(NB);
+        S.nsurv += n;
+        S.nsurv_total += (u32)n;
+        PG_SYNC();
+        PG_T(S, S.t_base);
+        PG_STOP_AT(S, 16);
+        fold_candidates<NB, Id, false>(S, Q, A, wb, origin, 0u, n, lane, Rings{ false, 0, 0, 0, 0 }, nullptr);
+        PG_STOPPED(S);
+        PG_T(S, S.t_base + 1);
+    }
 }
 
 // ---------------------------------------------------------------------------------
@@ -2045,7 +2098,7 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
             // compile-time constant (no orientation swap, no continued state, R = 0 folded into the window arithmetic: -44 vector and
             // -20 scalar instructions per read, -1.1 %) and, for that instance, the anchor's strand too (the candidate kind: another
             // -11 / -6, -0.6 %); attempts 1..3 as a loop.  Returns true when the attempt found points.
-            auto attempt = [&](const int att, const bool plus_k) __attribute__((always_inline)) -> bool {
+            auto attempt = [&](const int att, const bool plus_k, const bool staged = false) __attribute__((always_inline)) -> bool {
                 const int Rg = att >> 1;
 #ifdef PG_TIMING
                 PG_T(S, S.t_base + 2);
@@ -2091,6 +2144,9 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                 // of the R = 1 window
                 const bool own_grid = att == 0 && !shared_grid;
                 PG_STOP_AT_V(S, 12, true);
+                if (staged)       // (attempt 0 on the window the read started with: see scan_staged)
+                    scan_staged<NB, NS, Id>(S, Q, A, own_grid ? s1 : w1s, s1, e1, w1s, PG_LANE, shared_grid, cr0, cr1, vr);
+                else
                 scan_range<NB, NS, Id, !DEF>(ref, S, Q, A, chr_wo, own_grid ? s1 : w1s, s1, e1, own_grid ? e1 : w1e, ps, pe, w1s, 0u,
                                    PG_LANE, (att == 1 || att == 2 ? 1u : 0u) | shared_grid, cr0, cr1, vr);
                 PG_STOPPED_V(S, true);
@@ -2140,8 +2196,29 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                 }
                 return false;
             };
-            if (!(plus ? attempt(0, true) : attempt(0, false)))
-                for (int att = 1; att < 4; att++)
+            // Attempt 0 as straight-line code (scan_staged) when the window staged at the start of the read is the whole of its chunk --
+            // there is one (stage_s < stage_e: InsertSize > 0), attempt 0's range does not exceed a chunk (on the shared grid by
+            // definition; on its own grid InsertSize <= PG_CHUNK) -- and the first consumed base is one of ACGT.  Any other read takes
+            // attempt 0 through the retries' generic body, whose attempt number is a run-time value.  (Not in the EXACT instantiation:
+            // its reads change length between the attempts.)
+#if defined(PG_NO_SETUP_FAST) || defined(PG_DUP)       // (ablation; the duplication diagnostics sit in the generic path)
+            const bool staged0 = false;
+#else
+            const bool staged0 = !EXACT && (int)ra[2] < (int)ra[3] && isz <= (int)PG_CHUNK && (flags & PG_RF_FIRST_OK_REV) != 0u;
+#endif
+            bool found = false;
+            int att0 = 0;
+#ifdef PG_NO_SETUP_FAST
+            found = plus ? attempt(0, true) : attempt(0, false);
+            att0 = 1;
+#else
+            if (staged0) {
+                found = plus ? attempt(0, true, true) : attempt(0, false, true);
+                att0 = 1;
+            }
+#endif
+            if (!found)
+                for (int att = att0; att < 4; att++)
                     if (attempt(att, plus != 0u)) break;
             PG_STOPPED(S);
         }
@@ -2199,6 +2276,7 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
             asm volatile("s_load_dwordx4 %0, %1, 0x30\n\ts_waitcnt lgkmcnt(0)" : "=&s"(rc) : "s"(record_ptr<7>(KA(B, in), rid)));
             const int chr_size = (int)rc[0];
             S.jmask[1] = rc[3];
+            PG_STOP_AT(S, 35);
             int far_bases = 0;
             // a search window's result replaces UP_Far if its MaxLen is >= (NewUPFarIsBetter, farend_searcher.cpp:30-44)
             auto far_update = [&](int origin, const pg_window *bdw, int qmask) {
@@ -2279,8 +2357,17 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                 const int maxspan = 64 << (2 * k_mri);
                 const int origin = center - maxspan;
                 const int g0 = center - (int)PG_CHUNK / 2;
+                // NO CLIPPING (nearly every read): the widest range keeps clear of the spacers at both chromosome ends, and then so does
+                // every range -- one test instead of a compare / select pair per bound.  (reach >= k_spacer: the sum did not wrap; every
+                // sum range_of forms for a span <= maxspan is then below chr_size, its compares hold, and it yields center -/+ span.)
+                const u32 reach = (u32)maxspan + k_spacer;
+#if defined(PG_NO_SETUP_FAST) || defined(PG_NO_FAR_NOCLIP)       // (ablations)
+                const bool noclip = false;
+#else
+                const bool noclip = reach >= k_spacer && (u32)center > reach && (u32)chr_size > reach && (u32)center < (u32)chr_size - reach;
+#endif
                 int emax;
-                if ((u32)center + (u32)maxspan + k_spacer < (u32)chr_size) emax = center + maxspan;
+                if (noclip || (u32)center + (u32)maxspan + k_spacer < (u32)chr_size) emax = center + maxspan;
                 else emax = chr_size - (int)k_spacer;
                 u32 cacheF = 0u, cacheB = 0u;                    // seed-filter masks of the innermost chunk
                 u32 cache_valid = 0u;
@@ -2295,6 +2382,7 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                     else e = chr_size - (int)k_spacer;
                 };
                 int r_first = 0;
+                PG_STOP_AT(S, 36);
 #ifndef PG_NO_FUSED_RANGES
                 // FUSED RANGES.  The ranges that lie in the innermost chunk (spans 64, 256, 1024) share ONE candidate pass:
                 // the survivors of the whole chunk are queued at once, the pass keeps the rings apart (Rings), and the
@@ -2306,7 +2394,9 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                     int rs[3], re[3];
 #pragma unroll
                     for (int r = 0; r < 3; r++) {
-                        range_of(64 << (2 * (r < R ? r : R)), rs[r], re[r]);
+                        const int span = 64 << (2 * (r < R ? r : R));
+                        if (noclip) { rs[r] = center - span; re[r] = center + span; }
+                        else range_of(span, rs[r], re[r]);
                         rs[r] = uni(rs[r]);
                         re[r] = uni(re[r]);
                     }

@@ -1,12 +1,14 @@
 #!/bin/bash
 # Diagnostics (GPU box): PMC instruction counts per read of the stop-ladder builds, one process / one rocprofv3 pass.
 #   scripts/ladder_run.sh <tag> [reads]     -> gpurun_out/<tag>/ladder.txt
+#   PREFIX=nf_: the builds of that family (build_ladder.sh)
 tag=${1:-ladder}; reads=${2:-1000000}
 root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/$tag; mkdir -p "$out"
-names="plain"; libs="$root/pindel_amd/libpindel_pg_plain.so"
-for k in ${PTS:-1 10 11 12 13 14 15 16 17 18 19 20 21 22 23 24 25 26 27 28 29 30 31 32}; do
-    [ -f "$root/pindel_amd/libpindel_pg_stop$k.so" ] && { names="$names stop$k"; libs="$libs $root/pindel_amd/libpindel_pg_stop$k.so"; }
+pre=${PREFIX:-}
+names="${pre}plain"; libs="$root/pindel_amd/libpindel_pg_${pre}plain.so"
+for k in ${PTS:-1 10 11 12 33 34 13 37 14 15 16 17 18 19 20 21 22 35 36 23 24 25 26 27 28 29 30 31 32}; do
+    [ -f "$root/pindel_amd/libpindel_pg_${pre}stop$k.so" ] && { names="$names ${pre}stop$k"; libs="$libs $root/pindel_amd/libpindel_pg_${pre}stop$k.so"; }
 done
 export TMPDIR=/tmp PG_LAUNCHES=2
 cd /tmp || exit 1
