@@ -261,21 +261,16 @@ struct pg_device_batch {
     uint16_t *close_max = nullptr;
     uint64_t *bd_off = nullptr;
     pg_window *bd = nullptr;
-    uint32_t *close_off = nullptr, *close_cnt = nullptr, *far_off = nullptr, *far_cnt = nullptr;
-    uint32_t *alg = nullptr;
     PgInRec *in_rec = nullptr;         // packed per-read records the kernel reads / writes (pg_device.h)
     uint32_t ref_epoch = 0;            // pg_ctx::ref_epoch when the records were packed (a reload of the reference: pack again)
     uint64_t *planes = nullptr;        // the reads as bit planes (PgDevBatch::planes)
     PgOutRec *out_rec = nullptr;
-    bool unpacked = true;              // the SoA output arrays reflect out_rec
     bool in_arena = false;             // buffers belong to the ctx arena (not freed one by one)
     bool pool_owned = false;           // ... except a run pool that had to be regrown
     pg_run *pool = nullptr;
     uint32_t pool_shard_cap = 0;       // runs per shard (PG_POOL_SHARDS shards)
     uint32_t *pool_used = nullptr;     // [PG_POOL_SHARDS * 16]
     unsigned long long *run_tot = nullptr;   // running totals of the chunked delivery (zeroed with the outputs)
-    uint64_t runs_used = 0;            // total runs of the last search
-    int modes_done = 0;
     // reads with a character outside ACGTN, listed by the pack kernel for the exact kernel (pg_search_exact_kernel)
     uint32_t *exact_list = nullptr;    // [n]
     uint32_t *exact_count = nullptr;   // device counter (zeroed with the outputs / before a pack of the whole batch)
@@ -296,7 +291,6 @@ struct pg_result {
     HostBuf<uint8_t> rc_flag;
     HostBuf<uint32_t> close_last;
     HostBuf<uint16_t> close_max;
-    HostBuf<uint32_t> csr32[2];        // staging of the device-built 32-bit offsets
 };
 
 namespace {
@@ -441,8 +435,7 @@ void free_batch_buffers(pg_device_batch *b)
         return;
     }
     void *ptrs[] = { b->planes, b->seq, b->seq_off, b->strand, b->pos, b->isz, b->chr, b->rc_flag,
-                     b->close_last, b->close_max, b->bd_off, b->bd, b->close_off, b->close_cnt,
-                     b->far_off, b->far_cnt, b->alg, b->pool, b->pool_used, b->in_rec, b->out_rec, b->run_tot,
+                     b->close_last, b->close_max, b->bd_off, b->bd, b->pool, b->pool_used, b->in_rec, b->out_rec, b->run_tot,
                      b->exact_list, b->exact_count, b->d_soa };
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -659,8 +652,16 @@ int validate_and_measure(pg_ctx *ctx, const pg_read_batch *reads, uint32_t *max_
 }
 
 // Runs per list the chunked delivery of search_host has room for (1.04 per read on average; a batch that needs more
-// falls back to the whole-batch download).
+// falls back to download(), which scans the whole batch first and sizes its buffers from the totals).
 static size_t deliver_cap(size_t n) { return env().tiny_delivery ? n / 2 + 8 : 2 * n + 4096; }   // (tests: force the fallback)
+// Reads per chunk of download() (PG_HOST_CHUNK: several chunks on a small batch), and the bytes of its device temporaries but
+// the gathered runs: per-read sums, 64-bit offsets (2 lists), per-block sums (one slice of blocks per chunk), 64 B of info per chunk
+static size_t download_chunk() { return env().host_chunk ? env().host_chunk : PG_DELIVER_CHUNK; }
+static size_t download_scratch_bytes(size_t n)
+{
+    const size_t chunk = download_chunk(), n_chunks = (n + chunk - 1) / chunk;
+    return 3 * n * 8 + n_chunks * ((chunk + 255) / 256) * 8 + n_chunks * 64 + 5 * 512;
+}
 
 // Validates the batch and allocates its device buffers.  copy = true also copies the inputs
 // (synchronously); otherwise the caller streams them in (search_host).  off = read offsets rebased to 0.
@@ -707,8 +708,6 @@ int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint
         { (void **)&b->pool, (size_t)b->pool_shard_cap * PG_POOL_SHARDS * sizeof(pg_run) },
         // ---- zero-initialised from here
         { (void **)&b->rc_flag, n1 }, { (void **)&b->close_last, n1 * 4 }, { (void **)&b->close_max, n1 * 2 },
-        { (void **)&b->close_off, n1 * 4 }, { (void **)&b->close_cnt, (n + 1) * 4 },   // + 1: the CSR scan runs over n + 1 counts
-        { (void **)&b->far_off, n1 * 4 }, { (void **)&b->far_cnt, (n + 1) * 4 }, { (void **)&b->alg, n1 * 4 },
         { (void **)&b->out_rec, n1 * sizeof(PgOutRec) },
         // run-pool cursors, then per set of read counters (two: launches on the two kernel streams overlap) the counters and the
         // cycle accumulators of a -DPG_TIMING diagnostics build, which the kernel finds right behind its counters
@@ -716,7 +715,9 @@ int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint
         { (void **)&b->run_tot, 64 },
         { (void **)&b->exact_count, 64 },
     };
-    const size_t n_items = sizeof items / sizeof items[0], first_zero = 11;
+    const size_t n_items = sizeof items / sizeof items[0];
+    size_t first_zero = 0;             // the zeroed block starts at rc_flag
+    while (items[first_zero].p != (void **)&b->rc_flag) first_zero++;
     auto drop = [&](int code) {
         free_batch_buffers(b);
         delete b;
@@ -725,9 +726,8 @@ int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint
     if (use_arena) {
         size_t need = 4096;
         for (const Item &it : items) need += ((it.bytes + 255) & ~(size_t)255) + 256;
-        // room for the download's temporaries too: CSR offsets, gathered runs, scan scratch
-        need += 2 * (((n + 1) * 4 + 511) & ~(size_t)255) + (size_t)b->pool_shard_cap * PG_POOL_SHARDS * sizeof(pg_run) +
-                pg_scan_tmp_bytes((uint32_t)n) + 4096;
+        // room for the download's temporaries too: gathered runs (no more than the pool holds) and the rest
+        need += (size_t)b->pool_shard_cap * PG_POOL_SHARDS * sizeof(pg_run) + download_scratch_bytes(n) + 4096;
         // ... and for the chunk-by-chunk delivery of search_host: gathered runs (2 lists), 64-bit offsets (2 lists), scratch
         need += 2 * (deliver_cap(n) * sizeof(pg_run) + 512) + 2 * ((n + 1) * 8 + 512) + PG_DELIVER_CHUNK * 8 + 4096 * 8 +
                 (n / std::min<size_t>(PG_HOST_CHUNK / 4, env().host_chunk ? env().host_chunk : PG_HOST_CHUNK) + 16) * 64 +   // 64 B of info per chunk
@@ -754,7 +754,7 @@ int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint
     } else {
         for (size_t k = 0; k < n_items; k++) {
             hipError_t e = hipMalloc(items[k].p, items[k].bytes);
-            // the device-side CSR scan / gather trusts the counts: a failed memset must not go unnoticed
+            // the delivery's scan / gather trusts the counts: a failed memset must not go unnoticed
             if (e == hipSuccess && k >= first_zero) e = hipMemset(*items[k].p, 0, items[k].bytes);
             if (e != hipSuccess)
                 return drop(fail(ctx, e == hipErrorOutOfMemory ? PG_E_NOMEM : PG_E_DEVICE,
@@ -813,12 +813,6 @@ PgSoaOut soa_out(const pg_device_batch *b)
     a.rc_flag = b->rc_flag;
     a.close_last = b->close_last;
     a.close_max = b->close_max;
-    a.close_off = b->close_off;
-    a.close_cnt = b->close_cnt;
-    a.far_off = b->far_off;
-    a.far_cnt = b->far_cnt;
-    a.alg = b->alg;
-    a.cand = nullptr;
     return a;
 }
 
@@ -856,18 +850,6 @@ int pack_reads(pg_ctx *ctx, pg_device_batch *b, uint32_t lo, uint32_t cnt, hipSt
     int rc = pg_pack_reads(&a, b->in_rec, lo, cnt, st ? st : ctx->stream, &rec);
     if (rc) return fail(ctx, PG_E_DEVICE, std::string("pack kernel: ") + hipGetErrorString((hipError_t)rc));
     log_launch(ctx, rec);
-    return PG_OK;
-}
-
-// Scatters the kernel's output records into the SoA arrays the CSR scan / download read.
-int unpack_results(pg_ctx *ctx, pg_device_batch *b)
-{
-    if (b->unpacked) return PG_OK;
-    const PgSoaOut a = soa_out(b);
-    int rc = pg_unpack_results(b->out_rec, &a, b->n, ctx->stream);
-    if (rc) return fail(ctx, PG_E_DEVICE, std::string("unpack kernel: ") + hipGetErrorString((hipError_t)rc));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    b->unpacked = true;
     return PG_OK;
 }
 
@@ -1019,9 +1001,6 @@ int run_search(pg_ctx *ctx, pg_device_batch *b, int mode, bool pack = false)
         if (worst <= b->pool_shard_cap) {
             ctx->last_ms = ms;
             ctx->last_runs = total;
-            b->runs_used = total;
-            b->modes_done |= mode;
-            b->unpacked = false;
             return PG_OK;
         }
         // overflow: grow the pool and redo the launch
@@ -1037,15 +1016,40 @@ int run_search(pg_ctx *ctx, pg_device_batch *b, int mode, bool pack = false)
     return fail(ctx, PG_E_DEVICE, "run pool kept overflowing");
 }
 
-// Results to the host: the runs are gathered into read order on the device (prefix sums of the per-read
-// counts + one gather kernel per list), so only the compact CSR crosses PCIe; the host buffers are pinned.
+// Device temporaries of one call: from the ctx arena where the batch lives there and the arena has room, hipMalloc'd otherwise;
+// all given back when the call ends.
+struct DevTemps {
+    pg_ctx *ctx;
+    const bool in_arena;
+    const size_t arena_mark;
+    std::vector<void *> owned;                            // hipMalloc'd (none while the arena has room)
+    DevTemps(pg_ctx *c, const pg_device_batch *b) : ctx(c), in_arena(b->in_arena), arena_mark(c->arena.used) {}
+    DevTemps(const DevTemps &) = delete;
+    ~DevTemps()
+    {
+        for (void *p : owned) (void)hipFree(p);
+        if (in_arena) ctx->arena.used = arena_mark;
+    }
+    void *take(size_t bytes)
+    {
+        void *p = in_arena ? ctx->arena.take(bytes) : nullptr;
+        if (p) return p;
+        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
+        owned.push_back(p);
+        return p;
+    }
+};
+
+// Results of a searched batch to the host: the delivery kernels of the host path (pg_deliver_chunk) over the whole batch, in
+// two passes, so that the run buffers can be sized from the batch's totals and only the compact CSR crosses PCIe (pinned host
+// buffers).  Pass 1 scans every chunk -- per-read summaries, local sums, each chunk's base and run counts; pass 2 gathers the runs
+// in read order and writes the 64-bit offsets.
 int download(pg_ctx *ctx, pg_device_batch *b, pg_result *r)
 {
     const size_t n = b->n;
     r->n = b->n;
-    const bool has[2] = { (b->modes_done & PG_MODE_CLOSE) != 0, (b->modes_done & PG_MODE_FAR) != 0 };
     if (!r->close_off.resize(n + 1) || !r->far_off.resize(n + 1) || !r->rc_flag.resize(n) || !r->close_last.resize(n) ||
-        !r->close_max.resize(n) || !r->csr32[0].resize(n + 1) || !r->csr32[1].resize(n + 1))
+        !r->close_max.resize(n))
         return fail(ctx, PG_E_NOMEM, "pinned host memory for the result");
     r->close_runs.resize(0);
     r->far_runs.resize(0);
@@ -1053,72 +1057,59 @@ int download(pg_ctx *ctx, pg_device_batch *b, pg_result *r)
         r->close_off[0] = r->far_off[0] = 0;
         return PG_OK;
     }
-    {
-        int urc = unpack_results(ctx, b);
-        if (urc) return urc;
-    }
-    uint32_t *csr[2] = { nullptr, nullptr };
-    pg_run *outp[2] = { nullptr, nullptr };
-    void *tmp = nullptr;
-    std::vector<void *> owned;                            // hipMalloc'd temporaries (none in the arena case)
-    auto dev_take = [&](size_t bytes) -> void * {
-        if (b->in_arena) {
-            void *p = ctx->arena.take(bytes);
-            if (p) return p;
+    const size_t chunk = download_chunk(), n_chunks = (n + chunk - 1) / chunk, chunk_blks = (chunk + 255) / 256;
+    DevTemps tmp(ctx, b);
+    uint2 *local = (uint2 *)tmp.take(n * 8), *blk = (uint2 *)tmp.take(n_chunks * chunk_blks * 8);
+    unsigned long long *d_info = (unsigned long long *)tmp.take(n_chunks * 64), *d_off[2];
+    d_off[0] = (unsigned long long *)tmp.take(n * 8);
+    d_off[1] = (unsigned long long *)tmp.take(n * 8);
+    HostBuf<unsigned long long> info;
+    if (!local || !blk || !d_info || !d_off[0] || !d_off[1]) return fail(ctx, PG_E_NOMEM, "device memory for the download's scans");
+    if (!info.resize(n_chunks * 8)) return fail(ctx, PG_E_NOMEM, "pinned host memory");
+    // (search_host's fallback: its deliveries have advanced the running totals)
+    HIP_TRY(ctx, hipMemsetAsync(b->run_tot, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    for (size_t k = 0, lo = 0; k < n_chunks; k++, lo += chunk)
+        HIP_TRY(ctx, (hipError_t)pg_deliver_scan(b->out_rec + lo, (uint32_t)std::min(chunk, n - lo), b->rc_flag + lo, b->close_last + lo,
+                                                 b->close_max + lo, local + lo, blk + k * chunk_blks, b->run_tot, d_info + 8 * k,
+                                                 b->pool_used, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(info.data(), d_info, n_chunks * 64, hipMemcpyDeviceToHost, ctx->stream));
+    // (the per-read summaries travel while the host sizes the run buffers)
+    HIP_TRY(ctx, hipMemcpyAsync(r->rc_flag.data(), b->rc_flag, n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(r->close_last.data(), b->close_last, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(r->close_max.data(), b->close_max, n * 2, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // the totals: the last chunk's base + its runs.  A list without a run gets no buffer -- its null pointer is never written
+    // through (a null far buffer makes the gather place the far runs behind the close runs: there are none to place)
+    const unsigned long long *last = info.data() + 8 * (n_chunks - 1), tot[2] = { last[0] + last[2], last[1] + last[3] };
+    pg_run *d_runs[2] = { nullptr, nullptr };
+    if (!r->close_runs.resize((size_t)tot[0]) || !r->far_runs.resize((size_t)tot[1]))
+        return fail(ctx, PG_E_NOMEM, "pinned host memory for the runs");
+    for (int k = 0; k < 2; k++)
+        if (tot[k] && !(d_runs[k] = (pg_run *)tmp.take((size_t)tot[k] * sizeof(pg_run)))) return fail(ctx, PG_E_NOMEM, "gathered runs");
+    const unsigned long long pool_runs = (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS;
+    for (size_t k = 0, lo = 0; k < n_chunks; k++, lo += chunk)
+        HIP_TRY(ctx, (hipError_t)pg_deliver_gather_runs(b->out_rec + lo, (uint32_t)std::min(chunk, n - lo), local + lo, blk + k * chunk_blks,
+                                                        d_info + 8 * k, b->pool, pool_runs, d_runs[0], d_runs[1], std::max(tot[0], tot[1]),
+                                                        d_off[0] + lo, d_off[1] + lo, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(info.data(), d_info, n_chunks * 64, hipMemcpyDeviceToHost, ctx->stream));
+    HostBuf<uint64_t> *off[2] = { &r->close_off, &r->far_off };
+    HostBuf<pg_run> *runs[2] = { &r->close_runs, &r->far_runs };
+    for (int k = 0; k < 2; k++)
+        if (tot[k]) {
+            HIP_TRY(ctx, hipMemcpyAsync(off[k]->data(), d_off[k], n * 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(runs[k]->data(), d_runs[k], (size_t)tot[k] * sizeof(pg_run), hipMemcpyDeviceToHost, ctx->stream));
         }
-        void *p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
-        owned.push_back(p);
-        return p;
-    };
-    auto cleanup = [&](int code) {
-        for (void *p : owned) (void)hipFree(p);
-        return code;
-    };
-#define TRY2(call)                                                                           \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return cleanup(fail(ctx, e_ == hipErrorOutOfMemory ? PG_E_NOMEM : PG_E_DEVICE,   \
-                                std::string(#call) + ": " + hipGetErrorString(e_)));         \
-    } while (0)
-    const size_t arena_mark = ctx->arena.used;
-    const size_t tmp_bytes = pg_scan_tmp_bytes((uint32_t)n);
-    if (!(tmp = dev_take(tmp_bytes))) return cleanup(fail(ctx, PG_E_NOMEM, "scan scratch"));
-    const uint32_t *cnts[2] = { b->close_cnt, b->far_cnt }, *offs[2] = { b->close_off, b->far_off };
-    uint32_t totals[2] = { 0, 0 };
-    for (int k = 0; k < 2; k++) {
-        if (!has[k]) continue;
-        if (!(csr[k] = (uint32_t *)dev_take((n + 1) * sizeof(uint32_t)))) return cleanup(fail(ctx, PG_E_NOMEM, "CSR offsets"));
-        TRY2((hipError_t)pg_compact_runs(nullptr, nullptr, cnts[k], csr[k], nullptr, (uint32_t)n, tmp, tmp_bytes, 0, ctx->stream));
-        TRY2(hipMemcpyAsync(r->csr32[k].data(), csr[k], (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    // the per-read summaries travel while the scans run
-    TRY2(hipMemcpyAsync(r->rc_flag.data(), b->rc_flag, n, hipMemcpyDeviceToHost, ctx->stream));
-    TRY2(hipMemcpyAsync(r->close_last.data(), b->close_last, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TRY2(hipMemcpyAsync(r->close_max.data(), b->close_max, n * 2, hipMemcpyDeviceToHost, ctx->stream));
-    TRY2(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 2; k++) {
-        HostBuf<pg_run> &runs = k ? r->far_runs : r->close_runs;
-        HostBuf<uint64_t> &off64 = k ? r->far_off : r->close_off;
-        if (!has[k]) {
-            for (size_t i = 0; i <= n; i++) off64[i] = 0;
-            continue;
-        }
-        totals[k] = r->csr32[k][n];
-        if (!runs.resize(totals[k])) return cleanup(fail(ctx, PG_E_NOMEM, "pinned host memory for the runs"));
-        if (totals[k]) {
-            if (!(outp[k] = (pg_run *)dev_take((size_t)totals[k] * sizeof(pg_run)))) return cleanup(fail(ctx, PG_E_NOMEM, "gathered runs"));
-            TRY2((hipError_t)pg_compact_runs(b->pool, offs[k], cnts[k], csr[k], outp[k], (uint32_t)n, nullptr, 0, 1, ctx->stream));
-            TRY2(hipMemcpyAsync(runs.data(), outp[k], (size_t)totals[k] * sizeof(pg_run), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        const uint32_t *c32 = r->csr32[k].data();
-        for (size_t i = 0; i <= n; i++) off64[i] = c32[i];       // widening while the runs are in flight
-    }
-    TRY2(hipStreamSynchronize(ctx->stream));
-#undef TRY2
-    if (b->in_arena) ctx->arena.used = arena_mark;
-    return cleanup(PG_OK);
+    // (the offsets of a list without a run are all 0: written here while the other list is on its way, not sent -- the batch of
+    // the far-end seams has no close run)
+    for (int k = 0; k < 2; k++)
+        if (!tot[k]) std::memset(off[k]->data(), 0, n * 8);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    r->close_off[n] = tot[0];
+    r->far_off[n] = tot[1];
+    // the buffers hold the totals exactly and the search has checked its pool: a gather that ran out of either is a bug
+    for (size_t k = 0; k < n_chunks; k++)
+        if (info[8 * k + 5]) return fail(ctx, PG_E_DEVICE, "download: the gather of chunk " + std::to_string(k) + " found a run list out of bounds");
+    return PG_OK;
 }
 
 // Copies the packed planes and the chromosome tables of the ctx to the device.
@@ -1515,7 +1506,6 @@ int pg_device_batch_search(pg_ctx *ctx, pg_device_batch *b)
 {
     use_device(ctx);
     if (!ctx || !b) return PG_E_INVALID;
-    b->modes_done = 0;
     return run_search(ctx, b, PG_MODE_BOTH);
 }
 
@@ -1523,7 +1513,6 @@ int pg_device_batch_pack_search(pg_ctx *ctx, pg_device_batch *b)
 {
     use_device(ctx);
     if (!ctx || !b) return PG_E_INVALID;
-    b->modes_done = 0;
     int rc = run_search(ctx, b, PG_MODE_BOTH, true);
     if (rc) return rc;
     return b->exact_n < 0 ? read_exact_count(ctx, b) : PG_OK;      // (later searches of the batch skip the exact kernel when its list is empty)
@@ -1603,19 +1592,6 @@ int pg_debug_scribble_records(pg_ctx *ctx, pg_device_batch *b)
     return PG_OK;
 }
 
-// Diagnostics (not in the public header): raw per-read words of the alg-bytes array.
-int pg_debug_read_alg(pg_ctx *ctx, pg_device_batch *b, uint32_t *out, uint32_t n)
-{
-    use_device(ctx);
-    if (!ctx || !b || !out || n > b->n) return PG_E_INVALID;
-    {
-        int urc = unpack_results(ctx, b);
-        if (urc) return urc;
-    }
-    HIP_TRY(ctx, hipMemcpy(out, b->alg, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return PG_OK;
-}
-
 // Diagnostics (not in the public header): the `reserved` word of every output record (candidates per read; in a
 // -DPG_DIAG build the packed per-read counters).
 int pg_debug_read_reserved(pg_ctx *ctx, pg_device_batch *b, uint32_t *out, uint32_t n)
@@ -1647,14 +1623,22 @@ int pg_last_search_stats(const pg_ctx *ctx, double *kernel_ms, uint64_t *n_runs)
     return PG_OK;
 }
 
+// The output records of the batch's last search, for the two diagnostics below.
+static int fetch_out_recs(pg_ctx *ctx, pg_device_batch *b, std::vector<PgOutRec> &recs)
+{
+    recs.resize(b->n);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (b->n) HIP_TRY(ctx, hipMemcpy(recs.data(), b->out_rec, (size_t)b->n * sizeof(PgOutRec), hipMemcpyDeviceToHost));
+    return PG_OK;
+}
+
 // Diagnostics: candidates (survivors of the seed filter) the last search of this batch folded, in total.
 int pg_device_batch_candidates(pg_ctx *ctx, pg_device_batch *b, double *n_candidates)
 {
     use_device(ctx);
     if (!ctx || !b || !n_candidates) return PG_E_INVALID;
-    std::vector<PgOutRec> recs(b->n);
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (b->n) HIP_TRY(ctx, hipMemcpy(recs.data(), b->out_rec, (size_t)b->n * sizeof(PgOutRec), hipMemcpyDeviceToHost));
+    std::vector<PgOutRec> recs;
+    if (int rc = fetch_out_recs(ctx, b, recs)) return rc;
     double s = 0.0;
     for (const PgOutRec &r : recs) s += r.reserved;
     *n_candidates = s;
@@ -1665,14 +1649,10 @@ int pg_device_batch_algorithmic_bytes(pg_ctx *ctx, pg_device_batch *b, double *b
 {
     use_device(ctx);
     if (!ctx || !b || !bytes) return PG_E_INVALID;
-    {
-        int urc = unpack_results(ctx, b);
-        if (urc) return urc;
-    }
-    std::vector<uint32_t> alg(b->n);
-    if (b->n) HIP_TRY(ctx, hipMemcpy(alg.data(), b->alg, (size_t)b->n * 4, hipMemcpyDeviceToHost));
+    std::vector<PgOutRec> recs;
+    if (int rc = fetch_out_recs(ctx, b, recs)) return rc;
     double s = 0.0;
-    for (uint32_t v : alg) s += v;
+    for (const PgOutRec &r : recs) s += r.alg;
     *bytes = s;
     return PG_OK;
 }
@@ -1762,7 +1742,7 @@ static int search_host(pg_ctx *ctx, const pg_read_batch *reads, int mode, pg_res
         return bail(fail(ctx, PG_E_NOMEM, "pinned host memory for the result"));
     const double t_res = now_ms();
     double t_search = t_res;
-    bool whole_batch = false;                // fall back to run_search + download (pool or delivery overflow)
+    bool whole_batch = false;                // fall back to run_search (pool overflow) + download (pool or delivery overflow)
     if (n) {
         if (!ctx->copy_stream) TRY3(hipStreamCreate(&ctx->copy_stream));
         if (!ctx->dl_stream) TRY3(hipStreamCreate(&ctx->dl_stream));
@@ -1899,8 +1879,6 @@ static int search_host(pg_ctx *ctx, const pg_read_batch *reads, int mode, pg_res
         if (!whole_batch) {
             ctx->last_ms = ms;
             ctx->last_runs = total;
-            b->runs_used = total;
-            b->modes_done |= mode;
             TRY3(hipStreamSynchronize(ctx->dl_stream));
             r->close_off[n] = tot[0];
             r->far_off[n] = tot[1];
@@ -1911,18 +1889,15 @@ static int search_host(pg_ctx *ctx, const pg_read_batch *reads, int mode, pg_res
                 r->close_max.resize(0);
             }
         } else {
-            // a pool shard overflowed, or the lists outgrew the delivery buffers: the whole batch again, with the
-            // regrown pool where needed, and the whole-batch download
+            // a pool shard overflowed, or the lists outgrew the delivery buffers: the whole batch again with the regrown pool
+            // where needed, then download(): the same delivery kernels over the whole batch, into buffers sized from its totals
             TRY3(hipStreamSynchronize(ctx->dl_stream));
             if (worst > b->pool_shard_cap) {
                 if ((rc = run_search(ctx, b, mode))) return bail(rc);
             } else {
-                b->modes_done |= mode;
-                b->runs_used = total;
                 ctx->last_ms = ms;
                 ctx->last_runs = total;
             }
-            b->unpacked = false;
             if ((rc = download(ctx, b, r))) return bail(rc);
         }
     } else {

@@ -36,7 +36,7 @@ struct PgDevParams {
 enum PgMode { PG_MODE_CLOSE = 1, PG_MODE_FAR = 2, PG_MODE_BOTH = 3 };
 
 // Packed per-read records.  pg_pack_reads builds the input records on the device from the SoA arrays of the C ABI;
-// pg_unpack_results scatters the output records back into SoA arrays for the CSR scan / download.
+// the delivery kernels (pg_deliver_chunk) turn the output records into the read-order CSR the C ABI hands out.
 //
 // The input record is 128 bytes = two lines of the scalar data cache (the second: the seed filter's symbol programs): the search kernel fetches it with scalar loads straight
 // into SGPRs, and it holds everything about a read that is a function of (read, parameters) alone, worked out ONCE by the pack
@@ -134,7 +134,7 @@ struct PgDevBatch {
     const struct PgSoaIn *soa;
 };
 
-// SoA views for the pack / unpack kernels
+// SoA views for the pack kernels
 static inline uint32_t pg_plane_blocks(uint32_t max_len)
 {
     return max_len <= 64u ? 1u : (max_len <= 128u ? 2u : (max_len <= 192u ? 3u : (max_len <= 256u ? 4u : 8u)));
@@ -215,12 +215,10 @@ static inline struct PgLenRec pg_len_rec(int len, const uint32_t *mm, const uint
     r.pad[0] = r.pad[1] = r.pad[2] = 0u;
     return r;
 }
-struct PgSoaOut {
+struct PgSoaOut {                  // the close-end summary pg_pack_close_summary reads
     uint8_t *rc_flag;
     uint32_t *close_last;
     uint16_t *close_max;
-    uint32_t *close_off, *close_cnt, *far_off, *far_cnt, *alg;
-    uint32_t *cand;                // nullable
 };
 
 // Candidate id = position relative to the search origin | kind (F/B) | window index of a BreakDancer cluster.
@@ -314,17 +312,13 @@ int pg_pack_in_place_ok(int mode, uint32_t max_len, int small_ids, uint32_t n_re
 // (rec may be null; rec->kernel stays 0 when nothing was launched)
 int pg_launch_search_exact(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch, int mode,
                            uint32_t max_len, uint32_t levels, void *stream, struct PgLaunchRec *rec);
-// Device-side CSR of a result list: first the scan (gather = 0: csr[0..n] = exclusive sums of cnt, cnt has
-// n + 1 readable entries), then the gather (gather = 1: out[csr[i] + k] = pool[off[i] + k]).
-size_t pg_scan_tmp_bytes(uint32_t n);
 // in[lo .. lo + cnt) from the SoA input arrays; cnt = 0 is allowed (rec may be null; rec->kernel stays 0 when nothing was launched)
 int pg_pack_reads(const PgSoaIn *soa, PgInRec *in, uint32_t lo, uint32_t cnt, void *stream, struct PgLaunchRec *rec);
 // close-end summary (rc flag, last AbsLoc, max length) of a host result into the output records
 int pg_pack_close_summary(const PgSoaOut *soa, PgOutRec *out, uint32_t n, void *stream);
-int pg_unpack_results(const PgOutRec *out, const PgSoaOut *soa, uint32_t n, void *stream);
 // One chunk (cnt <= PG_DELIVER_CHUNK reads) of a searched batch to read-order CSR behind the earlier chunks: see the
 // delivery kernels in pg_kernels.hip.  local / blk: scratch of cnt and 4096 uint2; run_tot: 2 running totals (zeroed
-// per batch); info: 4 values for the host {close base, far base, close runs, far runs}.
+// per batch); info: 8 values for the host {close base, far base, close runs, far runs, fullest pool shard, overflow}.
 #define PG_DELIVER_CHUNK (1u << 20)     // reads a delivery handles at most (scan2: 4096 blocks of 256)
 #define PG_HOST_CHUNK (1u << 18)        // reads per chunk the host path starts from (and the largest batch that is ONE chunk)
 int pg_deliver_chunk(const PgOutRec *out, uint32_t cnt, uint8_t *rc_flag, uint32_t *close_last, uint16_t *close_max,
@@ -332,8 +326,13 @@ int pg_deliver_chunk(const PgOutRec *out, uint32_t cnt, uint8_t *rc_flag, uint32
                      const pg_run *pool, unsigned long long pool_runs, pg_run *close_runs, pg_run *far_runs /* null: behind the close runs */,
                      unsigned long long cap, unsigned long long *close_off, unsigned long long *far_off, const uint32_t *pool_used,
                      void *stream);
-int pg_compact_runs(const pg_run *pool, const uint32_t *off, const uint32_t *cnt, uint32_t *csr,
-                    pg_run *out, uint32_t n, void *tmp, size_t tmp_bytes, int gather, void *stream);
+// ... and its two halves: the scan (summaries, local / blk, info, the running totals) needs no run buffers; the gather writes the
+// offsets and copies the runs of a chunk whose local / blk / info the scan has left in place.
+int pg_deliver_scan(const PgOutRec *out, uint32_t cnt, uint8_t *rc_flag, uint32_t *close_last, uint16_t *close_max,
+                    void *local, void *blk, unsigned long long *run_tot, unsigned long long *info, const uint32_t *pool_used, void *stream);
+int pg_deliver_gather_runs(const PgOutRec *out, uint32_t cnt, const void *local, const void *blk, unsigned long long *info,
+                           const pg_run *pool, unsigned long long pool_runs, pg_run *close_runs, pg_run *far_runs /* null: behind the close runs */,
+                           unsigned long long cap, unsigned long long *close_off, unsigned long long *far_off, void *stream);
 #ifdef __cplusplus
 }
 #endif

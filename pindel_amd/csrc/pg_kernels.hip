@@ -3166,22 +3166,6 @@ __global__ void pg_pack_close_kernel(PgSoaOut a, PgOutRec *out, uint32_t n)
     out[i] = r;
 }
 
-__global__ void pg_unpack_kernel(const PgOutRec *out, PgSoaOut a, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const PgOutRec r = out[i];
-    a.rc_flag[i] = r.rc_flag;
-    a.close_last[i] = r.close_last;
-    a.close_max[i] = r.close_max;
-    a.close_off[i] = r.close_off;
-    a.close_cnt[i] = r.close_cnt;
-    a.far_off[i] = r.far_off;
-    a.far_cnt[i] = r.far_cnt;
-    a.alg[i] = r.alg;
-    if (a.cand) a.cand[i] = r.reserved;
-}
-
 template <int PB>
 static void launch_pack(const PgSoaIn *soa, PgInRec *in, uint32_t lo, uint32_t cnt, hipStream_t st)
 {
@@ -3209,50 +3193,6 @@ extern "C" int pg_pack_reads(const PgSoaIn *soa, PgInRec *in, uint32_t lo, uint3
 extern "C" int pg_pack_close_summary(const PgSoaOut *soa, PgOutRec *out, uint32_t n, void *stream)
 {
     if (n) pg_pack_close_kernel<<<(n + 255u) / 256u, 256, 0, (hipStream_t)stream>>>(*soa, out, n);
-    return (int)hipGetLastError();
-}
-
-extern "C" int pg_unpack_results(const PgOutRec *out, const PgSoaOut *soa, uint32_t n, void *stream)
-{
-    if (n) pg_unpack_kernel<<<(n + 255u) / 256u, 256, 0, (hipStream_t)stream>>>(out, *soa, n);
-    return (int)hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------
-// Results to CSR on the device: the kernel leaves each read's runs somewhere in its pool shard; before
-// the copy to the host they are gathered in read order (offsets = exclusive prefix sums of the per-read
-// counts), so that only the compact lists cross PCIe and the host does no per-read work.
-#include <hipcub/hipcub.hpp>
-
-__global__ void pg_gather_runs_kernel(const pg_run *pool, const uint32_t *off, const uint32_t *cnt,
-                                      const uint32_t *csr, pg_run *out, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t c = cnt[i];
-    const u32 *src = (const u32 *)(pool + off[i]);
-    u32 *dst = (u32 *)(out + csr[i]);
-    for (uint32_t k = 0; k < 3u * c; k++) dst[k] = src[k];
-}
-
-// csr[0..n] = exclusive prefix sums of cnt[0..n) (cnt[n] must be readable; it is ignored: the scan
-// runs over n + 1 items so that csr[n] = total).  tmp / tmp_bytes: scratch from pg_scan_tmp_bytes.
-extern "C" size_t pg_scan_tmp_bytes(uint32_t n)
-{
-    size_t bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)(n + 1));
-    return bytes;
-}
-
-extern "C" int pg_compact_runs(const pg_run *pool, const uint32_t *off, const uint32_t *cnt, uint32_t *csr,
-                               pg_run *out, uint32_t n, void *tmp, size_t tmp_bytes, int gather, void *stream)
-{
-    hipStream_t st = (hipStream_t)stream;
-    if (!gather) {
-        hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, cnt, csr, (int)(n + 1), st);
-        return (int)e;
-    }
-    if (n) pg_gather_runs_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(pool, off, cnt, csr, out, n);
     return (int)hipGetLastError();
 }
 
@@ -3353,7 +3293,7 @@ extern "C" int pg_launch_search(const PgDevRef *ref, const PgDevParams *prm, con
 }
 
 // ---------------------------------------------------------------------------------
-// Delivery of a searched read range to the host, chunk by chunk (pg_search_batch & co): three small kernels turn the
+// Delivery of a searched read range to the host, chunk by chunk (pg_search_batch & co, and the download of a whole batch): three small kernels turn the
 // pooled runs of reads [0, cnt) of a chunk (cnt <= PG_DELIVER_CHUNK) into their slice of the batch-wide CSR -- 64-bit
 // offsets exactly as the C ABI hands them out, runs gathered in read order behind the runs of the earlier chunks -- so
 // that a chunk's result can cross PCIe while the next chunk is still being searched and the host does no per-read work.
@@ -3465,18 +3405,36 @@ __global__ __launch_bounds__(256) void pg_deliver_gather(const PgOutRec *out, ui
     for (uint32_t k = 0; k < 3u * r.far_cnt; k++) df[k] = sf[k];
 }
 
-extern "C" int pg_deliver_chunk(const PgOutRec *out, uint32_t cnt, uint8_t *rc_flag, uint32_t *close_last, uint16_t *close_max,
-                                void *local, void *blk, unsigned long long *run_tot, unsigned long long *info,
-                                const pg_run *pool, unsigned long long pool_runs, pg_run *close_runs, pg_run *far_runs,
-                                unsigned long long cap, unsigned long long *close_off, unsigned long long *far_off,
-                                const uint32_t *pool_used, void *stream)
+// The delivery's two halves.  The scan needs no run buffers: the whole-batch download (pg_api.cpp) scans every chunk of a batch first --
+// local / blk / info hold a slice per chunk -- sizes its run buffers from the totals and gathers afterwards.
+extern "C" int pg_deliver_scan(const PgOutRec *out, uint32_t cnt, uint8_t *rc_flag, uint32_t *close_last, uint16_t *close_max,
+                               void *local, void *blk, unsigned long long *run_tot, unsigned long long *info,
+                               const uint32_t *pool_used, void *stream)
 {
     if (!cnt || cnt > PG_DELIVER_CHUNK) return cnt ? (int)hipErrorInvalidValue : 0;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t nblk = (cnt + 255u) / 256u;
     pg_deliver_scan1<<<nblk, 256, 0, st>>>(out, cnt, rc_flag, close_last, close_max, (uint2 *)local, (uint2 *)blk);
     pg_deliver_scan2<<<1, 1024, 0, st>>>((uint2 *)blk, nblk, run_tot, info, pool_used);
-    pg_deliver_gather<<<nblk, 256, 0, st>>>(out, cnt, (const uint2 *)local, (const uint2 *)blk, info, pool, pool_runs, close_runs,
-                                           far_runs, cap, close_off, far_off, info + 5);
     return (int)hipGetLastError();
+}
+
+extern "C" int pg_deliver_gather_runs(const PgOutRec *out, uint32_t cnt, const void *local, const void *blk, unsigned long long *info,
+                                      const pg_run *pool, unsigned long long pool_runs, pg_run *close_runs, pg_run *far_runs,
+                                      unsigned long long cap, unsigned long long *close_off, unsigned long long *far_off, void *stream)
+{
+    if (!cnt || cnt > PG_DELIVER_CHUNK) return cnt ? (int)hipErrorInvalidValue : 0;
+    pg_deliver_gather<<<(cnt + 255u) / 256u, 256, 0, (hipStream_t)stream>>>(out, cnt, (const uint2 *)local, (const uint2 *)blk, info, pool,
+                                                                            pool_runs, close_runs, far_runs, cap, close_off, far_off, info + 5);
+    return (int)hipGetLastError();
+}
+
+extern "C" int pg_deliver_chunk(const PgOutRec *out, uint32_t cnt, uint8_t *rc_flag, uint32_t *close_last, uint16_t *close_max,
+                                void *local, void *blk, unsigned long long *run_tot, unsigned long long *info,
+                                const pg_run *pool, unsigned long long pool_runs, pg_run *close_runs, pg_run *far_runs,
+                                unsigned long long cap, unsigned long long *close_off, unsigned long long *far_off,
+                                const uint32_t *pool_used, void *stream)
+{
+    if (int rc = pg_deliver_scan(out, cnt, rc_flag, close_last, close_max, local, blk, run_tot, info, pool_used, stream)) return rc;
+    return pg_deliver_gather_runs(out, cnt, local, blk, info, pool, pool_runs, close_runs, far_runs, cap, close_off, far_off, stream);
 }

@@ -24,6 +24,7 @@
 #endif
 #include "../pindel_amd/csrc/pg_kernels.hip"
 #include <stdio.h>
+#include <string.h>
 #include <vector>
 
 const PgEnvSwitches *pg_env_switches(void)

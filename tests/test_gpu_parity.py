@@ -719,6 +719,106 @@ def test_host_pipeline_chunk_boundaries_equal_the_device_resident_path(engine_fa
     compare_result(eng.search_batch(small), run_oracle({}, small_ref, small), small.n)
 
 
+@pytest.fixture(scope="module")
+def flush6500(small_ref):
+    """6500 100-base reads (several chunks under PG_HOST_CHUNK=1000, a ragged last 256-read block) and their oracle result."""
+    batch = synth.make_reads(small_ref[0][1], 6500, seed=16)
+    return batch, run_oracle({}, small_ref, batch)
+
+
+def _oracle_prefix(orc, n):
+    # (compare_result reads the first n reads of every oracle array but rc_flag, which it compares whole)
+    return dict(orc, rc_flag=orc["rc_flag"][:n])
+
+
+def _device_resident(eng, batch):
+    db = eng.upload(batch)
+    eng.search_device(db)
+    res = eng.download(db)
+    eng.free_device_batch(db)
+    return res
+
+
+def _assert_same_result(a, b, what):
+    from pindel_amd import shard
+    a, b = shard.result_arrays(a), shard.result_arrays(b)
+    for k in ("close_off", "far_off", "rc_flag"):
+        assert np.array_equal(a[k], b[k]), (what, k)
+    for k in ("close_runs", "far_runs"):
+        assert a[k].tobytes() == b[k].tobytes(), (what, k)
+
+
+def test_multi_chunk_download_of_a_device_resident_batch(engine_factory, small_ref, pg_env, flush6500):
+    """pg_device_batch_download runs the delivery kernels chunk by chunk over the whole batch (all scans, then all gathers):
+    with one 256-read scan block per chunk -- one read, a chunk minus / plus one, several chunks with a ragged tail -- and
+    with chunks that are no multiple of the block, the result is pg_search_batch's array for array, and the oracle's."""
+    batch, orc = flush6500
+    eng = engine_factory()
+    eng.load_reference(small_ref)
+    pg_env.set("PG_HOST_CHUNK", "256")
+    for n in (1, 255, 256, 257, 3 * 256 + 17):
+        b = batch.slice(0, n)
+        dev = _device_resident(eng, b)
+        _assert_same_result(dev, eng.search_batch(b), n)
+        compare_result(dev, _oracle_prefix(orc, n), n)
+    pg_env.set("PG_HOST_CHUNK", "1000")
+    dev = _device_resident(eng, batch)
+    _assert_same_result(dev, eng.search_batch(batch), batch.n)
+    compare_result(dev, orc, batch.n)
+
+
+@pytest.mark.parametrize("switch", ["PG_TEST_TINY_DELIVERY", "PG_TEST_TINY_POOL"])
+def test_fallback_download_after_several_deliveries(engine_factory, small_ref, pg_env, flush6500, switch):
+    """Seven chunks are delivered -- the running totals stand at the batch's run counts -- before the host finds that the
+    delivery buffers (or the run pool: searched again with a regrown one) were too small and downloads the whole batch."""
+    batch, orc = flush6500
+    eng = engine_factory()
+    eng.load_reference(small_ref)
+    pg_env.set("PG_HOST_CHUNK", "1000")
+    pg_env.set(switch, "1")
+    compare_result(eng.search_batch(batch), orc, batch.n)
+    compare_result(eng.close_end_batch(batch), orc, batch.n, check_far=False)
+
+
+def test_download_of_a_list_without_runs(engine_factory, small_ref, pg_env, flush6500):
+    """A list whose total is 0 gets no gather buffer: the far end of a close-end only search (all offsets 0), the close end
+    of the batch pg_far_end_batch searches (its close counts are all 0)."""
+    batch, orc = flush6500
+    eng = engine_factory()
+    eng.load_reference(small_ref)
+    pg_env.set("PG_HOST_CHUNK", "1000")
+    close = eng.close_end_batch(batch)
+    compare_result(close, orc, batch.n, check_far=False)
+    assert not np.asarray(close.far_off).any() and len(close.far_runs) == 0
+    compare_result(eng.far_end_batch(batch, close), orc, batch.n)
+    pg_env.set("PG_TEST_TINY_DELIVERY", "1")                    # (the close-end only result through the download)
+    close = eng.close_end_batch(batch)
+    compare_result(close, orc, batch.n, check_far=False)
+    assert not np.asarray(close.far_off).any() and len(close.far_runs) == 0
+    compare_result(eng.far_end_batch(batch, close), orc, batch.n)
+
+
+def test_download_is_repeatable(engine_factory, small_ref, pg_env, flush6500):
+    """Downloading a searched device batch changes nothing a later download or search of it reads."""
+    from pindel_amd import shard
+    batch, orc = flush6500
+    eng = engine_factory()
+    eng.load_reference(small_ref)
+    pg_env.set("PG_HOST_CHUNK", "1000")
+    db = eng.upload(batch)
+    eng.search_device(db)
+    first = eng.download(db)
+    compare_result(first, orc, batch.n)
+    digest = shard.digest_hex(shard.read_digests(first))
+    assert shard.digest_hex(shard.read_digests(eng.download(db))) == digest
+    eng.search_device(db)
+    again = eng.download(db)
+    assert shard.digest_hex(shard.read_digests(again)) == digest
+    _assert_same_result(again, first, "second search")
+    assert shard.digest_hex(shard.read_digests(eng.download(db))) == digest
+    eng.free_device_batch(db)
+
+
 def test_adapter_on_reference_shapes(engine_factory, tmp_path):
     """INTEGRATION.md's binding run against reference-shaped types (tests/ref_shapes.hpp = the public interface of
     src/pindel.h's SPLIT_READ / SortedUniquePoints / UniquePoint): seam 1 in 700-read flushes, the reads with a close end
