@@ -12,7 +12,8 @@
 // is the total length of (M / = / X block) n [beg, end).  A read is kept by the pileup's default mask (unmapped,
 // secondary, QC-fail and duplicate reads go; supplementary ones stay); a read without CIGAR is not piled up.
 // The mapping-quality floor the reference passes (20) never takes effect: bam2depth's local mapQ stays 0
-// (bam2depth.cpp:41, 59).  That quirk is kept: MAPQ is not looked at.
+// (bam2depth.cpp:41, 59).  That quirk is kept: MAPQ is not looked at -- unless a floor is asked for (`min_mapq`, what
+// --repair depth-mapq sets to the 20 the reference meant): then a record below it is not piled up.
 //
 // Deliberate differences: htslib's pileup cap of 8000 reads per position is not reproduced; a
 // chromosome that a BAM's header lacks gives depth 0 for that BAM (the reference then pileups the whole file with
@@ -47,14 +48,14 @@ struct DepthSums {
     double avg(int k) const { return (double)sum[k] / (double)(end[k] - beg[k]); }
 };
 
-inline bool depth_record_kept(const BamRecord &r)
+inline bool depth_record_kept(const BamRecord &r, unsigned min_mapq = 0)
 {
-    return !(r.flag & (BAM_FUNMAP | BAM_FSECONDARY | BAM_FQCFAIL | BAM_FDUP)) && !r.cigar.empty();
+    return !(r.flag & (BAM_FUNMAP | BAM_FSECONDARY | BAM_FQCFAIL | BAM_FDUP)) && !r.cigar.empty() && (unsigned)r.mapq >= min_mapq;
 }
 
-inline void depth_add_record(const BamRecord &r, DepthSums &d)
+inline void depth_add_record(const BamRecord &r, DepthSums &d, unsigned min_mapq = 0)
 {
-    if (!depth_record_kept(r)) return;
+    if (!depth_record_kept(r, min_mapq)) return;
     int64_t at = r.pos;
     for (uint32_t c : r.cigar) {
         const int op = c & 15;
@@ -71,7 +72,7 @@ inline void depth_add_record(const BamRecord &r, DepthSums &d)
 }
 
 // Fills d.sum from the records of chromosome chr_name in `bam`; false: the file could not be read.
-inline bool depth_sums(BamFile &bam, const std::string &chr_name, DepthSums &d)
+inline bool depth_sums(BamFile &bam, const std::string &chr_name, DepthSums &d, unsigned min_mapq = 0)
 {
     int64_t lo = 0, hi = 0;
     bool any = false;
@@ -84,20 +85,21 @@ inline bool depth_sums(BamFile &bam, const std::string &chr_name, DepthSums &d)
     }
     const int tid = bam.header().id_of(chr_name);
     if (!any || tid < 0 || hi <= 0) return true;
-    return bam.query(tid, lo, hi, [&](const BamRecord &r) { depth_add_record(r, d); });
+    return bam.query(tid, lo, hi, [&](const BamRecord &r) { depth_add_record(r, d, min_mapq); });
 }
 
 // getRelativeCoverageInternal for one BAM: the depth of [start, end) against its two flanks of the same length,
 // clipped to the chromosome (chr_size = its biological size).  -1 when both flanks are empty of reads; a flank of
 // length zero gives NaN, which the callers' comparisons let fall through as the reference's do.
-inline bool depth_ratio(BamFile &bam, const std::string &chr_name, int64_t chr_size, int64_t start, int64_t end, double &ratio)
+inline bool depth_ratio(BamFile &bam, const std::string &chr_name, int64_t chr_size, int64_t start, int64_t end, double &ratio,
+                        unsigned min_mapq = 0)
 {
     const int64_t L = end - start;
     DepthSums d;
     d.add(start - L >= 0 ? start - L : 0, start);
     d.add(start, end);
     d.add(end, end + L > chr_size ? chr_size : end + L);
-    if (!depth_sums(bam, chr_name, d)) return false;
+    if (!depth_sums(bam, chr_name, d, min_mapq)) return false;
     const double before = d.avg(0), sv = d.avg(1), after = d.avg(2);
     if (before + after == 0) ratio = -1;
     else ratio = 2 * (2 * sv) / (before + after);
@@ -118,8 +120,9 @@ inline bool depth_rule_td(const double *ratio, size_t n)
 // index), so the box-parallel reporters and the pipeline's reader thread never share a handle.
 class GermlineDepth {
 public:
-    bool open(const std::vector<std::string> &paths, const std::vector<std::string> &tags, std::string &err)
+    bool open(const std::vector<std::string> &paths, const std::vector<std::string> &tags, std::string &err, unsigned min_mapq = 0)
     {
+        min_mapq_ = min_mapq;
         files_ = std::vector<BamFile>(paths.size());
         tags_ = tags;
         for (size_t k = 0; k < paths.size(); k++)
@@ -138,7 +141,7 @@ public:
             double ratio = -1;
             BamFile mine;
             std::string err;
-            if (!mine.open_like(files_[k], err) || !depth_ratio(mine, chr_name, chr_size, start, end, ratio)) {
+            if (!mine.open_like(files_[k], err) || !depth_ratio(mine, chr_name, chr_size, start, end, ratio, min_mapq_)) {
                 std::lock_guard<std::mutex> g(mu_);
                 if (error_.empty()) error_ = err.empty() ? "BAM read failed during the germline filter" : err;
                 ratio = -1;
@@ -159,6 +162,7 @@ public:
 private:
     std::vector<BamFile> files_;
     std::vector<std::string> tags_;
+    unsigned min_mapq_ = 0;
     mutable std::mutex mu_;
     mutable double seconds_ = 0;
     mutable size_t queries_ = 0;

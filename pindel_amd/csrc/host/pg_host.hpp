@@ -26,6 +26,7 @@
 #include <fstream>
 #include <functional>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace pgh {
@@ -67,6 +68,35 @@ struct Chromosome {
 
 class GermlineDepth;              // pg_depth.hpp: the BAMs a -N run measures read depth in
 
+// --repair: opt-in fixes of reference defects that are reproduced by default.  A bit per name.
+enum : uint32_t {
+    REPAIR_INT_PAIRS = 1u,        // int-pairs: -I reports every chromosome pair of a window, not only the first
+    REPAIR_INV_PAIRS = 2u,        // inv-pairs: -N counts the window's read pairs for a large inversion (IsGoodINV's loop)
+    REPAIR_DEPTH_MAPQ = 4u,       // depth-mapq: -N's read depth counts records with MAPQ >= 20 only
+    REPAIR_BED0 = 8u,             // bed0: -j / -J records are 0-based and half-open
+    REPAIR_ALL = 15u
+};
+enum { DEPTH_MAPQ_FLOOR = 20 };   // what getRelativeCoverageForFiltering passes (and bam2depth ignores)
+
+// "name,name,..." or "all" -> bitmask.  false: an unknown name or an empty list (err says which).
+bool parse_repairs(const std::string &list, uint32_t &mask, std::string &err);
+// the names of `mask`, comma-separated, in the order of the bits ("" for 0)
+std::string repairs_text(uint32_t mask);
+
+// One same-chromosome discordant read pair of a window as BDData::UpdateBD leaves it before clearing its list
+// (RP_READ after ModifyRP, src/bddata.cpp:646-733): what IsGoodINV's loop reads of it.  InsertSize is
+// Experimental_InsertSize, the insert size of the BAM's configuration line (src/reader.cpp:1042).
+struct DiscordantPair {
+    char DA, DB;
+    unsigned PosA, PosB, InsertSize;
+    short ReadLength;
+};
+// IsGoodINV's loop (src/output_sorter.cpp:283-365) for an event of `support` reads with breakpoints [real_start,
+// real_end], as written -- plus one comparison of the two counts after the loop (the reference compares before it
+// counts the pair in hand, so the last pair of the list would never count).  counts (nullable): CountLeft, CountRight.
+bool inv_pairs_good(const std::vector<DiscordantPair> &pairs, unsigned support, unsigned real_start, unsigned real_end,
+                    unsigned *counts = nullptr);
+
 struct Settings {                 // the flags the downstream steps read (src/fn_parameters.cpp)
     unsigned spacer = 100000;
     unsigned NumRead2ReportCutOff = 1;   // -M
@@ -88,6 +118,8 @@ struct Settings {                 // the flags the downstream steps read (src/fn
     bool NormalSamples = false;
     std::shared_ptr<const GermlineDepth> germline;
     bool germline_filter() const { return NormalSamples && germline; }
+    uint32_t repairs = 0;                // --repair: REPAIR_* bits (default none: the reference's behaviour, defects included)
+    bool repair(uint32_t bit) const { return (repairs & bit) != 0; }
 };
 
 int load_fasta(const std::string &path, std::vector<Chromosome> &out, unsigned spacer, std::string &err);
@@ -155,6 +187,9 @@ public:
     struct RefReadSpan { uint32_t pos; uint16_t length; uint16_t tag; };
     void update_ref_coverage(const std::vector<RefReadSpan> &reads, const std::vector<std::string> &tags,
                              unsigned start, unsigned end);
+    // --repair inv-pairs: the same-chromosome discordant pairs of the window that process_window is called for next
+    // (all BAMs of the run); the inversion reporter's verdict is a function of the event and this list alone
+    void set_window_pairs(std::vector<DiscordantPair> pairs) { inv_pairs_ = std::move(pairs); }
     ~Caller();
 
 private:
@@ -227,6 +262,7 @@ private:
     // touch them (InterChromosome_SR, pindel.cpp:1905-1917), and their calls, appended to <prefix>_INT after the window's
     // other reports (pindel.cpp:1940-1942)
     std::vector<SplitRead> interchr_;
+    std::vector<DiscordantPair> inv_pairs_;
     void collect_interchr(const std::vector<SplitRead> &reads);
     void report_interchr();
 };

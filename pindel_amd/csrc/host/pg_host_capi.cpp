@@ -48,6 +48,7 @@ struct pgh_settings {
     int32_t normal_samples;      /* -N: the germline filter of _TD and _INV (acts with bam_config only) */
     const char *bam_config;      /* NULL or "" = the reads are text input; else the -i configuration they were derived from */
     const char *pindel_config;   /* -P: NULL or "" = none; else its files are read before reads_path */
+    uint32_t repairs;            /* --repair: REPAIR_* bits (pg_host.hpp; pgh_parse_repairs); 0 = none.  Last, so earlier layouts hold */
 };
 
 static std::string str_or_empty(const char *s) { return s ? s : ""; }
@@ -62,6 +63,8 @@ static std::string str_or_empty(const char *s) { return s ? s : ""; }
  * the concatenated reads in load order.  normal_samples with bam_config: the reads are taken as derived from the BAMs
  * of that -i configuration, so IsGoodTD / IsGoodINV filter as they do for BAM input and read depth comes from those
  * BAMs (pg_depth.hpp); without bam_config the reads are text input and -N changes nothing, as in the reference.
+ * repairs: int-pairs, depth-mapq and bed0 act as on the command line; inv-pairs, with normal_samples and
+ * bam_config, discovers the discordant read pairs of every window in those BAMs (-A 0) for the inversion filter.
  */
 int pgh_call_from_points(const char *fasta_path, const char *reads_path, const char *out_prefix,
                          const pgh_settings *st, uint32_t n_reads,
@@ -91,13 +94,34 @@ int pgh_call_from_points(const char *fasta_path, const char *reads_path, const c
     S.report_interchromosomal = st->report_interchromosomal != 0;
     memcpy(S.max_mismatch, st->max_mismatch, sizeof S.max_mismatch);
     S.NormalSamples = st->normal_samples != 0;
+    S.repairs = st->repairs;
+    if (S.repairs & ~(uint32_t)REPAIR_ALL) {
+        g_err = "unknown bits in the repairs field";
+        return -1;
+    }
+    std::vector<BamSource> bams;
     if (S.NormalSamples && st->bam_config && st->bam_config[0]) {
-        std::vector<BamSource> bams;
-        if (!read_bam_config(st->bam_config, bams, g_err) || !(S.germline = open_germline(bams, g_err))) return -1;
+        if (!read_bam_config(st->bam_config, bams, g_err) || !(S.germline = open_germline(bams, g_err, S.repairs))) return -1;
+    }
+    // --repair inv-pairs: readers of their own on the BAMs, one window at a time
+    std::vector<BamFile> pair_files;
+    std::vector<int> pair_isz;
+    std::vector<std::string> pair_tags;
+    WindowPairs pairs_of;
+    if (S.germline_filter() && S.repair(REPAIR_INV_PAIRS)) {
+        pair_files = std::vector<BamFile>(bams.size());
+        for (size_t k = 0; k < bams.size(); k++) {
+            if (!pair_files[k].open(bams[k].path, g_err)) return -1;
+            pair_isz.push_back(bams[k].insert_size);
+            pair_tags.push_back(bams[k].tag);
+        }
+        pairs_of = [&](const Chromosome &chrom, unsigned ws, unsigned we, std::vector<DiscordantPair> &out) {
+            return window_pairs(pair_files, pair_isz, pair_tags, chrom.name, ws, we, 0, S.spacer, out);
+        };
     }
     std::vector<RegionRecord> plan;
     if (region_plan(chromosome_names(genome), chromosome_sizes(genome, read_fai(fasta_path, genome), S.spacer), str_or_empty(st->region),
-                    str_or_empty(st->include_bed), str_or_empty(st->exclude_bed), plan, g_err))
+                    str_or_empty(st->include_bed), str_or_empty(st->exclude_bed), plan, g_err, S.repair(REPAIR_BED0)))
         return -1;
     auto to_up = [](const pg_point &p) {
         UniquePoint u;
@@ -122,7 +146,15 @@ int pgh_call_from_points(const char *fasta_path, const char *reads_path, const c
         }
         return 0;
     };
-    return run_pipeline(genome, plan, all, S, out_prefix, attach, pgh::NoFarSearch(), g_err);
+    return run_pipeline(genome, plan, all, S, out_prefix, attach, pgh::NoFarSearch(), g_err, nullptr, pairs_of);
+}
+
+/* "int-pairs,depth-mapq" / "all" -> the bits of pgh_settings.repairs; -1 = an unknown name or an empty list (pgh_last_error) */
+int64_t pgh_parse_repairs(const char *list)
+{
+    uint32_t mask = 0;
+    if (!parse_repairs(str_or_empty(list), mask, g_err)) return -1;
+    return (int64_t)mask;
 }
 
 /*
@@ -130,13 +162,20 @@ int pgh_call_from_points(const char *fasta_path, const char *reads_path, const c
  * (pg_depth.hpp): 0 when the BAM's header lacks the chromosome, NaN for an empty region.  0 = done, -1 = the file
  * cannot be read (pgh_last_error).
  */
+int pgh_region_depth_mapq(const char *bam_path, const char *chr_name, int64_t beg, int64_t end, uint32_t min_mapq, double *avg);
 int pgh_region_depth(const char *bam_path, const char *chr_name, int64_t beg, int64_t end, double *avg)
+{
+    return pgh_region_depth_mapq(bam_path, chr_name, beg, end, 0, avg);
+}
+
+/* ... counting only the records with MAPQ >= min_mapq (0: every record, as the reference does; 20: --repair depth-mapq) */
+int pgh_region_depth_mapq(const char *bam_path, const char *chr_name, int64_t beg, int64_t end, uint32_t min_mapq, double *avg)
 {
     BamFile bam;
     if (!bam.open(bam_path, g_err)) return -1;
     DepthSums d;
     d.add(beg, end);
-    if (!depth_sums(bam, chr_name, d)) {
+    if (!depth_sums(bam, chr_name, d, min_mapq)) {
         g_err = std::string(bam_path) + ": BAM read failed";
         return -1;
     }
@@ -148,13 +187,22 @@ int pgh_region_depth(const char *bam_path, const char *chr_name, int64_t beg, in
  * getRelativeCoverageInternal: per BAM the depth of the event [start, end) against its two flanks of the same length,
  * clipped to [0, chr_size): 2 * (2 * sv) / (before + after), -1 when before + after == 0, NaN when a flank has no length.
  */
+int pgh_depth_ratio_mapq(int32_t n_bams, const char *const *bam_paths, const char *chr_name, int64_t chr_size, int64_t start,
+                         int64_t end, uint32_t min_mapq, double *ratio);
 int pgh_depth_ratio(int32_t n_bams, const char *const *bam_paths, const char *chr_name, int64_t chr_size, int64_t start, int64_t end,
                     double *ratio)
+{
+    return pgh_depth_ratio_mapq(n_bams, bam_paths, chr_name, chr_size, start, end, 0, ratio);
+}
+
+/* ... counting only the records with MAPQ >= min_mapq */
+int pgh_depth_ratio_mapq(int32_t n_bams, const char *const *bam_paths, const char *chr_name, int64_t chr_size, int64_t start,
+                         int64_t end, uint32_t min_mapq, double *ratio)
 {
     for (int32_t k = 0; k < n_bams; k++) {
         BamFile bam;
         if (!bam.open(bam_paths[k], g_err)) return -1;
-        if (!depth_ratio(bam, chr_name, chr_size, start, end, ratio[k])) {
+        if (!depth_ratio(bam, chr_name, chr_size, start, end, ratio[k], min_mapq)) {
             g_err = std::string(bam_paths[k]) + ": BAM read failed";
             return -1;
         }
@@ -171,14 +219,23 @@ int pgh_depth_rule_td(int32_t n, const double *ratio) { return depth_rule_td(rat
  * number of records (also when it exceeds cap; only cap are written), -1 = unreadable input, unknown chromosome, start
  * beyond the chromosome or a malformed BED line, -2 = -c syntax (pgh_last_error says which).
  */
+int64_t pgh_region_plan_bed(const char *fasta_path, const char *region, const char *include_bed, const char *exclude_bed,
+                            int32_t bed_zero_based, uint32_t *out, uint64_t cap);
 int64_t pgh_region_plan(const char *fasta_path, const char *region, const char *include_bed, const char *exclude_bed,
                         uint32_t *out, uint64_t cap)
+{
+    return pgh_region_plan_bed(fasta_path, region, include_bed, exclude_bed, 0, out, cap);
+}
+
+/* ... with bed_zero_based != 0 the records of both BED files are 0-based and half-open (--repair bed0) */
+int64_t pgh_region_plan_bed(const char *fasta_path, const char *region, const char *include_bed, const char *exclude_bed,
+                            int32_t bed_zero_based, uint32_t *out, uint64_t cap)
 {
     std::vector<Chromosome> genome;
     if (load_fasta(fasta_path, genome, 0, g_err)) return -1;
     std::vector<RegionRecord> plan;
     const int rc = region_plan(chromosome_names(genome), chromosome_sizes(genome, read_fai(fasta_path, genome), 0), str_or_empty(region),
-                               str_or_empty(include_bed), str_or_empty(exclude_bed), plan, g_err);
+                               str_or_empty(include_bed), str_or_empty(exclude_bed), plan, g_err, bed_zero_based != 0);
     if (rc) return rc == REGION_BAD_SYNTAX ? -2 : -1;
     for (size_t k = 0; k < plan.size() && k < cap; k++) {
         out[3 * k] = (uint32_t)plan[k].chr;

@@ -71,6 +71,11 @@ std::string interchr_call(const SplitRead &r, bool close_ascending, unsigned spa
 // Every read is visited during the first pair, so later pairs find every name taken: only reads between the two
 // smallest names of the window are ever reported.  That is kept, as one pass with those two names.  A second read of
 // the same name is skipped.  Used is false for every copy (they are taken before the classifiers run).
+//
+// --repair int-pairs: every pair is looked at, in the reference's order, and a name is entered only when
+// its read matches the pair in hand; the calls are counted and written pair by pair.  The lines of the first pair come
+// first; they are the unrepaired lines unless one of its reads shares its name with an earlier read of another pair
+// (taken without the repair, free with it: the first pair's own count can then be higher).
 void Caller::report_interchr()
 {
     if (interchr_.empty()) return;
@@ -79,19 +84,27 @@ void Caller::report_interchr()
         names.insert(r.FragName);
         names.insert(r.FarFragName);
     }
-    const std::string &first = *names.begin(), &second = *std::next(names.begin());
+    std::vector<std::pair<std::string, std::string>> pairs;
+    for (auto first = names.begin(); first != names.end(); ++first)
+        for (auto second = std::next(first); second != names.end(); ++second) pairs.emplace_back(*first, *second);
+    if (!S.repair(REPAIR_INT_PAIRS)) pairs.resize(1);       // the first pair takes every name
     std::set<std::string> seen;
-    std::map<std::string, int> calls;                       // CallAndSupport: call string -> reads, in string order
-    for (const SplitRead &r : interchr_) {
-        if (!seen.insert(r.Name).second) continue;
-        std::string call;
-        if (r.FragName == first && r.FarFragName == second) call = interchr_call(r, r.MatchedD == '+', S.spacer);
-        else if (r.FragName == second && r.FarFragName == first) call = interchr_call(r, r.MatchedFarD == '-', S.spacer);   // (sic: the far strand)
-        if (!call.empty()) calls[call]++;
-    }
     std::ofstream &out = open_append(int_out_, int_buf_, "_INT");
-    for (const auto &kv : calls)
-        if (kv.second >= 2) out << kv.first << "\tsupport: " << kv.second << '\n';
+    for (const auto &pair : pairs) {
+        std::map<std::string, int> calls;                   // CallAndSupport: call string -> reads, in string order
+        for (const SplitRead &r : interchr_) {
+            const bool ab = r.FragName == pair.first && r.FarFragName == pair.second;
+            const bool ba = r.FragName == pair.second && r.FarFragName == pair.first;
+            if (S.repair(REPAIR_INT_PAIRS) && !ab && !ba) continue;
+            if (!seen.insert(r.Name).second) continue;
+            std::string call;
+            if (ab) call = interchr_call(r, r.MatchedD == '+', S.spacer);
+            else if (ba) call = interchr_call(r, r.MatchedFarD == '-', S.spacer);   // (sic: the far strand)
+            if (!call.empty()) calls[call]++;
+        }
+        for (const auto &kv : calls)
+            if (kv.second >= 2) out << kv.first << "\tsupport: " << kv.second << '\n';
+    }
     out.flush();
     interchr_.clear();
 }

@@ -597,12 +597,47 @@ void Caller::sort_output_inv(Ctx &c, std::vector<std::vector<unsigned>> &boxes, 
             if (ev.re < ev.rs || ev.rs == 0) continue;          // IsGoodINV (output_sorter.cpp:264-369)
             // ... under -N on BAM-derived reads: an event of two read lengths or more needs >= 5 supporting pairs on each
             // side among Reads_RP_Discovery -- a list UpdateBD has emptied by then (bddata.cpp:733; never filled with
-            // -R false), so none is ever counted and the event is dropped
-            if (S.germline_filter() && ev.re - ev.rs >= (unsigned)good[ev.s].getReadLength() * 2) continue;
+            // -R false), so none is ever counted and the event is dropped.  --repair inv-pairs counts in the list as
+            // it stood before it was emptied.
+            if (S.germline_filter() && ev.re - ev.rs >= (unsigned)good[ev.s].getReadLength() * 2 &&
+                !(S.repair(REPAIR_INV_PAIRS) && inv_pairs_good(inv_pairs_, ev.e - ev.s + 1, ev.rs, ev.re)))
+                continue;
             if (good[ev.s].IndelSize < S.BalanceCutoff || report_event(good, ev.s, ev.e))
                 output_inv(c, good, ev.s, ev.e, ev.rs, ev.re);
         }
     });
+}
+
+// The arithmetic is the reference's: unsigned 32-bit throughout (RP_READ's positions and Experimental_InsertSize are
+// unsigned, ReadLength is a short that the additions convert).  ChrNameA == ChrNameB holds for every pair of the list
+// (build_record_RP_Discovery puts the others into a list of their own).
+bool inv_pairs_good(const std::vector<DiscordantPair> &pairs, unsigned support, unsigned RealStart, unsigned RealEnd, unsigned *counts)
+{
+    unsigned Cutoff = support / 2;
+    if (Cutoff < 5) Cutoff = 5;
+    unsigned CountLeft = 0, CountRight = 0;
+    bool good = false;
+    for (const DiscordantPair &p : pairs) {
+        if (CountLeft >= Cutoff && CountRight >= Cutoff) {
+            good = true;
+            break;
+        }
+        if (p.DA != p.DB) continue;
+        const unsigned L = (unsigned)p.ReadLength, I = p.InsertSize;
+        // the smaller position first (the reference spells both orders out)
+        const unsigned lo = p.PosA < p.PosB ? p.PosA : p.PosB, hi = p.PosA < p.PosB ? p.PosB : p.PosA;
+        if (p.DA == '+') {
+            if (lo < RealStart + L && hi + L > RealStart && hi < RealEnd + L && lo + I + L > RealStart && hi + I + L > RealEnd) CountLeft++;
+        } else {
+            if (lo + L > RealStart && lo < RealEnd + L && hi + L > RealEnd && lo < RealStart + I + L && hi < RealEnd + I + L) CountRight++;
+        }
+    }
+    if (CountLeft >= Cutoff && CountRight >= Cutoff) good = true;      // the repair's addition: the last pair counts too
+    if (counts) {
+        counts[0] = CountLeft;
+        counts[1] = CountRight;
+    }
+    return good;
 }
 
 }  // namespace pgh

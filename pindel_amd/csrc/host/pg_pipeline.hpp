@@ -82,6 +82,32 @@ inline int germline_done(const Settings &S, bool timing, std::string &err)
     return 0;
 }
 
+// --repair inv-pairs: what IsGoodINV reads of the pairs rp_events left (pg_rp.hpp)
+inline std::vector<DiscordantPair> discordant_pairs(const std::vector<RpRead> &left)
+{
+    std::vector<DiscordantPair> out;
+    out.reserve(left.size());
+    for (const RpRead &r : left) {
+        DiscordantPair p = { r.DA, r.DB, r.PosA, r.PosB, (unsigned)r.InsertSize, r.ReadLength };
+        out.push_back(p);
+    }
+    return out;
+}
+
+// The same-chromosome discordant pairs of window [ws, we) of `chr_name` over all BAMs, for a pipeline that does not
+// discover them anyway: discovery and UpdateBD's steps, no event kept, no _RP line.  false: a BAM read failed.
+inline bool window_pairs(std::vector<BamFile> &files, const std::vector<int> &insert_sizes, const std::vector<std::string> &tags,
+                         const std::string &chr_name, unsigned ws, unsigned we, unsigned min_anchor_quality, unsigned spacer,
+                         std::vector<DiscordantPair> &out)
+{
+    std::vector<RpRead> rp, left;
+    for (size_t k = 0; k < files.size(); k++)
+        if (!rp_discover(files[k], chr_name, ws, we, insert_sizes[k], tags[k], min_anchor_quality, rp)) return false;
+    rp_events(rp, spacer, nullptr, &left);
+    out = discordant_pairs(left);
+    return true;
+}
+
 // The two seams, in the reference's order (src/pindel.cpp:1816-1888):
 //   search(chrom, chr_id, reads, index_in_all)   on ALL reads of the window: must fill UP_Close (empty when there is no
 //                                                close end) and leave UnmatchedSeq as GetCloseEnd would
@@ -93,6 +119,9 @@ inline int germline_done(const Settings &S, bool timing, std::string &err)
 // With S.close_mapped_output() the reads that kept a close end are written to <prefix>_CloseEndMapped before the far end
 // (src/pindel.cpp:1880-1883); with S.only_close_mapped (-S) that is all: no far end, no classifiers, no reports.
 // li_seconds (nullable) receives the host time of the _LI reporter over all windows.
+// pairs_of(chrom, ws, we, pairs) (may be empty): the window's discordant pairs for --repair inv-pairs, asked for every
+// window that is classified; false = a BAM could not be read.
+typedef std::function<bool(const Chromosome &, unsigned, unsigned, std::vector<DiscordantPair> &)> WindowPairs;
 struct NoFarSearch {
     int operator()(const Chromosome &, int, std::vector<SplitRead> &, unsigned, unsigned) const { return 0; }
 };
@@ -108,7 +137,8 @@ struct NoFarSearch {
 template <class Search, class FarSearch>
 int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<RegionRecord> &plan,
                  const std::vector<SplitRead> &all, const Settings &S, const std::string &prefix,
-                 Search search, FarSearch far_search, std::string &err, double *li_seconds = nullptr)
+                 Search search, FarSearch far_search, std::string &err, double *li_seconds = nullptr,
+                 const WindowPairs &pairs_of = WindowPairs())
 {
     Caller caller(S, &genome, prefix, true);
     const unsigned WINDOW = (unsigned)(S.window_mbp * 1000000);
@@ -202,6 +232,14 @@ int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<Region
                 return rc;
             }
             t_search += now() - t0; t0 = now();
+            if (pairs_of && !S.only_close_mapped && !kept.empty()) {
+                std::vector<DiscordantPair> pairs;
+                if (!pairs_of(chrom, ws, we, pairs)) {
+                    err = "BAM read failed during the read-pair discovery of --repair inv-pairs";
+                    return -1;
+                }
+                caller.set_window_pairs(std::move(pairs));
+            }
             if (!S.only_close_mapped && !kept.empty()) caller.process_window(chrom, kept, ws, we, bed_start, bed_end);
             t_call += now() - t0; t0 = now();
             release_reads(kept);
@@ -252,8 +290,8 @@ inline bool read_bam_config(const std::string &config, std::vector<BamSource> &b
 }
 
 // -N: the BAMs of the configuration as the germline filter measures them (pg_depth.hpp); null with err set when one
-// cannot be opened
-inline std::shared_ptr<const GermlineDepth> open_germline(const std::vector<BamSource> &bams, std::string &err)
+// cannot be opened.  repairs: with REPAIR_DEPTH_MAPQ the depth counts records of MAPQ >= 20 only.
+inline std::shared_ptr<const GermlineDepth> open_germline(const std::vector<BamSource> &bams, std::string &err, uint32_t repairs = 0)
 {
     std::vector<std::string> paths, tags;
     for (const BamSource &b : bams) {
@@ -261,7 +299,7 @@ inline std::shared_ptr<const GermlineDepth> open_germline(const std::vector<BamS
         tags.push_back(b.tag);
     }
     std::shared_ptr<GermlineDepth> g(new GermlineDepth());
-    if (!g->open(paths, tags, err)) return nullptr;
+    if (!g->open(paths, tags, err, (repairs & REPAIR_DEPTH_MAPQ) ? (unsigned)DEPTH_MAPQ_FLOOR : 0u)) return nullptr;
     return g;
 }
 
@@ -331,6 +369,7 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<Re
     struct WinData {
         IngestedReads in;
         std::vector<std::pair<BDHints::RpSide, BDHints::RpSide>> sides;   // read-pair events of the window
+        std::vector<DiscordantPair> pairs;                                // --repair inv-pairs: its same-chromosome pairs
         size_t n_events = 0;
         std::string error;
     };
@@ -340,16 +379,21 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<Re
         const Win &win = wins[w];
         const Chromosome &chrom = genome[win.c];
         double t0 = now();
-        if (bd && search_rp) {
-            std::vector<RpRead> rp, rp_inter;
+        // --repair inv-pairs under -N: the pairs are discovered with -R false too, for the filter alone (no hint, no _RP line)
+        const bool hints = bd && search_rp;
+        const bool inv_pairs = S.germline_filter() && S.repair(REPAIR_INV_PAIRS) && S.Analyze_INV && !S.only_close_mapped;
+        if (hints || inv_pairs) {
+            std::vector<RpRead> rp, rp_inter, left;
             for (size_t k = 0; k < bams.size(); k++)
                 if (!rp_discover(files[k], chrom.name, win.ws, win.we, bams[k].insert_size, bams[k].tag, ingest.min_anchor_quality, rp,
-                                 S.report_interchromosomal ? &rp_inter : nullptr)) {
+                                 hints && S.report_interchromosomal ? &rp_inter : nullptr)) {
                     d->error = bams[k].path + ": BAM read failed";
                     return d;
                 }
-            std::vector<RpEvent> ev = rp_events(rp, S.spacer, &rp_out);
-            if (S.report_interchromosomal) {
+            std::vector<RpEvent> ev = rp_events(rp, S.spacer, hints ? &rp_out : nullptr, inv_pairs ? &left : nullptr);
+            if (inv_pairs) d->pairs = discordant_pairs(left);
+            if (!hints) ev.clear();
+            if (hints && S.report_interchromosomal) {
                 const double t1 = now();
                 const std::vector<RpEvent> inter = rp_events_interchr(rp_inter, S.spacer, &rp_out);
                 ev.insert(ev.end(), inter.begin(), inter.end());
@@ -466,6 +510,7 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<Re
             caller.update_ref_coverage(spans, in.ref_tags, win.ws, win.we);
         }
         t_cov += now() - t0; t0 = now();
+        caller.set_window_pairs(std::move(d->pairs));
         if (!S.only_close_mapped && !kept.empty()) caller.process_window(chrom, kept, win.ws, win.we, bed_start, bed_end);
         t_call += now() - t0; t0 = now();
         // the window's reads are freed behind the next window's work (one disposal in flight)

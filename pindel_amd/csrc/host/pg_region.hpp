@@ -9,7 +9,9 @@
 //   -c <chr>:<s>-<e>      [s, min(e, size)]          (commas in the coordinates are ignored)
 //   -j include.bed        the file's records instead (with -c ALL as given; with a -c region only those on its
 //                         chromosome that overlap it, clipped to it).  BED values are taken as Pindel's 1-based
-//                         positions, with no 0-based shift, as the reference does.
+//                         positions, with no 0-based shift, as the reference does -- unless bed_zero_based is set
+//                         (--repair bed0): then a record [s, e) of either file is the positions s + 1 ... e,
+//                         before anything else is done with it, and a record without a base (s == e) is left out.
 //   -J exclude.bed        CleanUpBedRecord on the include list (see clean_up below)
 //
 // `size` is the chromosome's .fai length, or the FASTA length without an .fai (the same number for a consistent
@@ -216,13 +218,24 @@ inline int parse_region(const std::string &text, RegionSpec &spec, std::string &
 // chromosome, a start beyond the chromosome's end, an unreadable or malformed BED file); err says which.
 inline int region_plan(const std::vector<std::string> &names, const std::vector<unsigned> &sizes, const std::string &region,
                        const std::string &include_bed, const std::string &exclude_bed, std::vector<RegionRecord> &plan,
-                       std::string &err)
+                       std::string &err, bool bed_zero_based = false)
 {
     using namespace region_detail;
     plan.clear();
     RegionSpec spec;
     int rc = parse_region(region, spec, err);
     if (rc) return rc;
+    // BED's [s, e), 0-based, as Pindel positions s + 1 ... e (read_bed has put the smaller value first)
+    auto zero_based = [&](std::vector<BedLine> &bed) {
+        if (!bed_zero_based) return;
+        std::vector<BedLine> kept;
+        for (BedLine b : bed) {
+            if (b.start == b.end) continue;
+            b.start++;
+            kept.push_back(b);
+        }
+        bed.swap(kept);
+    };
     RegionRecord target;                                // the -c region, when there is one
     if (!spec.all) {
         target.chr = find_chr(names, spec.chr);
@@ -251,6 +264,7 @@ inline int region_plan(const std::vector<std::string> &names, const std::vector<
     } else {
         std::vector<BedLine> bed;
         if ((rc = read_bed(include_bed, bed, err))) return rc;
+        zero_based(bed);
         for (const BedLine &b : bed) {
             RegionRecord r;
             r.chr = find_chr(names, b.chr);
@@ -271,6 +285,7 @@ inline int region_plan(const std::vector<std::string> &names, const std::vector<
     if (!exclude_bed.empty()) {
         std::vector<BedLine> bed;
         if ((rc = read_bed(exclude_bed, bed, err))) return rc;
+        zero_based(bed);
         std::vector<RegionRecord> exc;
         for (const BedLine &b : bed) {                  // (an exclude on a chromosome the reference lacks matches nothing)
             RegionRecord r;

@@ -246,7 +246,10 @@ inline void summarize(std::vector<RpRead> &v)
 
 // BDData::UpdateBD for the read pairs of one window: the events they support (>= 5 identical pairs), in the
 // reference's order of discovery; `rp_out` (nullable) receives the lines the reference appends to <prefix>_RP.
-inline std::vector<RpEvent> rp_events(std::vector<RpRead> &reads, unsigned spacer, std::ofstream *rp_out)
+// `left` (nullable) receives the list as it stands when UpdateBD clears it (src/bddata.cpp:733): sorted, boxes set by
+// ModifyRP -- what IsGoodINV was written to count in (--repair inv-pairs).
+inline std::vector<RpEvent> rp_events(std::vector<RpRead> &reads, unsigned spacer, std::ofstream *rp_out,
+                                      std::vector<RpRead> *left = nullptr)
 {
     using namespace rp_detail;
     std::vector<RpEvent> events;
@@ -287,6 +290,7 @@ inline std::vector<RpEvent> rp_events(std::vector<RpRead> &reads, unsigned space
             o << std::endl;
         }
     }
+    if (left) left->swap(reads);
     reads.clear();
     return events;
 }

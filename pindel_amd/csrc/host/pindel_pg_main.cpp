@@ -2,7 +2,8 @@
 //   pindel_pg -f ref.fa (-p reads.txt[.gz] | -P text_config | -i bam_config) -o prefix
 //                                              [-x 2 -a 1 -m 3 -u 0.02 -e 0.01 -E 0.95 -H 8
 //                                               -M 1 -B 100 -d 30 -v 50 -w 5 -G device -l -s -S -I
-//                                               -c ALL|chr[:start[-end]] -j include.bed -J exclude.bed -N]
+//                                               -c ALL|chr[:start[-end]] -j include.bed -J exclude.bed -N
+//                                               --repair int-pairs,inv-pairs,depth-mapq,bed0|all]
 // FASTA + Pindel-text reads -> close/far-end search on the MI355X (C ABI, libpindel_pg.so)
 // -> SV classification and <prefix>_D/_SI/_TD/_INV reports (host code in this directory);
 // -l adds <prefix>_LI (long insertions), -s <prefix>_CloseEndMapped (the reads with a close end),
@@ -11,6 +12,10 @@
 // need window hints, i.e. BAM input with -R or `-b file --bd-hints on`).  -P lists Pindel-text files, one per line (read before a
 // -p file when both are given); a text file whose name ends in .gz is read through zlib.  -N (--NormalSamples) turns on the
 // germline filter of _TD and _INV for BAM input (pg_depth.hpp); for text input it changes nothing.
+// --repair LIST (off by default) turns on fixes of reference defects that are otherwise reproduced byte for byte:
+// int-pairs (-I reports every chromosome pair of a window), inv-pairs (-N counts read pairs for inversions of two read lengths or
+// more instead of dropping them all), depth-mapq (-N's read depth ignores records below MAPQ 20), bed0 (-j / -J files are 0-based,
+// half-open); `all` is all four.  An unknown name or an empty list is a usage error (exit status 2, nothing written).
 // Like the reference, every run
 // creates all seven files (_D _SI _TD _INV _LI _BP _CloseEndMapped); _BP stays empty, as the
 // reference's breakpoint report is not called.  -c, -j and -J select the regions searched (pg_region.hpp); they are
@@ -74,7 +79,7 @@ int main(int argc, char **argv)
         { "-d", "--min_num_matched_bases", 'i' }, { "-v", "--min_inversion_size", 'i' },
         { "-w", "--window_size", 'f' }, { "-T", "--number_of_threads", 'i' }, { "-b", "--breakdancer", 's' },
         { "-G", "--gpus", 's' }, { "", "--bd-hints", 's' }, { "", "--flush-reads", 'i' }, { "-c", "--chromosome", 's' },
-        { "-j", "--include", 's' }, { "-J", "--exclude", 's' },
+        { "-j", "--include", 's' }, { "-J", "--exclude", 's' }, { "", "--repair", 's' },
         { "-n", "--NM", 'i' }, { "", "--min_NT_size", 'i' }, { "-A", "--anchor_quality", 'i' }, { "-L", "--logfilename", 's' },
         { "-r", "--report_inversions", 'u' }, { "-t", "--report_duplications", 'u' },
         { "-l", "--report_long_insertions", 'u' }, { "-k", "--report_breakpoints", 'u' },
@@ -178,6 +183,13 @@ int main(int argc, char **argv)
         else if (key == "--MIN_DD_CLUSTER_SIZE") dd.min_cluster_size = (int)iv;
         else if (key == "--MIN_DD_BREAKPOINT_SUPPORT") dd.min_bp_support = (int)iv;
         else if (key == "--MIN_DD_MAP_DISTANCE") dd.min_map_distance = (int)iv;
+        else if (key == "--repair") {
+            std::string rerr;
+            if (!parse_repairs(v, S.repairs, rerr)) {
+                fprintf(stderr, "pindel_pg: %s\n", rerr.c_str());
+                return 2;
+            }
+        }
         else if (key == "-j") include_bed = v;
         else if (key == "-J") exclude_bed = v;
         else if (key == "-T") {
@@ -248,7 +260,7 @@ int main(int argc, char **argv)
     std::vector<RegionRecord> plan;
     {
         const int prc = region_plan(chromosome_names(genome), chromosome_sizes(genome, fai, prm.spacer), region, include_bed, exclude_bed,
-                                    plan, err);
+                                    plan, err, S.repair(REPAIR_BED0));
         if (prc) {
             fprintf(stderr, "pindel_pg: %s\n", err.c_str());
             return prc;
@@ -258,6 +270,7 @@ int main(int argc, char **argv)
         printf("pindel_pg: no region left to search (every record of the include list is excluded); the reports are empty\n");
         return 0;
     }
+    if (S.repairs) printf("pindel_pg: repairs in effect: %s\n", repairs_text(S.repairs).c_str());
     for (const RegionRecord &r : plan) printf("Processing region: %s\t%u\t%u\n", genome[r.chr].name.c_str(), r.start, r.end);
     std::vector<SplitRead> all;
     if (text_input && load_pindel_inputs(pindel_config, reads_path, genome, all, err)) {
@@ -271,7 +284,7 @@ int main(int argc, char **argv)
         return 1;
     }
     // -N: IsGoodTD / IsGoodINV filter only when the reads come from BAMs (they return true early for -p and -P)
-    if (S.NormalSamples && !bams.empty() && !(S.germline = open_germline(bams, err))) {
+    if (S.NormalSamples && !bams.empty() && !(S.germline = open_germline(bams, err, S.repairs))) {
         fprintf(stderr, "pindel_pg: %s\n", err.c_str());
         return 1;
     }

@@ -22,7 +22,13 @@ class HostSettings(C.Structure):
         ("analyze_li", C.c_int32), ("report_close_mapped", C.c_int32),
         ("region", C.c_char_p), ("include_bed", C.c_char_p), ("exclude_bed", C.c_char_p),
         ("report_interchromosomal", C.c_int32),
-        ("normal_samples", C.c_int32), ("bam_config", C.c_char_p), ("pindel_config", C.c_char_p)]
+        ("normal_samples", C.c_int32), ("bam_config", C.c_char_p), ("pindel_config", C.c_char_p),
+        ("repairs", C.c_uint32)]
+
+
+# --repair names -> bits of HostSettings.repairs (pindel_amd/csrc/host/pg_host.hpp REPAIR_*)
+REPAIRS = {"int-pairs": 1, "inv-pairs": 2, "depth-mapq": 4, "bed0": 8}
+DEPTH_MAPQ_FLOOR = 20
 
 
 class VcfOptions(C.Structure):
@@ -75,6 +81,13 @@ def lib():
             C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(HostSettings), C.c_uint32,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pgh_region_depth.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.POINTER(C.c_double)]
+        L.pgh_region_depth_mapq.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.c_uint32, C.POINTER(C.c_double)]
+        L.pgh_depth_ratio_mapq.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_uint32,
+                                           C.POINTER(C.c_double)]
+        L.pgh_region_plan_bed.restype = C.c_int64
+        L.pgh_region_plan_bed.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_uint64]
+        L.pgh_parse_repairs.restype = C.c_int64
+        L.pgh_parse_repairs.argtypes = [C.c_char_p]
         L.pgh_depth_ratio.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.c_char_p, C.c_int64, C.c_int64, C.c_int64,
                                       C.POINTER(C.c_double)]
         L.pgh_depth_rule_td.argtypes = [C.c_int32, C.POINTER(C.c_double)]
@@ -107,6 +120,7 @@ def default_settings(max_mismatch) -> HostSettings:
     s.normal_samples = 0       # -N (default false): the germline filter of _TD and _INV; acts with bam_config only
     s.bam_config = None        # the -i configuration the reads were derived from (None = text input)
     s.pindel_config = None     # -P (None = no list of Pindel-text files)
+    s.repairs = 0              # --repair (default none): bits of REPAIRS, see repairs_mask
     for i in range(500):
         s.max_mismatch[i] = int(max_mismatch[i])
     return s
@@ -116,9 +130,24 @@ def _enc(x):
     return None if x is None else str(x).encode()
 
 
-def region_plan(fasta, region=None, include_bed=None, exclude_bed=None):
+def repairs_mask(repairs):
+    """--repair's argument -> the bits of HostSettings.repairs.  repairs: None (no repair), a comma-separated string
+    ("int-pairs,depth-mapq", "all") or an iterable of names.  Raises ValueError for an unknown name or an empty list,
+    as the command line ends with status 2 (parsed by the host library, so both agree on the names)."""
+    if repairs is None:
+        return 0
+    text = repairs if isinstance(repairs, str) else ",".join(repairs)
+    mask = lib().pgh_parse_repairs(text.encode())
+    if mask < 0:
+        raise ValueError((lib().pgh_last_error() or b"").decode())
+    return int(mask)
+
+
+def region_plan(fasta, region=None, include_bed=None, exclude_bed=None, bed_zero_based=False):
     """The records a run with -c region -j include_bed -J exclude_bed searches, in order: a list of
     (chromosome name, start, end), Pindel coordinates, both ends included (pindel_amd/csrc/host/pg_region.hpp).
+    bed_zero_based (--repair bed0): the records of both BED files are 0-based and half-open, [s, e) = positions s + 1 ... e;
+    by default they are taken as Pindel positions, as the reference does.
     Raises ValueError for a malformed region, an unknown chromosome, a start beyond the chromosome, an
     unreadable or malformed BED file."""
     L = lib()
@@ -126,7 +155,8 @@ def region_plan(fasta, region=None, include_bed=None, exclude_bed=None):
     cap = 64
     while True:
         out = np.zeros(3 * cap, dtype=np.uint32)
-        n = L.pgh_region_plan(_enc(fasta), _enc(region), _enc(include_bed), _enc(exclude_bed), out.ctypes.data, cap)
+        n = L.pgh_region_plan_bed(_enc(fasta), _enc(region), _enc(include_bed), _enc(exclude_bed), int(bool(bed_zero_based)),
+                                  out.ctypes.data, cap)
         if n < 0:
             raise ValueError("region plan: " + (L.pgh_last_error() or b"").decode())
         if n <= cap:
@@ -145,25 +175,26 @@ def _fasta_names(fasta):
     return out
 
 
-def region_depth(bam, chrom, beg, end):
+def region_depth(bam, chrom, beg, end, min_mapq=0):
     """Average read depth of [beg, end) (0-based) of chromosome `chrom` in one BAM, counted as Pindel's bam2depth does
     (pindel_amd/csrc/host/pg_depth.hpp): M/=/X bases of the reads that are not unmapped, secondary, QC-fail or duplicate,
-    MAPQ ignored, over end - beg.  0.0 when the BAM's header lacks the chromosome, NaN for an empty region."""
+    over end - beg.  MAPQ is ignored by default, as in the reference; min_mapq=20 is what --repair depth-mapq counts with
+    (records below it are left out).  0.0 when the BAM's header lacks the chromosome, NaN for an empty region."""
     L = lib()
     out = C.c_double(0.0)
-    if L.pgh_region_depth(_enc(bam), _enc(chrom), int(beg), int(end), C.byref(out)):
+    if L.pgh_region_depth_mapq(_enc(bam), _enc(chrom), int(beg), int(end), int(min_mapq), C.byref(out)):
         raise RuntimeError("pgh_region_depth: " + (L.pgh_last_error() or b"").decode())
     return out.value
 
 
-def depth_ratio(bams, chrom, chrom_size, start, end):
+def depth_ratio(bams, chrom, chrom_size, start, end, min_mapq=0):
     """Per BAM the standardised depth of the event [start, end) against its two flanks of the same length, clipped to
     [0, chrom_size): 2 * (2 * sv) / (before + after); -1.0 when before + after == 0, NaN when a flank has no length
-    (getRelativeCoverageInternal).  Returns a list of floats in the order of `bams`."""
+    (getRelativeCoverageInternal).  min_mapq as for region_depth.  Returns a list of floats in the order of `bams`."""
     L = lib()
     paths = (C.c_char_p * len(bams))(*[_enc(b) for b in bams])
     out = (C.c_double * len(bams))()
-    if L.pgh_depth_ratio(len(bams), paths, _enc(chrom), int(chrom_size), int(start), int(end), out):
+    if L.pgh_depth_ratio_mapq(len(bams), paths, _enc(chrom), int(chrom_size), int(start), int(end), int(min_mapq), out):
         raise RuntimeError("pgh_depth_ratio: " + (L.pgh_last_error() or b"").decode())
     return list(out)
 
@@ -176,7 +207,7 @@ def depth_rule_td(ratios):
 
 def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pts, far_off, far_pts,
                      rc_flag, region=None, include_bed=None, exclude_bed=None, reads_config=None, normal_samples=None,
-                     bam_config=None):
+                     bam_config=None, repairs=None):
     """Classify + report (_D, _SI, _TD, _INV) from per-read UP_Close / UP_Far points (CSR over
     all reads of the file, 12-byte pg_point records).  settings.analyze_li / settings.report_close_mapped
     add <out_prefix>_LI / <out_prefix>_CloseEndMapped, settings.report_interchromosomal <out_prefix>_INT and
@@ -186,7 +217,10 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
     before reads_txt (which may then be None), and the point arrays cover the concatenated reads in load order.  A text file
     whose name ends in .gz is read through zlib.  normal_samples (-N) with bam_config (an -i configuration): the reads are
     taken as derived from those BAMs, and _TD / _INV pass the germline filter with read depth from them; without bam_config
-    -N changes nothing (text input).  Both override the settings' fields when given."""
+    -N changes nothing (text input).  Both override the settings' fields when given.  repairs (--repair; see repairs_mask):
+    opt-in fixes of reference defects, replacing the settings' field when given: int-pairs, depth-mapq and bed0 as on the
+    command line; inv-pairs, with normal_samples and bam_config, discovers the discordant read pairs of every window in those
+    BAMs for the inversion filter."""
     L = lib()
     tmp_cfg = None
     if reads_config is not None and not isinstance(reads_config, (str, bytes, os.PathLike)):
@@ -194,13 +228,15 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
             f.write("".join(f"{os.path.abspath(str(x))}\n" for x in reads_config))
             tmp_cfg = reads_config = f.name
     keep = [_enc(region), _enc(include_bed), _enc(exclude_bed), _enc(reads_config), _enc(bam_config)]     # (alive until the call returns)
-    if any(k is not None for k in keep) or normal_samples is not None:
+    if any(k is not None for k in keep) or normal_samples is not None or repairs is not None:
         settings = HostSettings.from_buffer_copy(settings)
         for field, v in zip(("region", "include_bed", "exclude_bed", "pindel_config", "bam_config"), keep):
             if v is not None:
                 setattr(settings, field, v)
         if normal_samples is not None:
             settings.normal_samples = int(bool(normal_samples))
+        if repairs is not None:
+            settings.repairs = repairs_mask(repairs)
     close_off = np.ascontiguousarray(close_off, dtype=np.uint64)
     far_off = np.ascontiguousarray(far_off, dtype=np.uint64)
     close_pts = np.ascontiguousarray(close_pts)
