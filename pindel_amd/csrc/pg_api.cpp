@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "pg_device.h"
+#include "pg_host_plan.h"
 #include "pindel_pg.h"
 
 #include <chrono>
@@ -186,7 +187,7 @@ struct DevArena {
     size_t cap = 0, used = 0;
     void *take(size_t bytes)
     {
-        const size_t at = (used + 255) & ~(size_t)255;
+        const size_t at = pg_arena_align(used);
         if (at + bytes > cap) return nullptr;
         used = at + bytes;
         return base + at;
@@ -651,9 +652,6 @@ int validate_and_measure(pg_ctx *ctx, const pg_read_batch *reads, uint32_t *max_
     return PG_OK;
 }
 
-// Runs per list the chunked delivery of search_host has room for (1.04 per read on average; a batch that needs more
-// falls back to download(), which scans the whole batch first and sizes its buffers from the totals).
-static size_t deliver_cap(size_t n) { return env().tiny_delivery ? n / 2 + 8 : 2 * n + 4096; }   // (tests: force the fallback)
 // Reads per chunk of download() (PG_HOST_CHUNK: several chunks on a small batch), and the bytes of its device temporaries but
 // the gathered runs: per-read sums, 64-bit offsets (2 lists), per-block sums (one slice of blocks per chunk), 64 B of info per chunk
 static size_t download_chunk() { return env().host_chunk ? env().host_chunk : PG_DELIVER_CHUNK; }
@@ -666,16 +664,15 @@ static size_t download_scratch_bytes(size_t n)
 // Validates the batch and allocates its device buffers.  copy = true also copies the inputs
 // (synchronously); otherwise the caller streams them in (search_host).  off = read offsets rebased to 0.
 // use_arena: carve the buffers out of the ctx arena (host-path calls: the batch dies with the call).
+// plan (search_host; needs use_arena): the arena gets room for the delivery buffers the caller takes behind the batch, and
+// `off` room for the one-copy upload (pg_host_plan.h).
 PgSoaIn soa_in(const pg_ctx *ctx, const pg_device_batch *b);
 int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint64_t> &off, pg_device_batch **out,
-                bool use_arena = false)
+                bool use_arena = false, const PgHostPlan *plan = nullptr)
 {
     uint32_t max_len = 0, levels = 0;
     int32_t max_isz = 0;
-    // (room behind the offsets for the four small per-read arrays in the arena's layout: search_host sends a one-chunk batch's
-    // small inputs with ONE copy from this pinned block)
-    const size_t n_in = reads ? reads->n_reads : 0;
-    if (!off.resize(n_in + 1 + (use_arena ? (n_in * 11 + 6 * 512) / 8 + 8 : 0))) return fail(ctx, PG_E_NOMEM, "host memory for the read offsets");
+    if (!off.resize(plan ? plan->off_words : (reads ? reads->n_reads : 0) + (size_t)1)) return fail(ctx, PG_E_NOMEM, "host memory for the read offsets");
     int rc = validate_and_measure(ctx, reads, &max_len, &levels, &max_isz, off.data());
     if (rc) return rc;
     pg_device_batch *b = new pg_device_batch();
@@ -693,11 +690,14 @@ int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint
     b->pool_shard_cap = (uint32_t)std::min<uint64_t>(((PG_RESERVE + 2ull) * n) / PG_POOL_SHARDS + 512ull, 0x7fffffffull / PG_POOL_SHARDS);
     if (env().tiny_pool) b->pool_shard_cap = 1;      // tests: force the overflow/regrow path
     const size_t n1 = std::max<size_t>(n, 1);
+    const PgInputLayout in = pg_input_layout(n);
     // (pointer, bytes) of every buffer; the zeroed block (outputs) is contiguous in the arena case
     struct Item { void **p; size_t bytes; };
     const Item items[] = {
-        { (void **)&b->seq, (size_t)nseq + 16 }, { (void **)&b->seq_off, (n + 1) * 8 },
-        { (void **)&b->strand, n1 }, { (void **)&b->pos, n1 * 4 }, { (void **)&b->isz, n1 * 2 }, { (void **)&b->chr, n1 * 4 },
+        { (void **)&b->seq, (size_t)nseq + 16 },
+        // the five small inputs, one after the other: in the arena they lie as PgInputLayout says (the one-copy upload)
+        { (void **)&b->seq_off, in.a[PG_IN_SEQ_OFF].bytes }, { (void **)&b->strand, in.a[PG_IN_STRAND].bytes },
+        { (void **)&b->pos, in.a[PG_IN_POS].bytes }, { (void **)&b->isz, in.a[PG_IN_ISZ].bytes }, { (void **)&b->chr, in.a[PG_IN_CHR].bytes },
         // INVARIANT: every allocation of in_rec carries PG_IN_PAD records behind the last read -- search_read touches `rp + 1` with a
         // scalar load whose value is discarded (the next read's record into the scalar cache); this is the only place in_rec is
         // allocated, and a launch over a sub-range [lo, lo + cnt) of the batch touches at most record lo + cnt, which exists.
@@ -711,7 +711,7 @@ int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint
         { (void **)&b->out_rec, n1 * sizeof(PgOutRec) },
         // run-pool cursors, then per set of read counters (two: launches on the two kernel streams overlap) the counters and the
         // cycle accumulators of a -DPG_TIMING diagnostics build, which the kernel finds right behind its counters
-        { (void **)&b->pool_used, (PG_POOL_SHARDS * 16 + 2 * (PG_WORK_CTRS * 16 + PG_DIAG_WORDS * 2)) * 4 },   // + a second set of read counters  // run-pool cursors + the launch's read counters
+        { (void **)&b->pool_used, (PG_POOL_SHARDS * 16 + 2 * (PG_WORK_CTRS * 16 + PG_DIAG_WORDS * 2)) * 4 },   // + a second set of read counters
         { (void **)&b->run_tot, 64 },
         { (void **)&b->exact_count, 64 },
     };
@@ -725,13 +725,11 @@ int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint
     };
     if (use_arena) {
         size_t need = 4096;
-        for (const Item &it : items) need += ((it.bytes + 255) & ~(size_t)255) + 256;
+        for (const Item &it : items) need += pg_arena_room(it.bytes);
         // room for the download's temporaries too: gathered runs (no more than the pool holds) and the rest
         need += (size_t)b->pool_shard_cap * PG_POOL_SHARDS * sizeof(pg_run) + download_scratch_bytes(n) + 4096;
-        // ... and for the chunk-by-chunk delivery of search_host: gathered runs (2 lists), 64-bit offsets (2 lists), scratch
-        need += 2 * (deliver_cap(n) * sizeof(pg_run) + 512) + 2 * ((n + 1) * 8 + 512) + PG_DELIVER_CHUNK * 8 + 4096 * 8 +
-                (n / std::min<size_t>(PG_HOST_CHUNK / 4, env().host_chunk ? env().host_chunk : PG_HOST_CHUNK) + 16) * 64 +   // 64 B of info per chunk
-                8192 + 8 * n + 4096;                                           // (+ the summaries of a one-block delivery)
+        // ... and for the chunk-by-chunk delivery of search_host
+        if (plan) need += plan->arena_bytes;
         if (need > ctx->arena.cap) {
             if (ctx->arena.base) (void)hipFree(ctx->arena.base);
             ctx->arena.base = nullptr;
@@ -747,6 +745,7 @@ int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint
         ctx->arena.used = 0;
         b->in_arena = true;
         for (const Item &it : items) *it.p = ctx->arena.take(it.bytes);
+        if ((size_t)((char *)b->chr - (char *)b->seq_off) != in.a[PG_IN_CHR].off) return drop(fail(ctx, PG_E_DEVICE, "the batch inputs do not lie as PgInputLayout says"));
         char *z0 = (char *)*items[first_zero].p;
         char *z1 = (char *)*items[n_items - 1].p + items[n_items - 1].bytes;
         hipError_t e = hipMemsetAsync(z0, 0, (size_t)(z1 - z0), ctx->stream);
@@ -1109,6 +1108,261 @@ int download(pg_ctx *ctx, pg_device_batch *b, pg_result *r)
     // the buffers hold the totals exactly and the search has checked its pool: a gather that ran out of either is a bug
     for (size_t k = 0; k < n_chunks; k++)
         if (info[8 * k + 5]) return fail(ctx, PG_E_DEVICE, "download: the gather of chunk " + std::to_string(k) + " found a run list out of bounds");
+    return PG_OK;
+}
+
+// ---------------------------------------------------------------- host in / host out
+// Host buffers in, host results out, as a three-stage pipeline over chunks of 64 k to 1 M reads (PgHostPlan::bounds):
+//   copy stream      the chunk's inputs, host -> HBM
+//   compute stream   pack, search (the kernel takes a read range of the batch), delivery kernels: the chunk's runs
+//                    gathered in read order behind the earlier chunks', its 64-bit CSR offsets (pg_deliver_chunk)
+//   download stream  the chunk's slice of every result array -> pinned host memory, while the next chunk is searched
+// The host only waits for "chunk k delivered", reads the chunk's base and run counts (32 bytes) and queues its copies.
+// search_host is the driver: the plan (pg_host_plan.h) says what the call will do, the steps of HostCall do it and return a status.
+int hip_status(pg_ctx *ctx, hipError_t e, const char *what)
+{
+    if (e == hipSuccess) return PG_OK;
+    return fail(ctx, e == hipErrorOutOfMemory ? PG_E_NOMEM : PG_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// Owns the arena batch of one call and the result it has not returned yet.  A call that leaves without setting `ok` has failed:
+// nothing it queued on the four streams may outlive the buffers it points at.
+struct BatchGuard {
+    pg_device_batch *b = nullptr;
+    pg_result *r = nullptr;
+    bool ok = false;
+    ~BatchGuard()
+    {
+        if (!b) return;                                          // (alloc_batch failed: nothing was queued)
+        if (!ok) (void)hipDeviceSynchronize();
+        free_batch_buffers(b);
+        delete b;
+        if (!ok) delete r;
+    }
+};
+
+// The arrays a delivery writes and a result holds: parts of ONE block (block_views walks PgHostPlan::blk, for the pinned host
+// block and the device block alike; runs[1] is null, the far runs follow the close runs) or buffers of their own.
+struct DeliveryViews { unsigned long long *off[2]; uint8_t *rc; uint32_t *last; uint16_t *max; pg_run *runs[2]; };
+DeliveryViews block_views(const PgHostPlan &p, uint8_t *base)
+{
+    auto at = [&](int part) { return (void *)(base + p.blk[part].off); };
+    return { { (unsigned long long *)at(PG_BLK_CLOSE_OFF), (unsigned long long *)at(PG_BLK_FAR_OFF) }, (uint8_t *)at(PG_BLK_RC),
+             (uint32_t *)at(PG_BLK_LAST), (uint16_t *)at(PG_BLK_MAX), { (pg_run *)at(PG_BLK_RUNS), nullptr } };
+}
+
+struct Copy { void *dst; const void *src; size_t bytes; };
+int queue_copies(pg_ctx *ctx, std::initializer_list<Copy> copies, hipMemcpyKind kind, hipStream_t st, const char *what)
+{
+    for (const Copy &x : copies)
+        if (x.bytes)                                             // (reads without bases, a list without a run in this chunk)
+            if (int rc = hip_status(ctx, hipMemcpyAsync(x.dst, x.src, x.bytes, kind, st), what)) return rc;
+    return PG_OK;
+}
+
+// One call of search_host: what the steps share.
+struct HostCall {
+    pg_ctx *ctx;
+    const pg_read_batch *reads;
+    int mode;
+    const PgHostPlan &plan;
+    HostBuf<uint64_t> &off;                                      // the read offsets rebased to 0 (pinned; one block: + room for the one-copy upload)
+    pg_device_batch *b;
+    pg_result *r;
+    DeliveryViews d{};                                           // device side of the delivery
+    uint8_t *d_block = nullptr;
+    void *d_local = nullptr, *d_blk = nullptr;
+    unsigned long long *d_info = nullptr, tot[2] = { 0, 0 };
+    HostBuf<unsigned long long> info;                            // pinned mirror of d_info: 8 values per chunk
+    bool whole_batch = false;                // fall back to run_search (pool overflow) + download (pool or delivery overflow)
+    double t_res = 0, t_search = 0;
+
+    int setup();
+    int queue_chunk(uint32_t k);
+    int collect_chunk(uint32_t k);
+    int finish();
+};
+
+// The result's arrays (views into one pinned block, or buffers of their own with room for `cap` runs per list); then, for a batch
+// with reads, streams and events, the delivery buffers (arena: PgHostPlan::takes in order), the info's mirror, the clock's start.
+int HostCall::setup()
+{
+    const PgHostPlan &p = plan;
+    const size_t n = r->n = p.n;
+    if (p.single) {
+        if (!r->block.resize(p.blk_bytes)) return fail(ctx, PG_E_NOMEM, "pinned host memory for the result");
+        const DeliveryViews h = block_views(p, r->block.data());
+        r->close_off.set_view(h.off[0], n + 1, n + 1);
+        r->far_off.set_view(h.off[1], n + 1, n + 1);
+        r->rc_flag.set_view(h.rc, n, n);
+        r->close_last.set_view(h.last, n, n);
+        r->close_max.set_view(h.max, n, n);
+        r->close_runs.set_view(h.runs[0], 0, p.cap);
+        r->far_runs.set_view(h.runs[0], 0, 0);                   // (placed behind the close runs once their number is known)
+    } else if (!r->close_off.resize(n + 1) || !r->far_off.resize(n + 1) || !r->rc_flag.resize(n) || !r->close_last.resize(n) ||
+               !r->close_max.resize(n) || !r->close_runs.resize(n ? p.cap : 0) || !r->far_runs.resize(n ? p.cap : 0))
+        return fail(ctx, PG_E_NOMEM, "pinned host memory for the result");
+    t_res = t_search = now_ms();
+    if (!n) {
+        r->close_off[0] = r->far_off[0] = 0;
+        return PG_OK;
+    }
+    for (hipStream_t *s : { &ctx->copy_stream, &ctx->dl_stream, &ctx->stream2 })
+        if (!*s)
+            if (int rc = hip_status(ctx, hipStreamCreate(s), "hipStreamCreate")) return rc;
+    while (ctx->events.size() < 2 * (size_t)p.n_chunks + 1) {
+        hipEvent_t ev = nullptr;
+        if (int rc = hip_status(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreateWithFlags")) return rc;
+        ctx->events.push_back(ev);
+    }
+    void *got[PG_PLAN_MAX_TAKES], **t = got;
+    for (int k = 0; k < p.n_takes; k++)
+        if (!(got[k] = ctx->arena.take(p.takes[k]))) return fail(ctx, PG_E_NOMEM, "device arena too small for the delivery buffers");
+    if (p.single) {
+        d = block_views(p, d_block = (uint8_t *)*t++);
+    } else {
+        d = { { (unsigned long long *)t[2], (unsigned long long *)t[3] }, b->rc_flag, b->close_last, b->close_max, { (pg_run *)t[0], (pg_run *)t[1] } };
+        t += 4;
+    }
+    d_local = *t++;
+    d_blk = *t++;
+    d_info = (unsigned long long *)*t++;
+    if (!info.resize((size_t)p.n_chunks * 8)) return fail(ctx, PG_E_NOMEM, "pinned host memory");
+    // (the run-pool cursors, both sets of read counters and the delivery's running totals are zero from alloc_batch's one
+    // memset of the output block, queued on ctx->stream)
+    if (int rc = hip_status(ctx, hipEventRecord(ctx->ev0, ctx->stream), "hipEventRecord")) return rc;
+    if (p.n_chunks > 1) return hip_status(ctx, hipEventRecord(ctx->events[2 * p.n_chunks], ctx->stream), "hipEventRecord");
+    return PG_OK;
+}
+
+// Chunk k: input copy, waits, search launch, delivery, info copy, event; behind the last chunk the clock's end.
+int HostCall::queue_chunk(uint32_t k)
+{
+    const uint32_t n_chunks = plan.n_chunks, lo = plan.bounds[k], hi = plan.bounds[k + 1], cn = hi - lo;
+    const char *ev = "hipEventRecord", *wait = "hipStreamWaitEvent";
+    hipStream_t cs = ctx->copy_stream;
+    const Copy bases = { b->seq + off[lo], reads->seq ? reads->seq + reads->seq_off[0] + off[lo] : nullptr, (size_t)(off[hi] - off[lo]) };
+    // A one-chunk batch (Pindel's own 50 000-read flush): the five small arrays lie one after the other in the arena
+    // (alloc_batch, PgInputLayout), so they go as ONE copy from the pinned block that already holds the offsets -- queued before
+    // the bases, whose copy from pageable memory blocks the call.  (Five copies cost 60 us of calls and 40 us of serial DMA.)
+    const PgInputLayout &in = plan.in;
+    int rc;
+    if (plan.single && b->in_arena && in.span <= off.cap_bytes) {
+        char *h = (char *)off.data();
+        memcpy(h + in.a[PG_IN_STRAND].off, reads->anchor_strand, cn);
+        memcpy(h + in.a[PG_IN_POS].off, reads->anchor_pos, (size_t)cn * 4);
+        memcpy(h + in.a[PG_IN_ISZ].off, reads->insert_size, (size_t)cn * 2);
+        memcpy(h + in.a[PG_IN_CHR].off, reads->chr_id, (size_t)cn * 4);
+        rc = queue_copies(ctx, { { b->seq_off, h, in.span }, bases }, hipMemcpyHostToDevice, cs, "input copy");
+    } else
+        rc = queue_copies(ctx, { bases, { b->seq_off + lo, off.data() + lo, (size_t)(cn + 1) * 8 }, { b->strand + lo, reads->anchor_strand + lo, cn },
+                                 { b->pos + lo, reads->anchor_pos + lo, (size_t)cn * 4 }, { b->isz + lo, reads->insert_size + lo, (size_t)cn * 2 },
+                                 { b->chr + lo, reads->chr_id + lo, (size_t)cn * 4 } }, hipMemcpyHostToDevice, cs, "input copy");
+    if (rc || (rc = hip_status(ctx, hipEventRecord(ctx->events[2 * k], cs), ev))) return rc;
+    // even chunks on one kernel stream, odd chunks on the other: the next chunk's workgroups move in while this
+    // chunk's persistent launch drains; the deliveries stay in chunk order (running totals, shared scratch)
+    hipStream_t ks = (k & 1u) ? ctx->stream2 : ctx->stream;
+    if (k == 1 && (rc = hip_status(ctx, hipStreamWaitEvent(ks, ctx->events[2 * n_chunks], 0), wait))) return rc;   // (alloc_batch's memset)
+    if ((rc = hip_status(ctx, hipStreamWaitEvent(ks, ctx->events[2 * k], 0), wait))) return rc;
+    // (the chunk's records: packed by its search launch itself -- pack in place -- or, 64-bit candidate ids, by a launch of their own)
+    if ((rc = launch_range(ctx, b, mode, lo, cn, ks, (int)(k & 1u), k < 2, true))) return rc;
+    if (k > 0 && (rc = hip_status(ctx, hipStreamWaitEvent(ks, ctx->events[2 * (k - 1) + 1], 0), wait))) return rc;
+    const unsigned long long pool_runs = (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS;
+    rc = hip_status(ctx, (hipError_t)pg_deliver_chunk(b->out_rec + lo, cn, d.rc + lo, d.last + lo, d.max + lo, d_local, d_blk, b->run_tot, d_info + 8 * k,
+                                                      b->pool, pool_runs, d.runs[0], d.runs[1], plan.cap, d.off[0] + lo, d.off[1] + lo, b->pool_used, ks),
+                    "pg_deliver_chunk");
+    if (rc || (rc = queue_copies(ctx, { { info.data() + 8 * k, d_info + 8 * k, 64 } }, hipMemcpyDeviceToHost, ks, "info copy"))) return rc;
+    if ((rc = hip_status(ctx, hipEventRecord(ctx->events[2 * k + 1], ks), ev))) return rc;
+    if (k + 1 < n_chunks) return PG_OK;
+    // (the last delivery waited for every earlier one, so its stream's end is the end of the batch)
+    if (ks != ctx->stream && (rc = hip_status(ctx, hipStreamWaitEvent(ctx->stream, ctx->events[2 * k + 1], 0), wait))) return rc;
+    return hip_status(ctx, hipEventRecord(ctx->ev1, ctx->stream), ev);
+}
+
+// Chunk k is delivered: its slices (or the one block) to the host on the download stream -- or, an overflow, whole_batch.
+int HostCall::collect_chunk(uint32_t k)
+{
+    const uint32_t lo = plan.bounds[k], cn = plan.bounds[k + 1] - lo;
+    if (int rc = hip_status(ctx, hipEventSynchronize(ctx->events[2 * k + 1]), "hipEventSynchronize")) return rc;
+    const unsigned long long *in = info.data() + 8 * k, cap = plan.cap;
+    whole_batch = (plan.single ? in[2] + in[3] > cap : (in[0] + in[2] > cap || in[1] + in[3] > cap)) || in[5] || in[4] > b->pool_shard_cap;
+    if (whole_batch) return PG_OK;
+    tot[0] = in[0] + in[2];                                      // (one block: the bases are 0)
+    tot[1] = in[1] + in[3];
+    if (plan.single) {
+        // offsets, summaries, close runs, far runs: one copy
+        const size_t far_at = pg_plan_far_runs_at(plan, (size_t)in[2]), used = far_at + (size_t)in[3] * sizeof(pg_run);
+        r->far_runs.set_view(r->block.data() + far_at, (size_t)in[3], (size_t)in[3]);
+        return hip_status(ctx, hipMemcpyAsync(r->block.data(), d_block, used, hipMemcpyDeviceToHost, ctx->dl_stream), "result copy");
+    }
+    // (the close-end summary: only a later pg_far_end_batch on a close-only result reads it)
+    const size_t summary = mode == PG_MODE_CLOSE ? cn : 0;
+    return queue_copies(ctx, { { r->close_runs.data() + in[0], d.runs[0] + in[0], (size_t)in[2] * sizeof(pg_run) },
+                               { r->far_runs.data() + in[1], d.runs[1] + in[1], (size_t)in[3] * sizeof(pg_run) },
+                               { r->close_off.data() + lo, d.off[0] + lo, (size_t)cn * 8 }, { r->far_off.data() + lo, d.off[1] + lo, (size_t)cn * 8 },
+                               { r->rc_flag.data() + lo, d.rc + lo, cn }, { r->close_last.data() + lo, d.last + lo, summary * 4 },
+                               { r->close_max.data() + lo, d.max + lo, summary * 2 } }, hipMemcpyDeviceToHost, ctx->dl_stream, "result copy");
+}
+
+// Every chunk is queued and collected: the totals and the trimmed result, or the whole batch again.
+int HostCall::finish()
+{
+    float ms = 0.f;
+    int rc = hip_status(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    if (rc || (rc = hip_status(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1), "hipEventElapsedTime"))) return rc;
+    t_search = now_ms();
+    // (the last chunk's info saw every launch's pool cursors: its delivery waited for all the earlier ones)
+    const bool pool_overflow = info[8 * (size_t)(plan.n_chunks - 1) + 4] > b->pool_shard_cap;
+    if (pool_overflow) whole_batch = true;
+    if ((rc = hip_status(ctx, hipStreamSynchronize(ctx->dl_stream), "hipStreamSynchronize"))) return rc;
+    if (!pool_overflow) {
+        ctx->last_ms = ms;
+        ctx->last_runs = tot[0] + tot[1];
+    }
+    if (whole_batch) {
+        // a pool shard overflowed, or the lists outgrew the delivery buffers: the whole batch again with the regrown pool
+        // where needed, then download(): the same delivery kernels over the whole batch, into buffers sized from its totals
+        if (pool_overflow && (rc = run_search(ctx, b, mode))) return rc;
+        return download(ctx, b, r);
+    }
+    r->close_off[plan.n] = tot[0];
+    r->far_off[plan.n] = tot[1];
+    r->close_runs.resize((size_t)tot[0]);
+    r->far_runs.resize((size_t)tot[1]);
+    if (mode != PG_MODE_CLOSE) {                                 // not downloaded: pg_far_end_batch refuses such a result
+        r->close_last.resize(0);
+        r->close_max.resize(0);
+    }
+    return PG_OK;
+}
+
+int search_host(pg_ctx *ctx, const pg_read_batch *reads, int mode, pg_result **out)
+{
+    use_device(ctx);
+    if (!ctx || !out) return PG_E_INVALID;
+    *out = nullptr;
+    // (pinned, from the cache: as a malloc'd array the runtime locks its pages for the copy and the free() of 80 MB after a
+    // 10 M-read call spent 13 ms in munmap + unpinning)
+    HostBuf<uint64_t> off;
+    const double t_start = now_ms();
+    const PgHostPlan plan = pg_host_plan(reads ? reads->n_reads : 0u, env().host_chunk, env().no_single_block, env().tiny_delivery);
+    BatchGuard g;
+    int rc = alloc_batch(ctx, reads, false, off, &g.b, true, &plan);
+    if (rc) return rc;
+    const double t_alloc = now_ms();
+    HostCall c{ ctx, reads, mode, plan, off, g.b, g.r = new pg_result() };
+    if ((rc = c.setup())) return rc;
+    for (uint32_t k = 0; k < plan.n_chunks; k++)
+        if ((rc = c.queue_chunk(k))) return rc;
+    // as the chunks get delivered: their slices to the host
+    for (uint32_t k = 0; k < plan.n_chunks && !c.whole_batch; k++)
+        if ((rc = c.collect_chunk(k))) return rc;
+    if (plan.n && (rc = c.finish())) return rc;
+    if (g_host_timing)
+        fprintf(stderr, "pg_search_batch: %u reads: validate+alloc %.2f ms, result buffers %.2f ms, copy+search+delivery %.2f ms, tail %.2f ms%s\n",
+                plan.n, t_alloc - t_start, c.t_res - t_alloc, c.t_search - c.t_res, now_ms() - c.t_search, c.whole_batch ? " (whole-batch fallback)" : "");
+    g.ok = true;
+    *out = g.r;
     return PG_OK;
 }
 
@@ -1657,260 +1911,6 @@ int pg_device_batch_algorithmic_bytes(pg_ctx *ctx, pg_device_batch *b, double *b
     return PG_OK;
 }
 
-// ---------------------------------------------------------------- host in / host out
-// Host buffers in, host results out, as a three-stage pipeline over chunks of 64 k to 1 M reads (see `bounds` below):
-//   copy stream      the chunk's inputs, host -> HBM
-//   compute stream   pack, search (the kernel takes a read range of the batch), delivery kernels: the chunk's runs
-//                    gathered in read order behind the earlier chunks', its 64-bit CSR offsets (pg_deliver_chunk)
-//   download stream  the chunk's slice of every result array -> pinned host memory, while the next chunk is searched
-// The host only waits for "chunk k delivered", reads the chunk's base and run counts (32 bytes) and queues its copies.
-static int search_host(pg_ctx *ctx, const pg_read_batch *reads, int mode, pg_result **out)
-{
-    use_device(ctx);
-    if (!ctx || !out) return PG_E_INVALID;
-    *out = nullptr;
-    pg_device_batch *b = nullptr;
-    // (pinned, from the cache: as a malloc'd array the runtime locks its pages for the copy and the free() of 80 MB after a
-    // 10 M-read call spent 13 ms in munmap + unpinning)
-    HostBuf<uint64_t> off;
-    const double t_start = now_ms();
-    int rc = alloc_batch(ctx, reads, false, off, &b, true);
-    if (rc) return rc;
-    double t_alloc = now_ms();
-    pg_result *r = nullptr;
-    auto bail = [&](int code) {
-        // on an error nothing queued on the four streams may outlive the buffers it points at
-        if (code) (void)hipDeviceSynchronize();
-        free_batch_buffers(b);
-        delete b;
-        if (code && r) delete r;
-        return code;
-    };
-#define TRY3(call)                                                                           \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return bail(fail(ctx, e_ == hipErrorOutOfMemory ? PG_E_NOMEM : PG_E_DEVICE,      \
-                             std::string(#call) + ": " + hipGetErrorString(e_)));            \
-    } while (0)
-    const uint32_t n = b->n;
-    r = new pg_result();
-    r->n = n;
-    const bool chunk_env = env().host_chunk != 0u;               // (tests: several chunks on a small batch)
-    const uint32_t chunk = chunk_env ? env().host_chunk : PG_HOST_CHUNK;
-    // Chunk boundaries.  A launch of 256 k reads runs at 278 M reads/s, one of 1 M at ~310, one of 10 M at 323 (ramp-up and
-    // tail of the launch itself: profiles/r04/kernel_experiments.txt), but the first chunk's copy and the last chunk's
-    // delivery + download are exposed: small chunks first (a quarter of the base chunk, doubling), up to 2^20 reads in the
-    // middle, a third of what is left towards the end.
-    std::vector<uint32_t> bounds(1, 0u);
-    if (n > chunk && !chunk_env) {
-        uint64_t ramp = chunk / 4;
-        while (bounds.back() < n) {
-            const uint64_t left = n - bounds.back();
-            const uint64_t mid = std::min<uint64_t>(std::max<uint64_t>(left / 3, chunk), PG_DELIVER_CHUNK);
-            bounds.push_back((uint32_t)(bounds.back() + std::min<uint64_t>(std::min(ramp, mid), left)));
-            ramp *= 2;
-        }
-    }
-    while (bounds.back() < n) bounds.push_back((uint32_t)std::min<uint64_t>((uint64_t)bounds.back() + chunk, n));
-    const uint32_t n_chunks = (uint32_t)bounds.size() - 1;
-    // A batch that is ONE chunk (Pindel's own 50 000-read flushes) gets its whole result in ONE device-to-host copy: offsets,
-    // summaries and both run lists are laid out in one device block and one pinned host block (pg_result::block), the
-    // result's arrays are views into it -- five copies and their ~10 us of runtime call each otherwise.
-    const bool single = n_chunks == 1 && !env().no_single_block;
-    const size_t cap = single ? 2 * deliver_cap(n) : deliver_cap(n);       // (single: both lists share one buffer)
-    size_t o_coff = 0, o_foff = 0, o_rc = 0, o_last = 0, o_max = 0, o_runs = 0, blk_bytes = 0;
-    if (single) {
-        auto put = [&](size_t bytes) { const size_t at = blk_bytes; blk_bytes += (bytes + 15) & ~(size_t)15; return at; };
-        o_coff = put(((size_t)n + 1) * 8);
-        o_foff = put(((size_t)n + 1) * 8);
-        o_rc = put(n);
-        o_last = put((size_t)n * 4);
-        o_max = put((size_t)n * 2);
-        o_runs = put(cap * sizeof(pg_run));
-        if (!r->block.resize(blk_bytes)) return bail(fail(ctx, PG_E_NOMEM, "pinned host memory for the result"));
-        uint8_t *h = r->block.data();
-        r->close_off.set_view(h + o_coff, (size_t)n + 1, (size_t)n + 1);
-        r->far_off.set_view(h + o_foff, (size_t)n + 1, (size_t)n + 1);
-        r->rc_flag.set_view(h + o_rc, n, n);
-        r->close_last.set_view(h + o_last, n, n);
-        r->close_max.set_view(h + o_max, n, n);
-        r->close_runs.set_view(h + o_runs, 0, cap);
-        r->far_runs.set_view(h + o_runs, 0, 0);                  // (placed behind the close runs once their number is known)
-    } else if (!r->close_off.resize((size_t)n + 1) || !r->far_off.resize((size_t)n + 1) || !r->rc_flag.resize(n) ||
-               !r->close_last.resize(n) || !r->close_max.resize(n) || !r->close_runs.resize(n ? cap : 0) || !r->far_runs.resize(n ? cap : 0))
-        return bail(fail(ctx, PG_E_NOMEM, "pinned host memory for the result"));
-    const double t_res = now_ms();
-    double t_search = t_res;
-    bool whole_batch = false;                // fall back to run_search (pool overflow) + download (pool or delivery overflow)
-    if (n) {
-        if (!ctx->copy_stream) TRY3(hipStreamCreate(&ctx->copy_stream));
-        if (!ctx->dl_stream) TRY3(hipStreamCreate(&ctx->dl_stream));
-        if (!ctx->stream2) TRY3(hipStreamCreate(&ctx->stream2));
-        while (ctx->events.size() < 2 * (size_t)n_chunks + 1) {
-            hipEvent_t ev = nullptr;
-            TRY3(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            ctx->events.push_back(ev);
-        }
-        // delivery buffers (arena): gathered runs, 64-bit offsets, scratch, per-chunk info; pinned mirror of the info
-        pg_run *d_runs[2] = { nullptr, nullptr };
-        unsigned long long *d_off[2], *d_tot = b->run_tot, *d_info;
-        uint8_t *d_block = nullptr, *d_rc = b->rc_flag;
-        uint32_t *d_last = b->close_last;
-        uint16_t *d_max = b->close_max;
-        void *d_local, *d_blk;
-        if (single) {
-            if (!(d_block = (uint8_t *)ctx->arena.take(blk_bytes))) return bail(fail(ctx, PG_E_NOMEM, "device arena too small for the delivery buffers"));
-            d_off[0] = (unsigned long long *)(d_block + o_coff);
-            d_off[1] = (unsigned long long *)(d_block + o_foff);
-            d_rc = d_block + o_rc;
-            d_last = (uint32_t *)(d_block + o_last);
-            d_max = (uint16_t *)(d_block + o_max);
-            d_runs[0] = (pg_run *)(d_block + o_runs);            // d_runs[1] stays null: the far runs follow the close runs
-        } else if (!(d_runs[0] = (pg_run *)ctx->arena.take(cap * sizeof(pg_run))) || !(d_runs[1] = (pg_run *)ctx->arena.take(cap * sizeof(pg_run))) ||
-                   !(d_off[0] = (unsigned long long *)ctx->arena.take(((size_t)n + 1) * 8)) ||
-                   !(d_off[1] = (unsigned long long *)ctx->arena.take(((size_t)n + 1) * 8)))
-            return bail(fail(ctx, PG_E_NOMEM, "device arena too small for the delivery buffers"));
-        if (!(d_local = ctx->arena.take((size_t)PG_DELIVER_CHUNK * 8)) || !(d_blk = ctx->arena.take(4096 * 8)) ||
-            !(d_info = (unsigned long long *)ctx->arena.take((size_t)n_chunks * 64)))
-            return bail(fail(ctx, PG_E_NOMEM, "device arena too small for the delivery buffers"));
-        HostBuf<unsigned long long> info;
-        if (!info.resize((size_t)n_chunks * 8)) return bail(fail(ctx, PG_E_NOMEM, "pinned host memory"));
-        const uint64_t base0 = reads->seq_off[0];
-        const unsigned long long pool_runs = (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS;
-        // (the run-pool cursors, both sets of read counters and the delivery's running totals are zero from alloc_batch's one
-        // memset of the output block, queued on ctx->stream)
-        TRY3(hipEventRecord(ctx->ev0, ctx->stream));
-        if (n_chunks > 1) TRY3(hipEventRecord(ctx->events[2 * n_chunks], ctx->stream));
-        hipError_t e = hipSuccess;
-        for (uint32_t k = 0; k < n_chunks && e == hipSuccess && rc == PG_OK; k++) {
-            const uint32_t lo = bounds[k], hi = bounds[k + 1], cn = hi - lo;
-            hipStream_t cs = ctx->copy_stream;
-            // A one-chunk batch (Pindel's own 50 000-read flush): the five small arrays lie one after the other in the arena
-            // (alloc_batch), so they go as ONE copy from the pinned block that already holds the offsets -- queued before the
-            // bases, whose copy from pageable memory blocks the call.  (Five copies cost 60 us of calls and 40 us of serial DMA.)
-            const char *d0 = (const char *)b->seq_off;
-            const size_t o_str = (size_t)((const char *)b->strand - d0), o_pos = (size_t)((const char *)b->pos - d0),
-                         o_isz = (size_t)((const char *)b->isz - d0), o_chr = (size_t)((const char *)b->chr - d0), span = o_chr + (size_t)n * 4;
-            const bool one_copy = single && b->in_arena && (const char *)b->strand > d0 && o_str < o_pos && o_pos < o_isz && o_isz < o_chr &&
-                                  span <= off.cap_bytes && !env().no_single_block;
-            if (one_copy) {
-                char *h = (char *)off.data();
-                memcpy(h + o_str, reads->anchor_strand, n);
-                memcpy(h + o_pos, reads->anchor_pos, (size_t)n * 4);
-                memcpy(h + o_isz, reads->insert_size, (size_t)n * 2);
-                memcpy(h + o_chr, reads->chr_id, (size_t)n * 4);
-                e = hipMemcpyAsync(b->seq_off, h, span, hipMemcpyHostToDevice, cs);
-            }
-            if (e == hipSuccess && off[hi] > off[lo])
-                e = hipMemcpyAsync(b->seq + off[lo], reads->seq + base0 + off[lo], (size_t)(off[hi] - off[lo]), hipMemcpyHostToDevice, cs);
-            if (!one_copy) {
-                if (e == hipSuccess) e = hipMemcpyAsync(b->seq_off + lo, off.data() + lo, (size_t)(cn + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, cs);
-                if (e == hipSuccess) e = hipMemcpyAsync(b->strand + lo, reads->anchor_strand + lo, cn, hipMemcpyHostToDevice, cs);
-                if (e == hipSuccess) e = hipMemcpyAsync(b->pos + lo, reads->anchor_pos + lo, (size_t)cn * sizeof(int32_t), hipMemcpyHostToDevice, cs);
-                if (e == hipSuccess) e = hipMemcpyAsync(b->isz + lo, reads->insert_size + lo, (size_t)cn * sizeof(int16_t), hipMemcpyHostToDevice, cs);
-                if (e == hipSuccess) e = hipMemcpyAsync(b->chr + lo, reads->chr_id + lo, (size_t)cn * sizeof(int32_t), hipMemcpyHostToDevice, cs);
-            }
-            if (e == hipSuccess) e = hipEventRecord(ctx->events[2 * k], cs);
-            // even chunks on one kernel stream, odd chunks on the other: the next chunk's workgroups move in while this
-            // chunk's persistent launch drains; the deliveries stay in chunk order (running totals, shared scratch)
-            hipStream_t ks = (k & 1u) ? ctx->stream2 : ctx->stream;
-            if (e == hipSuccess && k == 1) e = hipStreamWaitEvent(ks, ctx->events[2 * n_chunks], 0);     // (the memsets above)
-            if (e == hipSuccess) e = hipStreamWaitEvent(ks, ctx->events[2 * k], 0);
-            // (the chunk's records: packed by its search launch itself -- pack in place -- or, 64-bit candidate ids, by a launch of their own)
-            if (e == hipSuccess) rc = launch_range(ctx, b, mode, lo, cn, ks, (int)(k & 1u), k < 2, true);
-            if (e == hipSuccess && rc == PG_OK) {
-                if (k > 0) e = hipStreamWaitEvent(ks, ctx->events[2 * (k - 1) + 1], 0);
-                if (e == hipSuccess)
-                    e = (hipError_t)pg_deliver_chunk(b->out_rec + lo, cn, d_rc + lo, d_last + lo, d_max + lo, d_local,
-                                                     d_blk, d_tot, d_info + 8 * k, b->pool, pool_runs, d_runs[0], d_runs[1], cap, d_off[0] + lo,
-                                                     d_off[1] + lo, b->pool_used, ks);
-                if (e == hipSuccess) e = hipMemcpyAsync(info.data() + 8 * k, d_info + 8 * k, 64, hipMemcpyDeviceToHost, ks);
-                if (e == hipSuccess) e = hipEventRecord(ctx->events[2 * k + 1], ks);
-            }
-        }
-        // (the last delivery waited for every earlier one, so its stream's end is the end of the batch)
-        hipStream_t last = ((n_chunks - 1) & 1u) ? ctx->stream2 : ctx->stream;
-        if (e == hipSuccess && last != ctx->stream) e = hipStreamWaitEvent(ctx->stream, ctx->events[2 * (n_chunks - 1) + 1], 0);
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
-        // as the chunks get delivered: their slices to the host
-        unsigned long long tot[2] = { 0, 0 };
-        for (uint32_t k = 0; k < n_chunks && e == hipSuccess && rc == PG_OK && !whole_batch; k++) {
-            const uint32_t lo = bounds[k], hi = bounds[k + 1], cn = hi - lo;
-            e = hipEventSynchronize(ctx->events[2 * k + 1]);
-            if (e != hipSuccess) break;
-            const unsigned long long *in = info.data() + 8 * k;
-            if ((single ? in[2] + in[3] > cap : (in[0] + in[2] > cap || in[1] + in[3] > cap)) || in[5] || in[4] > b->pool_shard_cap) {
-                whole_batch = true;
-                break;
-            }
-            hipStream_t ds = ctx->dl_stream;
-            if (single) {
-                // offsets, summaries, close runs, far runs: one copy
-                e = hipMemcpyAsync(r->block.data(), d_block, o_runs + (size_t)(in[2] + in[3]) * sizeof(pg_run), hipMemcpyDeviceToHost, ds);
-                r->far_runs.set_view(r->block.data() + o_runs + (size_t)in[2] * sizeof(pg_run), (size_t)in[3], (size_t)in[3]);
-                tot[0] = in[2];
-                tot[1] = in[3];
-                break;
-            }
-            if (in[2]) e = hipMemcpyAsync(r->close_runs.data() + in[0], d_runs[0] + in[0], (size_t)in[2] * sizeof(pg_run), hipMemcpyDeviceToHost, ds);
-            if (e == hipSuccess && in[3])
-                e = hipMemcpyAsync(r->far_runs.data() + in[1], d_runs[1] + in[1], (size_t)in[3] * sizeof(pg_run), hipMemcpyDeviceToHost, ds);
-            if (e == hipSuccess) e = hipMemcpyAsync(r->close_off.data() + lo, d_off[0] + lo, (size_t)cn * 8, hipMemcpyDeviceToHost, ds);
-            if (e == hipSuccess) e = hipMemcpyAsync(r->far_off.data() + lo, d_off[1] + lo, (size_t)cn * 8, hipMemcpyDeviceToHost, ds);
-            if (e == hipSuccess) e = hipMemcpyAsync(r->rc_flag.data() + lo, b->rc_flag + lo, cn, hipMemcpyDeviceToHost, ds);
-            if (mode == PG_MODE_CLOSE) {          // the close-end summary: only a later pg_far_end_batch on this result reads it
-                if (e == hipSuccess) e = hipMemcpyAsync(r->close_last.data() + lo, b->close_last + lo, (size_t)cn * 4, hipMemcpyDeviceToHost, ds);
-                if (e == hipSuccess) e = hipMemcpyAsync(r->close_max.data() + lo, b->close_max + lo, (size_t)cn * 2, hipMemcpyDeviceToHost, ds);
-            }
-            tot[0] = in[0] + in[2];
-            tot[1] = in[1] + in[3];
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (rc) return bail(rc);
-        TRY3(e);
-        float ms = 0.f;
-        TRY3(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        t_search = now_ms();
-        // (the last chunk's info saw every launch's pool cursors: its delivery waited for all the earlier ones)
-        const uint32_t worst = (uint32_t)std::min<unsigned long long>(info[8 * (size_t)(n_chunks - 1) + 4], 0xffffffffull);
-        const uint64_t total = tot[0] + tot[1];
-        if (worst > b->pool_shard_cap) whole_batch = true;
-        if (!whole_batch) {
-            ctx->last_ms = ms;
-            ctx->last_runs = total;
-            TRY3(hipStreamSynchronize(ctx->dl_stream));
-            r->close_off[n] = tot[0];
-            r->far_off[n] = tot[1];
-            r->close_runs.resize((size_t)tot[0]);
-            r->far_runs.resize((size_t)tot[1]);
-            if (mode != PG_MODE_CLOSE) {                  // not downloaded: pg_far_end_batch refuses such a result
-                r->close_last.resize(0);
-                r->close_max.resize(0);
-            }
-        } else {
-            // a pool shard overflowed, or the lists outgrew the delivery buffers: the whole batch again with the regrown pool
-            // where needed, then download(): the same delivery kernels over the whole batch, into buffers sized from its totals
-            TRY3(hipStreamSynchronize(ctx->dl_stream));
-            if (worst > b->pool_shard_cap) {
-                if ((rc = run_search(ctx, b, mode))) return bail(rc);
-            } else {
-                ctx->last_ms = ms;
-                ctx->last_runs = total;
-            }
-            if ((rc = download(ctx, b, r))) return bail(rc);
-        }
-    } else {
-        r->close_off[0] = r->far_off[0] = 0;
-    }
-#undef TRY3
-    if (g_host_timing)
-        fprintf(stderr, "pg_search_batch: %u reads: validate+alloc %.2f ms, result buffers %.2f ms, copy+search+delivery %.2f ms, tail %.2f ms%s\n",
-                b->n, t_alloc - t_start, t_res - t_alloc, t_search - t_res, now_ms() - t_search, whole_batch ? " (whole-batch fallback)" : "");
-    *out = r;
-    return bail(PG_OK);
-}
-
 int pg_close_end_batch(pg_ctx *ctx, const pg_read_batch *reads, pg_result **out)
 {
     return search_host(ctx, reads, PG_MODE_CLOSE, out);
@@ -1924,6 +1924,19 @@ int pg_search_batch(pg_ctx *ctx, const pg_read_batch *reads, pg_result **out)
     return rc;
 }
 
+// reads [lo, hi) of a batch; the offsets of a slice need not start at 0
+static pg_read_batch slice(const pg_read_batch &reads, uint32_t lo, uint32_t hi)
+{
+    pg_read_batch sub = reads;
+    sub.n_reads = hi - lo;
+    sub.seq_off += lo;
+    sub.anchor_strand += lo;
+    sub.anchor_pos += lo;
+    sub.insert_size += lo;
+    sub.chr_id += lo;
+    return sub;
+}
+
 int pg_search_batch_multi(pg_ctx *const *ctxs, int32_t n_ctx, const pg_read_batch *reads, pg_result **out)
 {
     if (!ctxs || n_ctx <= 0 || !reads || !out) return PG_E_INVALID;
@@ -1932,20 +1945,14 @@ int pg_search_batch_multi(pg_ctx *const *ctxs, int32_t n_ctx, const pg_read_batc
     *out = nullptr;
     const uint32_t n = reads->n_reads;
     if (n_ctx == 1 || n < 2u * (uint32_t)n_ctx) return search_host(ctxs[0], reads, PG_MODE_BOTH, out);
-    // contiguous ranges, one host thread per context; the offsets of a sub-batch need not start at 0
+    // contiguous ranges, one host thread per context
     std::vector<pg_result *> parts((size_t)n_ctx, nullptr);
     std::vector<int> rcs((size_t)n_ctx, PG_OK);
     std::vector<std::thread> th;
     for (int k = 0; k < n_ctx; k++)
         th.emplace_back([&, k]() {
             const uint32_t lo = (uint32_t)((uint64_t)n * k / n_ctx), hi = (uint32_t)((uint64_t)n * (k + 1) / n_ctx);
-            pg_read_batch sub = *reads;
-            sub.n_reads = hi - lo;
-            sub.seq_off += lo;
-            sub.anchor_strand += lo;
-            sub.anchor_pos += lo;
-            sub.insert_size += lo;
-            sub.chr_id += lo;
+            const pg_read_batch sub = slice(*reads, lo, hi);
             rcs[(size_t)k] = search_host(ctxs[k], &sub, PG_MODE_BOTH, &parts[(size_t)k]);
         });
     for (std::thread &t : th) t.join();
@@ -2075,37 +2082,31 @@ static int attach_windows(pg_ctx *ctx, pg_device_batch *b, const pg_windows *bd_
 static int far_end_impl(pg_ctx *ctx, const pg_read_batch *reads, const uint8_t *rc_flag, const uint32_t *close_last,
                         const uint16_t *close_max, const pg_windows *bd_hints, pg_result *dst)
 {
-    pg_device_batch *b = nullptr;
+    BatchGuard g;
     HostBuf<uint64_t> off0;
-    int rc = alloc_batch(ctx, reads, true, off0, &b, true);
+    int rc = alloc_batch(ctx, reads, true, off0, &g.b, true);
     if (rc) return rc;
-    auto bail = [&](int code) {
-        free_batch_buffers(b);
-        delete b;
-        return code;
-    };
+    pg_device_batch *b = g.b;
     const size_t n = b->n;
     if (n) {
         // (the output block of the batch, rc_flag included, was zeroed by alloc_batch; the records are packed by the search launch)
         if ((rc_flag && hipMemcpyAsync(b->rc_flag, rc_flag, n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) ||
             hipMemcpyAsync(b->close_last, close_last, n * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
             hipMemcpyAsync(b->close_max, close_max, n * 2, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-            return bail(fail(ctx, PG_E_DEVICE, "upload of close-end summary failed"));
+            return fail(ctx, PG_E_DEVICE, "upload of close-end summary failed");
         const PgSoaOut a = soa_out(b);
         if (pg_pack_close_summary(&a, b->out_rec, b->n, ctx->stream) != 0)
-            return bail(fail(ctx, PG_E_DEVICE, "close-end summary pack kernel failed"));
+            return fail(ctx, PG_E_DEVICE, "close-end summary pack kernel failed");
         if (hipStreamSynchronize(ctx->stream) != hipSuccess)       // the host arrays may be pageable temporaries
-            return bail(fail(ctx, PG_E_DEVICE, "upload of close-end summary failed"));
+            return fail(ctx, PG_E_DEVICE, "upload of close-end summary failed");
     }
-    if ((rc = attach_windows(ctx, b, bd_hints, false))) return bail(rc);
-    rc = run_search(ctx, b, PG_MODE_FAR, true);
-    if (rc) return bail(rc);
+    if ((rc = attach_windows(ctx, b, bd_hints, false)) || (rc = run_search(ctx, b, PG_MODE_FAR, true))) return rc;
     pg_result tmp;
-    rc = download(ctx, b, &tmp);
-    if (rc) return bail(rc);
+    if ((rc = download(ctx, b, &tmp))) return rc;
     dst->far_off.swap(tmp.far_off);
     dst->far_runs.swap(tmp.far_runs);
-    return bail(PG_OK);
+    g.ok = true;
+    return PG_OK;
 }
 
 int pg_far_end_batch(pg_ctx *ctx, const pg_read_batch *reads, pg_result *close, const pg_windows *bd_hints)

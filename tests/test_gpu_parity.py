@@ -819,6 +819,40 @@ def test_download_is_repeatable(engine_factory, small_ref, pg_env, flush6500):
     eng.free_device_batch(db)
 
 
+def test_one_arena_across_calls_whose_plans_differ(engine_factory, small_ref, pg_env, flush6500):
+    """The host path sizes its arena and takes its delivery buffers from one list per call (pg_host_plan.h); ONE engine -- one
+    arena, one event list -- goes through calls whose plans differ: one block, one chunk without the block, 15 chunks of 7
+    reads with a ragged last one (more chunks than any other test: the event list and the per-chunk info grow), no read, one
+    read, the large batch again, the close end and the far end apart.  Every result is the oracle's; those of the several-chunk
+    and no-block calls are also the device-resident path's array for array."""
+    batch, orc = flush6500
+    eng = engine_factory()
+    eng.load_reference(small_ref)
+    sub = {n: batch.slice(0, n) for n in (0, 1, 100, 300)}
+    dev100, dev6500 = _device_resident(eng, sub[100]), _device_resident(eng, batch)
+
+    def check(res, n, dev=None, **kw):
+        compare_result(res, _oracle_prefix(orc, n), n, **kw)
+        if dev is not None:
+            _assert_same_result(res, dev, n)
+
+    check(eng.search_batch(sub[300]), 300)
+    pg_env.set("PG_NO_SINGLE_BLOCK", "1")
+    check(eng.search_batch(batch), batch.n, dev6500)
+    pg_env.unset("PG_NO_SINGLE_BLOCK")
+    pg_env.set("PG_HOST_CHUNK", "7")
+    check(eng.search_batch(sub[100]), 100, dev100)
+    pg_env.unset("PG_HOST_CHUNK")
+    res = eng.search_batch(sub[0])
+    check(res, 0)
+    assert len(res.close_runs) == 0 and len(res.far_runs) == 0
+    check(eng.search_batch(sub[1]), 1)
+    check(eng.search_batch(batch), batch.n, dev6500)
+    close = eng.close_end_batch(batch)
+    check(close, batch.n, check_far=False)
+    check(eng.far_end_batch(batch, close), batch.n, dev6500)
+
+
 def test_adapter_on_reference_shapes(engine_factory, tmp_path):
     """INTEGRATION.md's binding run against reference-shaped types (tests/ref_shapes.hpp = the public interface of
     src/pindel.h's SPLIT_READ / SortedUniquePoints / UniquePoint): seam 1 in 700-read flushes, the reads with a close end
