@@ -275,5 +275,25 @@ private:
     unsigned win_start_ = 0, win_end_ = 0;
 };
 
+// The clusters of a list of query positions (each a read's last close-end AbsLoc) in the loaded region, as CSR: off has
+// n + 1 entries, win the windows of all positions in order -- what the far end takes as per-read window hints.
+struct HintWindows {
+    std::vector<uint64_t> off;
+    std::vector<BDWindow> win;
+};
+template <class PosOf>
+HintWindows hint_windows(const BDHints &bd, size_t n, PosOf pos_of)
+{
+    HintWindows h;
+    h.off.reserve(n + 1);
+    h.off.push_back(0);
+    for (size_t i = 0; i < n; i++) {
+        const std::vector<BDWindow> &c = bd.cluster(pos_of(i));
+        h.win.insert(h.win.end(), c.begin(), c.end());
+        h.off.push_back(h.win.size());
+    }
+    return h;
+}
+
 }  // namespace pgh
 #endif

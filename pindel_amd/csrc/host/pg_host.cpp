@@ -249,45 +249,6 @@ int load_pindel_text(const std::string &path, const std::vector<Chromosome> &gen
     return 0;
 }
 
-// ------------------------------------------------------------------ --repair
-namespace {
-const struct { const char *name; uint32_t bit; } repair_names[] = {
-    { "int-pairs", REPAIR_INT_PAIRS }, { "inv-pairs", REPAIR_INV_PAIRS }, { "depth-mapq", REPAIR_DEPTH_MAPQ }, { "bed0", REPAIR_BED0 },
-};
-}  // namespace
-
-bool parse_repairs(const std::string &list, uint32_t &mask, std::string &err)
-{
-    mask = 0;
-    const std::string known = "int-pairs, inv-pairs, depth-mapq, bed0 or all";
-    if (list.empty()) {
-        err = "--repair needs a list of names: " + known;
-        return false;
-    }
-    for (size_t at = 0; at <= list.size();) {
-        const size_t comma = std::min(list.find(',', at), list.size());
-        const std::string name = list.substr(at, comma - at);
-        uint32_t bit = name == "all" ? (uint32_t)REPAIR_ALL : 0;
-        for (const auto &r : repair_names)
-            if (name == r.name) bit = r.bit;
-        if (!bit) {
-            err = "--repair: unknown name '" + name + "' (known: " + known + ")";
-            return false;
-        }
-        mask |= bit;
-        at = comma + 1;
-    }
-    return true;
-}
-
-std::string repairs_text(uint32_t mask)
-{
-    std::string out;
-    for (const auto &r : repair_names)
-        if (mask & r.bit) out += (out.empty() ? "" : ",") + std::string(r.name);
-    return out;
-}
-
 // ------------------------------------------------------------------ caller
 Caller::Caller(const Settings &s, const std::vector<Chromosome> *g, const std::string &out_prefix,
                bool truncate_outputs)

@@ -15,10 +15,11 @@
 //                SortAndReportInterChromosomalEvents src/reporter.cpp:2428-2665 and MergeInterChr
 //                src/pindel.cpp:1514-1579 (pg_host_int.cpp)
 // The search itself is NOT here: UP_Close / UP_Far come from the GPU through the C ABI
-// (include/pindel_pg.h).  No HIP dependency in this file; plain g++.
+// (include/pindel_pg.h, of which this file uses the plain C types).  No HIP dependency in this file; plain g++.
 #ifndef PG_HOST_HPP
 #define PG_HOST_HPP
 
+#include <algorithm>
 #include <cstdint>
 #include <map>
 #include <memory>
@@ -28,6 +29,8 @@
 #include <string>
 #include <utility>
 #include <vector>
+
+#include "pindel_pg.h"
 
 namespace pgh {
 
@@ -39,6 +42,19 @@ struct UniquePoint {              // src/pindel.h:137-158
     char Strand = 'N';            // '+' SENSE, '-' ANTISENSE
     short Mismatches = 0;
 };
+
+// A point of the C ABI as the classifiers read it (inline: it runs per point of every read that has a close end)
+inline UniquePoint to_unique_point(const pg_point &p)
+{
+    UniquePoint u;
+    u.chr = p.chr_id;
+    u.LengthStr = p.length;
+    u.AbsLoc = p.abs_loc;
+    u.Direction = p.direction;
+    u.Strand = p.strand;
+    u.Mismatches = p.mismatches;
+    return u;
+}
 
 struct SplitRead {                // the SPLIT_READ fields used downstream, src/pindel.h:265-383
     std::string Name, UnmatchedSeq, FragName, FarFragName, Tag, NT_str;
@@ -78,10 +94,42 @@ enum : uint32_t {
 };
 enum { DEPTH_MAPQ_FLOOR = 20 };   // what getRelativeCoverageForFiltering passes (and bam2depth ignores)
 
-// "name,name,..." or "all" -> bitmask.  false: an unknown name or an empty list (err says which).
-bool parse_repairs(const std::string &list, uint32_t &mask, std::string &err);
+const struct { const char *name; uint32_t bit; } repair_names[] = {
+    { "int-pairs", REPAIR_INT_PAIRS }, { "inv-pairs", REPAIR_INV_PAIRS }, { "depth-mapq", REPAIR_DEPTH_MAPQ }, { "bed0", REPAIR_BED0 },
+};
+// "name,name,..." or "all" -> bitmask.  false: an unknown name or an empty list (err says which).  (Inline, like the
+// rest of what the command line's parser needs: pg_cli.hpp links against nothing.)
+inline bool parse_repairs(const std::string &list, uint32_t &mask, std::string &err)
+{
+    mask = 0;
+    const std::string known = "int-pairs, inv-pairs, depth-mapq, bed0 or all";
+    if (list.empty()) {
+        err = "--repair needs a list of names: " + known;
+        return false;
+    }
+    for (size_t at = 0; at <= list.size();) {
+        const size_t comma = std::min(list.find(',', at), list.size());
+        const std::string name = list.substr(at, comma - at);
+        uint32_t bit = name == "all" ? (uint32_t)REPAIR_ALL : 0;
+        for (const auto &r : repair_names)
+            if (name == r.name) bit = r.bit;
+        if (!bit) {
+            err = "--repair: unknown name '" + name + "' (known: " + known + ")";
+            return false;
+        }
+        mask |= bit;
+        at = comma + 1;
+    }
+    return true;
+}
 // the names of `mask`, comma-separated, in the order of the bits ("" for 0)
-std::string repairs_text(uint32_t mask);
+inline std::string repairs_text(uint32_t mask)
+{
+    std::string out;
+    for (const auto &r : repair_names)
+        if (mask & r.bit) out += (out.empty() ? "" : ",") + std::string(r.name);
+    return out;
+}
 
 // One same-chromosome discordant read pair of a window as BDData::UpdateBD leaves it before clearing its list
 // (RP_READ after ModifyRP, src/bddata.cpp:646-733): what IsGoodINV's loop reads of it.  InsertSize is

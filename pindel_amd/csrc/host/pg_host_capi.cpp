@@ -123,16 +123,6 @@ int pgh_call_from_points(const char *fasta_path, const char *reads_path, const c
     if (region_plan(chromosome_names(genome), chromosome_sizes(genome, read_fai(fasta_path, genome), S.spacer), str_or_empty(st->region),
                     str_or_empty(st->include_bed), str_or_empty(st->exclude_bed), plan, g_err, S.repair(REPAIR_BED0)))
         return -1;
-    auto to_up = [](const pg_point &p) {
-        UniquePoint u;
-        u.chr = p.chr_id;
-        u.LengthStr = p.length;
-        u.AbsLoc = p.abs_loc;
-        u.Direction = p.direction;
-        u.Strand = p.strand;
-        u.Mismatches = p.mismatches;
-        return u;
-    };
     auto attach = [&](const Chromosome &, int, std::vector<SplitRead> &reads, const std::vector<uint32_t> &index) {
         for (size_t k = 0; k < reads.size(); k++) {
             const uint32_t i = index[k];
@@ -141,8 +131,8 @@ int pgh_call_from_points(const char *fasta_path, const char *reads_path, const c
                 r.UnmatchedSeq = reverse_complement(r.UnmatchedSeq);
                 while (!r.UnmatchedSeq.empty() && !std::isalnum((unsigned char)r.UnmatchedSeq.back())) r.UnmatchedSeq.pop_back();
             }
-            for (uint64_t q = close_off[i]; q < close_off[i + 1]; q++) r.UP_Close.push_back(to_up(close_pts[q]));
-            for (uint64_t q = far_off[i]; q < far_off[i + 1]; q++) r.UP_Far.push_back(to_up(far_pts[q]));
+            for (uint64_t q = close_off[i]; q < close_off[i + 1]; q++) r.UP_Close.push_back(to_unique_point(close_pts[q]));
+            for (uint64_t q = far_off[i]; q < far_off[i + 1]; q++) r.UP_Far.push_back(to_unique_point(far_pts[q]));
         }
         return 0;
     };
@@ -321,6 +311,21 @@ int pgh_reports_to_vcf(const pgh_vcf_options *o)
     return reports_to_vcf(v, g_err) ? 1 : 0;
 }
 
+// The clusters of the n_q query positions q (hint_windows, pg_bdhints.hpp) into the caller's arrays: out_off has n_q + 1
+// entries, out_win 3 ints (chr id, start, end) per window.  false: out_win (room for cap windows) is too small.
+static bool pack_hint_windows(const pgh::BDHints &h, uint32_t n_q, const uint32_t *q, uint64_t *out_off, int32_t *out_win, uint64_t cap)
+{
+    const pgh::HintWindows hw = pgh::hint_windows(h, n_q, [&](size_t i) { return q[i]; });
+    if (hw.win.size() > cap) return false;
+    std::copy(hw.off.begin(), hw.off.end(), out_off);
+    for (size_t k = 0; k < hw.win.size(); k++) {
+        out_win[3 * k] = hw.win[k].chr_id;
+        out_win[3 * k + 1] = (int32_t)hw.win[k].start;
+        out_win[3 * k + 2] = (int32_t)hw.win[k].end;
+    }
+    return true;
+}
+
 // BreakDancer hints (pg_bdhints.hpp) for one bin: clusters of the reads whose last close-end point is at
 // q[i].  out_off has n_q + 1 entries, out_win 3 ints (chr id, start, end) per window; returns the status
 // of load_file (0 / 1 = ignored), -1 = cannot open, -2 = unknown chromosome, -3 = out_win too small.
@@ -336,19 +341,7 @@ int pgh_bd_query(const char *path, uint32_t spacer, int32_t n_chr, const char *c
     if (rc < 0) return -1;
     std::vector<std::string> nm(names, names + n_chr);
     if (!h.load_region(nm, chr_id, start, end, g_err)) return -2;
-    uint64_t k = 0;
-    out_off[0] = 0;
-    for (uint32_t i = 0; i < n_q; i++) {
-        for (const pgh::BDWindow &w : h.cluster(q[i])) {
-            if (k >= cap) return -3;
-            out_win[3 * k] = w.chr_id;
-            out_win[3 * k + 1] = (int32_t)w.start;
-            out_win[3 * k + 2] = (int32_t)w.end;
-            k++;
-        }
-        out_off[i + 1] = k;
-    }
-    return rc;
+    return pack_hint_windows(h, n_q, q, out_off, out_win, cap) ? rc : -3;
 }
 
 // BAM ingest (pg_bam.hpp): the split-read candidates of one window of one BAM file as the SoA batch of the C ABI.
@@ -439,68 +432,41 @@ int32_t pgh_bai_summary(const char *bai_path, uint64_t *out, uint32_t cap_refs)
     return (int32_t)bins.size();
 }
 
-// Read-pair discovery (pg_rp.hpp): the BreakDancer-like events of one window of one BAM.  out receives 4 values per
-// event (pos1, pos1b, pos2, pos2b, Pindel coordinates); rp_path (nullable): the lines of <prefix>_RP.
+// Read-pair discovery (pg_rp.hpp) on one window of one BAM: its BreakDancer-like events, with the interchromosomal pairs'
+// events after the same-chromosome ones when interchr is set (what -I adds).  rp_path (nullable): the lines of <prefix>_RP.
+// names (nullable) receives the chromosome names of the BAM header.  false: a file error (g_err).
+static bool window_rp_events(const char *bam_path, const char *chr_name, int64_t win_start, int64_t win_end, int32_t insert_size,
+                             const char *tag, uint32_t min_anchor_quality, uint32_t spacer, bool interchr, const char *rp_path,
+                             std::vector<pgh::RpEvent> &ev, std::vector<std::string> *names = nullptr)
+{
+    pgh::BamFile bam;
+    if (!bam.open(bam_path, g_err)) return false;
+    std::vector<pgh::RpRead> rp, rp_inter;
+    if (!pgh::rp_discover(bam, chr_name, win_start, win_end, insert_size, tag ? tag : "", min_anchor_quality, rp, interchr ? &rp_inter : nullptr))
+        return false;
+    std::ofstream f;
+    if (rp_path) f.open(rp_path, std::ios::trunc);
+    ev = pgh::rp_events(rp, spacer, rp_path ? &f : nullptr);
+    if (interchr) {
+        const std::vector<pgh::RpEvent> inter = pgh::rp_events_interchr(rp_inter, spacer, rp_path ? &f : nullptr);
+        ev.insert(ev.end(), inter.begin(), inter.end());
+    }
+    if (names) *names = bam.header().names;
+    return true;
+}
+
+// The same-chromosome events of one window of one BAM: out receives 4 values per event (pos1, pos1b, pos2, pos2b, Pindel
+// coordinates).  Returns the number of events, -1 on a file error.
 int64_t pgh_rp_events(const char *bam_path, const char *chr_name, int64_t win_start, int64_t win_end, int32_t insert_size,
                       const char *tag, uint32_t min_anchor_quality, uint32_t spacer, const char *rp_path, uint32_t *out, uint64_t cap)
 {
-    pgh::BamFile bam;
-    if (!bam.open(bam_path, g_err)) return -1;
-    std::vector<pgh::RpRead> rp;
-    if (!pgh::rp_discover(bam, chr_name, win_start, win_end, insert_size, tag ? tag : "", min_anchor_quality, rp)) return -1;
-    std::ofstream f;
-    if (rp_path) f.open(rp_path, std::ios::trunc);
-    const std::vector<pgh::RpEvent> ev = pgh::rp_events(rp, spacer, rp_path ? &f : nullptr);
+    std::vector<pgh::RpEvent> ev;
+    if (!window_rp_events(bam_path, chr_name, win_start, win_end, insert_size, tag, min_anchor_quality, spacer, false, rp_path, ev)) return -1;
     for (size_t i = 0; i < ev.size() && i < cap; i++) {
         out[4 * i] = ev[i].pos1;
         out[4 * i + 1] = ev[i].pos1b;
         out[4 * i + 2] = ev[i].pos2;
         out[4 * i + 3] = ev[i].pos2b;
-    }
-    return (int64_t)ev.size();
-}
-
-// The window hints of one bin exactly as `pindel_pg -i ... [-b file]` with -R hands them to the far end
-// (run_bam_pipeline): events of the -b file (bd_path may be null / empty) + the read-pair events of this window of
-// this BAM (UpdateBD; [win_start, win_end) = the window as clipped to the chromosome), loadRegion for the bin
-// [win_start, region_end) (the unclipped bin, as main() hands it over), then the cluster of every query position
-// (= last close-end AbsLoc).
-// out_off: n_q + 1 entries, out_win: 3 ints (chr id, start, end) per window.  Returns the number of read-pair
-// events, -1 on a file error, -2 unknown chromosome, -3 out_win too small.
-int64_t pgh_window_hints(const char *bd_path, const char *bam_path, int32_t n_chr, const char *const *names, int32_t chr_id,
-                         int64_t win_start, int64_t win_end, int64_t region_end, int32_t insert_size, const char *tag,
-                         uint32_t min_anchor_quality, uint32_t spacer, uint32_t n_q, const uint32_t *q, uint64_t *out_off, int32_t *out_win, uint64_t cap)
-{
-    pgh::BDHints h;
-    std::string note;
-    if (bd_path && bd_path[0] && h.load_file(bd_path, spacer, note) < 0) {
-        g_err = note;
-        return -1;
-    }
-    std::vector<std::string> nm(names, names + n_chr);
-    pgh::BamFile bam;
-    if (!bam.open(bam_path, g_err)) return -1;
-    std::vector<pgh::RpRead> rp;
-    if (!pgh::rp_discover(bam, nm[chr_id], win_start, win_end, insert_size, tag ? tag : "", min_anchor_quality, rp)) return -1;
-    const std::vector<pgh::RpEvent> ev = pgh::rp_events(rp, spacer, nullptr);
-    std::vector<std::pair<pgh::BDHints::RpSide, pgh::BDHints::RpSide>> sides;
-    for (const pgh::RpEvent &e : ev) {
-        pgh::BDHints::RpSide a = { e.chr1, e.pos1, e.pos1b }, b = { e.chr2, e.pos2, e.pos2b };
-        sides.push_back(std::make_pair(a, b));
-    }
-    h.update_with_rp(sides);
-    if (!h.load_region(nm, chr_id, (unsigned)win_start + spacer, (unsigned)region_end + spacer, g_err)) return -2;
-    uint64_t k = 0;
-    out_off[0] = 0;
-    for (uint32_t i = 0; i < n_q; i++) {
-        for (const pgh::BDWindow &w : h.cluster(q[i])) {
-            if (k >= cap) return -3;
-            out_win[3 * k] = w.chr_id;
-            out_win[3 * k + 1] = (int32_t)w.start;
-            out_win[3 * k + 2] = (int32_t)w.end;
-            k++;
-        }
-        out_off[i + 1] = k;
     }
     return (int64_t)ev.size();
 }
@@ -527,19 +493,11 @@ int64_t pgh_rp_events_chr(const char *bam_path, const char *chr_name, int64_t wi
                           const char *tag, uint32_t min_anchor_quality, uint32_t spacer, int32_t interchr, const char *rp_path, int64_t *out,
                           uint64_t cap)
 {
-    pgh::BamFile bam;
-    if (!bam.open(bam_path, g_err)) return -1;
-    std::vector<pgh::RpRead> rp, rp_inter;
-    if (!pgh::rp_discover(bam, chr_name, win_start, win_end, insert_size, tag ? tag : "", min_anchor_quality, rp, interchr ? &rp_inter : nullptr))
+    std::vector<pgh::RpEvent> ev;
+    std::vector<std::string> names;
+    if (!window_rp_events(bam_path, chr_name, win_start, win_end, insert_size, tag, min_anchor_quality, spacer, interchr != 0, rp_path, ev, &names))
         return -1;
-    std::ofstream f;
-    if (rp_path) f.open(rp_path, std::ios::trunc);
-    std::vector<pgh::RpEvent> ev = pgh::rp_events(rp, spacer, rp_path ? &f : nullptr);
-    if (interchr) {
-        const std::vector<pgh::RpEvent> inter = pgh::rp_events_interchr(rp_inter, spacer, rp_path ? &f : nullptr);
-        ev.insert(ev.end(), inter.begin(), inter.end());
-    }
-    events_with_chromosomes(ev, bam.header().names, out, cap);
+    events_with_chromosomes(ev, names, out, cap);
     return (int64_t)ev.size();
 }
 
@@ -580,8 +538,15 @@ int64_t pgh_rp_interchr_pairs(uint32_t n, const int32_t *chr_a, const int32_t *c
     return (int64_t)ev.size();
 }
 
-// pgh_window_hints with -I's interchromosomal pairs when interchr != 0 (UpdateBD hands both kinds to the event list), and with the
-// read-pair events themselves: ev_out (nullable) receives 6 values per event (events_with_chromosomes, indices into names).
+// The window hints of one bin exactly as `pindel_pg -i ... [-b file]` with -R hands them to the far end
+// (run_bam_pipeline): events of the -b file (bd_path may be null / empty) + the read-pair events of this window of
+// this BAM (UpdateBD; [win_start, win_end) = the window as clipped to the chromosome), loadRegion for the bin
+// [win_start, region_end) (the unclipped bin, as main() hands it over), then the cluster of every query position
+// (= last close-end AbsLoc).
+// out_off: n_q + 1 entries, out_win: 3 ints (chr id, start, end) per window.  Returns the number of read-pair
+// events, -1 on a file error, -2 unknown chromosome, -3 out_win too small.
+// interchr != 0: with -I's interchromosomal pairs (UpdateBD hands both kinds to the event list).  ev_out (nullable) receives the
+// read-pair events themselves, 6 values per event (events_with_chromosomes, indices into names).
 int64_t pgh_window_hints_chr(const char *bd_path, const char *bam_path, int32_t n_chr, const char *const *names, int32_t chr_id,
                              int64_t win_start, int64_t win_end, int64_t region_end, int32_t insert_size, const char *tag,
                              uint32_t min_anchor_quality, uint32_t spacer, int32_t interchr, uint32_t n_q, const uint32_t *q, uint64_t *out_off,
@@ -594,37 +559,22 @@ int64_t pgh_window_hints_chr(const char *bd_path, const char *bam_path, int32_t 
         return -1;
     }
     std::vector<std::string> nm(names, names + n_chr);
-    pgh::BamFile bam;
-    if (!bam.open(bam_path, g_err)) return -1;
-    std::vector<pgh::RpRead> rp, rp_inter;
-    if (!pgh::rp_discover(bam, nm[chr_id], win_start, win_end, insert_size, tag ? tag : "", min_anchor_quality, rp, interchr ? &rp_inter : nullptr))
+    std::vector<pgh::RpEvent> ev;
+    if (!window_rp_events(bam_path, nm[chr_id].c_str(), win_start, win_end, insert_size, tag, min_anchor_quality, spacer, interchr != 0, nullptr, ev))
         return -1;
-    std::vector<pgh::RpEvent> ev = pgh::rp_events(rp, spacer, nullptr);
-    if (interchr) {
-        const std::vector<pgh::RpEvent> inter = pgh::rp_events_interchr(rp_inter, spacer, nullptr);
-        ev.insert(ev.end(), inter.begin(), inter.end());
-    }
     if (ev_out) events_with_chromosomes(ev, nm, ev_out, ev_cap);
-    std::vector<std::pair<pgh::BDHints::RpSide, pgh::BDHints::RpSide>> sides;
-    for (const pgh::RpEvent &e : ev) {
-        pgh::BDHints::RpSide a = { e.chr1, e.pos1, e.pos1b }, b = { e.chr2, e.pos2, e.pos2b };
-        sides.push_back(std::make_pair(a, b));
-    }
-    h.update_with_rp(sides);
+    h.update_with_rp(rp_sides(ev));
     if (!h.load_region(nm, chr_id, (unsigned)win_start + spacer, (unsigned)region_end + spacer, g_err)) return -2;
-    uint64_t k = 0;
-    out_off[0] = 0;
-    for (uint32_t i = 0; i < n_q; i++) {
-        for (const pgh::BDWindow &w : h.cluster(q[i])) {
-            if (k >= cap) return -3;
-            out_win[3 * k] = w.chr_id;
-            out_win[3 * k + 1] = (int32_t)w.start;
-            out_win[3 * k + 2] = (int32_t)w.end;
-            k++;
-        }
-        out_off[i + 1] = k;
-    }
-    return (int64_t)ev.size();
+    return pack_hint_windows(h, n_q, q, out_off, out_win, cap) ? (int64_t)ev.size() : -3;
+}
+
+// ... for the same-chromosome pairs alone, without the events
+int64_t pgh_window_hints(const char *bd_path, const char *bam_path, int32_t n_chr, const char *const *names, int32_t chr_id,
+                         int64_t win_start, int64_t win_end, int64_t region_end, int32_t insert_size, const char *tag,
+                         uint32_t min_anchor_quality, uint32_t spacer, uint32_t n_q, const uint32_t *q, uint64_t *out_off, int32_t *out_win, uint64_t cap)
+{
+    return pgh_window_hints_chr(bd_path, bam_path, n_chr, names, chr_id, win_start, win_end, region_end, insert_size, tag, min_anchor_quality,
+                                spacer, 0, n_q, q, out_off, out_win, cap, NULL, 0);
 }
 
 // MergeInterChr alone: the _INT_final text of an _INT file (write_int_final, pg_host_int.cpp)

@@ -94,6 +94,18 @@ inline std::vector<DiscordantPair> discordant_pairs(const std::vector<RpRead> &l
     return out;
 }
 
+// Read-pair events as BDHints::update_with_rp takes them: the two sides of each
+inline std::vector<std::pair<BDHints::RpSide, BDHints::RpSide>> rp_sides(const std::vector<RpEvent> &ev)
+{
+    std::vector<std::pair<BDHints::RpSide, BDHints::RpSide>> sides;
+    sides.reserve(ev.size());
+    for (const RpEvent &e : ev) {
+        BDHints::RpSide a = { e.chr1, e.pos1, e.pos1b }, b = { e.chr2, e.pos2, e.pos2b };
+        sides.push_back(std::make_pair(a, b));
+    }
+    return sides;
+}
+
 // The same-chromosome discordant pairs of window [ws, we) of `chr_name` over all BAMs, for a pipeline that does not
 // discover them anyway: discovery and UpdateBD's steps, no event kept, no _RP line.  false: a BAM read failed.
 inline bool window_pairs(std::vector<BamFile> &files, const std::vector<int> &insert_sizes, const std::vector<std::string> &tags,
@@ -399,10 +411,7 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<Re
                 ev.insert(ev.end(), inter.begin(), inter.end());
                 t_rp_inter += now() - t1;
             }
-            for (const RpEvent &e : ev) {
-                BDHints::RpSide a = { e.chr1, e.pos1, e.pos1b }, b = { e.chr2, e.pos2, e.pos2b };
-                d->sides.push_back(std::make_pair(a, b));
-            }
+            d->sides = rp_sides(ev);
             d->n_events = ev.size();
         }
         t_rp += now() - t0; t0 = now();
@@ -478,16 +487,8 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<Re
                 r.FragName = chrom.name;
                 r.chr_id = (int)c;
                 r.MAX_SNP_ERROR = (short)S.max_mismatch[std::min<int>(r.ReadLength, 499)];
-                pg_adapter::fill_points(r.UP_Close, p.close_runs, p.close_off[j], p.close_off[j + 1], [](const pg_point &q) {
-                    UniquePoint u;
-                    u.chr = q.chr_id;
-                    u.LengthStr = q.length;
-                    u.AbsLoc = q.abs_loc;
-                    u.Direction = q.direction;
-                    u.Strand = q.strand;
-                    u.Mismatches = q.mismatches;
-                    return u;
-                });
+                pg_adapter::fill_points(r.UP_Close, p.close_runs, p.close_off[j], p.close_off[j + 1],
+                                        [](const pg_point &q) { return to_unique_point(q); });   // (a lambda, not the function's address: inlined)
             }
         });
         if (view.release) view.release();
