@@ -400,6 +400,13 @@ class Engine:
         self._L.pg_debug_last_pack_in_place.argtypes = [C.c_void_p]
         return bool(self._L.pg_debug_last_pack_in_place(self._h))
 
+    def last_fixed_len(self) -> int:
+        """tests: the read length of the fixed-length kernel (pg_search_fixed_kernel) the last search launch ran; 0 when it ran
+        any other kernel, or none yet"""
+        self._L.pg_debug_last_fixed_len.argtypes = [C.c_void_p]
+        self._L.pg_debug_last_fixed_len.restype = C.c_uint32
+        return int(self._L.pg_debug_last_fixed_len(self._h))
+
     def launch_log(self):
         """tests: the kernels the search path launched since the last clear_launch_log, in launch order -- LaunchRec tuples
         (kernel 1 search / 2 exact / 3 pack, blocks = NB or PB, ns, id_bits, mode, default, in_place)."""

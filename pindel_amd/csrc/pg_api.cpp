@@ -55,6 +55,7 @@ void load_env()
     e.no_pack_in_place = getenv("PG_NO_PACK_IN_PLACE") != nullptr;
     e.pack_claim = getenv("PG_PACK_CLAIM") ? (uint32_t)std::max(1, atoi(getenv("PG_PACK_CLAIM"))) : 0u;
     e.pack_in_place_min = getenv("PG_PACK_IN_PLACE_MIN") ? (uint32_t)std::max(1, atoi(getenv("PG_PACK_IN_PLACE_MIN"))) : PG_PACK_IN_PLACE_MIN;
+    e.no_fixed_len = getenv("PG_NO_FIXED_LEN") != nullptr;
     g_env = e;
 }
 const PgEnvSwitches &env()
@@ -230,6 +231,10 @@ struct pg_ctx {
     uint32_t ref_epoch = 0;            // counts reference (re)loads: a device batch's records hold chromosome offsets and sizes
     bool kargs_checked = false;        // the kernels' view of the kernarg segment was checked on this device (pg_debug_kargs_check)
     bool last_in_place = false;        // the last launch asked to pack did so inside the search kernel (pg_debug_last_pack_in_place)
+    // the fixed-length kernels (PgFixedLen, pg_device.h): this context's length tables reproduce every baked row (compared once, at
+    // pg_create: only then may a launch run one); the LEN of the last search launch's kernel, 0 if it was any other (pg_debug_last_fixed_len)
+    bool fixed_ok = false;
+    std::atomic<uint32_t> last_fixed_len{0};
     // The launch log (pg_debug_launch_log): every kernel launch on the search path in launch order, the first PG_LAUNCH_LOG_CAP
     // since the last pg_debug_clear_launch_log; launch_n counts them all.  A slot is claimed atomically (launches of one context
     // may come from more than one host thread) and costs a few host stores, no device work.
@@ -248,6 +253,7 @@ void log_launch(pg_ctx *ctx, const PgLaunchRec &r)
 struct pg_device_batch {
     uint32_t n = 0;
     uint32_t max_len = 0, levels = 0;
+    uint32_t uniform_len = 0;          // the length of every read of the batch when they all have one (0: mixed lengths, no reads)
     int32_t max_isz = 0;
     int64_t max_bd_window = 0;         // largest BreakDancer window attached (positions)
     uint64_t max_bd_cluster = 0;       // most windows attached to one read
@@ -583,8 +589,9 @@ void host_ranges(size_t n, Fn fn)
 
 // max_isz (nullable): largest insert size of the batch
 // off_out (nullable, n + 1 entries): the read offsets rebased to 0, written in the same pass
+// uniform_len (nullable): the one length all reads have, 0 when they differ (or there are none)
 int validate_and_measure(pg_ctx *ctx, const pg_read_batch *reads, uint32_t *max_len, uint32_t *levels, int32_t *max_isz = nullptr,
-                         uint64_t *off_out = nullptr)
+                         uint64_t *off_out = nullptr, uint32_t *uniform_len = nullptr)
 {
     if (!reads || (reads->n_reads && (!reads->seq_off || !reads->anchor_strand || !reads->anchor_pos ||
                                       !reads->insert_size || !reads->chr_id)))
@@ -594,7 +601,12 @@ int validate_and_measure(pg_ctx *ctx, const pg_read_batch *reads, uint32_t *max_
     if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
     const int n_chr = (int)ctx->names.size();
     // per range: first problem found (0 = none; the lowest code wins, as in a sequential scan the first one would), longest read
-    struct Part { int code = 0; uint32_t ml = 1; int32_t isz = 0; };
+    // ... and the one length of its reads (NO_LEN: no read yet, MIXED: more than one length)
+    static constexpr uint64_t NO_LEN = ~0ull, MIXED = ~0ull - 1ull;
+    struct Part {
+        int code = 0; uint32_t ml = 1; int32_t isz = 0; uint64_t ul = NO_LEN;
+        void see(uint64_t len) { ul = ul == NO_LEN || ul == len ? len : MIXED; }
+    };
     std::mutex mu;
     Part all;
     size_t first_bad = (size_t)-1;
@@ -624,11 +636,13 @@ int validate_and_measure(pg_ctx *ctx, const pg_read_batch *reads, uint32_t *max_
                 break;
             }
             p.ml = std::max<uint32_t>(p.ml, (uint32_t)len);
+            p.see(len);
             p.isz = std::max<int32_t>(p.isz, reads->insert_size[i]);
         }
         std::lock_guard<std::mutex> lk(mu);
         all.ml = std::max(all.ml, p.ml);
         all.isz = std::max(all.isz, p.isz);
+        if (p.ul != NO_LEN) all.see(p.ul);
         if (p.code && bad < first_bad) {
             first_bad = bad;
             all.code = p.code;
@@ -644,6 +658,7 @@ int validate_and_measure(pg_ctx *ctx, const pg_read_batch *reads, uint32_t *max_
     const uint32_t ml = all.ml;
     *max_len = ml;
     if (max_isz) *max_isz = all.isz;
+    if (uniform_len) *uniform_len = all.ul == NO_LEN || all.ul == MIXED ? 0u : (uint32_t)all.ul;
     uint32_t lv = ctx->mm[ml] + (uint32_t)ctx->prm.additional_mismatch + 1;
     for (uint32_t l = 0; l <= ml; l++)
         lv = std::max<uint32_t>(lv, ctx->mm[l] + (uint32_t)ctx->prm.additional_mismatch + 1);
@@ -670,10 +685,10 @@ PgSoaIn soa_in(const pg_ctx *ctx, const pg_device_batch *b);
 int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint64_t> &off, pg_device_batch **out,
                 bool use_arena = false, const PgHostPlan *plan = nullptr)
 {
-    uint32_t max_len = 0, levels = 0;
+    uint32_t max_len = 0, levels = 0, uniform_len = 0;
     int32_t max_isz = 0;
     if (!off.resize(plan ? plan->off_words : (reads ? reads->n_reads : 0) + (size_t)1)) return fail(ctx, PG_E_NOMEM, "host memory for the read offsets");
-    int rc = validate_and_measure(ctx, reads, &max_len, &levels, &max_isz, off.data());
+    int rc = validate_and_measure(ctx, reads, &max_len, &levels, &max_isz, off.data(), &uniform_len);
     if (rc) return rc;
     pg_device_batch *b = new pg_device_batch();
     b->n = reads->n_reads;
@@ -681,6 +696,7 @@ int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint
     // a repack or a new set of windows after a reload of the reference is refused, not re-stamped (stale_batch)
     b->ref_epoch = ctx->ref_epoch;
     b->max_len = max_len;
+    b->uniform_len = uniform_len;
     b->levels = levels;
     b->max_isz = max_isz;
     const size_t n = b->n;
@@ -949,7 +965,11 @@ int launch_range(pg_ctx *ctx, pg_device_batch *b, int mode, uint32_t lo, uint32_
     }
     PgLaunchRec recs[PG_LAUNCH_RECS_MAX];
     int n_recs = 0;
-    int lrc = pg_launch_search(&ref, &prm, &d, mode, b->max_len, b->levels, small_ids(ctx, b) ? 1 : 0, st, recs, &n_recs);
+    // (a batch of one read length under the baked length tables: the launch may run that length's kernel)
+    uint32_t fixed_len = 0;
+    int lrc = pg_launch_search(&ref, &prm, &d, mode, b->max_len, b->levels, small_ids(ctx, b) ? 1 : 0, st, recs, &n_recs,
+                               ctx->fixed_ok ? b->uniform_len : 0u, &fixed_len);
+    ctx->last_fixed_len.store(fixed_len, std::memory_order_relaxed);
     if (lrc != 0) return fail(ctx, PG_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString((hipError_t)lrc));
     for (int k = 0; k < n_recs; k++) log_launch(ctx, recs[k]);
     // ... then, behind it on the same stream, the reads of this range that hold a character outside ACGTN, with the reference's
@@ -1411,6 +1431,44 @@ void pg_default_params(pg_params *p)
     p->spacer = 100000;
 }
 
+// Do the context's length tables (pg_len_rec of its parameters) reproduce every baked row of the fixed-length kernels ?
+static bool fixed_row_matches(const PgFixedLen &f, const PgLenRec &r)
+{
+    return f.lvl == r.lvl && f.depth == r.depth && f.jmask0 == r.jmask0 && f.ro == r.ro && f.jmask1 == r.jmask1;
+}
+static bool fixed_rows_match(const PgLenRec *len_tab)
+{
+    const PgFixedLen rows[PG_FIXED_LENS] = PG_FIXED_LEN_ROWS;
+    for (const PgFixedLen &f : rows)
+        if (!fixed_row_matches(f, len_tab[f.len])) return false;
+    return true;
+}
+// (the parameters the default-parameter kernels are built for, pg_launch_search: only such a context would run a fixed-length kernel)
+static bool fixed_len_wanted(const pg_params &p)
+{
+    pg_params d;
+    pg_default_params(&d);
+    return p.max_range_index == d.max_range_index && p.additional_mismatch == d.additional_mismatch &&
+           p.min_perfect_match_around_bp == d.min_perfect_match_around_bp && p.min_close == d.min_close && p.spacer == d.spacer;
+}
+// Diagnostics (not in the public header; needs no device): the k-th baked row of the fixed-length kernels and what the host's tables
+// give for that length under pg_default_params -- five words each: lvl, depth, jmask0, ro, jmask1.  Returns the number of rows
+// (k out of range: nothing is written).
+int pg_debug_fixed_len_row(int k, uint32_t *len, uint32_t *baked, uint32_t *host)
+{
+    const PgFixedLen rows[PG_FIXED_LENS] = PG_FIXED_LEN_ROWS;
+    if (k < 0 || k >= PG_FIXED_LENS) return PG_FIXED_LENS;
+    const PgFixedLen &f = rows[k];
+    std::unique_ptr<pg_ctx> ctx(new pg_ctx());
+    pg_default_params(&ctx->prm);
+    make_tables(ctx.get());
+    const PgLenRec r = pg_len_rec((int)f.len, ctx->mm, ctx->thr, ctx->prm.additional_mismatch, ctx->prm.min_close);
+    if (len) *len = f.len;
+    if (baked) { baked[0] = f.lvl; baked[1] = f.depth; baked[2] = f.jmask0; baked[3] = f.ro; baked[4] = f.jmask1; }
+    if (host) { host[0] = r.lvl; host[1] = r.depth; host[2] = r.jmask0; host[3] = r.ro; host[4] = r.jmask1; }
+    return PG_FIXED_LENS;
+}
+
 int pg_create(const pg_params *p, pg_ctx **out)
 {
     if (!p || !out) return PG_E_INVALID;
@@ -1466,6 +1524,11 @@ int pg_create(const pg_params *p, pg_ctx **out)
         }
     std::vector<PgLenRec> len_tab(512);
     for (int len = 0; len < 512; len++) len_tab[len] = pg_len_rec(len, ctx->mm, ctx->thr, ctx->prm.additional_mismatch, ctx->prm.min_close);
+    // the fixed-length kernels hold these fields as constants: this context may run them only if its tables give the baked rows
+    ctx->fixed_ok = fixed_rows_match(len_tab.data());
+    if (!ctx->fixed_ok && fixed_len_wanted(ctx->prm) && getenv("PG_QUIET") == nullptr)
+        fprintf(stderr, "pindel_pg: note: the length tables of these parameters differ from the ones the fixed-length kernels were "
+                        "built for; this context runs the other kernels\n");
     if (dev_upload(ctx, &ctx->d_thr, ctx->thr, 512) || dev_upload(ctx, &ctx->d_mm, ctx->mm, 512) ||
         dev_upload(ctx, &ctx->d_len_tab, len_tab.data(), 512)) {
         pg_destroy(ctx);
@@ -1813,6 +1876,8 @@ void pg_device_batch_free(pg_ctx *ctx, pg_device_batch *b)
 
 // Diagnostics (not in the public header): did the last launch that was asked to pack build its records inside the search kernel ?
 int pg_debug_last_pack_in_place(const pg_ctx *ctx) { return ctx && ctx->last_in_place ? 1 : 0; }
+// ... and the read length of the fixed-length kernel the last search launch ran (0: it ran any other kernel, or none yet)
+uint32_t pg_debug_last_fixed_len(const pg_ctx *ctx) { return ctx ? ctx->last_fixed_len.load(std::memory_order_relaxed) : 0u; }
 
 // Diagnostics (not in the public header): the launch log -- the kernels the search path launched since the last
 // pg_debug_clear_launch_log, seven int32 per launch (PgLaunchRec: kernel, NB / PB, NS, id bits, mode, DEF, packed in place).

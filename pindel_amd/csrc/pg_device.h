@@ -215,6 +215,30 @@ static inline struct PgLenRec pg_len_rec(int len, const uint32_t *mm, const uint
     r.pad[0] = r.pad[1] = r.pad[2] = 0u;
     return r;
 }
+// FIXED-LENGTH KERNELS (pg_search_fixed_kernel<NB, NS, LEN>): a sequencer produces reads of one length, and for a batch whose reads
+// all have one of the lengths below -- under Pindel's default parameter set -- the length and every record field that follows
+// from it (PgLenRec) are compile-time constants of the search kernel instead of scalar registers that live through the whole read.
+// One literal row per built length: what pg_len_rec() gives for pg_default_params (tests/test_fixed_length_table.py compares
+// them with the host's tables; pg_create compares the context's own and keeps to the other kernels on a mismatch).
+struct PgFixedLen { uint32_t len, lvl, depth, jmask0, ro, jmask1; };
+#define PG_FIXED_LENS 4
+#define PG_FIXED_LEN_ROWS { \
+    { 100u, 0x06040002u, 0x03031210u, 0x0000fffeu, 0x80030365u, 0x0003fffeu },   /* M 4, T 6, threshold 2; J 16 / 18; 5 / 6 groups */ \
+    { 101u, 0x06040003u, 0x03031210u, 0x0000fffeu, 0x80030365u, 0x0003fffeu },   /* as 100, threshold 3 */ \
+    { 150u, 0x07050003u, 0x03031412u, 0x0003fffeu, 0x80030366u, 0x000ffffeu },   /* M 5, T 7, threshold 3; J 18 / 20; 6 / 6 groups */ \
+    { 151u, 0x07050004u, 0x03031412u, 0x0003fffeu, 0x80030366u, 0x000ffffeu },   /* as 150, threshold 4 */ \
+}
+// the row of `len` (len = 0 when it is none of the built lengths)
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+constexpr PgFixedLen pg_fixed_len_row(uint32_t len)
+{
+    constexpr PgFixedLen rows[PG_FIXED_LENS] = PG_FIXED_LEN_ROWS;
+    for (int k = 0; k < PG_FIXED_LENS; k++)
+        if (rows[k].len == len) return rows[k];
+    return PgFixedLen{ 0u, 0u, 0u, 0u, 0u, 0u };
+}
 struct PgSoaOut {                  // the close-end summary pg_pack_close_summary reads
     uint8_t *rc_flag;
     uint32_t *close_last;
@@ -271,6 +295,7 @@ struct PgEnvSwitches {
     bool no_pack_in_place;      // PG_NO_PACK_IN_PLACE: pg_device_batch_pack_search = pack launch + search launch
     uint32_t pack_claim;        // PG_PACK_CLAIM: reads per claim of a launch that packs in place (0 = the default)
     uint32_t pack_in_place_min; // PG_PACK_IN_PLACE_MIN: fewest reads of such a launch (tests: the path on small batches)
+    bool no_fixed_len;          // PG_NO_FIXED_LEN: never the fixed-length kernels (same-process A/B runs)
 };
 
 #ifdef __cplusplus
@@ -297,10 +322,12 @@ struct PgLaunchRec {
 #define PG_LAUNCH_RECS_MAX 2       // records one pg_launch_search writes at most (PG_SPLIT_LAUNCH: close kernel, far kernel)
 // Launches the search kernel for the reads of the batch on `stream`.  small_ids selects the
 // 32-bit candidate ids (see above for when that is valid).  rec (may be null): room for PG_LAUNCH_RECS_MAX records of the
-// kernels launched, *n_rec their number.
+// kernels launched, *n_rec their number.  uniform_len: the one length every read of the launch has, if the caller vouches for
+// it and for the length tables being the baked ones (0: lengths unknown or mixed) -- the launch may then run a fixed-length kernel;
+// *fixed_len (may be null): the LEN of the one it ran, 0 for any other kernel.
 int pg_launch_search(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch,
                      int mode, uint32_t max_len, uint32_t levels, int small_ids, void *stream,
-                     struct PgLaunchRec *rec, int *n_rec);
+                     struct PgLaunchRec *rec, int *n_rec, uint32_t uniform_len, uint32_t *fixed_len);
 // may that launch build the records of its reads itself (PgDevBatch::soa) ?
 // -q: contains_subseq_any_strand per item (pg_dd.hip); n_tasks = 2 x items (strand = task & 1), out2[task]; workgroups of four
 // waves, each wave with scratch_stride words of d_scratch (the boundary row between its 64-row blocks).

@@ -1937,7 +1937,10 @@ __device__ __forceinline__ u32 pool_alloc(const PgDevBatch &B, int n, int lane, 
 // characters (ja = leading characters outside ACGTN); the second reverse complement before attempt 3 strips what the read ENDED
 // with (jb): attempt 3 and a far end after it see the read without either.  In plane terms: orientation 0 loses its first ja bits,
 // orientation 1 its first jb, the length and everything that follows from it (levels, thresholds, filter depths) shrink.
-template <int NB, int NS, typename Id, int mode, bool DEF, bool EXACT = false>
+// LEN > 0 (pg_search_fixed_kernel): every read of the launch has LEN bases and the length tables are the baked ones
+// (PgFixedLen, pg_device.h; the host vouches for both): the length and what follows from it -- levels, threshold, filter depths,
+// masks, group counts -- are constants of the instantiation, not decoded from the record and kept in scalar registers.
+template <int NB, int NS, typename Id, int mode, bool DEF, bool EXACT = false, int LEN = 0>
 __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevParams &prm, const PgDevBatch &B,
                                             Search &S, u64 *qplanes, const uint32_t rid, const int touch_next, const int lane,
                                             const u32 res_base, const u32 res_fits)
@@ -1986,6 +1989,19 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
     S.jmask[0] = rb[1];
     S.jmask[1] = 0u;                                        // (the wide depth's mask comes with the far end's part of the record)
     S.ro = rb[2];
+    if (LEN > 0) {
+        static_assert(LEN == 0 || (!EXACT && DEF && mode == PG_MODE_BOTH), "fixed length: the fused default-parameter kernels only");
+        constexpr PgFixedLen F = pg_fixed_len_row((uint32_t)LEN);
+        static_assert(LEN == 0 || F.len == (uint32_t)LEN, "no baked row for this length");
+        len = LEN;
+        S.len = LEN;
+        S.thr = (int)(F.lvl & 0xffffu);
+        S.M = (int)((F.lvl >> 16) & 0xffu);
+        S.T = (int)(F.lvl >> 24);
+        S.depth = F.depth;
+        S.jmask[0] = F.jmask0;
+        S.ro = F.ro;
+    }
     S.rid = rid;
     S.rp_lo = (u32)uni((int)(u32)(u64)(uintptr_t)rp);
     S.rp_hi = (u32)uni((int)(u32)((u64)(uintptr_t)rp >> 32));
@@ -2275,7 +2291,7 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
             u32x4 rc;
             asm volatile("s_load_dwordx4 %0, %1, 0x30\n\ts_waitcnt lgkmcnt(0)" : "=&s"(rc) : "s"(record_ptr<7>(KA(B, in), rid)));
             const int chr_size = (int)rc[0];
-            S.jmask[1] = rc[3];
+            S.jmask[1] = LEN > 0 ? pg_fixed_len_row((uint32_t)LEN).jmask1 : rc[3];
             PG_STOP_AT(S, 35);
             int far_bases = 0;
             // a search window's result replaces UP_Far if its MaxLen is >= (NewUPFarIsBetter, farend_searcher.cpp:30-44)
@@ -2558,127 +2574,20 @@ template <int NB, int NS, typename Id, int mode, bool DEF>
 __global__ __launch_bounds__(WAVE, PG_WAVES(NB, Id)) void pg_search_kernel(PgDevRef ref, PgDevParams prm,
                                                          PgDevBatch B, uint32_t max_len, uint32_t levels)
 {
-    __shared__ Lds<NB, Id> lds;
-    const int lane = threadIdx.x;
-    if (PG_WIN_DYN_BYTES(NB) != 0u) {
-        // the window's dynamic tail must begin where the static LDS object ends (see Lds::win)
-        extern __shared__ uint4 pg_dyn_lds[];
-        if ((const char *)pg_dyn_lds != (const char *)&lds + sizeof(lds)) __builtin_trap();
-    }
-    if (PG_MM_IN_WIN(NB)) {
-        for (int w = lane; w < 16 * NB + 16; w += WAVE) {
-            u32 v = 0u;
-#pragma unroll
-            for (int k = 0; k < 4; k++) v |= (u32)max_mismatch_at(prm.mm_bp, 4 * w + k) << (8 * k);
-            lds.win[w].w = v;
-        }
-    } else
-        for (int L = lane; L < 64 * NB + 64; L += WAVE) lds.mm_tab[L] = (uint8_t)max_mismatch_at(prm.mm_bp, L);
-    if (lane < PG_CHR_TAB_N(NB) && lane < ref.n_chr) {
-        const u64 wo = ref.chr_word_off[lane];
-        lds.chr_tab[lane] = make_uint2((u32)wo, (wo >> 32) == 0ull ? ref.chr_size[lane] : 0u);
-    }
-    PG_SYNC();
-    Search S;
-    S.queue = lds.queue;
-    S.win = lds.win;
-    S.bufA = lds.bufA;
-    S.bufB = lds.bufB;
-    S.hdrB = lds.hdrB;
-    S.ringB = lds.ringB;
-    S.accB = lds.accB;
-    S.mm_tab = lds.mm_tab;
-    S.chr_tab = lds.chr_tab;
-    u64 *qplanes = lds.qp;                        // [0]: forward, [1]: reversed consumption order
-    if (lane < 8 * NB) qplanes[lane] = 0ull;      // (blocks beyond the batch's plane layout are never written)
-#ifdef PG_TIMING
-    S.t_acc = lds.t_acc;
-    S.t_last = &lds.t_last;
-    if (lane == 0) {
-        for (int k = 0; k < 12; k++) S.t_acc[k] = 0u;
-        *S.t_last = __builtin_readcyclecounter();
-    }
-    S.t_base = 1;
-#endif
-
-    // Reads claimed per atomic (PgDevBatch::claim, worked out by pg_launch_search): a workgroup's share of the launch in the fewest
-    // equal claims of at most PG_CLAIM reads.  The host
-    // launches one workgroup per PG_CLAIM reads up to the chip's resident slots, so up to 57 k reads every wave takes exactly one claim
-    // of eight; between that and a few hundred thousand reads the share is 8..64 reads and claims of exactly eight would leave some
-    // waves a whole claim more than others (100 000 reads: 14 per wave = two claims of seven).  Measured, seven waves per SIMD:
-    // 50 000 reads 0.262 ms with claims of two, 0.23 with eight; 100 000: 0.403 -> 0.36; 5000 reads on 633 workgroups 0.106 either way,
-    // and 0.125 on 5008 workgroups of one read each -- a small launch pays for the NUMBER of workgroups.  A wave that looks at the
-    // other parts' counters before claiming from them (the walk over the eight parts at the end of a launch is one atomic per wave
-    // and address) gained nothing.
-    // (Claims of ONE read for the last round and a half of a launch, to shorten its tail, were measured and rejected: a claim
-    // is a dependent chain atomic -> records -> first window, 2 us that eight reads share -- 262 144 reads 0.94 -> 0.98 ms.)
-    // Nothing but `part` and `tried` lives from one claim to the next: the launch's size comes from the kernarg segment again.
-    // (Quarter claims for the last rounds of a launch that packs in place -- the waves finish spread over one claim's duration -- were
-    // measured and rejected, round 6: a claim is a dependent chain atomic -> pack (three HBM round trips) -> records, and the short
-    // claims cost more than the shorter tail gives back: 2 M reads at -x 5 22.16 -> 22.24 ms, 2 M at -x 2 4.55 -> 4.58 / 4.70 ms
-    // for two / four rounds.  Claims of eight, as without the pack: sixteen and more lose at -x 5, where a read takes 79 us.)
-    uint32_t part = blockIdx.x % PG_N_XCD, tried = 0;
-    while (tried < PG_N_XCD) {
-        const uint32_t n = KA(B, n_reads);
-#ifdef PG_FORCE_CLAIM
-        const uint32_t claim = PG_FORCE_CLAIM;
-#else
-        const uint32_t claim = KA(B, claim);              // (pg_launch_search: the share of a workgroup in the fewest equal claims <= PG_CLAIM)
-#endif
-        const uint32_t per = n / PG_N_XCD;
-        const uint32_t lo = part * per, hi = part + 1 == PG_N_XCD ? n : lo + per;
-        // (the single-lane atomics by hand: the compiler wraps an atomicAdd in its wave-reduction form -- exec juggling, mbcnt,
-        // bcnt, a multiply -- some 25 instructions each)
-        uint32_t got = 0;
-        uint32_t *ctr = KA(B, work_ctr) + part * 16u;
-        if (lane == 0) asm volatile("global_atomic_add %0, %1, %2, %3 sc0\n\ts_waitcnt vmcnt(0)" : "=&v"(got) : "v"(0u), "v"(claim), "s"(ctr) : "memory");
-        got = (u32)uni((int)got);
-        if (got >= hi - lo) {                             // this part is exhausted
-            part = part + 1 == PG_N_XCD ? 0 : part + 1;
-            tried++;
-            continue;
-        }
-        const uint32_t first = lo + got, end = hi - first < claim ? hi : first + claim;
-        PG_T(S, 11);
-        uint32_t no_touch = ~0u;                          // the read that must not touch its successor's record (none)
-        {
-            // PACK IN PLACE (PgDevBatch::soa set; any mode -- the two seams' launches pack their reads too): the wave builds the records and bit planes of its claim from the SoA arrays
-            // before it searches them -- the pack kernel's body on the claim's reads.  A streaming transpose (HBM-bound on its own,
-            // 3 TB/s) inside a kernel that is bound by instruction issue and leaves 90 % of the HBM bandwidth idle: ~30 instructions
-            // per read instead of a launch of its own in front of this one.  What the wave wrote it reads back itself, through the
-            // caches of its own CU and XCD (scalar loads of the records, vector loads of the planes): the stores' completion is all
-            // there is to wait for.  (The host sets soa only when the batch's plane layout is this kernel's: plane_blocks == NB.)
-            const PgSoaIn *soa = KA(B, soa);
-            if (soa) {
-                const PgSoaIn a = *soa;
-                pack_block<NB>(a, const_cast<PgInRec *>(KA(B, in)), KA(B, first_read) + first, 0u, end - first, (u32)lane_now());
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                // (a read touches the next read's record while it waits for its first window: the claim's last read would bring
-                // the line of a record nobody has written yet into the scalar cache, where its owner might then find it)
-                no_touch = end - 1u;
-            }
-        }
-        // run-pool slots of the claim's reads: one atomic per claim
-        u32 res = 0u;
-        {
-            const u32 shard = blockIdx.x & (PG_POOL_SHARDS - 1u);
-            uint32_t *cur = KA(B, pool_used) + shard * 16u;
-            if (lane == 0) asm volatile("global_atomic_add %0, %1, %2, %3 sc0\n\ts_waitcnt vmcnt(0)" : "=&v"(res) : "v"(0u), "v"(claim * PG_RESERVE), "s"(cur) : "memory");
-            res = (u32)uni((int)res);
-            const u32 res_fits = (u64)res + (u64)(claim * PG_RESERVE) <= (u64)KA(B, pool_shard_cap) ? 1u : 0u;
-            res += shard * KA(B, pool_shard_cap);
-            for (uint32_t i = first; i < end; i++)
-                search_read<NB, NS, Id, mode, DEF>(ref, prm, B, S, qplanes, KA(B, first_read) + i, i != no_touch ? 1 : 0, lane_now(),
-                                          res + (i - first) * PG_RESERVE, res_fits);
-            PG_T(S, 10);
-        }
-    }
-#ifdef PG_TIMING
-    if (lane == 0) {
-        u64 *dg = (u64 *)(KA(B, work_ctr) + PG_WORK_CTRS * 16u);
-        for (int k = 0; k < 12; k++) atomicAdd((unsigned long long *)(dg + k), (unsigned long long)S.t_acc[k]);
-    }
-#endif
+    constexpr int LEN = 0;                        // (the read's length comes from its record)
+#include "pg_search_kernel_body.h"
+}
+// FIXED LENGTH: the fused kernel of the default parameter set with 32-bit ids for a launch whose reads all have LEN bases (same
+// parameter list: KA()).  pg_launch_search picks it; PgFixedLen (pg_device.h) lists the lengths.
+template <int NB, int NS, int LEN>
+__global__ __launch_bounds__(WAVE, PG_WAVES(NB, u32)) void pg_search_fixed_kernel(PgDevRef ref, PgDevParams prm,
+                                                         PgDevBatch B, uint32_t max_len, uint32_t levels)
+{
+    static_assert(LEN > 64 * (NB - 1) && LEN <= 64 * NB, "the block class of the length");
+    typedef u32 Id;
+    constexpr int mode = PG_MODE_BOTH;
+    constexpr bool DEF = true;
+#include "pg_search_kernel_body.h"
 }
 
 // EXACT kernel (search_read<..., EXACT = true>): the reads the pack kernel listed because they hold a character outside ACGTN
@@ -2824,9 +2733,31 @@ static void launch_modes(const PgDevRef *ref, const PgDevParams *prm, const PgDe
 #endif
 }
 
+// The fixed-length kernel of this class for a launch whose reads all have `len` bases, if there is one: the class and the counter
+// slices must be the ones the length was built for, the launch's levels the baked row's.  false: nothing was launched.
+template <int NB, int NS>
+static bool launch_fixed(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch, uint32_t max_len, uint32_t levels,
+                         hipStream_t st, unsigned lds_pad, dim3 grid, dim3 block, uint32_t len)
+{
+    if (len == 0u || len != max_len || levels != pg_fixed_len_row(len).lvl >> 24) return false;
+#define PG_FIXED(nb, ns, L)                                                                                                           \
+    if constexpr (NB == nb && NS == ns)                                                                                               \
+        if (len == L) {                                                                                                               \
+            hipLaunchKernelGGL((pg_search_fixed_kernel<nb, ns, L>), grid, block, lds_pad, st, *ref, *prm, *batch, max_len, levels);   \
+            return true;                                                                                                              \
+        }
+    PG_FIXED(2, 3, 100)
+    PG_FIXED(2, 3, 101)
+    PG_FIXED(3, 3, 150)
+    PG_FIXED(3, 3, 151)
+#undef PG_FIXED
+    return false;
+}
+
 template <int NB, int NS, typename Id>
 static void launch_ns(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch, int mode,
-                   uint32_t max_len, uint32_t levels, hipStream_t st, unsigned lds_pad, PgLaunchRec *rec, int *n_rec)
+                   uint32_t max_len, uint32_t levels, hipStream_t st, unsigned lds_pad, PgLaunchRec *rec, int *n_rec,
+                   uint32_t uniform_len, uint32_t *fixed_len)
 {
     // a few resident workgroups per CU (the launch is persistent); more than fit simply queue up and find
     // the remaining chunks
@@ -2872,6 +2803,15 @@ static void launch_ns(const PgDevRef *ref, const PgDevParams *prm, const PgDevBa
                      prm->spacer == PG_DEF_SPACER;
     if constexpr (HAS_DEF) {
         if (def) {
+            // ... and, fused, a kernel of their own for a launch whose reads all have one of the built lengths
+            if (mode == PG_MODE_BOTH && !pg_env_switches()->split_launch && !pg_env_switches()->no_fixed_len &&
+                launch_fixed<NB, NS>(ref, prm, batch, max_len, levels, st, lds_pad, grid, block, uniform_len)) {
+                // (the launch log names the family the kernel belongs to -- the fused default-parameter kernel of this class; the
+                // length goes to *fixed_len)
+                note_search<NB, NS, Id, true>(rec, n_rec, PG_MODE_BOTH, batch);
+                *fixed_len = uniform_len;
+                return;
+            }
             launch_modes<NB, NS, Id, true>(ref, prm, batch, mode, max_len, levels, st, lds_pad, grid, block, rec, n_rec);
             return;
         }
@@ -2882,14 +2822,15 @@ static void launch_ns(const PgDevRef *ref, const PgDevParams *prm, const PgDevBa
 // the seed filter's counter width follows the batch's largest number of mismatch levels (validate_and_measure)
 template <int NB, typename Id>
 static void launch(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch, int mode,
-                   uint32_t max_len, uint32_t levels, hipStream_t st, unsigned lds_pad, PgLaunchRec *rec, int *n_rec)
+                   uint32_t max_len, uint32_t levels, hipStream_t st, unsigned lds_pad, PgLaunchRec *rec, int *n_rec,
+                   uint32_t uniform_len, uint32_t *fixed_len)
 {
-    if (levels <= 8) launch_ns<NB, 3, Id>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
+    if (levels <= 8) launch_ns<NB, 3, Id>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec, uniform_len, fixed_len);
 #ifdef PG_ONLY_BENCH
     else abort();     // experiment builds: default parameters only
 #else
-    else if (levels <= 16) launch_ns<NB, 4, Id>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
-    else launch_ns<NB, 5, Id>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
+    else if (levels <= 16) launch_ns<NB, 4, Id>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec, uniform_len, fixed_len);
+    else launch_ns<NB, 5, Id>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec, uniform_len, fixed_len);
 #endif
 }
 
@@ -3256,11 +3197,14 @@ extern "C" int pg_pack_in_place_ok(int mode, uint32_t max_len, int small_ids, ui
 
 extern "C" int pg_launch_search(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch,
                                 int mode, uint32_t max_len, uint32_t levels, int small_ids, void *stream,
-                                PgLaunchRec *rec, int *n_rec)
+                                PgLaunchRec *rec, int *n_rec, uint32_t uniform_len, uint32_t *fixed_len)
 {
     int n_local = 0;
+    uint32_t fixed_local = 0;
     if (!n_rec) n_rec = &n_local;
+    if (!fixed_len) fixed_len = &fixed_local;
     *n_rec = 0;
+    *fixed_len = 0;
     if (batch->n_reads == 0) return 0;
     // a launch that packs in place must be one pg_pack_in_place_ok admits (the kernels run the pack of THEIR class on the batch's planes)
     if (batch->soa && !pg_pack_in_place_ok(mode, max_len, small_ids, batch->n_reads, batch->plane_blocks)) return (int)hipErrorInvalidValue;
@@ -3273,20 +3217,20 @@ extern "C" int pg_launch_search(const PgDevRef *ref, const PgDevParams *prm, con
     // experiment builds: only the instantiations of the bench workloads (100 / 150-base reads, 32-bit ids), compiled in a
     // fraction of the time
     if (!small_ids || max_len > 192) abort();
-    if (nb == 2 && max_len > 64) launch<2, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
-    else launch<3, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
+    if (nb == 2 && max_len > 64) launch<2, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec, uniform_len, fixed_len);
+    else launch<3, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec, uniform_len, fixed_len);
     return (int)hipGetLastError();
 #else
     if (small_ids) {
-        if (max_len <= 64) launch<1, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
-        else if (nb == 2) launch<2, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
-        else if (max_len <= 192) launch<3, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
-        else if (nb == 4) launch<4, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
-        else launch<8, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
+        if (max_len <= 64) launch<1, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec, uniform_len, fixed_len);
+        else if (nb == 2) launch<2, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec, uniform_len, fixed_len);
+        else if (max_len <= 192) launch<3, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec, uniform_len, fixed_len);
+        else if (nb == 4) launch<4, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec, uniform_len, fixed_len);
+        else launch<8, u32>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec, uniform_len, fixed_len);
     } else {
-        if (nb == 2) launch<2, u64>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
-        else if (nb == 4) launch<4, u64>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
-        else launch<8, u64>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec);
+        if (nb == 2) launch<2, u64>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec, uniform_len, fixed_len);
+        else if (nb == 4) launch<4, u64>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec, uniform_len, fixed_len);
+        else launch<8, u64>(ref, prm, batch, mode, max_len, levels, st, lds_pad, rec, n_rec, uniform_len, fixed_len);
     }
     return (int)hipGetLastError();
 #endif

@@ -5,6 +5,7 @@ tag=${1:-fuzz}
 root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/$tag; mkdir -p "$out"
 cd "$root" || exit 1
+export PG_QUIET=1     # (no notes on stderr: a context whose length tables are not the fixed-length kernels' says so, once per context)
 {
     echo "library: $(sha256sum pindel_amd/libpindel_pg.so | cut -c1-16)  kernels source: $(sha256sum pindel_amd/csrc/pg_kernels.hip | cut -c1-16)  $(date -u +%FT%TZ)"
     echo "== random parameters, lengths, references, window clusters (seeds < 200000: -x <= 4)"

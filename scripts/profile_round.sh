@@ -24,7 +24,7 @@ f=$(find /tmp/rp_10m -name '*kernel_stats.csv' | head -1)
 python - "$out/bench_traced_10m.json" "$out/kernel_stats_10m.csv" <<'PY' | tee "$out/reconciliation.txt"
 import csv, json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][0])
-rows = [r for r in csv.DictReader(open(sys.argv[2])) if "pg_search_kernel" in r["Name"]]
+rows = [r for r in csv.DictReader(open(sys.argv[2])) if "pg_search_kernel" in r["Name"] or "pg_search_fixed_kernel" in r["Name"]]
 avg = float(rows[0]["AverageNs"]) / 1e6 if rows else float("nan")
 calls = rows[0]["Calls"] if rows else "?"
 prow = [r for r in csv.DictReader(open(sys.argv[2])) if "pg_pack_kernel" in r["Name"]]

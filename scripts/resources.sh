@@ -21,6 +21,9 @@ for blk in t.split("\n  - ")[1:]:
     if d:
         name = (f"pg_search_kernel<NB={d.group(1)}, NS={d.group(2)}, {'u32' if d.group(3) == 'j' else 'u64'}, "
                 f"{['', 'CLOSE', 'FAR', 'BOTH'][int(d.group(4))]}, {'defaults' if d.group(5) == '1' else 'generic'}>")
+    elif re.match(r"_Z22pg_search_fixed_kernelILi(\d+)ELi(\d+)ELi(\d+)EE", name):
+        f = re.match(r"_Z22pg_search_fixed_kernelILi(\d+)ELi(\d+)ELi(\d+)EE", name)
+        name = f"pg_search_fixed_kernel<NB={f.group(1)}, NS={f.group(2)}, LEN={f.group(3)}>"
     else:
         k = re.match(r"_Z(\d+)", name)
         if k:

@@ -14,14 +14,14 @@ def counter(directory, kernel, name):
     vals = []
     for path in glob.glob(directory + "/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(path)):
-            if kernel in r["Kernel_Name"] and r["Counter_Name"] == name:
+            if any(k in r["Kernel_Name"] for k in kernel.split("|")) and r["Counter_Name"] == name:
                 vals.append(float(r["Counter_Value"]))
     return (sum(vals) / len(vals), len(vals)) if vals else (None, 0)
 
 
 fetch_dir, write_dir, calib_dir, reads = sys.argv[1], sys.argv[2], sys.argv[3], float(sys.argv[4])
-fetch_kb, nf = counter(fetch_dir, "pg_search_kernel", "FETCH_SIZE")
-write_kb, nw = counter(write_dir, "pg_search_kernel", "WRITE_SIZE")
+fetch_kb, nf = counter(fetch_dir, "pg_search_kernel|pg_search_fixed_kernel", "FETCH_SIZE")
+write_kb, nw = counter(write_dir, "pg_search_kernel|pg_search_fixed_kernel", "WRITE_SIZE")
 calib_kb, _ = counter(calib_dir, "pg_calib_stream", "FETCH_SIZE")
 true_bytes = 2147483648
 factor = true_bytes / (calib_kb * 1024.0) if calib_kb else 2.0
