@@ -898,7 +898,7 @@ PgDevBatch dev_batch(const pg_device_batch *b)
     d.pool_shard_cap = b->pool_shard_cap;
     d.pool_used = b->pool_used;
     d.work_ctr = b->pool_used + PG_POOL_SHARDS * 16;
-    d.claim = PG_CLAIM_DEFAULT;        // (pg_launch_search sets it from the launch's grid)
+    d.claim = PG_CLAIM;       // (pg_launch_search sets it from the launch's grid)
     d.exact_list = b->exact_list;
     d.exact_count = b->exact_count;
     d.thr_tab = nullptr;               // (launch_range: the ctx's table)

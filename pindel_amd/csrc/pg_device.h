@@ -89,7 +89,7 @@ struct PgInRec {
 #define PG_PACK_CLAIM 8u            // ... of a launch that packs in place (PgDevBatch::soa) ...
 #define PG_PACK_CLAIM_LONG 16u      // ... and when a wave takes many of them (pg_launch_search)
 #define PG_PACK_IN_PLACE_MIN 1u            // fewest reads of such a launch (measured 20 000 reads .. 10 M: never slower than a pack launch in front)
-#define PG_CLAIM_DEFAULT 8u  // reads a workgroup of the persistent launch claims per atomic, at most
+#define PG_CLAIM 8u          // reads a workgroup of the persistent launch claims per atomic, at most
 #define PG_IN_PAD 8u        // records allocated behind the last one (the kernel prefetches the next read's record)
 struct PgOutRec {
     uint32_t close_off, close_cnt, far_off, far_cnt;   // runs in the pool
@@ -160,12 +160,8 @@ struct PgSoaIn {
 };
 // consumed bases the seed filter inspects for a read of `len` bases with T mismatch levels (wide: the chunks of wide far-end
 // windows, where a survivor costs a whole candidate pass for a handful of candidates: two more)
-#ifndef PG_SEED_J
 #define PG_SEED_J(T) (2 * (T) + 4)
-#endif
-#ifndef PG_SEED_J_WIDE
 #define PG_SEED_J_WIDE 2
-#endif
 #ifdef __HIPCC__
 __host__ __device__
 #endif

@@ -69,11 +69,7 @@ struct PgKArgs { PgDevRef ref; PgDevParams prm; PgDevBatch B; uint32_t max_len, 
 // counter too -- every wait for an LDS read then also waits for the HBM loads in flight, and "request early, use late" is lost.
 template <typename T> struct KaGlobal { static __device__ __forceinline__ T of(unsigned long long v) { return (T)v; } };
 template <typename E> struct KaGlobal<E *> {
-#ifdef PG_FLAT_KARGS       // (ablation)
-    static __device__ __forceinline__ E *of(unsigned long long v) { return (E *)v; }
-#else
     static __device__ __forceinline__ E *of(unsigned long long v) { return (E *)(__attribute__((address_space(1))) E *)v; }
-#endif
 };
 template <typename T>
 __device__ __forceinline__ T karg_load(int off)
@@ -115,9 +111,7 @@ __device__ __forceinline__ void karg_load3(T &a, T &b, T &c)
 #define PG_DEF_SPACER 100000u
 
 #define WAVE 64
-#ifndef PG_N_XCD
 #define PG_N_XCD 8u        // MI355X: 8 accelerator complex dies, 32 CUs and one L2 each
-#endif
 // Register budget the kernel is compiled for, in waves per SIMD (= resident single-wave workgroups per CU / 4), decided by the
 // size of the kernel's LDS object -- LDS comes in granules of 1280 bytes:
 //   seven (72 VGPRs)  up to 5120 B = four granules, 28 workgroups per CU: reads of up to 128 bases with 32-bit candidate ids
@@ -126,14 +120,7 @@ __device__ __forceinline__ void karg_load3(T &a, T &b, T &c)
 // History of the measurement (100 bp, ms per 2 M reads): four waves 6.69, five 6.03, six 5.60 once the kernel's arguments had
 // stopped occupying scalar registers (round 4), seven then 6.02 (50 VGPR spills); with the default-parameter kernels and without
 // machine LICM seven fit 72 VGPRs with 3 spills: 4.97 -> 4.91 (generic kernels 5.35 -> 5.24).
-#ifdef PG_WAVES_PER_EU
-#define PG_WAVES(NB, Id) PG_WAVES_PER_EU
-#else
 #define PG_WAVES(NB, Id) (sizeof(Lds<NB, Id>) <= 5120 ? 7 : (sizeof(Lds<NB, Id>) <= 6400 ? 6 : (sizeof(Lds<NB, Id>) <= 7680 ? 5 : 4)))
-#endif
-#ifndef PG_CLAIM
-#define PG_CLAIM 8u         // reads claimed per atomic
-#endif
 #define PG_BIG 0xffffu      // "no candidate" level
 #define PG_CHR_TAB 24       // chromosomes whose word offset / size are kept in LDS (window clusters on other chromosomes)
 // Candidates per pass.  Reads over 128 bases (NB >= 3) take 32: the tier B entries (PASS x NB mismatch words), the queue and the
@@ -186,16 +173,12 @@ __device__ __forceinline__ u64 read_lane(u64 v, int l)
 // this has to do is keep the compiler from moving LDS reads above LDS writes of other lanes.  (__syncthreads() costs
 // nothing as a barrier here -- the compiler drops s_barrier for a 64-thread workgroup -- but its workgroup-scope fences
 // also wait for every outstanding global load and STORE.)
-#ifdef PG_SYNCTHREADS
-#define PG_SYNC() __syncthreads()
-#else
 #define PG_SYNC()                                              \
     do {                                                       \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
         __builtin_amdgcn_wave_barrier();                       \
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
     } while (0)
-#endif
 // tells the compiler a value is wave-uniform (keeps it in SGPRs)
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 // An opaque copy of a per-lane value: expressions built on it cannot be hoisted out of the enclosing
@@ -818,7 +801,6 @@ __device__ __forceinline__ void stage_window(const PgDevRef &ref, Search &S, lon
         // two window words per lane and pass, all six loads in flight before the first is used: a 2048-base window with its
         // overhangs is 74-78 words, and 64 + 10 in two dependent passes was two HBM round trips.  (Hand-written: the compiler
         // sinks the second set of loads behind the first set's wait however the source is arranged.)
-#ifndef PG_NO_WIDE3
         if (WIDE && nw > 2 * WAVE) {
             // TWO chunks of a wide far-end window with their overhangs are 134-142 words: 128 + 10 in two dependent passes was two HBM
             // round trips per fill, twelve fills per read at -x 5.  Three words per lane, all nine loads in flight together.
@@ -843,7 +825,6 @@ __device__ __forceinline__ void stage_window(const PgDevRef &ref, Search &S, lon
                     make_uint3(__builtin_amdgcn_alignbit((u32)(g >> 32), (u32)g, sh), __builtin_amdgcn_alignbit((u32)(h >> 32), (u32)h, sh),
                                __builtin_amdgcn_alignbit((u32)(m >> 32), (u32)m, sh));
         } else
-#endif
         for (int i = lane; i < nw; i += 2 * WAVE) {
             const int j = i + WAVE;
             const bool two = j < nw;
@@ -1216,8 +1197,6 @@ __device__ __forceinline__ void seed_filter_run(const Search &S, const Query<NB>
 // highest scalar register on purpose: with VCC, FLAT_SCRATCH and XNACK_MASK that is 95 of the 96 scalar registers a wave may own at
 // seven waves per SIMD.  Reads with more than 16 mismatch levels (NS = 5 launches), fewer than four groups, a base outside ACGTN among
 // the first 25 of either orientation, or g_MinClose < 8 keep the filter above.
-#ifndef PG_NO_RO_FILTER
-#define PG_RO 1
 // planes of the window word in (x, y, z) = (code bit 0, code bit 1, N): A, C, G, T, not-N into the five registers given
 #define RO_ONEHOT(dA, dC, dG, dT, dN, x, y, z)                                                                       \
     "v_bitop3_b32 " dA ", " x ", " y ", " z " bitop3:0x01\n\tv_bitop3_b32 " dC ", " x ", " y ", " z " bitop3:0x10\n\t" \
@@ -1251,10 +1230,8 @@ __device__ __forceinline__ void seed_filter_run(const Search &S, const Query<NB>
 // index changes are done and is waited for behind that group's add), the seed's index is kept in s88: five scalar registers, the
 // highest s88 -- with VCC, FLAT_SCRATCH and XNACK_MASK that is 95 of the 96 a wave may have at seven waves per SIMD (the first
 // version held all eight dwords in s84 .. s91 + s92: 99, and ran at six waves per SIMD).
-#ifndef RO_PROG_LOAD
 #define RO_PROG_LOAD "s_load_dwordx4 s[84:87], %[rp], %[off]\n\t"
 #define RO_PROG_LOAD2 "s_load_dwordx4 s[84:87], %[rp], %[off] offset:0x10\n\t"
-#endif
 // kind F: base j against the pair (own word, next word) shifted by j; kind B: (previous word, own word) shifted by 32 - j
 #define RO_SH_F(P, j1, j2, j3, n1, n2, n3) RO_SH(P, j1, j2, j3)
 #define RO_SH_B(P, j1, j2, j3, n1, n2, n3) RO_SH(P, n1, n2, n3)
@@ -1311,11 +1288,7 @@ __device__ __forceinline__ u32 seed_filter_ro1(const Search &S, bool o1, bool wi
     const u32 off = o1 ? 0x60u : 0x40u;                                   // PgInRec::prog[o1]
     // kind F reads the words (own, next), kind B (previous, own)
     const u32 wa = (u32)(uintptr_t)(const __attribute__((address_space(3))) uint4 *)(S.win + (2 * NB + word - (KIND == 1 ? 1 : 0)));
-#ifdef PG_RO_RP_RECOMPUTE     // (ablation: the record's address worked out again at every run: a kernarg fetch + wait + four scalar instructions)
-    const PgInRec *rp = record_ptr<7>(karg_load<const PgInRec *>((int)offsetof(PgKArgs, B.in)), S.rid);
-#else
     const PgInRec *rp = KaGlobal<const PgInRec *>::of((u64)S.rp_lo | ((u64)S.rp_hi << 32));
-#endif
     u32 m;
 #define RO_HEAD(INIT) RO_PROG_LOAD "ds_read_b128 v[32:35], %[wa]\n\tds_read_b128 v[36:39], %[wa] offset:16\n\t" INIT "s_waitcnt lgkmcnt(0)\n\ts_lshr_b32 s88, s84, 24\n\t"
 #define RO_OPERANDS(MORE) : [m] "=&v"(m) : [rp] "s"(rp), [off] "s"(off), [wa] "v"(wa), [t] "s"(t), [G] "s"(G) : MORE RO_CLOBBERS
@@ -1347,7 +1320,6 @@ __device__ __forceinline__ void seed_filter_ro(const Search &S, bool o1, bool wi
     } else
         mF = seed_filter_ro1<NB, KIND, false, NS>(S, o1, wide, word);
 }
-#endif
 
 template <int NB, int NS, bool DUAL>
 __device__ __forceinline__ void seed_filter(const Search &S, const Query<NB> &Q, bool kindB, bool wide, int lane,
@@ -1355,93 +1327,13 @@ __device__ __forceinline__ void seed_filter(const Search &S, const Query<NB> &Q,
 {
     const int T = S.T;
     PG_DG(const_cast<Search &>(S), 8);
-#ifdef PG_RO
-#ifndef PG_RO_KINDS
-#define PG_RO_KINDS 7      // (ablation: bit 0 = kind F alone, bit 1 = kind B alone, bit 2 = both kinds)
-#endif
-#ifdef PG_RO_CHECK
-    // diagnostics: both filters on every run; every seed the symbol-by-symbol filter keeps must survive the read-order one (plain
-    // depth: same bases in the final count, a shorter prefix in the snapshot).  Counters behind the launch's read counters
-    // (pg_debug_read_phase_cycles): [0] runs, [1 + kind] runs with a seed lost, [4] lanes with a seed lost.
-    // PG_RO_CHECK = 1: the search goes on with the OLD masks, 2: with the new ones.
-    if (NS <= 4 && (S.ro & PG_RO_OK) && !wide) {
-        constexpr int RNS = NS <= 3 ? 3 : 4;
-        u32 nF = 0u, nB = 0u, oF = 0u, oB = 0u;
-        {   // the program as the run will fetch it: every byte 0x30 | symbol <= 4 ?  ([5] counts the runs with another)
-            const PgInRec *rp = record_ptr<7>(karg_load<const PgInRec *>((int)offsetof(PgKArgs, B.in)), S.rid);
-            u32x8 P;
-            asm volatile("s_load_dwordx8 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&s"(P) : "s"(rp), "s"(Q.o1_ ? 0x60u : 0x40u));
-            u32 badp = 0u;
-#pragma unroll
-            for (int k = 0; k < 8; k++) badp |= ((P[k] & 0xf8f8f8f8u) ^ 0x30303030u) | ((P[k] & 0x07070707u) + 0x03030303u) & 0x08080808u;
-            if (badp != 0u) {
-                if (threadIdx.x == 0) atomicAdd((unsigned long long *)(karg_load<uint32_t *>((int)offsetof(PgKArgs, B.work_ctr)) + PG_WORK_CTRS * 16u) + 5, 1ull);
-                const u32 jm = S.jmask[0], g0 = jm & low32(S.bps);
-                int c0 = (int)((S.depth >> 16) & 0xffu);
-                if (c0 > S.cap_state) c0 = S.cap_state;
-                seed_filter_run<NB, NS, DUAL>(S, Q, kindB, lane, jm, g0, c0, mF, mB);
-                return;
-            }
-        }
-#if PG_RO_CHECK == 3
-        {   // (the old filter alone: does the check code itself disturb anything?)
-            const u32 jm = S.jmask[0], g0 = jm & low32(S.bps);
-            int c0 = (int)((S.depth >> 16) & 0xffu);
-            if (c0 > S.cap_state) c0 = S.cap_state;
-            seed_filter_run<NB, NS, DUAL>(S, Q, kindB, lane, jm, g0, c0, mF, mB);
-            return;
-        }
-#endif
-        if (DUAL) seed_filter_ro<NB, 2, RNS>(S, Q.o1_, wide, lane, nF, nB);
-        else if (kindB) seed_filter_ro<NB, 1, RNS>(S, Q.o1_, wide, lane, nF, nB);
-        else seed_filter_ro<NB, 0, RNS>(S, Q.o1_, wide, lane, nF, nB);
-        {
-            const u32 jm = S.jmask[0], g0 = jm & low32(S.bps);
-            int c0 = (int)((S.depth >> 16) & 0xffu);
-            if (c0 > S.cap_state) c0 = S.cap_state;
-            seed_filter_run<NB, NS, DUAL>(S, Q, kindB, lane, jm, g0, c0, oF, oB);
-        }
-        const u64 bad = ballot64(((oF & ~nF) | (DUAL ? (oB & ~nB) : 0u)) != 0u);
-        if (threadIdx.x == 0) {
-            unsigned long long *dg = (unsigned long long *)(karg_load<uint32_t *>((int)offsetof(PgKArgs, B.work_ctr)) + PG_WORK_CTRS * 16u);
-            atomicAdd(dg, 1ull);
-            if (bad) { atomicAdd(dg + 1 + (DUAL ? 2 : (kindB ? 1 : 0)), 1ull); atomicAdd(dg + 4, (unsigned long long)__popcll(bad)); }
-        }
-        mF = PG_RO_CHECK == 1 ? oF : nF;
-        mB = PG_RO_CHECK == 1 ? oB : nB;
-        return;
-    }
-#endif
-    if (NS <= 4 && (S.ro & PG_RO_OK) && ((PG_RO_KINDS >> (DUAL ? 2 : (kindB ? 1 : 0))) & 1)) {
+    if (NS <= 4 && (S.ro & PG_RO_OK)) {
         constexpr int RNS = NS <= 3 ? 3 : 4;          // (the counter of the launch: three slices up to 8 mismatch levels, four up to 16)
         if (DUAL) seed_filter_ro<NB, 2, RNS>(S, Q.o1_, wide, lane, mF, mB);
         else if (kindB) seed_filter_ro<NB, 1, RNS>(S, Q.o1_, wide, lane, mF, mB);       // (kindB is a constant at every call site)
         else seed_filter_ro<NB, 0, RNS>(S, Q.o1_, wide, lane, mF, mB);
         return;
     }
-#endif
-#if defined(PG_PAD_S) || defined(PG_PAD_VF) || defined(PG_PAD_VS)
-    {   // diagnostics: what do 128 more scalar / fast-rate vector / slow-rate vector instructions per filter run cost?
-        u32 pa = (u32)lane;
-#define PG_R16(x) x x x x x x x x x x x x x x x x
-#if defined(PG_PAD_S)
-        asm volatile("s_mov_b32 s100, 1\n\t"
-                     PG_R16("s_add_u32 s100, s100, 3\n\ts_xor_b32 s100, s100, 5\n\ts_add_u32 s100, s100, 7\n\ts_xor_b32 s100, s100, 9\n\t"
-                            "s_add_u32 s100, s100, 3\n\ts_xor_b32 s100, s100, 5\n\ts_add_u32 s100, s100, 7\n\ts_xor_b32 s100, s100, 9\n\t")
-                     "v_xor_b32 %0, s100, %0"
-                     : "+v"(pa) : : "scc", "s100");
-#elif defined(PG_PAD_VF)
-        asm volatile(PG_R16("v_xor_b32 %0, 3, %0\n\tv_add_u32 %0, 5, %0\n\tv_xor_b32 %0, 7, %0\n\tv_add_u32 %0, 9, %0\n\t"
-                            "v_xor_b32 %0, 3, %0\n\tv_add_u32 %0, 5, %0\n\tv_xor_b32 %0, 7, %0\n\tv_add_u32 %0, 9, %0\n\t")
-                     : "+v"(pa));
-#else
-        asm volatile(PG_R16("v_alignbit_b32 %0, %0, %0, 3\n\tv_alignbit_b32 %0, %0, %0, 5\n\tv_alignbit_b32 %0, %0, %0, 7\n\tv_alignbit_b32 %0, %0, %0, 9\n\t"
-                            "v_alignbit_b32 %0, %0, %0, 3\n\tv_alignbit_b32 %0, %0, %0, 5\n\tv_alignbit_b32 %0, %0, %0, 7\n\tv_alignbit_b32 %0, %0, %0, 9\n\t")
-                     : "+v"(pa));
-#endif
-        asm volatile("" : : "v"(pa));
-    }
-#endif
     // bases inspected: two more in the chunks of wide far-end windows, where survivors cost a whole pass of
     // fold_candidates for a handful of candidates (measured: -4 % time at -x 5, +2 % if used everywhere).  Depths, base masks and
     // bounds come with the read's record (pg_pack_kernel): bits [1, J), and of those the ones below the first evaluated length
@@ -1522,20 +1414,12 @@ __device__ __forceinline__ void scan_impl(const PgDevRef &ref, Search &S,
                 else if (h < nh) {                            // every survivor so far is queued: the next half
                     const int word = 64 * h + lane;
                     seed_filter<NB, NS, true>(S, Q, false, true, word, mF, mB);
-#if defined(PG_DUP) && PG_DUP == 3
-                    u32 dF, dB;
-                    seed_filter<NB, NS, true>(S, Q, false, true, opaque(word), dF, dB);
-                    mF &= dF | (u32)opaque(0);
-                    mB &= dB | (u32)opaque(0);
-#endif
                     const int pbase = cs + 32 * word;
                     const u32 rmask = bits32(ns - pbase, ne - pbase) & ~bits32(xs - pbase, xe - pbase);
                     mF &= rmask;
                     mB &= rmask;
                     h++;
-#ifndef PG_NO_WIDE_SKIP
                     if (ballot64((mF | mB) != 0u) == 0ull) continue;      // (most halves of a wide window: nobody passed the filter -- no prefix sum)
-#endif
                     const u32 cnt = (u32)(__popc(mF) + __popc(mB));
                     const u32 incl = wave_scan(cnt);
                     slot = end + (int)(incl - cnt);
@@ -1566,12 +1450,7 @@ __device__ __forceinline__ void scan_impl(const PgDevRef &ref, Search &S,
         const int se = e_max < cs + (int)PG_CHUNK ? e_max : cs + (int)PG_CHUNK;
         PG_STOP_AT(S, 34);
         if (!(wo == S.win_wo && S.wbase == wb && se + 64 * NB <= S.win_hi))
-        {
             stage_window<NB>(ref, S, wo, wb, se + 64 * NB, lane);
-#if defined(PG_DUP) && PG_DUP == 2
-            stage_window<NB>(ref, S, wo, wb, se + 64 * NB, opaque(lane));
-#endif
-        }
         PG_STOP_AT(S, 13);
         const int pbase = cs + 32 * lane;
         const u32 rmask = (low32_lane(ne - pbase) & ~low32_lane(ns - pbase)) & ~(low32_lane(xe - pbase) & ~low32_lane(xs - pbase));
@@ -1589,11 +1468,6 @@ __device__ __forceinline__ void scan_impl(const PgDevRef &ref, Search &S,
                 u32 unused;
                 if (Q.allowF()) seed_filter<NB, NS, false>(S, Q, false, false, lane, mF, unused);
                 if (Q.allowB()) seed_filter<NB, NS, false>(S, Q, true, false, lane, mB, unused);
-#if defined(PG_DUP) && PG_DUP == 3
-                u32 d = 0u;
-                if (Q.allowF()) { seed_filter<NB, NS, false>(S, Q, false, false, opaque(lane), d, unused); mF &= d | (u32)opaque(0); }
-                if (Q.allowB()) { seed_filter<NB, NS, false>(S, Q, true, false, opaque(lane), d, unused); mB &= d | (u32)opaque(0); }
-#endif
             }
             if (use_cache && k == 0) { cacheF = mF; cacheB = mB; }
         }
@@ -1626,13 +1500,6 @@ __device__ __forceinline__ void scan_impl(const PgDevRef &ref, Search &S,
             S.nsurv += n;
             S.nsurv_total += (u32)n;
             PG_SYNC();
-#if defined(PG_DUP) && PG_DUP == 4
-            {   // diagnostics: the same pass into a throw-away copy of the state
-                Acc<NB, Id> A2 = A;
-                fold_candidates<NB, Id, MIXED>(S, Q, A2, wb, origin, region, n, opaque(lane), Rings{ false, 0, 0, 0, 0 }, nullptr);
-                if (A2.m1 == 0x12345u) A.m1 = A2.m2;
-            }
-#endif
             PG_T(S, S.t_base);
             PG_STOP_AT(S, 16);
             fold_candidates<NB, Id, MIXED>(S, Q, A, wb, origin, region, n, lane, Rings{ false, 0, 0, 0, 0 }, nullptr);
@@ -2172,20 +2039,6 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                 if (S.nsurv != nsurv_eval) {
                     nsurv_eval = S.nsurv;
                     Eval<NB, Id> E;
-#if defined(PG_DUP) && PG_DUP == 5
-                    {   // diagnostics: the evaluation twice (on an opaque copy of the state: two calls on the same state are merged)
-                        Acc<NB, Id> A2 = A;
-                        A2.m1 = (u32)opaque((int)A.m1); A2.a1 = (u32)opaque((int)A.a1);
-                        Eval<NB, Id> E2;
-                        evaluate<NB, Id>(S, A2, E2, PG_LANE);
-                        {
-                            u32 chk = (u32)E2.n_runs ^ (u32)E2.max_len ^ (u32)E2.id_last;
-#pragma unroll
-                            for (int r = 0; r < NB; r++) chk ^= (u32)E2.id[r] ^ E2.lo[r] ^ (u32)E2.startm[r] ^ (u32)(E2.brkm[r] >> 32);
-                            if (__builtin_amdgcn_ballot_w64(chk == 0x12345u) == ~0ull) A.m1 = chk;
-                        }
-                    }
-#endif
                     evaluate<NB, Id>(S, A, E, PG_LANE);
                     PG_STOP_AT_V(S, 20, true);
                     close_max = uni(E.max_len);
@@ -2198,9 +2051,6 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                             fits = res_fits;
                         } else
                             close_base = pool_alloc(B, n_close, lane, fits);
-#if defined(PG_DUP) && PG_DUP == 7
-                        if (fits) emit_runs<NB, Id>(S, true, false, chr, opaque(w1s), nullptr, E, kept, KA(B, pool) + close_base, PG_LANE);
-#endif
                         if (fits) emit_runs<NB, Id>(S, true, false, chr, w1s, nullptr, E, kept, KA(B, pool) + close_base, PG_LANE);
                         // AbsLoc of the last point (getLastAbsLocCloseEnd)
                         const u64 idl = (u64)E.id_last;
@@ -2217,22 +2067,13 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
             // definition; on its own grid InsertSize <= PG_CHUNK) -- and the first consumed base is one of ACGT.  Any other read takes
             // attempt 0 through the retries' generic body, whose attempt number is a run-time value.  (Not in the EXACT instantiation:
             // its reads change length between the attempts.)
-#if defined(PG_NO_SETUP_FAST) || defined(PG_DUP)       // (ablation; the duplication diagnostics sit in the generic path)
-            const bool staged0 = false;
-#else
             const bool staged0 = !EXACT && (int)ra[2] < (int)ra[3] && isz <= (int)PG_CHUNK && (flags & PG_RF_FIRST_OK_REV) != 0u;
-#endif
             bool found = false;
             int att0 = 0;
-#ifdef PG_NO_SETUP_FAST
-            found = plus ? attempt(0, true) : attempt(0, false);
-            att0 = 1;
-#else
             if (staged0) {
                 found = plus ? attempt(0, true, true) : attempt(0, false, true);
                 att0 = 1;
             }
-#endif
             if (!found)
                 for (int att = att0; att < 4; att++)
                     if (attempt(att, plus != 0u)) break;
@@ -2297,20 +2138,6 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
             // a search window's result replaces UP_Far if its MaxLen is >= (NewUPFarIsBetter, farend_searcher.cpp:30-44)
             auto far_update = [&](int origin, const pg_window *bdw, int qmask) {
                 Eval<NB, Id> E;
-#if defined(PG_DUP) && PG_DUP == 5
-                {
-                    Acc<NB, Id> A2 = A;
-                    A2.m1 = (u32)opaque((int)A.m1); A2.a1 = (u32)opaque((int)A.a1);
-                    Eval<NB, Id> E2;
-                    evaluate<NB, Id>(S, A2, E2, PG_LANE, qmask);
-                    {
-                        u32 chk = (u32)E2.n_runs ^ (u32)E2.max_len ^ (u32)E2.id_last;
-#pragma unroll
-                        for (int r = 0; r < NB; r++) chk ^= (u32)E2.id[r] ^ E2.lo[r] ^ (u32)E2.startm[r] ^ (u32)(E2.brkm[r] >> 32);
-                        if (__builtin_amdgcn_ballot_w64(chk == 0x12345u) == ~0ull) A.m1 = chk;
-                    }
-                }
-#endif
                 evaluate<NB, Id>(S, A, E, PG_LANE, qmask);
                 const int mx = uni(E.max_len);
                 if (mx >= far_max) {
@@ -2328,9 +2155,6 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                             far_base = pool_alloc(B, n_far, lane, f2);
                             fits &= f2;
                         }
-#if defined(PG_DUP) && PG_DUP == 7
-                        if (fits) emit_runs<NB, Id>(S, false, true, chr, opaque(origin), bdw, E, kept, KA(B, pool) + far_base, PG_LANE);
-#endif
                         if (fits) emit_runs<NB, Id>(S, false, true, chr, origin, bdw, E, kept, KA(B, pool) + far_base, PG_LANE);
                     }
                 }
@@ -2364,11 +2188,7 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                 // did not cover are scanned.  Chunk grid: the innermost 2048 positions are one chunk (one LDS
                 // fill and one seed-filter pass serve the ranges up to 1024).
                 const int center = (int)close_last;
-#ifdef PG_DEF_X_RUNTIME      // (experiment: -x a launch argument of the default-parameter kernels too)
-                const int k_mri = KA(prm, max_range_index);
-#else
                 const int k_mri = PRM(max_range_index, PG_DEF_MAX_RANGE_INDEX);
-#endif
                 const u32 k_spacer = PRM(spacer, PG_DEF_SPACER);
                 const int maxspan = 64 << (2 * k_mri);
                 const int origin = center - maxspan;
@@ -2377,11 +2197,7 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                 // every range -- one test instead of a compare / select pair per bound.  (reach >= k_spacer: the sum did not wrap; every
                 // sum range_of forms for a span <= maxspan is then below chr_size, its compares hold, and it yields center -/+ span.)
                 const u32 reach = (u32)maxspan + k_spacer;
-#if defined(PG_NO_SETUP_FAST) || defined(PG_NO_FAR_NOCLIP)       // (ablations)
-                const bool noclip = false;
-#else
                 const bool noclip = reach >= k_spacer && (u32)center > reach && (u32)chr_size > reach && (u32)center < (u32)chr_size - reach;
-#endif
                 int emax;
                 if (noclip || (u32)center + (u32)maxspan + k_spacer < (u32)chr_size) emax = center + maxspan;
                 else emax = chr_size - (int)k_spacer;
@@ -2399,7 +2215,6 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                 };
                 int r_first = 0;
                 PG_STOP_AT(S, 36);
-#ifndef PG_NO_FUSED_RANGES
                 // FUSED RANGES.  The ranges that lie in the innermost chunk (spans 64, 256, 1024) share ONE candidate pass:
                 // the survivors of the whole chunk are queued at once, the pass keeps the rings apart (Rings), and the
                 // ranges are then evaluated one after the other exactly as the reference walks them -- ring r's long-lived
@@ -2426,14 +2241,6 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                         u32 mF = 0u, mB = 0u;
                         seed_filter<NB, NS, true>(S, Q, false, false, lane, mF, mB);
                         PG_STOP_AT(S, 25);
-#if defined(PG_DUP) && PG_DUP == 8
-                        {
-                            u32 dF, dB;
-                            seed_filter<NB, NS, true>(S, Q, false, false, PG_LANE, dF, dB);
-                            mF &= dF | (u32)opaque(0);
-                            mB &= dB | (u32)opaque(0);
-                        }
-#endif
                         cacheF = mF;
                         cacheB = mB;
                         cache_valid = 1u;
@@ -2470,15 +2277,6 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                                 PG_STOP_AT(S, 27);
                                 int ring_n[3];
                                 PG_T(S, 7);
-#if defined(PG_DUP) && PG_DUP == 9
-                                {
-                                    Acc<NB, Id> A2 = A;
-                                    int rn2[3];
-                                    fold_candidates<NB, Id, true>(S, Q, A2, wb, origin, 0u, total, PG_LANE,
-                                                                  Rings{ true, rs[0], re[0], rs[1], re[1] }, rn2);
-                                    if (A2.m1 == 0x12345u) A.m1 = A2.m2;
-                                }
-#endif
                                 fold_candidates<NB, Id, true>(S, Q, A, wb, origin, 0u, total, lane,
                                                               Rings{ true, rs[0], re[0], rs[1], re[1] }, ring_n);
                                 PG_STOPPED(S);
@@ -2489,13 +2287,6 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                                         u64 longm[NB];
 #pragma unroll
                                         for (int k = 0; k < NB; k++) longm[k] = read_lane(S.ringB[r * NB + k], 0);
-#if defined(PG_DUP) && PG_DUP == 6
-                                        {
-                                            Acc<NB, Id> A2 = A;
-                                            fold_tier_b<NB, Id>(S, Q, A2, longm, PG_LANE);
-                                            if (A2.m1 == 0x12345u) A.m1 = A2.m2;
-                                        }
-#endif
                                         fold_tier_b<NB, Id>(S, Q, A, longm, lane);
                                         far_update(origin, nullptr, r == 0 ? 1 : (r == 1 ? 3 : 15));
                                     }
@@ -2512,7 +2303,6 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                     }
                     PG_STOP_AT(S, 31);
                 }
-#endif
                 int span = 64 << (2 * r_first);
                 for (int r = r_first; r <= k_mri && !done; r++, span *= 4) {
                     int s, e;
@@ -2794,11 +2584,7 @@ static void launch_ns(const PgDevRef *ref, const PgDevParams *prm, const PgDevBa
     if (PG_WIN_DYN_BYTES(NB) != 0u && prm->max_range_index >= 3) lds_pad += PG_WIN_DYN_BYTES(NB);   // two chunks per fill need their LDS
     // Pindel's default parameters have kernels of their own (see PRM): up to 16 mismatch levels, 32-bit candidate ids
     constexpr bool HAS_DEF = NS <= 4 && sizeof(Id) == 4;
-#ifdef PG_DEF_X_RUNTIME
-    const bool def = HAS_DEF && !pg_env_switches()->generic_kernels &&
-#else
     const bool def = HAS_DEF && !pg_env_switches()->generic_kernels && prm->max_range_index == PG_DEF_MAX_RANGE_INDEX &&
-#endif
                      prm->add_mm == PG_DEF_ADD_MM && prm->min_perfect == PG_DEF_MIN_PERFECT && prm->min_close == PG_DEF_MIN_CLOSE &&
                      prm->spacer == PG_DEF_SPACER;
     if constexpr (HAS_DEF) {
@@ -2859,12 +2645,8 @@ static void launch(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch
 //   phase B  RPW reads per step (8 PB lanes each, lane L = bases [8 L, 8 L + 8)): offset and length of the step's reads come
 //            from phase A's lanes by ds_bpermute, the bases as one 12-byte load per lane (the wave walks the concatenated
 //            sequence buffer), PG_PACK_UNROLL steps' loads in flight together.
-#ifndef PG_PACK_UNROLL
 #define PG_PACK_UNROLL 2
-#endif
-#ifndef PG_PACK_GRID
 #define PG_PACK_GRID 65536u
-#endif
 static_assert(sizeof(PgOutRec) == 32, "record_ptr<5>");
 static_assert(sizeof(PgInRec) == 128 && offsetof(PgInRec, prog) == 64 && offsetof(PgInRec, w1s) == 0 && offsetof(PgInRec, isz) == 4 && offsetof(PgInRec, stage_s) == 8 &&
               offsetof(PgInRec, stage_e) == 12 && offsetof(PgInRec, chr_wo_lo) == 16 && offsetof(PgInRec, lenf) == 24 && offsetof(PgInRec, lvl) == 28 &&

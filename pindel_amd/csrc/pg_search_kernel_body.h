@@ -66,11 +66,7 @@
     uint32_t part = blockIdx.x % PG_N_XCD, tried = 0;
     while (tried < PG_N_XCD) {
         const uint32_t n = KA(B, n_reads);
-#ifdef PG_FORCE_CLAIM
-        const uint32_t claim = PG_FORCE_CLAIM;
-#else
         const uint32_t claim = KA(B, claim);              // (pg_launch_search: the share of a workgroup in the fewest equal claims <= PG_CLAIM)
-#endif
         const uint32_t per = n / PG_N_XCD;
         const uint32_t lo = part * per, hi = part + 1 == PG_N_XCD ? n : lo + per;
         // (the single-lane atomics by hand: the compiler wraps an atomicAdd in its wave-reduction form -- exec juggling, mbcnt,

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Diagnostics (GPU box): PMC instruction counts per read of the stop-ladder builds, one process / one rocprofv3 pass.
 #   scripts/ladder_run.sh <tag> [reads]     -> gpurun_out/<tag>/ladder.txt
-#   PREFIX=nf_: the builds of that family (build_ladder.sh)
+#   PREFIX=dg_: the builds of that family (build_ladder.sh)
 tag=${1:-ladder}; reads=${2:-1000000}
 root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/$tag; mkdir -p "$out"

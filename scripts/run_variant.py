@@ -1,5 +1,5 @@
 """Diagnostics: run the device-resident search of the bench workload with another build of the library
-(e.g. one compiled with -DPG_STOP=n or -DPG_DUP=n), for rocprofv3 counter passes and A/B timing.  Prints the kernel
+(e.g. one compiled with -DPG_STOP=n), for rocprofv3 counter passes and A/B timing.  Prints the kernel
 time, the candidates per read and a digest of the downloaded result (equal digests = bit-identical results).
   PG_X=<n> selects -x n, PG_LEN=<bases> the read length, PG_SORT=1 the reads in coordinate order, PG_STEP=1 the step of bench.py
   (pg_device_batch_pack_search: a million reads and more = one launch that packs in place) instead of the search of packed records."""

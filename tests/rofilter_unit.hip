@@ -19,8 +19,6 @@
 #define RO_IDX_1(P) "s_set_gpr_idx_off\n\ts_lshr_b32 s92, " P ", 8\n\ts_set_gpr_idx_on s92, 0x3\n\t"
 #define RO_IDX_2(P) "s_set_gpr_idx_off\n\ts_lshr_b32 s92, " P ", 16\n\ts_set_gpr_idx_on s92, 0x3\n\t"
 #define RO_IDX_OFF "s_set_gpr_idx_off\n\t"
-#elif RO_TEST_VARIANT == 10
-#define RO_TEST_RP 1
 #endif
 #include "../pindel_amd/csrc/pg_kernels.hip"
 #include <stdio.h>
