@@ -12,7 +12,9 @@
  *   pg_far_end_batch    <->  SearchFarEnds(chrSeq, reads, chr) src/pindel.cpp:1115-1138
  *                            (SearchFarEnd per read,        src/pindel.cpp:1001-1074,
  *                             SearchFarEndAtPos             src/farend_searcher.cpp:46-103)
- *   pg_search_batch     <->  both of the above back to back (no BreakDancer hints)
+ *   pg_search_batch     <->  both of the above back to back (no BreakDancer hints: the hints of a read depend on
+ *                            its close end, which the caller does not have yet -- pg_search_batch_table takes them
+ *                            as a position-keyed pg_hint_table and looks them up on the device between the two)
  *   pg_load_reference   <->  Genome::loadAll / Chromosome::getSeq()  src/pindel.cpp:236-312
  *   pg_params           <->  the globals the path reads: g_maxMismatch (pindel.cpp:794-819),
  *                            g_MinClose (:88), userSettings->{MaxRangeIndex, ADDITIONAL_MISMATCH,
@@ -95,6 +97,23 @@ typedef struct {
     const uint64_t  *offset;   /* n_reads+1 */
     const pg_window *windows;
 } pg_windows;
+
+/* BreakDancer hints keyed by POSITION: the per-window object behind g_bdData.getCorrespondingSearchWindowCluster
+ * (src/bddata.cpp:852-967) -- a mask over positions, run-length encoded, and the clusters it indexes.  The library looks
+ * each read up on the device, from the close end it has just found or been given:
+ *   - a read without a close end (close_max <= 0) gets no windows;
+ *   - with p = UP_Close.back().AbsLoc outside [run_first[0], run_first[n_runs]) it gets none either;
+ *   - otherwise it gets the windows of cluster run_cluster[k], in order, for the run k that holds p.
+ * Any cluster may be empty.  NULL / n_runs = 0 means "no hints".  Every entry that takes a table gives bit for bit the
+ * result of its pg_windows sibling fed the per-read clusters this rule expands to; the same limits apply. */
+typedef struct {
+    uint32_t         n_runs;
+    const uint32_t  *run_first;    /* n_runs+1, strictly ascending AbsLoc; run k = [run_first[k], run_first[k+1]) */
+    const uint32_t  *run_cluster;  /* n_runs, each < n_clusters */
+    uint32_t         n_clusters;
+    const uint64_t  *cluster_off;  /* n_clusters+1, monotone */
+    const pg_window *windows;      /* as in pg_windows: start < 0 means end-1 */
+} pg_hint_table;
 
 /* Run-length-encoded UniquePoints (src/pindel.h:137-158).  A run stands for
  * the points  LengthStr = len_first..len_last  with
@@ -198,7 +217,22 @@ int  pg_far_end_batch(pg_ctx *ctx, const pg_read_batch *reads, pg_result *close,
  * its rc flags zero. */
 int  pg_far_end_batch_from_close(pg_ctx *ctx, const pg_read_batch *reads, const uint32_t *close_last,
                                  const int16_t *close_max, const pg_windows *bd_hints /* nullable */, pg_result **out);
+/* Close end + far end of one batch, host buffers in, host results out.  It takes no BreakDancer hints: they follow from
+ * each read's close end (see pg_search_batch_table). */
 int  pg_search_batch(pg_ctx *ctx, const pg_read_batch *reads, pg_result **out);
+
+/* The same three entries with the hints as a pg_hint_table: the lookup runs on the device (count, scan, fill: three small
+ * kernels on the ctx's stream) from the close-end summary that is already there, and the host waits once more, for 16 bytes.
+ * A malformed table -- unsorted run_first, a run_cluster value >= n_clusters, non-monotone cluster_off, a window on an
+ * unknown chromosome, a null array with a non-zero count -- is PG_E_INVALID before anything is launched.
+ *   pg_far_end_batch_from_close_table   seam 2 as the reference calls it, hints included
+ *   pg_far_end_batch_table              both seams on one read vector (sibling of pg_far_end_batch)
+ *   pg_search_batch_table               close end, lookup and far end in one call: the reads are uploaded once, and the
+ *                                       close-end summary stays on the device until the far end has run */
+int  pg_far_end_batch_from_close_table(pg_ctx *ctx, const pg_read_batch *reads, const uint32_t *close_last,
+                                       const int16_t *close_max, const pg_hint_table *table /* nullable */, pg_result **out);
+int  pg_far_end_batch_table(pg_ctx *ctx, const pg_read_batch *reads, pg_result *close, const pg_hint_table *table /* nullable */);
+int  pg_search_batch_table(pg_ctx *ctx, const pg_read_batch *reads, const pg_hint_table *table /* nullable */, pg_result **out);
 
 /* Multi-GPU form of pg_search_batch: the reads are split into n_ctx contiguous ranges (reads are independent:
  * the loop of ReadBuffer::flush / SearchFarEnds, src/read_buffer.cpp:36-101, src/pindel.cpp:1115-1138), context k

@@ -46,6 +46,11 @@ class PgWindows(C.Structure):
     _fields_ = [("offset", C.c_void_p), ("windows", C.c_void_p)]
 
 
+class PgHintTable(C.Structure):
+    _fields_ = [("n_runs", C.c_uint32), ("run_first", C.c_void_p), ("run_cluster", C.c_void_p),
+                ("n_clusters", C.c_uint32), ("cluster_off", C.c_void_p), ("windows", C.c_void_p)]
+
+
 class PgResultView(C.Structure):
     _fields_ = [
         ("n_reads", C.c_uint32), ("close_off", C.POINTER(C.c_uint64)), ("close_runs", C.c_void_p),
@@ -69,7 +74,7 @@ EXPORTS = [
     "pg_default_params", "pg_create", "pg_destroy", "pg_last_error", "pg_get_max_mismatch",
     "pg_load_reference", "pg_load_fasta", "pg_reference_save_packed", "pg_reference_load_packed", "pg_reference_n_chr", "pg_reference_name",
     "pg_reference_comp_size", "pg_reference_fetch", "pg_close_end_batch", "pg_far_end_batch",
-    "pg_far_end_batch_from_close",
+    "pg_far_end_batch_from_close", "pg_far_end_batch_from_close_table", "pg_far_end_batch_table", "pg_search_batch_table",
     "pg_search_batch", "pg_search_batch_multi", "pg_result_view_get", "pg_result_free", "pg_expand_runs",
     "pg_device_batch_upload", "pg_device_batch_set_windows", "pg_device_batch_search", "pg_device_batch_download",
     "pg_device_batch_free", "pg_last_search_stats", "pg_device_batch_algorithmic_bytes",
@@ -140,6 +145,9 @@ def lib():
     L.pg_far_end_batch.argtypes = [vp, C.POINTER(PgReadBatch), vp, C.POINTER(PgWindows)]
     L.pg_far_end_batch_from_close.argtypes = [vp, C.POINTER(PgReadBatch), vp, vp, C.POINTER(PgWindows), C.POINTER(vp)]
     L.pg_search_batch.argtypes = [vp, C.POINTER(PgReadBatch), C.POINTER(vp)]
+    L.pg_far_end_batch_table.argtypes = [vp, C.POINTER(PgReadBatch), vp, C.POINTER(PgHintTable)]
+    L.pg_far_end_batch_from_close_table.argtypes = [vp, C.POINTER(PgReadBatch), vp, vp, C.POINTER(PgHintTable), C.POINTER(vp)]
+    L.pg_search_batch_table.argtypes = [vp, C.POINTER(PgReadBatch), C.POINTER(PgHintTable), C.POINTER(vp)]
     L.pg_search_batch_multi.argtypes = [C.POINTER(vp), i32, C.POINTER(PgReadBatch), C.POINTER(vp)]
     L.pg_result_view_get.argtypes = [vp, C.POINTER(PgResultView)]
     L.pg_result_free.argtypes = [vp]
@@ -215,6 +223,48 @@ class Result:
             self.free()
         except Exception:
             pass
+
+
+class HintTable:
+    """A pg_hint_table: BreakDancer hints keyed by position.  Run k covers the close-end positions
+    [run_first[k], run_first[k + 1]) and names cluster run_cluster[k], whose windows are windows[cluster_off[c]:cluster_off[c + 1]].
+    The arrays are taken as they are (the library validates them)."""
+
+    def __init__(self, run_first, run_cluster, cluster_off, windows):
+        self.run_first = np.ascontiguousarray(run_first, dtype=np.uint32)
+        self.run_cluster = np.ascontiguousarray(run_cluster, dtype=np.uint32)
+        self.cluster_off = np.ascontiguousarray(cluster_off, dtype=np.uint64)
+        self.windows = np.ascontiguousarray(windows, dtype=WINDOW_DTYPE)
+
+    def struct(self):
+        def ptr(a):
+            return a.ctypes.data if len(a) else None
+        return PgHintTable(len(self.run_cluster), ptr(self.run_first), ptr(self.run_cluster),
+                           max(len(self.cluster_off) - 1, 0), ptr(self.cluster_off), ptr(self.windows))
+
+    def expand(self, close_last, close_max):
+        """The lookup rule restated in numpy: the per-read (bd, bd_off) the table stands for."""
+        p = np.asarray(close_last, dtype=np.int64)
+        has = np.asarray(close_max, dtype=np.int64) > 0
+        n_runs = len(self.run_cluster)
+        counts = np.zeros(len(p), dtype=np.int64)
+        first = np.zeros(len(p), dtype=np.int64)
+        if n_runs and len(p):
+            rf = self.run_first.astype(np.int64)
+            k = np.searchsorted(rf, p, side="right") - 1
+            ok = has & (p >= rf[0]) & (p < rf[n_runs])
+            c = self.run_cluster[np.clip(k, 0, n_runs - 1)].astype(np.int64)
+            off = self.cluster_off.astype(np.int64)
+            counts = np.where(ok, off[c + 1] - off[c], 0)
+            first = off[c]
+        bd_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+        idx = np.repeat(first - bd_off[:-1].astype(np.int64), counts) + np.arange(int(bd_off[-1]), dtype=np.int64)
+        return self.windows[idx], bd_off
+
+
+def _hint_args(bd, hints):
+    if bd is not None and hints is not None:
+        raise ValueError("give either per-read windows (bd, bd_off) or a HintTable (hints), not both")
 
 
 def _batch_struct(batch):
@@ -328,8 +378,14 @@ class Engine:
         self._check(self._L.pg_close_end_batch(self._h, C.byref(s), C.byref(h)))
         return Result(h, self)
 
-    def far_end_batch(self, batch, close: Result, bd=None, bd_off=None) -> Result:
+    def far_end_batch(self, batch, close: Result, bd=None, bd_off=None, hints=None) -> Result:
+        _hint_args(bd, hints)
         s, keep = _batch_struct(batch)
+        if hints is not None:
+            t = hints.struct()
+            self._check(self._L.pg_far_end_batch_table(self._h, C.byref(s), close._h, C.byref(t)))
+            close.refresh()
+            return close
         w = None
         if bd is not None:
             bd = np.ascontiguousarray(bd, dtype=WINDOW_DTYPE)
@@ -340,11 +396,19 @@ class Engine:
         close.refresh()
         return close
 
-    def far_end_batch_from_close(self, batch, close_last, close_max, bd=None, bd_off=None) -> Result:
-        """pg_far_end_batch_from_close: the reads as the close end left them + UP_Close.back()'s AbsLoc / LengthStr."""
+    def far_end_batch_from_close(self, batch, close_last, close_max, bd=None, bd_off=None, hints=None) -> Result:
+        """pg_far_end_batch_from_close: the reads as the close end left them + UP_Close.back()'s AbsLoc / LengthStr.
+        hints: a HintTable looked up on the device (pg_far_end_batch_from_close_table) instead of per-read windows."""
+        _hint_args(bd, hints)
         s, keep = _batch_struct(batch)
         cl = np.ascontiguousarray(close_last, dtype=np.uint32)
         cm = np.ascontiguousarray(close_max, dtype=np.int16)
+        if hints is not None:
+            t = hints.struct()
+            h = C.c_void_p()
+            self._check(self._L.pg_far_end_batch_from_close_table(self._h, C.byref(s), cl.ctypes.data, cm.ctypes.data,
+                                                                  C.byref(t), C.byref(h)))
+            return Result(h, self)
         w = None
         if bd is not None:
             bd = np.ascontiguousarray(bd, dtype=WINDOW_DTYPE)
@@ -355,11 +419,26 @@ class Engine:
                                                         C.byref(w) if w is not None else None, C.byref(h)))
         return Result(h, self)
 
-    def search_batch(self, batch) -> Result:
+    def search_batch(self, batch, hints=None) -> Result:
+        """hints: a HintTable -- close end, lookup on the device, far end (pg_search_batch_table)."""
         s, keep = _batch_struct(batch)
         h = C.c_void_p()
-        self._check(self._L.pg_search_batch(self._h, C.byref(s), C.byref(h)))
+        if hints is not None:
+            t = hints.struct()
+            self._check(self._L.pg_search_batch_table(self._h, C.byref(s), C.byref(t), C.byref(h)))
+        else:
+            self._check(self._L.pg_search_batch(self._h, C.byref(s), C.byref(h)))
         return Result(h, self)
+
+    def last_hint_stats(self):
+        """measurement: the last hint-table lookup of this context -- HIP-event ms of its count + scan kernels and of its fill
+        kernel, bytes of the table uploaded, windows written"""
+        L = self._L
+        L.pg_debug_last_hint_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64),
+                                               C.POINTER(C.c_uint64)]
+        a, b, c, d = C.c_double(), C.c_double(), C.c_uint64(), C.c_uint64()
+        self._check(L.pg_debug_last_hint_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return a.value, b.value, c.value, d.value
 
     @staticmethod
     def search_batch_multi(engines, batch) -> "Result":

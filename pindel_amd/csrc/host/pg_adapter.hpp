@@ -213,8 +213,10 @@ int CloseEndBatch(pg_ctx *ctx, std::vector<Read> &reads, ChrOf chr_of, MakePoint
 // then -- the reads of many CloseEndBatch flushes that kept a close end, in any order -- each carrying UnmatchedSeq
 // as GetCloseEnd left it and a non-empty UP_Close (a read with an empty UP_Close is passed through: no far end).
 // `hints` may be null.
+// `table` (nullable, instead of `hints`): the hints as a position-keyed table, looked up on the device.
 template <class Read, class ChrOf, class MakePoint>
-int SearchFarEnds(pg_ctx *ctx, std::vector<Read> &reads, ChrOf chr_of, MakePoint make_point, const pg_windows *hints)
+int SearchFarEndsFromClose(pg_ctx *ctx, std::vector<Read> &reads, ChrOf chr_of, MakePoint make_point, const pg_windows *hints,
+                           const pg_hint_table *table)
 {
     Batch b = make_batch(reads, chr_of);
     const size_t n = reads.size();
@@ -229,7 +231,8 @@ int SearchFarEnds(pg_ctx *ctx, std::vector<Read> &reads, ChrOf chr_of, MakePoint
     });
     pg_read_batch v = b.view();
     pg_result *res = nullptr;
-    int rc_ = pg_far_end_batch_from_close(ctx, &v, close_last.data(), close_max.data(), hints, &res);
+    int rc_ = table ? pg_far_end_batch_from_close_table(ctx, &v, close_last.data(), close_max.data(), table, &res)
+                    : pg_far_end_batch_from_close(ctx, &v, close_last.data(), close_max.data(), hints, &res);
     if (rc_) return rc_;
     pg_result_view rv;
     pg_result_view_get(res, &rv);
@@ -239,6 +242,18 @@ int SearchFarEnds(pg_ctx *ctx, std::vector<Read> &reads, ChrOf chr_of, MakePoint
     });
     pg_result_free(res);
     return PG_OK;
+}
+
+template <class Read, class ChrOf, class MakePoint>
+int SearchFarEnds(pg_ctx *ctx, std::vector<Read> &reads, ChrOf chr_of, MakePoint make_point, const pg_windows *hints)
+{
+    return SearchFarEndsFromClose(ctx, reads, chr_of, make_point, hints, nullptr);
+}
+// ... with the hints of the window as a table (pg_far_end_batch_from_close_table)
+template <class Read, class ChrOf, class MakePoint>
+int SearchFarEndsTable(pg_ctx *ctx, std::vector<Read> &reads, ChrOf chr_of, MakePoint make_point, const pg_hint_table *table)
+{
+    return SearchFarEndsFromClose(ctx, reads, chr_of, make_point, nullptr, table);
 }
 
 // Both seams on ONE read vector (same order, same count as CloseEndBatch; saves the close-summary upload when a

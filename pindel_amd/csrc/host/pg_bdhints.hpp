@@ -157,6 +157,35 @@ public:
         return clusters_[ci];
     }
 
+    // The loaded region as a position-keyed table (pg_hint_table, pindel_pg.h): the run-length form of what cluster() answers
+    // from the mask -- the runs over win_start_ < p < win_end_ (outside them, and at the never-written last mask entry, cluster()
+    // answers "none"), equal neighbours merged, and the clusters as loaded (cluster 0 is the empty one).  run_first has one
+    // entry more than run_cluster; a region without such positions gives a table without runs.
+    struct Table {
+        std::vector<uint32_t> run_first, run_cluster;
+        std::vector<uint64_t> cluster_off;
+        std::vector<BDWindow> win;
+    };
+    Table table() const
+    {
+        Table t;
+        if (clusters_.empty() || win_end_ <= win_start_ + 1) return t;
+        for (unsigned p = win_start_ + 1; p < win_end_; p++) {
+            const unsigned ci = mask_[p - win_start_];
+            if (t.run_cluster.empty() || t.run_cluster.back() != ci) {
+                t.run_first.push_back(p);
+                t.run_cluster.push_back(ci);
+            }
+        }
+        t.run_first.push_back(win_end_);
+        t.cluster_off.push_back(0);
+        for (const std::vector<BDWindow> &c : clusters_) {
+            t.win.insert(t.win.end(), c.begin(), c.end());
+            t.cluster_off.push_back(t.win.size());
+        }
+        return t;
+    }
+
 private:
     struct Coord {
         std::string chr;

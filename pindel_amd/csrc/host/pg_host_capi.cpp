@@ -344,6 +344,41 @@ int pgh_bd_query(const char *path, uint32_t spacer, int32_t n_chr, const char *c
     return pack_hint_windows(h, n_q, q, out_off, out_win, cap) ? rc : -3;
 }
 
+// The same region as a position-keyed table (BDHints::table, pg_hint_table of pindel_pg.h) into the caller's arrays: run_first
+// (room for cap_runs + 1), run_cluster (cap_runs), cluster_off (cap_clusters + 1), out_win 3 ints (chr id, start, end) per window
+// (cap_win windows); counts[0 .. 2] = runs, clusters, windows -- filled in whatever the capacities, so that a caller may ask with
+// capacities of 0 first.  Returns as pgh_bd_query; -3 = an array is too small (nothing but counts was written).
+int pgh_bd_table(const char *path, uint32_t spacer, int32_t n_chr, const char *const *names, int32_t chr_id, uint32_t start,
+                 uint32_t end, uint32_t *run_first, uint32_t *run_cluster, uint64_t cap_runs, uint64_t *cluster_off,
+                 uint64_t cap_clusters, int32_t *out_win, uint64_t cap_win, uint64_t *counts, uint64_t *n_events)
+{
+    pgh::BDHints h;
+    std::string note;
+    const int rc = h.load_file(path, spacer, note);
+    if (n_events) *n_events = h.n_events();
+    g_err = note;
+    if (rc < 0) return -1;
+    std::vector<std::string> nm(names, names + n_chr);
+    if (!h.load_region(nm, chr_id, start, end, g_err)) return -2;
+    const pgh::BDHints::Table t = h.table();
+    const uint64_t n_clusters = t.cluster_off.empty() ? 0 : t.cluster_off.size() - 1;
+    if (counts) {
+        counts[0] = t.run_cluster.size();
+        counts[1] = n_clusters;
+        counts[2] = t.win.size();
+    }
+    if (t.run_cluster.size() > cap_runs || n_clusters > cap_clusters || t.win.size() > cap_win) return -3;
+    std::copy(t.run_first.begin(), t.run_first.end(), run_first);
+    std::copy(t.run_cluster.begin(), t.run_cluster.end(), run_cluster);
+    std::copy(t.cluster_off.begin(), t.cluster_off.end(), cluster_off);
+    for (size_t k = 0; k < t.win.size(); k++) {
+        out_win[3 * k] = t.win[k].chr_id;
+        out_win[3 * k + 1] = (int32_t)t.win[k].start;
+        out_win[3 * k + 2] = (int32_t)t.win[k].end;
+    }
+    return rc;
+}
+
 // BAM ingest (pg_bam.hpp): the split-read candidates of one window of one BAM file as the SoA batch of the C ABI.
 // Returns a handle (pgh_bam_ingest_free) or null (pgh_last_error).
 void *pgh_bam_ingest(const char *bam_path, const char *chr_name, int32_t chr_id, uint64_t chr_padded_size, int64_t win_start,

@@ -22,6 +22,7 @@
 // checked before the first device call (exit status 2 for -c syntax, 1 for an unreadable file or an unknown chromosome).
 // Flags and their defaults follow src/fn_parameters.cpp; BAM input (-i) is read without htslib (pg_bam.hpp).
 #include <cstdio>
+#include <cstdlib>
 #include <chrono>
 #include <fstream>
 #include <algorithm>
@@ -289,8 +290,28 @@ struct CloseSoa {
     }
 };
 
+// BDHints::table() as the C ABI takes it: a pg_hint_table over the arrays kept here
+struct HintTableView {
+    BDHints::Table tab;
+    std::vector<pg_window> win;
+    pg_hint_table t = { 0, nullptr, nullptr, 0, nullptr, nullptr };
+    void set(BDHints::Table &&from)
+    {
+        tab = std::move(from);
+        win.resize(tab.win.size());
+        for (size_t k = 0; k < win.size(); k++) win[k] = { tab.win[k].chr_id, (int32_t)tab.win[k].start, (int32_t)tab.win[k].end };
+        t.n_runs = (uint32_t)tab.run_cluster.size();
+        t.run_first = tab.run_first.data();
+        t.run_cluster = tab.run_cluster.data();
+        t.n_clusters = tab.cluster_off.empty() ? 0u : (uint32_t)(tab.cluster_off.size() - 1);
+        t.cluster_off = tab.cluster_off.data();
+        t.windows = win.empty() ? nullptr : win.data();
+    }
+};
+
 // Seam 2 (SearchFarEnds, src/pindel.cpp:1115-1138, called at :1888 on state.Reads_SR): the far end of the reads that
-// kept a close end -- the filtered union of the flushes -- through pg_far_end_batch_from_close.
+// kept a close end -- the filtered union of the flushes -- through pg_far_end_batch_from_close (a hinted window: through
+// pg_far_end_batch_from_close_table, with the window's hints as one table).
 struct FarSearch {
     const Seams &s;
     int operator()(const Chromosome &, int chr_id, std::vector<SplitRead> &kept, unsigned ws, unsigned we) const
@@ -306,8 +327,19 @@ struct FarSearch {
             if (!s.bd.load_region(s.chr_names, chr_id, ws + s.o.prm.spacer, we + s.o.prm.spacer, berr)) return fail(berr, (int)PG_E_INVALID);
         }
         const BDHints &bd = s.bd;
-        const int r = on_devices(s.ctxs, kept, [&bd, hinted](pg_ctx *c, std::vector<SplitRead> &part) {
+        // the window's hints as ONE position-keyed table, looked up per read on the device (pg_far_end_batch_from_close_table);
+        // PGH_HINT_LOOKUP=host: the per-read lookup on the host and the replicated upload instead (same reports)
+        static const bool host_lookup = [] { const char *e = getenv("PGH_HINT_LOOKUP"); return e && std::string(e) == "host"; }();
+        HintTableView tab;
+        if (hinted && !host_lookup) tab.set(bd.table());
+        if (hinted) {
+            if (host_lookup) printf("Window hints: host lookup, per-read clusters uploaded\n");
+            else printf("Window hints: device lookup, table of %u runs / %u clusters / %zu windows\n", tab.t.n_runs, tab.t.n_clusters, tab.win.size());
+        }
+        const pg_hint_table *tp = hinted && !host_lookup ? &tab.t : nullptr;
+        const int r = on_devices(s.ctxs, kept, [&bd, hinted, tp](pg_ctx *c, std::vector<SplitRead> &part) {
             if (!hinted || part.empty()) return pg_adapter::SearchFarEnds(c, part, chr_of, make_point, nullptr);
+            if (tp) return pg_adapter::SearchFarEndsTable(c, part, chr_of, make_point, tp);
             const HintWindows hw = hint_windows(bd, part.size(), [&](size_t i) { return part[i].UP_Close.back().AbsLoc; });
             std::vector<pg_window> win(hw.win.size());
             for (size_t k = 0; k < win.size(); k++) win[k] = { hw.win[k].chr_id, (int32_t)hw.win[k].start, (int32_t)hw.win[k].end };

@@ -214,6 +214,12 @@ struct pg_ctx {
     hipStream_t stream2 = nullptr;                         // second kernel stream of the chunked host path (odd chunks)
     std::vector<hipEvent_t> events;                        // reused by the chunked host path (no timing)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // hint tables (pg_hints.hip): events around the fill kernel (created on first use), and the last lookup's figures
+    // (pg_debug_last_hint_stats): HIP-event ms of count + scan and of the fill, bytes of the table uploaded, windows written
+    hipEvent_t evh0 = nullptr, evh1 = nullptr;
+    bool hint_fill_timed = false;
+    double hint_scan_ms = 0.0, hint_fill_ms = 0.0;
+    uint64_t hint_table_bytes = 0, hint_windows = 0;
     // reference
     std::vector<std::string> names;
     std::vector<uint64_t> comp_size;
@@ -1063,7 +1069,8 @@ struct DevTemps {
 // two passes, so that the run buffers can be sized from the batch's totals and only the compact CSR crosses PCIe (pinned host
 // buffers).  Pass 1 scans every chunk -- per-read summaries, local sums, each chunk's base and run counts; pass 2 gathers the runs
 // in read order and writes the 64-bit offsets.
-int download(pg_ctx *ctx, pg_device_batch *b, pg_result *r)
+// summaries = false (pg_search_batch_table, between its two launches): the per-read close-end summaries stay on the device
+int download(pg_ctx *ctx, pg_device_batch *b, pg_result *r, bool summaries = true)
 {
     const size_t n = b->n;
     r->n = b->n;
@@ -1093,9 +1100,11 @@ int download(pg_ctx *ctx, pg_device_batch *b, pg_result *r)
                                                  b->pool_used, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(info.data(), d_info, n_chunks * 64, hipMemcpyDeviceToHost, ctx->stream));
     // (the per-read summaries travel while the host sizes the run buffers)
-    HIP_TRY(ctx, hipMemcpyAsync(r->rc_flag.data(), b->rc_flag, n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(r->close_last.data(), b->close_last, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(r->close_max.data(), b->close_max, n * 2, hipMemcpyDeviceToHost, ctx->stream));
+    if (summaries) {
+        HIP_TRY(ctx, hipMemcpyAsync(r->rc_flag.data(), b->rc_flag, n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(r->close_last.data(), b->close_last, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(r->close_max.data(), b->close_max, n * 2, hipMemcpyDeviceToHost, ctx->stream));
+    }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // the totals: the last chunk's base + its runs.  A list without a run gets no buffer -- its null pointer is never written
     // through (a null far buffer makes the gather place the far runs behind the close runs: there are none to place)
@@ -1562,6 +1571,8 @@ void pg_destroy(pg_ctx *ctx)
     if (ctx->d_len_tab) (void)hipFree(ctx->d_len_tab);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
+    if (ctx->evh0) (void)hipEventDestroy(ctx->evh0);
+    if (ctx->evh1) (void)hipEventDestroy(ctx->evh1);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->dl_stream) (void)hipStreamDestroy(ctx->dl_stream);
@@ -2144,8 +2155,155 @@ static int attach_windows(pg_ctx *ctx, pg_device_batch *b, const pg_windows *bd_
 
 // Far end of `reads` given each read's close-end summary (host arrays; rc_flag may be null = the sequences are
 // already in the orientation GetCloseEnd left them in).  far_off / far_runs of `dst` are replaced.
+// A pg_hint_table validated, its windows split into pieces the position field of a candidate id can hold (once per cluster
+// window, as attach_windows does per read), in device memory for the lifetime of one call.
+struct HintTableDev {
+    PgDevHintTable t{};
+    void *bufs[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    uint64_t bytes = 0;
+    HintTableDev() = default;
+    HintTableDev(const HintTableDev &) = delete;
+    ~HintTableDev()
+    {
+        for (void *p : bufs)
+            if (p) (void)hipFree(p);
+    }
+    bool live() const { return t.n_runs != 0; }
+};
+
+// Everything that can be wrong with a table is found here, before anything is launched.  A null table or one without runs
+// leaves d without runs: "no hints".
+static int upload_hint_table(pg_ctx *ctx, const pg_hint_table *table, HintTableDev &d)
+{
+    if (!table || !table->n_runs) return PG_OK;
+    if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
+    const uint32_t nr = table->n_runs, nc = table->n_clusters;
+    if (!table->run_first || !table->run_cluster) return fail(ctx, PG_E_INVALID, "hint table: null run arrays");
+    if (nc && !table->cluster_off) return fail(ctx, PG_E_INVALID, "hint table: null cluster offsets");
+    for (uint32_t k = 0; k < nr; k++)
+        if (table->run_first[k + 1] <= table->run_first[k]) return fail(ctx, PG_E_INVALID, "hint table: run_first not strictly ascending");
+    for (uint32_t k = 0; k < nr; k++)
+        if (table->run_cluster[k] >= nc) return fail(ctx, PG_E_INVALID, "hint table: run_cluster names a cluster the table does not have");
+    for (uint32_t c = 0; c < nc; c++)
+        if (table->cluster_off[c + 1] < table->cluster_off[c]) return fail(ctx, PG_E_INVALID, "hint table: cluster_off not monotone");
+    const uint64_t w0 = table->cluster_off[0], nw = table->cluster_off[nc] - w0;
+    if (nw && !table->windows) return fail(ctx, PG_E_INVALID, "null window array");
+    const long long piece = (1ll << PG_REL_BITS) - 1;
+    for (uint64_t k = 0; k < nw; k++) {
+        const pg_window &w = table->windows[w0 + k];
+        if (w.chr_id < 0 || w.chr_id >= (int)ctx->names.size()) return fail(ctx, PG_E_INVALID, "BreakDancer window on unknown chromosome");
+    }
+    std::vector<uint64_t> off(nc + (size_t)1, 0);
+    std::vector<uint32_t> longest(nc, 0u);
+    std::vector<pg_window> win;
+    win.reserve((size_t)nw);
+    for (uint32_t c = 0; c < nc; c++) {
+        long long most = 0;
+        for (uint64_t k = table->cluster_off[c]; k < table->cluster_off[c + 1]; k++) {
+            const pg_window &w = table->windows[k];
+            const long long st = w.start < 0 ? (long long)w.end - 1 : w.start;       // farend_searcher.cpp:69-71
+            if ((long long)w.end - st <= piece) {
+                most = std::max(most, (long long)w.end - st);
+                win.push_back(w);
+                continue;
+            }
+            most = piece;
+            for (long long s0 = st; s0 < (long long)w.end; s0 += piece) {
+                const pg_window q = { w.chr_id, (int32_t)s0, (int32_t)std::min<long long>(s0 + piece, w.end) };
+                win.push_back(q);
+            }
+        }
+        longest[c] = (uint32_t)most;
+        off[c + (size_t)1] = win.size();
+    }
+    uint32_t *d_first = nullptr, *d_cluster = nullptr, *d_longest = nullptr;
+    uint64_t *d_off = nullptr;
+    pg_window *d_win = nullptr;
+    int rc;
+    if ((rc = dev_upload(ctx, &d_first, table->run_first, nr + (size_t)1))) return rc;
+    d.bufs[0] = d_first;
+    if ((rc = dev_upload(ctx, &d_cluster, table->run_cluster, nr))) return rc;
+    d.bufs[1] = d_cluster;
+    if ((rc = dev_upload(ctx, &d_off, off.data(), off.size()))) return rc;
+    d.bufs[2] = d_off;
+    if ((rc = dev_upload(ctx, &d_longest, longest.data(), longest.size()))) return rc;
+    d.bufs[3] = d_longest;
+    if ((rc = dev_upload(ctx, &d_win, win.data(), win.size()))) return rc;
+    d.bufs[4] = d_win;
+    d.t.n_runs = nr;
+    d.t.run_first = d_first;
+    d.t.run_cluster = d_cluster;
+    d.t.cluster_off = d_off;
+    d.t.cluster_longest = d_longest;
+    d.t.windows = d_win;
+    d.bytes = (nr + 1ull) * 4 + (uint64_t)nr * 4 + off.size() * 8 + longest.size() * 4 + win.size() * sizeof(pg_window);
+    return PG_OK;
+}
+
+// The per-read window clusters of the batch from a hint table and the close-end summary in the batch's device arrays
+// (close_last / close_max): what attach_windows builds from a host CSR, built by the three kernels of pg_hints.hip.  The host
+// waits once, for 16 bytes: the total and the two maxima attach_windows would have computed.  The far launch that follows packs
+// the batch itself.
+static int attach_table(pg_ctx *ctx, pg_device_batch *b, const HintTableDev &d)
+{
+    const uint32_t n = b->n;
+    if (int stale = stale_batch(ctx, b)) return stale;
+    if (b->bd_off) { (void)hipFree(b->bd_off); b->bd_off = nullptr; }
+    if (b->bd) { (void)hipFree(b->bd); b->bd = nullptr; }
+    b->max_bd_window = 0;
+    b->max_bd_cluster = 0;
+    ctx->hint_fill_timed = false;
+    ctx->hint_scan_ms = ctx->hint_fill_ms = 0.0;
+    ctx->hint_table_bytes = d.bytes;
+    ctx->hint_windows = 0;
+    if (!n || !d.live()) return PG_OK;
+    if (!ctx->evh0) HIP_TRY(ctx, hipEventCreate(&ctx->evh0));
+    if (!ctx->evh1) HIP_TRY(ctx, hipEventCreate(&ctx->evh1));
+    int rc = dev_alloc(ctx, &b->bd_off, (size_t)n + 1);
+    if (rc) return rc;
+    uint32_t info[4] = { 0u, 0u, 0u, 0u };
+    {
+        DevTemps tmp(ctx, b);
+        unsigned long long *blk = (unsigned long long *)tmp.take((size_t)pg_hint_scan_blocks(n) * 8);
+        uint32_t *d_info = (uint32_t *)tmp.take(sizeof info);
+        if (!blk || !d_info) return fail(ctx, PG_E_NOMEM, "device memory for the hint lookup's scan");
+        HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        if (int e = pg_hint_count_scan(&d.t, b->close_last, b->close_max, n, (unsigned long long *)b->bd_off, blk, d_info, ctx->stream))
+            return fail(ctx, PG_E_DEVICE, std::string("hint count / scan kernels: ") + hipGetErrorString((hipError_t)e));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(info, d_info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        float ms = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        ctx->hint_scan_ms = ms;
+    }
+    const uint64_t total = (uint64_t)info[0] | ((uint64_t)info[1] << 32);
+    if (total > 0xffffffffull) return fail(ctx, PG_E_UNSUPPORTED, "more than 2^32 BreakDancer windows in a batch");
+    if (info[2] >= (1u << 29)) return fail(ctx, PG_E_UNSUPPORTED, "more than 2^29 windows in a BreakDancer cluster");
+    b->max_bd_cluster = info[2];
+    b->max_bd_window = info[3];
+    ctx->hint_windows = total;
+    if ((rc = dev_alloc(ctx, &b->bd, (size_t)total))) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->evh0, ctx->stream));
+    if (int e = pg_hint_fill(&d.t, b->close_last, b->close_max, n, (const unsigned long long *)b->bd_off, b->bd, ctx->stream))
+        return fail(ctx, PG_E_DEVICE, std::string("hint fill kernel: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(ctx, hipEventRecord(ctx->evh1, ctx->stream));
+    ctx->hint_fill_timed = true;
+    return PG_OK;
+}
+
+// ... and once the far launch behind the fill has been waited for: the fill's duration (no wait of its own)
+static void note_hint_fill(pg_ctx *ctx)
+{
+    if (!ctx->hint_fill_timed) return;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ctx->evh0, ctx->evh1) == hipSuccess) ctx->hint_fill_ms = ms;
+    ctx->hint_fill_timed = false;
+}
+
+// table (nullable): the windows come from a hint table instead of bd_hints
 static int far_end_impl(pg_ctx *ctx, const pg_read_batch *reads, const uint8_t *rc_flag, const uint32_t *close_last,
-                        const uint16_t *close_max, const pg_windows *bd_hints, pg_result *dst)
+                        const uint16_t *close_max, const pg_windows *bd_hints, pg_result *dst, const HintTableDev *table = nullptr)
 {
     BatchGuard g;
     HostBuf<uint64_t> off0;
@@ -2165,7 +2323,10 @@ static int far_end_impl(pg_ctx *ctx, const pg_read_batch *reads, const uint8_t *
         if (hipStreamSynchronize(ctx->stream) != hipSuccess)       // the host arrays may be pageable temporaries
             return fail(ctx, PG_E_DEVICE, "upload of close-end summary failed");
     }
-    if ((rc = attach_windows(ctx, b, bd_hints, false)) || (rc = run_search(ctx, b, PG_MODE_FAR, true))) return rc;
+    if ((rc = table && table->live() ? attach_table(ctx, b, *table) : attach_windows(ctx, b, bd_hints, false)) ||
+        (rc = run_search(ctx, b, PG_MODE_FAR, true)))
+        return rc;
+    note_hint_fill(ctx);
     pg_result tmp;
     if ((rc = download(ctx, b, &tmp))) return rc;
     dst->far_off.swap(tmp.far_off);
@@ -2185,12 +2346,92 @@ int pg_far_end_batch(pg_ctx *ctx, const pg_read_batch *reads, pg_result *close, 
     return far_end_impl(ctx, reads, close->rc_flag.data(), close->close_last.data(), close->close_max.data(), bd_hints, close);
 }
 
+int pg_far_end_batch_table(pg_ctx *ctx, const pg_read_batch *reads, pg_result *close, const pg_hint_table *table)
+{
+    use_device(ctx);
+    if (!ctx || !reads || !close) return PG_E_INVALID;
+    if (close->n != reads->n_reads) return fail(ctx, PG_E_INVALID, "close result does not belong to these reads");
+    const size_t n = reads->n_reads;
+    if (n && (close->rc_flag.size() != n || close->close_last.size() != n || close->close_max.size() != n))
+        return fail(ctx, PG_E_INVALID, "close result carries no close-end summary");
+    HintTableDev d;
+    if (int rc = upload_hint_table(ctx, table, d)) return rc;
+    return far_end_impl(ctx, reads, close->rc_flag.data(), close->close_last.data(), close->close_max.data(), nullptr, close, &d);
+}
+
+static int far_end_from_close(pg_ctx *ctx, const pg_read_batch *reads, const uint32_t *close_last, const int16_t *close_max,
+                              const pg_windows *bd_hints, const pg_hint_table *table, pg_result **out);
+
 int pg_far_end_batch_from_close(pg_ctx *ctx, const pg_read_batch *reads, const uint32_t *close_last,
                                 const int16_t *close_max, const pg_windows *bd_hints, pg_result **out)
+{
+    return far_end_from_close(ctx, reads, close_last, close_max, bd_hints, nullptr, out);
+}
+
+int pg_far_end_batch_from_close_table(pg_ctx *ctx, const pg_read_batch *reads, const uint32_t *close_last,
+                                      const int16_t *close_max, const pg_hint_table *table, pg_result **out)
+{
+    return far_end_from_close(ctx, reads, close_last, close_max, nullptr, table, out);
+}
+
+// Close end, lookup and far end of one batch: the reads are uploaded once; the close runs are delivered to the host before the
+// far launch (run_search zeroes the run-pool cursors per launch), the close-end SUMMARY -- what the lookup and the far end read --
+// stays in the batch's device arrays and reaches the host with the far end's results.
+int pg_search_batch_table(pg_ctx *ctx, const pg_read_batch *reads, const pg_hint_table *table, pg_result **out)
 {
     use_device(ctx);
     if (!ctx || !reads || !out) return PG_E_INVALID;
     *out = nullptr;
+    HintTableDev d;
+    int rc = upload_hint_table(ctx, table, d);
+    if (rc) return rc;
+    if (!d.live() || !reads->n_reads) return pg_search_batch(ctx, reads, out);      // (no hints, or nobody to look up)
+    BatchGuard g;
+    HostBuf<uint64_t> off0;
+    if ((rc = alloc_batch(ctx, reads, true, off0, &g.b, true))) return rc;
+    pg_device_batch *b = g.b;
+    if ((rc = run_search(ctx, b, PG_MODE_CLOSE, true))) return rc;
+    g.r = new pg_result();
+    if ((rc = download(ctx, b, g.r, false))) return rc;
+    if (b->n) {
+        // the output records back to the summary alone (no runs in the pool any more), as pg_far_end_batch starts from
+        const PgSoaOut a = soa_out(b);
+        if (pg_pack_close_summary(&a, b->out_rec, b->n, ctx->stream) != 0)
+            return fail(ctx, PG_E_DEVICE, "close-end summary pack kernel failed");
+    }
+    if ((rc = attach_table(ctx, b, d)) || (rc = run_search(ctx, b, PG_MODE_FAR, true))) return rc;
+    note_hint_fill(ctx);
+    pg_result tmp;
+    if ((rc = download(ctx, b, &tmp))) return rc;
+    g.r->far_off.swap(tmp.far_off);
+    g.r->far_runs.swap(tmp.far_runs);
+    g.r->rc_flag.swap(tmp.rc_flag);
+    g.r->close_last.swap(tmp.close_last);
+    g.r->close_max.swap(tmp.close_max);
+    *out = g.r;
+    g.r = nullptr;
+    g.ok = true;
+    return PG_OK;
+}
+
+int pg_debug_last_hint_stats(const pg_ctx *ctx, double *scan_ms, double *fill_ms, uint64_t *table_bytes, uint64_t *n_windows)
+{
+    if (!ctx) return PG_E_INVALID;
+    if (scan_ms) *scan_ms = ctx->hint_scan_ms;
+    if (fill_ms) *fill_ms = ctx->hint_fill_ms;
+    if (table_bytes) *table_bytes = ctx->hint_table_bytes;
+    if (n_windows) *n_windows = ctx->hint_windows;
+    return PG_OK;
+}
+
+static int far_end_from_close(pg_ctx *ctx, const pg_read_batch *reads, const uint32_t *close_last, const int16_t *close_max,
+                              const pg_windows *bd_hints, const pg_hint_table *table, pg_result **out)
+{
+    use_device(ctx);
+    if (!ctx || !reads || !out) return PG_E_INVALID;
+    *out = nullptr;
+    HintTableDev d;
+    if (int trc = upload_hint_table(ctx, table, d)) return trc;
     const size_t n = reads->n_reads;
     if (n && (!close_last || !close_max)) return fail(ctx, PG_E_INVALID, "null close-end summary");
     // MaxLenCloseEnd() of a read without UP_Close is 0: such a read is not searched (farend_searcher.cpp:60-66)
@@ -2207,7 +2448,7 @@ int pg_far_end_batch_from_close(pg_ctx *ctx, const pg_read_batch *reads, const u
         r->close_last[i] = close_last[i];
         r->close_max[i] = cmax[i];
     }
-    int rc = far_end_impl(ctx, reads, nullptr, close_last, cmax.data(), bd_hints, r);
+    int rc = far_end_impl(ctx, reads, nullptr, close_last, cmax.data(), bd_hints, r, &d);
     if (rc) {
         delete r;
         return rc;

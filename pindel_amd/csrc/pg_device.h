@@ -331,6 +331,24 @@ int pg_dd_launch(const PgDevRef *ref, const uint32_t *d_mm, const uint8_t *d_que
                  const uint64_t *d_ws, const uint32_t *d_wl, uint8_t *d_out2, uint32_t *d_scratch, uint64_t scratch_stride, uint32_t n_tasks,
                  uint32_t n_blocks, void *stream);
 int pg_pack_in_place_ok(int mode, uint32_t max_len, int small_ids, uint32_t n_reads, uint32_t plane_blocks);
+// Position-keyed hint tables (pg_hints.hip): a pg_hint_table in device memory, its windows already split into pieces of at most
+// 2^26 - 1 positions, and per cluster the longest of its windows.  pg_hint_count_scan: the reads' window counts scanned into
+// bd_off (n + 1 offsets) -- blk: scratch of pg_hint_scan_blocks(n) words; info (4 dwords): the total (64 bits), the most windows
+// of one read (saturated at 2^32 - 1), the longest window used.  pg_hint_fill: bd[bd_off[i] .. bd_off[i + 1]) = read i's windows.
+struct PgDevHintTable {
+    uint32_t n_runs;
+    const uint32_t *run_first;       // n_runs + 1
+    const uint32_t *run_cluster;     // n_runs
+    const uint64_t *cluster_off;     // n_clusters + 1
+    const uint32_t *cluster_longest; // n_clusters: positions of the cluster's longest window (0: none)
+    const pg_window *windows;
+};
+#define PG_HINT_SCAN_TILE 1024u      // counts per workgroup of the scan
+static inline uint32_t pg_hint_scan_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + 1u + PG_HINT_SCAN_TILE - 1u) / PG_HINT_SCAN_TILE); }
+int pg_hint_count_scan(const struct PgDevHintTable *t, const uint32_t *close_last, const uint16_t *close_max, uint32_t n,
+                       unsigned long long *bd_off, unsigned long long *blk, uint32_t *info, void *stream);
+int pg_hint_fill(const struct PgDevHintTable *t, const uint32_t *close_last, const uint16_t *close_max, uint32_t n,
+                 const unsigned long long *bd_off, pg_window *bd, void *stream);
 // ... then the reads on the batch's exact list that lie in the launch's range, with the reference's read-shortening semantics
 // (rec may be null; rec->kernel stays 0 when nothing was launched)
 int pg_launch_search_exact(const PgDevRef *ref, const PgDevParams *prm, const PgDevBatch *batch, int mode,
