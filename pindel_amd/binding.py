@@ -165,6 +165,7 @@ def lib():
     L.pg_device_batch_candidates.argtypes = [vp, vp, C.POINTER(C.c_double)]
     L.pg_device_batch_repack.argtypes = [vp, vp, C.POINTER(C.c_double)]
     L.pg_device_batch_pack_search.argtypes = [vp, vp]
+    L.pg_debug_last_hint_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u64), C.POINTER(u64)]
     _lib = L
     return L
 
@@ -265,6 +266,15 @@ class HintTable:
 def _hint_args(bd, hints):
     if bd is not None and hints is not None:
         raise ValueError("give either per-read windows (bd, bd_off) or a HintTable (hints), not both")
+
+
+def _windows_struct(bd, bd_off):
+    """(bd, bd_off) -> (PgWindows or None, keepalive)."""
+    if bd is None:
+        return None, ()
+    bd = np.ascontiguousarray(bd, dtype=WINDOW_DTYPE)
+    bd_off = np.ascontiguousarray(bd_off, dtype=np.uint64)
+    return PgWindows(bd_off.ctypes.data, bd.ctypes.data), (bd, bd_off)
 
 
 def _batch_struct(batch):
@@ -382,17 +392,11 @@ class Engine:
         _hint_args(bd, hints)
         s, keep = _batch_struct(batch)
         if hints is not None:
-            t = hints.struct()
-            self._check(self._L.pg_far_end_batch_table(self._h, C.byref(s), close._h, C.byref(t)))
-            close.refresh()
-            return close
-        w = None
-        if bd is not None:
-            bd = np.ascontiguousarray(bd, dtype=WINDOW_DTYPE)
-            bd_off = np.ascontiguousarray(bd_off, dtype=np.uint64)
-            w = PgWindows(bd_off.ctypes.data, bd.ctypes.data)
-        self._check(self._L.pg_far_end_batch(self._h, C.byref(s), close._h,
-                                             C.byref(w) if w is not None else None))
+            entry, h = self._L.pg_far_end_batch_table, hints.struct()
+        else:
+            entry = self._L.pg_far_end_batch
+            h, keep_w = _windows_struct(bd, bd_off)
+        self._check(entry(self._h, C.byref(s), close._h, C.byref(h) if h is not None else None))
         close.refresh()
         return close
 
@@ -404,20 +408,13 @@ class Engine:
         cl = np.ascontiguousarray(close_last, dtype=np.uint32)
         cm = np.ascontiguousarray(close_max, dtype=np.int16)
         if hints is not None:
-            t = hints.struct()
-            h = C.c_void_p()
-            self._check(self._L.pg_far_end_batch_from_close_table(self._h, C.byref(s), cl.ctypes.data, cm.ctypes.data,
-                                                                  C.byref(t), C.byref(h)))
-            return Result(h, self)
-        w = None
-        if bd is not None:
-            bd = np.ascontiguousarray(bd, dtype=WINDOW_DTYPE)
-            bd_off = np.ascontiguousarray(bd_off, dtype=np.uint64)
-            w = PgWindows(bd_off.ctypes.data, bd.ctypes.data)
-        h = C.c_void_p()
-        self._check(self._L.pg_far_end_batch_from_close(self._h, C.byref(s), cl.ctypes.data, cm.ctypes.data,
-                                                        C.byref(w) if w is not None else None, C.byref(h)))
-        return Result(h, self)
+            entry, h = self._L.pg_far_end_batch_from_close_table, hints.struct()
+        else:
+            entry = self._L.pg_far_end_batch_from_close
+            h, keep_w = _windows_struct(bd, bd_off)
+        out = C.c_void_p()
+        self._check(entry(self._h, C.byref(s), cl.ctypes.data, cm.ctypes.data, C.byref(h) if h is not None else None, C.byref(out)))
+        return Result(out, self)
 
     def search_batch(self, batch, hints=None) -> Result:
         """hints: a HintTable -- close end, lookup on the device, far end (pg_search_batch_table)."""
@@ -433,11 +430,8 @@ class Engine:
     def last_hint_stats(self):
         """measurement: the last hint-table lookup of this context -- HIP-event ms of its count + scan kernels and of its fill
         kernel, bytes of the table uploaded, windows written"""
-        L = self._L
-        L.pg_debug_last_hint_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64),
-                                               C.POINTER(C.c_uint64)]
         a, b, c, d = C.c_double(), C.c_double(), C.c_uint64(), C.c_uint64()
-        self._check(L.pg_debug_last_hint_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        self._check(self._L.pg_debug_last_hint_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return a.value, b.value, c.value, d.value
 
     @staticmethod
@@ -460,11 +454,7 @@ class Engine:
 
     def set_windows(self, dbatch, bd=None, bd_off=None):
         """Per-read BreakDancer window clusters for a device-resident batch (None detaches them)."""
-        w = None
-        if bd is not None:
-            bd = np.ascontiguousarray(bd, dtype=WINDOW_DTYPE)
-            bd_off = np.ascontiguousarray(bd_off, dtype=np.uint64)
-            w = PgWindows(bd_off.ctypes.data, bd.ctypes.data)
+        w, keep = _windows_struct(bd, bd_off)
         self._check(self._L.pg_device_batch_set_windows(self._h, dbatch, C.byref(w) if w is not None else None))
 
     def search_device(self, dbatch):

@@ -19,6 +19,7 @@
 
 #include "pg_device.h"
 #include "pg_host_plan.h"
+#include "pg_window_plan.h"
 #include "pindel_pg.h"
 
 #include <chrono>
@@ -2087,86 +2088,69 @@ int pg_search_batch_multi(pg_ctx *const *ctxs, int32_t n_ctx, const pg_read_batc
     return rc;
 }
 
-// Validates per-read window clusters and uploads them to the batch (replacing earlier ones).  Nothing the reference
-// accepts is refused: BDData::getCorrespondingSearchWindowCluster (src/bddata.cpp:949-979) has no cap on the windows of
-// a cluster -- clusters of more than 127 windows switch the launch to 64-bit candidate ids (29 bits of window index) --
-// and a window of 2^26 positions or more (the width of the position field) is searched as consecutive pieces: the
-// reduction over candidates is additive over disjoint position sets.
-// repack = false: the caller's next search launch packs the batch itself (launch_range with pack)
-static int attach_windows(pg_ctx *ctx, pg_device_batch *b, const pg_windows *bd_hints, bool repack)
+// ---------------------------------------------------------------- window hints and the far end
+// Windows are made ready by pg_window_plan (pg_window_plan.h): validated, and a window of 2^26 positions or more (the width of
+// the position field) cut into consecutive pieces -- the reduction over candidates is additive over disjoint position sets.
+static const char *window_error(PgWindowStatus s, const char *offsets_not_monotone)
 {
-    const size_t n = b->n;
+    return s == PG_WINDOWS_OFFSETS_NOT_MONOTONE ? offsets_not_monotone
+           : s == PG_WINDOWS_NULL_ARRAY         ? "null window array"
+                                                : "BreakDancer window on unknown chromosome";
+}
+
+// Every attach starts here: the batch is left without windows.
+static int clear_windows(pg_ctx *ctx, pg_device_batch *b)
+{
     if (int stale = stale_batch(ctx, b)) return stale;
     if (b->bd_off) { (void)hipFree(b->bd_off); b->bd_off = nullptr; }
     if (b->bd) { (void)hipFree(b->bd); b->bd = nullptr; }
     b->max_bd_window = 0;
     b->max_bd_cluster = 0;
+    return PG_OK;
+}
+
+// ... and passes here before it keeps any: the windows of the batch in all, and the most of one read.
+static int window_limits(pg_ctx *ctx, uint64_t in_batch, uint64_t in_cluster)
+{
+    if (pg_too_many_windows(in_batch)) return fail(ctx, PG_E_UNSUPPORTED, "more than 2^32 BreakDancer windows in a batch");
+    if (pg_too_many_in_cluster(in_cluster)) return fail(ctx, PG_E_UNSUPPORTED, "more than 2^29 windows in a BreakDancer cluster");
+    return PG_OK;
+}
+
+// Validates per-read window clusters and uploads them to the batch (replacing earlier ones).  Nothing the reference
+// accepts is refused: BDData::getCorrespondingSearchWindowCluster (src/bddata.cpp:949-979) has no cap on the windows of
+// a cluster -- clusters of more than 127 windows switch the launch to 64-bit candidate ids (29 bits of window index) --
+// and a long window is searched as pieces.  A batch without a long window is uploaded from the caller's arrays: no copy.
+// repack = false: the caller's next search launch packs the batch itself (launch_range with pack)
+static int attach_windows(pg_ctx *ctx, pg_device_batch *b, const pg_windows *bd_hints, bool repack)
+{
+    const size_t n = b->n;
+    int rc = clear_windows(ctx, b);
+    if (rc) return rc;
     if (!(bd_hints && bd_hints->offset && n)) return n && repack ? pack_reads(ctx, b, 0, b->n) : PG_OK;
-    const uint64_t nw = bd_hints->offset[n];
-    const long long piece = (1ll << PG_REL_BITS) - 1;
-    bool split = false;
-    for (size_t i = 0; i < n; i++)
-        if (bd_hints->offset[i + 1] < bd_hints->offset[i]) return fail(ctx, PG_E_INVALID, "window offsets not monotone");
-    if (nw && !bd_hints->windows) return fail(ctx, PG_E_INVALID, "null window array");
-    for (uint64_t k = 0; k < nw; k++) {
-        const pg_window &w = bd_hints->windows[k];
-        if (w.chr_id < 0 || w.chr_id >= (int)ctx->names.size())
-            return fail(ctx, PG_E_INVALID, "BreakDancer window on unknown chromosome");
-        const long long st = w.start < 0 ? (long long)w.end - 1 : w.start;
-        if ((long long)w.end - st > piece) split = true;
-    }
-    const uint64_t *off = bd_hints->offset;
-    const pg_window *win = bd_hints->windows;
-    std::vector<uint64_t> off2;
-    std::vector<pg_window> win2;
-    if (split) {
-        off2.reserve(n + 1);
-        off2.push_back(0);
-        for (size_t i = 0; i < n; i++) {
-            for (uint64_t k = bd_hints->offset[i]; k < bd_hints->offset[i + 1]; k++) {
-                const pg_window &w = bd_hints->windows[k];
-                const long long st = w.start < 0 ? (long long)w.end - 1 : w.start;       // farend_searcher.cpp:69-71
-                if ((long long)w.end - st <= piece) {
-                    win2.push_back(w);
-                    continue;
-                }
-                for (long long s0 = st; s0 < (long long)w.end; s0 += piece) {
-                    pg_window p = { w.chr_id, (int32_t)s0, (int32_t)std::min<long long>(s0 + piece, w.end) };
-                    win2.push_back(p);
-                }
-            }
-            off2.push_back(win2.size());
-        }
-        off = off2.data();
-        win = win2.data();
-    }
-    const uint64_t nw2 = off[n];
-    if (nw2 > 0xffffffffull) return fail(ctx, PG_E_UNSUPPORTED, "more than 2^32 BreakDancer windows in a batch");
-    for (size_t i = 0; i < n; i++) b->max_bd_cluster = std::max<uint64_t>(b->max_bd_cluster, off[i + 1] - off[i]);
-    if (b->max_bd_cluster >= (1ull << 29)) return fail(ctx, PG_E_UNSUPPORTED, "more than 2^29 windows in a BreakDancer cluster");
-    for (uint64_t k = 0; k < nw2; k++) {
-        const long long st = win[k].start < 0 ? (long long)win[k].end - 1 : win[k].start;
-        b->max_bd_window = std::max<int64_t>(b->max_bd_window, (long long)win[k].end - st);
-    }
-    int rc;
-    if ((rc = dev_upload(ctx, &b->bd_off, off, n + 1)) || (rc = dev_upload(ctx, &b->bd, win, (size_t)nw2))) return rc;
+    const PgWindowPlan p = pg_window_plan(bd_hints->offset, n, bd_hints->windows, (int)ctx->names.size(), false, nullptr);
+    if (p.status) return fail(ctx, PG_E_INVALID, window_error(p.status, "window offsets not monotone"));
+    const uint64_t *off = p.offsets(bd_hints->offset);
+    if ((rc = window_limits(ctx, off[n], p.largest_group))) return rc;
+    b->max_bd_cluster = p.largest_group;
+    b->max_bd_window = p.longest;
+    if ((rc = dev_upload(ctx, &b->bd_off, off, n + 1)) || (rc = dev_upload(ctx, &b->bd, p.windows(bd_hints->windows), (size_t)off[n])))
+        return rc;
     return repack ? pack_reads(ctx, b, 0, b->n) : PG_OK;
 }
 
-// Far end of `reads` given each read's close-end summary (host arrays; rc_flag may be null = the sequences are
-// already in the orientation GetCloseEnd left them in).  far_off / far_runs of `dst` are replaced.
 // A pg_hint_table validated, its windows split into pieces the position field of a candidate id can hold (once per cluster
-// window, as attach_windows does per read), in device memory for the lifetime of one call.
+// window, as attach_windows does per read), in device memory for the lifetime of one call.  The five arrays of `t` are owned here.
 struct HintTableDev {
     PgDevHintTable t{};
-    void *bufs[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
     uint64_t bytes = 0;
     HintTableDev() = default;
     HintTableDev(const HintTableDev &) = delete;
     ~HintTableDev()
     {
-        for (void *p : bufs)
-            if (p) (void)hipFree(p);
+        for (const void *p : { (const void *)t.run_first, (const void *)t.run_cluster, (const void *)t.cluster_off,
+                               (const void *)t.cluster_longest, (const void *)t.windows })
+            if (p) (void)hipFree(const_cast<void *>(p));
     }
     bool live() const { return t.n_runs != 0; }
 };
@@ -2184,59 +2168,18 @@ static int upload_hint_table(pg_ctx *ctx, const pg_hint_table *table, HintTableD
         if (table->run_first[k + 1] <= table->run_first[k]) return fail(ctx, PG_E_INVALID, "hint table: run_first not strictly ascending");
     for (uint32_t k = 0; k < nr; k++)
         if (table->run_cluster[k] >= nc) return fail(ctx, PG_E_INVALID, "hint table: run_cluster names a cluster the table does not have");
-    for (uint32_t c = 0; c < nc; c++)
-        if (table->cluster_off[c + 1] < table->cluster_off[c]) return fail(ctx, PG_E_INVALID, "hint table: cluster_off not monotone");
-    const uint64_t w0 = table->cluster_off[0], nw = table->cluster_off[nc] - w0;
-    if (nw && !table->windows) return fail(ctx, PG_E_INVALID, "null window array");
-    const long long piece = (1ll << PG_REL_BITS) - 1;
-    for (uint64_t k = 0; k < nw; k++) {
-        const pg_window &w = table->windows[w0 + k];
-        if (w.chr_id < 0 || w.chr_id >= (int)ctx->names.size()) return fail(ctx, PG_E_INVALID, "BreakDancer window on unknown chromosome");
-    }
-    std::vector<uint64_t> off(nc + (size_t)1, 0);
-    std::vector<uint32_t> longest(nc, 0u);
-    std::vector<pg_window> win;
-    win.reserve((size_t)nw);
-    for (uint32_t c = 0; c < nc; c++) {
-        long long most = 0;
-        for (uint64_t k = table->cluster_off[c]; k < table->cluster_off[c + 1]; k++) {
-            const pg_window &w = table->windows[k];
-            const long long st = w.start < 0 ? (long long)w.end - 1 : w.start;       // farend_searcher.cpp:69-71
-            if ((long long)w.end - st <= piece) {
-                most = std::max(most, (long long)w.end - st);
-                win.push_back(w);
-                continue;
-            }
-            most = piece;
-            for (long long s0 = st; s0 < (long long)w.end; s0 += piece) {
-                const pg_window q = { w.chr_id, (int32_t)s0, (int32_t)std::min<long long>(s0 + piece, w.end) };
-                win.push_back(q);
-            }
-        }
-        longest[c] = (uint32_t)most;
-        off[c + (size_t)1] = win.size();
-    }
-    uint32_t *d_first = nullptr, *d_cluster = nullptr, *d_longest = nullptr;
-    uint64_t *d_off = nullptr;
-    pg_window *d_win = nullptr;
+    std::vector<uint32_t> longest;
+    const PgWindowPlan p = pg_window_plan(table->cluster_off, nc, table->windows, (int)ctx->names.size(), true, &longest);
+    if (p.status) return fail(ctx, PG_E_INVALID, window_error(p.status, "hint table: cluster_off not monotone"));
     int rc;
-    if ((rc = dev_upload(ctx, &d_first, table->run_first, nr + (size_t)1))) return rc;
-    d.bufs[0] = d_first;
-    if ((rc = dev_upload(ctx, &d_cluster, table->run_cluster, nr))) return rc;
-    d.bufs[1] = d_cluster;
-    if ((rc = dev_upload(ctx, &d_off, off.data(), off.size()))) return rc;
-    d.bufs[2] = d_off;
-    if ((rc = dev_upload(ctx, &d_longest, longest.data(), longest.size()))) return rc;
-    d.bufs[3] = d_longest;
-    if ((rc = dev_upload(ctx, &d_win, win.data(), win.size()))) return rc;
-    d.bufs[4] = d_win;
+    if ((rc = dev_upload(ctx, const_cast<uint32_t **>(&d.t.run_first), table->run_first, nr + (size_t)1)) ||
+        (rc = dev_upload(ctx, const_cast<uint32_t **>(&d.t.run_cluster), table->run_cluster, nr)) ||
+        (rc = dev_upload(ctx, const_cast<uint64_t **>(&d.t.cluster_off), p.off.data(), p.off.size())) ||
+        (rc = dev_upload(ctx, const_cast<uint32_t **>(&d.t.cluster_longest), longest.data(), longest.size())) ||
+        (rc = dev_upload(ctx, const_cast<pg_window **>(&d.t.windows), p.win.data(), p.win.size())))
+        return rc;
     d.t.n_runs = nr;
-    d.t.run_first = d_first;
-    d.t.run_cluster = d_cluster;
-    d.t.cluster_off = d_off;
-    d.t.cluster_longest = d_longest;
-    d.t.windows = d_win;
-    d.bytes = (nr + 1ull) * 4 + (uint64_t)nr * 4 + off.size() * 8 + longest.size() * 4 + win.size() * sizeof(pg_window);
+    d.bytes = (nr + 1ull) * 4 + (uint64_t)nr * 4 + p.off.size() * 8 + longest.size() * 4 + p.win.size() * sizeof(pg_window);
     return PG_OK;
 }
 
@@ -2247,11 +2190,8 @@ static int upload_hint_table(pg_ctx *ctx, const pg_hint_table *table, HintTableD
 static int attach_table(pg_ctx *ctx, pg_device_batch *b, const HintTableDev &d)
 {
     const uint32_t n = b->n;
-    if (int stale = stale_batch(ctx, b)) return stale;
-    if (b->bd_off) { (void)hipFree(b->bd_off); b->bd_off = nullptr; }
-    if (b->bd) { (void)hipFree(b->bd); b->bd = nullptr; }
-    b->max_bd_window = 0;
-    b->max_bd_cluster = 0;
+    int rc = clear_windows(ctx, b);
+    if (rc) return rc;
     ctx->hint_fill_timed = false;
     ctx->hint_scan_ms = ctx->hint_fill_ms = 0.0;
     ctx->hint_table_bytes = d.bytes;
@@ -2259,8 +2199,7 @@ static int attach_table(pg_ctx *ctx, pg_device_batch *b, const HintTableDev &d)
     if (!n || !d.live()) return PG_OK;
     if (!ctx->evh0) HIP_TRY(ctx, hipEventCreate(&ctx->evh0));
     if (!ctx->evh1) HIP_TRY(ctx, hipEventCreate(&ctx->evh1));
-    int rc = dev_alloc(ctx, &b->bd_off, (size_t)n + 1);
-    if (rc) return rc;
+    if ((rc = dev_alloc(ctx, &b->bd_off, (size_t)n + 1))) return rc;
     uint32_t info[4] = { 0u, 0u, 0u, 0u };
     {
         DevTemps tmp(ctx, b);
@@ -2278,8 +2217,7 @@ static int attach_table(pg_ctx *ctx, pg_device_batch *b, const HintTableDev &d)
         ctx->hint_scan_ms = ms;
     }
     const uint64_t total = (uint64_t)info[0] | ((uint64_t)info[1] << 32);
-    if (total > 0xffffffffull) return fail(ctx, PG_E_UNSUPPORTED, "more than 2^32 BreakDancer windows in a batch");
-    if (info[2] >= (1u << 29)) return fail(ctx, PG_E_UNSUPPORTED, "more than 2^29 windows in a BreakDancer cluster");
+    if ((rc = window_limits(ctx, total, info[2]))) return rc;
     b->max_bd_cluster = info[2];
     b->max_bd_window = info[3];
     ctx->hint_windows = total;
@@ -2301,29 +2239,25 @@ static void note_hint_fill(pg_ctx *ctx)
     ctx->hint_fill_timed = false;
 }
 
-// table (nullable): the windows come from a hint table instead of bd_hints
-static int far_end_impl(pg_ctx *ctx, const pg_read_batch *reads, const uint8_t *rc_flag, const uint32_t *close_last,
-                        const uint16_t *close_max, const pg_windows *bd_hints, pg_result *dst, const HintTableDev *table = nullptr)
+// The hints of one far end, in either form: a table with runs is looked up on the device, per-read windows are attached
+// otherwise (both null: no hints).
+struct FarHints {
+    const pg_windows *per_read;
+    const HintTableDev *table;
+};
+
+// The far end of a batch whose close-end summary (rc_flag, close_last, close_max) is in its device arrays: the output records
+// back to that summary alone (no runs in the pool any more), the windows, the far launch -- which packs the reads -- and the
+// download.  far_off / far_runs of `dst` are replaced; summaries: rc_flag, close_last and close_max of `dst` as well.
+static int far_end_of_batch(pg_ctx *ctx, pg_device_batch *b, FarHints hints, pg_result *dst, bool summaries)
 {
-    BatchGuard g;
-    HostBuf<uint64_t> off0;
-    int rc = alloc_batch(ctx, reads, true, off0, &g.b, true);
-    if (rc) return rc;
-    pg_device_batch *b = g.b;
-    const size_t n = b->n;
-    if (n) {
-        // (the output block of the batch, rc_flag included, was zeroed by alloc_batch; the records are packed by the search launch)
-        if ((rc_flag && hipMemcpyAsync(b->rc_flag, rc_flag, n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) ||
-            hipMemcpyAsync(b->close_last, close_last, n * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(b->close_max, close_max, n * 2, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-            return fail(ctx, PG_E_DEVICE, "upload of close-end summary failed");
+    if (b->n) {
         const PgSoaOut a = soa_out(b);
         if (pg_pack_close_summary(&a, b->out_rec, b->n, ctx->stream) != 0)
             return fail(ctx, PG_E_DEVICE, "close-end summary pack kernel failed");
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess)       // the host arrays may be pageable temporaries
-            return fail(ctx, PG_E_DEVICE, "upload of close-end summary failed");
     }
-    if ((rc = table && table->live() ? attach_table(ctx, b, *table) : attach_windows(ctx, b, bd_hints, false)) ||
+    int rc;
+    if ((rc = hints.table && hints.table->live() ? attach_table(ctx, b, *hints.table) : attach_windows(ctx, b, hints.per_read, false)) ||
         (rc = run_search(ctx, b, PG_MODE_FAR, true)))
         return rc;
     note_hint_fill(ctx);
@@ -2331,22 +2265,38 @@ static int far_end_impl(pg_ctx *ctx, const pg_read_batch *reads, const uint8_t *
     if ((rc = download(ctx, b, &tmp))) return rc;
     dst->far_off.swap(tmp.far_off);
     dst->far_runs.swap(tmp.far_runs);
+    if (summaries) {
+        dst->rc_flag.swap(tmp.rc_flag);
+        dst->close_last.swap(tmp.close_last);
+        dst->close_max.swap(tmp.close_max);
+    }
+    return PG_OK;
+}
+
+// Far end of `reads` given each read's close-end summary (host arrays; rc_flag may be null = the sequences are
+// already in the orientation GetCloseEnd left them in).  far_off / far_runs of `dst` are replaced.
+static int far_end_impl(pg_ctx *ctx, const pg_read_batch *reads, const uint8_t *rc_flag, const uint32_t *close_last,
+                        const uint16_t *close_max, FarHints hints, pg_result *dst)
+{
+    BatchGuard g;
+    HostBuf<uint64_t> off0;
+    int rc = alloc_batch(ctx, reads, true, off0, &g.b, true);
+    if (rc) return rc;
+    pg_device_batch *b = g.b;
+    const size_t n = b->n;
+    // (the output block of the batch, rc_flag included, was zeroed by alloc_batch; the records are packed by the search launch)
+    if (n && ((rc_flag && hipMemcpyAsync(b->rc_flag, rc_flag, n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) ||
+              hipMemcpyAsync(b->close_last, close_last, n * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+              hipMemcpyAsync(b->close_max, close_max, n * 2, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+              hipStreamSynchronize(ctx->stream) != hipSuccess))       // the host arrays may be pageable temporaries
+        return fail(ctx, PG_E_DEVICE, "upload of close-end summary failed");
+    if ((rc = far_end_of_batch(ctx, b, hints, dst, false))) return rc;
     g.ok = true;
     return PG_OK;
 }
 
-int pg_far_end_batch(pg_ctx *ctx, const pg_read_batch *reads, pg_result *close, const pg_windows *bd_hints)
-{
-    use_device(ctx);
-    if (!ctx || !reads || !close) return PG_E_INVALID;
-    if (close->n != reads->n_reads) return fail(ctx, PG_E_INVALID, "close result does not belong to these reads");
-    const size_t n = reads->n_reads;
-    if (n && (close->rc_flag.size() != n || close->close_last.size() != n || close->close_max.size() != n))
-        return fail(ctx, PG_E_INVALID, "close result carries no close-end summary");
-    return far_end_impl(ctx, reads, close->rc_flag.data(), close->close_last.data(), close->close_max.data(), bd_hints, close);
-}
-
-int pg_far_end_batch_table(pg_ctx *ctx, const pg_read_batch *reads, pg_result *close, const pg_hint_table *table)
+// pg_far_end_batch and pg_far_end_batch_table: at most one of bd_hints and table is given
+static int far_end_batch(pg_ctx *ctx, const pg_read_batch *reads, pg_result *close, const pg_windows *bd_hints, const pg_hint_table *table)
 {
     use_device(ctx);
     if (!ctx || !reads || !close) return PG_E_INVALID;
@@ -2356,11 +2306,51 @@ int pg_far_end_batch_table(pg_ctx *ctx, const pg_read_batch *reads, pg_result *c
         return fail(ctx, PG_E_INVALID, "close result carries no close-end summary");
     HintTableDev d;
     if (int rc = upload_hint_table(ctx, table, d)) return rc;
-    return far_end_impl(ctx, reads, close->rc_flag.data(), close->close_last.data(), close->close_max.data(), nullptr, close, &d);
+    return far_end_impl(ctx, reads, close->rc_flag.data(), close->close_last.data(), close->close_max.data(), { bd_hints, &d }, close);
+}
+
+int pg_far_end_batch(pg_ctx *ctx, const pg_read_batch *reads, pg_result *close, const pg_windows *bd_hints)
+{
+    return far_end_batch(ctx, reads, close, bd_hints, nullptr);
+}
+
+int pg_far_end_batch_table(pg_ctx *ctx, const pg_read_batch *reads, pg_result *close, const pg_hint_table *table)
+{
+    return far_end_batch(ctx, reads, close, nullptr, table);
 }
 
 static int far_end_from_close(pg_ctx *ctx, const pg_read_batch *reads, const uint32_t *close_last, const int16_t *close_max,
-                              const pg_windows *bd_hints, const pg_hint_table *table, pg_result **out);
+                              const pg_windows *bd_hints, const pg_hint_table *table, pg_result **out)
+{
+    use_device(ctx);
+    if (!ctx || !reads || !out) return PG_E_INVALID;
+    *out = nullptr;
+    HintTableDev d;
+    if (int trc = upload_hint_table(ctx, table, d)) return trc;
+    const size_t n = reads->n_reads;
+    if (n && (!close_last || !close_max)) return fail(ctx, PG_E_INVALID, "null close-end summary");
+    // MaxLenCloseEnd() of a read without UP_Close is 0: such a read is not searched (farend_searcher.cpp:60-66)
+    std::vector<uint16_t> cmax(n);
+    for (size_t i = 0; i < n; i++) cmax[i] = close_max[i] > 0 ? (uint16_t)close_max[i] : (uint16_t)0;
+    pg_result *r = new pg_result();
+    r->n = (uint32_t)n;
+    if (!r->close_off.assign(n + 1, 0) || !r->rc_flag.assign(n, 0) || !r->close_last.resize(n) || !r->close_max.resize(n)) {
+        delete r;
+        return fail(ctx, PG_E_NOMEM, "pinned host memory for the result");
+    }
+    r->close_runs.resize(0);
+    for (size_t i = 0; i < n; i++) {
+        r->close_last[i] = close_last[i];
+        r->close_max[i] = cmax[i];
+    }
+    int rc = far_end_impl(ctx, reads, nullptr, close_last, cmax.data(), { bd_hints, &d }, r);
+    if (rc) {
+        delete r;
+        return rc;
+    }
+    *out = r;
+    return PG_OK;
+}
 
 int pg_far_end_batch_from_close(pg_ctx *ctx, const pg_read_batch *reads, const uint32_t *close_last,
                                 const int16_t *close_max, const pg_windows *bd_hints, pg_result **out)
@@ -2389,25 +2379,9 @@ int pg_search_batch_table(pg_ctx *ctx, const pg_read_batch *reads, const pg_hint
     BatchGuard g;
     HostBuf<uint64_t> off0;
     if ((rc = alloc_batch(ctx, reads, true, off0, &g.b, true))) return rc;
-    pg_device_batch *b = g.b;
-    if ((rc = run_search(ctx, b, PG_MODE_CLOSE, true))) return rc;
+    if ((rc = run_search(ctx, g.b, PG_MODE_CLOSE, true))) return rc;
     g.r = new pg_result();
-    if ((rc = download(ctx, b, g.r, false))) return rc;
-    if (b->n) {
-        // the output records back to the summary alone (no runs in the pool any more), as pg_far_end_batch starts from
-        const PgSoaOut a = soa_out(b);
-        if (pg_pack_close_summary(&a, b->out_rec, b->n, ctx->stream) != 0)
-            return fail(ctx, PG_E_DEVICE, "close-end summary pack kernel failed");
-    }
-    if ((rc = attach_table(ctx, b, d)) || (rc = run_search(ctx, b, PG_MODE_FAR, true))) return rc;
-    note_hint_fill(ctx);
-    pg_result tmp;
-    if ((rc = download(ctx, b, &tmp))) return rc;
-    g.r->far_off.swap(tmp.far_off);
-    g.r->far_runs.swap(tmp.far_runs);
-    g.r->rc_flag.swap(tmp.rc_flag);
-    g.r->close_last.swap(tmp.close_last);
-    g.r->close_max.swap(tmp.close_max);
+    if ((rc = download(ctx, g.b, g.r, false)) || (rc = far_end_of_batch(ctx, g.b, { nullptr, &d }, g.r, true))) return rc;
     *out = g.r;
     g.r = nullptr;
     g.ok = true;
@@ -2421,39 +2395,6 @@ int pg_debug_last_hint_stats(const pg_ctx *ctx, double *scan_ms, double *fill_ms
     if (fill_ms) *fill_ms = ctx->hint_fill_ms;
     if (table_bytes) *table_bytes = ctx->hint_table_bytes;
     if (n_windows) *n_windows = ctx->hint_windows;
-    return PG_OK;
-}
-
-static int far_end_from_close(pg_ctx *ctx, const pg_read_batch *reads, const uint32_t *close_last, const int16_t *close_max,
-                              const pg_windows *bd_hints, const pg_hint_table *table, pg_result **out)
-{
-    use_device(ctx);
-    if (!ctx || !reads || !out) return PG_E_INVALID;
-    *out = nullptr;
-    HintTableDev d;
-    if (int trc = upload_hint_table(ctx, table, d)) return trc;
-    const size_t n = reads->n_reads;
-    if (n && (!close_last || !close_max)) return fail(ctx, PG_E_INVALID, "null close-end summary");
-    // MaxLenCloseEnd() of a read without UP_Close is 0: such a read is not searched (farend_searcher.cpp:60-66)
-    std::vector<uint16_t> cmax(n);
-    for (size_t i = 0; i < n; i++) cmax[i] = close_max[i] > 0 ? (uint16_t)close_max[i] : (uint16_t)0;
-    pg_result *r = new pg_result();
-    r->n = (uint32_t)n;
-    if (!r->close_off.assign(n + 1, 0) || !r->rc_flag.assign(n, 0) || !r->close_last.resize(n) || !r->close_max.resize(n)) {
-        delete r;
-        return fail(ctx, PG_E_NOMEM, "pinned host memory for the result");
-    }
-    r->close_runs.resize(0);
-    for (size_t i = 0; i < n; i++) {
-        r->close_last[i] = close_last[i];
-        r->close_max[i] = cmax[i];
-    }
-    int rc = far_end_impl(ctx, reads, nullptr, close_last, cmax.data(), bd_hints, r, &d);
-    if (rc) {
-        delete r;
-        return rc;
-    }
-    *out = r;
     return PG_OK;
 }
 

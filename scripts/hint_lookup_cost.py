@@ -10,7 +10,7 @@ reference sequence is synthetic at chr20's size.  Half of the reads have their c
 a caller looks for), the rest anywhere in the window.  The two ways alternate, REPEATS times after one warm-up each; medians are
 reported, and the results of the two must be identical.  Prints one JSON line.
 
-    python scripts/hint_lookup_cost.py [--reads 1000000] [--repeats 5]
+    python scripts/hint_lookup_cost.py [--reads 1000000] [--repeats 5] [--lib pindel_amd/libpindel_pg_parent.so]
 """
 import argparse
 import gzip
@@ -39,7 +39,10 @@ def main():
     ap.add_argument("--reads", type=int, default=1_000_000)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--read-len", type=int, default=100)
+    ap.add_argument("--lib", help="measure this build of the library (binding.use_library)")
     a = ap.parse_args()
+    if a.lib:
+        binding.use_library(os.path.abspath(a.lib))
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("hint_lookup_cost.py measures on the GPU: none is visible")
