@@ -277,6 +277,45 @@ int  pg_device_batch_algorithmic_bytes(pg_ctx *ctx, pg_device_batch *b, double *
  * comparison in the last search of this batch -- what a repeat-rich reference drives up. */
 int  pg_device_batch_candidates(pg_ctx *ctx, pg_device_batch *b, double *n_candidates);
 
+/* ---- device buffers in and out: reference, reads and results in the memory of the ctx's GPU -----------------------------
+ * For a caller whose data is already in HBM (a GPU decoder, a torch pipeline): the three host round trips of the
+ * device-resident path have a sibling that takes or fills device memory.  Common rules:
+ *   - Synchronous, like the rest of the ABI: the caller makes sure its inputs are complete (its own streams have finished
+ *     writing them) before the call; when a call returns, everything the library wrote is complete.  There is no stream argument.
+ *   - Inputs are copied, device to device, into buffers of the library's own: the caller owns its buffers and may release them
+ *     when the call returns.  Results are written into buffers the caller allocated.
+ *   - Every non-null pointer is checked before anything is launched: it must be device memory of the ctx's own GPU, aligned for
+ *     its element type, and the bytes the library will touch must lie inside its allocation -- otherwise PG_E_INVALID, with
+ *     pg_last_error naming the array.  A host pointer ends in a status code, never in a fault.  (seq and the run buffers are
+ *     checked once their size is known: after the measurement / the first pass.)  A pointer may point INTO an allocation.
+ *   - Nothing is launched for an empty batch. */
+/* pg_load_reference with the bases in device memory.  names, len_padded and the array d_seq_padded itself are host memory;
+ * d_seq_padded[c] points to len_padded[c] ASCII bytes on the device, spacers included, with any alignment.  The planes are
+ * built on the device and are bit for bit those of pg_load_reference: A C G T in upper case, every other byte value is N.
+ * The same argument checks and status codes; the reference counts as reloaded (device batches uploaded before are refused).
+ * pg_reference_fetch and pg_reference_save_packed work as after a host load: the first of them copies the planes to the host. */
+int  pg_load_reference_device(pg_ctx *ctx, int32_t n_chr, const char *const *names,
+                              const uint8_t *const *d_seq_padded, const uint64_t *len_padded);
+/* pg_device_batch_upload with the batch in device memory: d_reads is a host struct whose six array members are device
+ * pointers.  The reads are validated and measured on the device in one pass; the status codes and pg_last_error texts are
+ * those of pg_device_batch_upload for the same batch (of several bad reads the one with the lowest index is reported), and the
+ * result is an ordinary pg_device_batch: set_windows, search, pack_search, repack, download and the diagnostics take it. */
+int  pg_device_batch_upload_device(pg_ctx *ctx, const pg_read_batch *d_reads, pg_device_batch **out);
+/* Where pg_device_batch_download_device puts a searched batch: device buffers of the caller, laid out as pg_result_view. */
+typedef struct {
+    uint64_t *close_off;  pg_run *close_runs;  uint64_t close_cap;   /* n+1 offsets; capacity in runs */
+    uint64_t *far_off;    pg_run *far_runs;    uint64_t far_cap;
+    uint8_t  *rc_flag;    uint32_t *close_last; int16_t *close_max;  /* n each; any of the three may be NULL */
+} pg_device_result;
+/* The number of runs a download of the batch holds: close_off[n] and far_off[n]. */
+int  pg_device_batch_result_sizes(pg_ctx *ctx, pg_device_batch *b, uint64_t *n_close_runs, uint64_t *n_far_runs);
+/* pg_device_batch_download into the caller's device buffers: runs and offsets are gathered straight into them (off[n]
+ * included; a list without runs gets zeroed offsets and its run pointer may be NULL), only a few bytes per 2^20 reads come
+ * to the host.  A capacity below the list's total is PG_E_INVALID and nothing is written.  close_last / close_max are
+ * UP_Close.back()'s AbsLoc / LengthStr as pg_far_end_batch_from_close takes them.  The batch stays searchable and
+ * downloadable, by either download. */
+int  pg_device_batch_download_device(pg_ctx *ctx, pg_device_batch *b, const pg_device_result *dst);
+
 /* -q (dispersed duplications): per item i, contains_subseq_any_strand(query_i, window_i, 15) of Pindel's MEI search
  * (src/search_MEI_util.cpp:188-351, bit-exact), where query_i = query[query_off[i] .. query_off[i+1]) (at most
  * PG_MAX_READ_LEN bases) and window_i = the loaded chromosome chr_id[i] at padded (AbsLoc) positions

@@ -51,6 +51,13 @@ class PgHintTable(C.Structure):
                 ("n_clusters", C.c_uint32), ("cluster_off", C.c_void_p), ("windows", C.c_void_p)]
 
 
+class PgDeviceResult(C.Structure):
+    _fields_ = [
+        ("close_off", C.c_void_p), ("close_runs", C.c_void_p), ("close_cap", C.c_uint64),
+        ("far_off", C.c_void_p), ("far_runs", C.c_void_p), ("far_cap", C.c_uint64),
+        ("rc_flag", C.c_void_p), ("close_last", C.c_void_p), ("close_max", C.c_void_p)]
+
+
 class PgResultView(C.Structure):
     _fields_ = [
         ("n_reads", C.c_uint32), ("close_off", C.POINTER(C.c_uint64)), ("close_runs", C.c_void_p),
@@ -78,7 +85,8 @@ EXPORTS = [
     "pg_search_batch", "pg_search_batch_multi", "pg_result_view_get", "pg_result_free", "pg_expand_runs",
     "pg_device_batch_upload", "pg_device_batch_set_windows", "pg_device_batch_search", "pg_device_batch_download",
     "pg_device_batch_free", "pg_last_search_stats", "pg_device_batch_algorithmic_bytes",
-    "pg_device_batch_candidates", "pg_device_batch_repack", "pg_device_batch_pack_search", "pg_dd_contains_batch"]
+    "pg_device_batch_candidates", "pg_device_batch_repack", "pg_device_batch_pack_search", "pg_dd_contains_batch",
+    "pg_load_reference_device", "pg_device_batch_upload_device", "pg_device_batch_result_sizes", "pg_device_batch_download_device"]
 
 
 def build(force: bool = False) -> str:
@@ -166,6 +174,10 @@ def lib():
     L.pg_device_batch_repack.argtypes = [vp, vp, C.POINTER(C.c_double)]
     L.pg_device_batch_pack_search.argtypes = [vp, vp]
     L.pg_debug_last_hint_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u64), C.POINTER(u64)]
+    L.pg_load_reference_device.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(u64)]
+    L.pg_device_batch_upload_device.argtypes = [vp, C.POINTER(PgReadBatch), C.POINTER(vp)]
+    L.pg_device_batch_result_sizes.argtypes = [vp, vp, C.POINTER(u64), C.POINTER(u64)]
+    L.pg_device_batch_download_device.argtypes = [vp, vp, C.POINTER(PgDeviceResult)]
     _lib = L
     return L
 
@@ -290,6 +302,57 @@ def _batch_struct(batch):
     return s, (seq, off, st, pos, isz, cid)
 
 
+# ---- torch tensors in device memory (Engine.load_reference_tensors / upload_tensors / download_tensors).  The checks are plain
+# functions of the tensors' attributes: they need no GPU and do not import torch (the methods that call them do).
+# seq_off and the result offsets travel as int64: the same bits as the ABI's uint64 below 2^63 (torch has no full uint64);
+# close_last likewise as int32.
+READ_TENSOR_DTYPES = (("seq", ("torch.uint8",)), ("seq_off", ("torch.int64", "torch.uint64")), ("anchor_strand", ("torch.uint8",)),
+                      ("anchor_pos", ("torch.int32",)), ("insert_size", ("torch.int16",)), ("chr_id", ("torch.int32",)))
+
+
+def check_tensor(name, t, dtypes, device, length=None):
+    """ValueError unless t is a 1-D contiguous tensor of one of `dtypes` (their str(), e.g. "torch.uint8") on `device` (its str(),
+    e.g. "cuda:0"), with `length` elements when one is given."""
+    if not hasattr(t, "dtype") or not hasattr(t, "is_contiguous") or not hasattr(t, "data_ptr"):
+        raise ValueError(f"{name}: a torch tensor is expected, got {type(t).__name__}")
+    if str(t.dtype) not in dtypes:
+        raise ValueError(f"{name}: dtype {t.dtype}, expected {' or '.join(dtypes)}")
+    if t.dim() != 1:
+        raise ValueError(f"{name}: {t.dim()} dimensions, expected 1")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: not contiguous")
+    if str(t.device) != device:
+        raise ValueError(f"{name}: on {t.device}, expected {device}")
+    if length is not None and t.numel() != length:
+        raise ValueError(f"{name}: {t.numel()} elements, expected {length}")
+
+
+def check_read_tensors(seq, seq_off, anchor_strand, anchor_pos, insert_size, chr_id, device):
+    """The wrapper's checks of upload_tensors, before the library is called; returns the number of reads."""
+    if not hasattr(seq_off, "numel") or seq_off.numel() < 1:
+        raise ValueError("seq_off: n + 1 offsets are expected, at least one")
+    n = seq_off.numel() - 1
+    given = dict(seq=seq, seq_off=seq_off, anchor_strand=anchor_strand, anchor_pos=anchor_pos, insert_size=insert_size, chr_id=chr_id)
+    for name, dtypes in READ_TENSOR_DTYPES:
+        check_tensor(name, given[name], dtypes, device, None if name == "seq" else n + 1 if name == "seq_off" else n)
+    last = int(seq_off[-1].item())
+    if seq.numel() < last:
+        raise ValueError(f"seq: {seq.numel()} bases, shorter than seq_off[-1] = {last}")
+    return n
+
+
+def check_reference_tensors(chroms, device):
+    """The wrapper's checks of load_reference_tensors: [(name, uint8 tensor)]."""
+    for nm, t in chroms:
+        check_tensor(f"chromosome {nm}", t, ("torch.uint8",), device)
+
+
+def runs_from_tensor(t) -> np.ndarray:
+    """The uint8[n_runs, 12] tensor of download_tensors as a RUN_DTYPE array (a CPU copy)."""
+    a = np.ascontiguousarray(t.detach().cpu().numpy())
+    return a.reshape(-1).view(RUN_DTYPE)
+
+
 class Engine:
     """One pg_ctx = one GPU."""
 
@@ -314,6 +377,8 @@ class Engine:
             raise PgError(rc, "pg_create failed (no usable HIP device?)" if rc == PG_E_DEVICE else "pg_create")
         self._h = h
         self._L = L
+        self._device = device
+        self._batch_n = {}       # reads of every live device batch, by handle (download_tensors sizes its tensors from it)
 
     def _check(self, rc):
         if rc:
@@ -450,7 +515,79 @@ class Engine:
         s, keep = _batch_struct(batch)
         h = C.c_void_p()
         self._check(self._L.pg_device_batch_upload(self._h, C.byref(s), C.byref(h)))
+        self._batch_n[h.value] = s.n_reads
         return h
+
+    # ---- device memory in and out (torch tensors on this engine's GPU)
+    def _torch_ready(self):
+        """torch, this engine's device string, after waiting for torch's current stream on it (the library's calls are synchronous
+        and run on streams of its own: what the caller queued must have finished)."""
+        import torch
+        torch.cuda.current_stream(self._device).synchronize()
+        return torch, f"cuda:{self._device}"
+
+    def load_reference_tensors(self, chroms):
+        """load_reference with the padded chromosomes as uint8 tensors on the GPU: [(name, tensor)] (pg_load_reference_device).
+        A tensor may be a slice of a larger one."""
+        _, dev = self._torch_ready()
+        check_reference_tensors(chroms, dev)
+        n = len(chroms)
+        names = (C.c_char_p * n)(*[nm.encode() for nm, _ in chroms])
+        ptrs = (C.c_void_p * n)(*[t.data_ptr() for _, t in chroms])
+        lens = (C.c_uint64 * n)(*[t.numel() for _, t in chroms])
+        self._check(self._L.pg_load_reference_device(self._h, n, names, ptrs, lens))
+
+    def upload_tensors(self, seq, seq_off, anchor_strand, anchor_pos, insert_size, chr_id):
+        """upload with the batch's six arrays as tensors on the GPU (pg_device_batch_upload_device); the library copies them."""
+        _, dev = self._torch_ready()
+        n = check_read_tensors(seq, seq_off, anchor_strand, anchor_pos, insert_size, chr_id, dev)
+        s = PgReadBatch(n, seq.data_ptr() if seq.numel() else None, seq_off.data_ptr(), anchor_strand.data_ptr(),
+                        anchor_pos.data_ptr(), insert_size.data_ptr(), chr_id.data_ptr())
+        h = C.c_void_p()
+        self._check(self._L.pg_device_batch_upload_device(self._h, C.byref(s), C.byref(h)))
+        self._batch_n[h.value] = n
+        return h
+
+    def result_sizes(self, dbatch):
+        """(close runs, far runs) a download of the searched batch holds (pg_device_batch_result_sizes)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._check(self._L.pg_device_batch_result_sizes(self._h, dbatch, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def download_into(self, dbatch, close_off, close_runs, far_off, far_runs, rc_flag=None, close_last=None, close_max=None):
+        """pg_device_batch_download_device into tensors of the caller's: offsets int64[n + 1], runs uint8[capacity, 12], the
+        optional summaries uint8 / int32 / int16 [n]."""
+        _, dev = self._torch_ready()
+        n = self._batch_n[dbatch.value]
+        check_tensor("close_off", close_off, ("torch.int64", "torch.uint64"), dev, n + 1)
+        check_tensor("far_off", far_off, ("torch.int64", "torch.uint64"), dev, n + 1)
+        for name, t in (("close_runs", close_runs), ("far_runs", far_runs)):
+            if str(t.dtype) != "torch.uint8" or t.dim() != 2 or t.shape[1] != 12 or not t.is_contiguous() or str(t.device) != dev:
+                raise ValueError(f"{name}: a contiguous uint8[capacity, 12] tensor on {dev} is expected")
+        for name, t, dt in (("rc_flag", rc_flag, "torch.uint8"), ("close_last", close_last, "torch.int32"), ("close_max", close_max, "torch.int16")):
+            if t is not None:
+                check_tensor(name, t, (dt,), dev, n)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None and t.numel() else None
+        d = PgDeviceResult(close_off.data_ptr(), ptr(close_runs), close_runs.shape[0], far_off.data_ptr(), ptr(far_runs),
+                           far_runs.shape[0], ptr(rc_flag), ptr(close_last), ptr(close_max))
+        self._check(self._L.pg_device_batch_download_device(self._h, dbatch, C.byref(d)))
+
+    def download_tensors(self, dbatch, summaries=True):
+        """download with the result staying on the GPU: a dict of tensors on this engine's device -- close_off / far_off int64[n + 1],
+        close_runs / far_runs uint8[n_runs, 12] (runs_from_tensor views a CPU copy as RUN_DTYPE), and unless summaries is False
+        rc_flag uint8[n], close_last int32[n], close_max int16[n]."""
+        torch, dev = self._torch_ready()
+        n = self._batch_n[dbatch.value]
+        nc, nf = self.result_sizes(dbatch)
+        out = dict(close_off=torch.empty(n + 1, dtype=torch.int64, device=dev), close_runs=torch.empty((nc, 12), dtype=torch.uint8, device=dev),
+                   far_off=torch.empty(n + 1, dtype=torch.int64, device=dev), far_runs=torch.empty((nf, 12), dtype=torch.uint8, device=dev))
+        if summaries:
+            out.update(rc_flag=torch.empty(n, dtype=torch.uint8, device=dev), close_last=torch.empty(n, dtype=torch.int32, device=dev),
+                       close_max=torch.empty(n, dtype=torch.int16, device=dev))
+        self.download_into(dbatch, **out)
+        return out
 
     def set_windows(self, dbatch, bd=None, bd_off=None):
         """Per-read BreakDancer window clusters for a device-resident batch (None detaches them)."""
@@ -512,6 +649,7 @@ class Engine:
         return Result(h, self)
 
     def free_device_batch(self, dbatch):
+        self._batch_n.pop(dbatch.value, None)
         self._L.pg_device_batch_free(self._h, dbatch)
 
     def last_stats(self):

@@ -225,7 +225,11 @@ struct pg_ctx {
     std::vector<std::string> names;
     std::vector<uint64_t> comp_size;
     std::vector<uint64_t> word_off;   // index of the word holding AbsLoc 0
-    std::vector<uint32_t> h_lo, h_hi, h_nn;
+    // host mirror of the planes: only pg_reference_fetch and pg_reference_save_packed read it.  A host load fills it on its way
+    // to the device; after pg_load_reference_device it is empty (mirror_ok false) until one of the two asks (host_mirror)
+    mutable std::vector<uint32_t> h_lo, h_hi, h_nn;
+    mutable bool mirror_ok = false;
+    uint64_t plane_words = 0;          // words of each plane in HBM
     uint32_t *d_lo = nullptr, *d_hi = nullptr, *d_nn = nullptr;
     uint64_t *d_word_off = nullptr;
     uint32_t *d_chr_size = nullptr;
@@ -319,7 +323,10 @@ int fail(pg_ctx *ctx, int code, const std::string &msg)
     return code;
 }
 
-#define HIP_TRY(ctx, call)                                                                   \
+// (the device-buffer entries: a caller's pointer, checked before anything is launched -- defined with them, below)
+int check_device_ptr(pg_ctx *ctx, const void *p, size_t bytes, size_t align, const char *what);
+
+#define HIP_TRY(ctx, call)                                                                  \
     do {                                                                                     \
         hipError_t e_ = (call);                                                              \
         if (e_ != hipSuccess)                                                                \
@@ -398,6 +405,8 @@ void free_reference(pg_ctx *ctx)
     ctx->h_lo.clear();
     ctx->h_hi.clear();
     ctx->h_nn.clear();
+    ctx->mirror_ok = false;
+    ctx->plane_words = 0;
 }
 
 void use_device(const pg_ctx *ctx)
@@ -597,6 +606,8 @@ void host_ranges(size_t n, Fn fn)
 // max_isz (nullable): largest insert size of the batch
 // off_out (nullable, n + 1 entries): the read offsets rebased to 0, written in the same pass
 // uniform_len (nullable): the one length all reads have, 0 when they differ (or there are none)
+int batch_levels(pg_ctx *ctx, uint32_t ml, uint32_t *levels);
+int validation_failure(pg_ctx *ctx, int code);
 int validate_and_measure(pg_ctx *ctx, const pg_read_batch *reads, uint32_t *max_len, uint32_t *levels, int32_t *max_isz = nullptr,
                          uint64_t *off_out = nullptr, uint32_t *uniform_len = nullptr)
 {
@@ -655,23 +666,12 @@ int validate_and_measure(pg_ctx *ctx, const pg_read_batch *reads, uint32_t *max_
             all.code = p.code;
         }
     });
-    switch (all.code) {
-    case 1: return fail(ctx, PG_E_INVALID, "seq_off not monotone");
-    case 2: return fail(ctx, PG_E_READ_TOO_LONG, "read longer than 499 bases");
-    case 3: return fail(ctx, PG_E_INVALID, "chr_id out of range");
-    case 4: return fail(ctx, PG_E_INVALID, "anchor position/insert size reach outside the padded chromosome");
-    default: break;
-    }
+    if (all.code) return validation_failure(ctx, all.code);
     const uint32_t ml = all.ml;
     *max_len = ml;
     if (max_isz) *max_isz = all.isz;
     if (uniform_len) *uniform_len = all.ul == NO_LEN || all.ul == MIXED ? 0u : (uint32_t)all.ul;
-    uint32_t lv = ctx->mm[ml] + (uint32_t)ctx->prm.additional_mismatch + 1;
-    for (uint32_t l = 0; l <= ml; l++)
-        lv = std::max<uint32_t>(lv, ctx->mm[l] + (uint32_t)ctx->prm.additional_mismatch + 1);
-    if (lv > PG_MAX_LEVELS) return fail(ctx, PG_E_UNSUPPORTED, "more than 32 mismatch levels");
-    *levels = lv;
-    return PG_OK;
+    return batch_levels(ctx, ml, levels);
 }
 
 // Reads per chunk of download() (PG_HOST_CHUNK: several chunks on a small batch), and the bytes of its device temporaries but
@@ -683,32 +683,58 @@ static size_t download_scratch_bytes(size_t n)
     return 3 * n * 8 + n_chunks * ((chunk + 255) / 256) * 8 + n_chunks * 64 + 5 * 512;
 }
 
-// Validates the batch and allocates its device buffers.  copy = true also copies the inputs
-// (synchronously); otherwise the caller streams them in (search_host).  off = read offsets rebased to 0.
-// use_arena: carve the buffers out of the ctx arena (host-path calls: the batch dies with the call).
-// plan (search_host; needs use_arena): the arena gets room for the delivery buffers the caller takes behind the batch, and
-// `off` room for the one-copy upload (pg_host_plan.h).
 PgSoaIn soa_in(const pg_ctx *ctx, const pg_device_batch *b);
-int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint64_t> &off, pg_device_batch **out,
-                bool use_arena = false, const PgHostPlan *plan = nullptr)
-{
-    uint32_t max_len = 0, levels = 0, uniform_len = 0;
+
+// What the allocation needs to know about a validated batch: measured on host threads (validate_and_measure) or by the
+// measurement kernel of pg_device_batch_upload_device.
+struct BatchMeasure {
+    uint32_t n = 0, max_len = 1, levels = 0, uniform_len = 0;
     int32_t max_isz = 0;
-    if (!off.resize(plan ? plan->off_words : (reads ? reads->n_reads : 0) + (size_t)1)) return fail(ctx, PG_E_NOMEM, "host memory for the read offsets");
-    int rc = validate_and_measure(ctx, reads, &max_len, &levels, &max_isz, off.data(), &uniform_len);
-    if (rc) return rc;
+    uint64_t nseq = 0;                 // bases of the batch: seq_off[n] - seq_off[0]
+};
+
+// The mismatch levels a batch whose longest read has max_len bases needs (PG_E_UNSUPPORTED beyond PG_MAX_LEVELS).
+int batch_levels(pg_ctx *ctx, uint32_t ml, uint32_t *levels)
+{
+    uint32_t lv = ctx->mm[ml] + (uint32_t)ctx->prm.additional_mismatch + 1;
+    for (uint32_t l = 0; l <= ml; l++)
+        lv = std::max<uint32_t>(lv, ctx->mm[l] + (uint32_t)ctx->prm.additional_mismatch + 1);
+    if (lv > PG_MAX_LEVELS) return fail(ctx, PG_E_UNSUPPORTED, "more than 32 mismatch levels");
+    *levels = lv;
+    return PG_OK;
+}
+
+// The text and status of a validation code (validate_and_measure and its device twin report the same ones).
+int validation_failure(pg_ctx *ctx, int code)
+{
+    switch (code) {
+    case 1: return fail(ctx, PG_E_INVALID, "seq_off not monotone");
+    case 2: return fail(ctx, PG_E_READ_TOO_LONG, "read longer than 499 bases");
+    case 3: return fail(ctx, PG_E_INVALID, "chr_id out of range");
+    case 4: return fail(ctx, PG_E_INVALID, "anchor position/insert size reach outside the padded chromosome");
+    default: return PG_OK;
+    }
+}
+
+// Allocates the device buffers of a measured batch: the one item table of both upload entries.  No input is copied here.
+// seq_off_ready (hipMalloc'd batches only): the batch's seq_off buffer, already allocated and filled (the measurement kernel of
+// the device upload writes the rebased offsets straight into it); the batch takes it over, also when this call fails.
+int alloc_batch_buffers(pg_ctx *ctx, const BatchMeasure &m, pg_device_batch **out, bool use_arena, const PgHostPlan *plan,
+                        uint64_t *seq_off_ready = nullptr)
+{
     pg_device_batch *b = new pg_device_batch();
-    b->n = reads->n_reads;
+    b->n = m.n;
     // the batch is bound to the reference it was VALIDATED against (anchor windows, chromosome ids): stamped here and nowhere else --
     // a repack or a new set of windows after a reload of the reference is refused, not re-stamped (stale_batch)
     b->ref_epoch = ctx->ref_epoch;
-    b->max_len = max_len;
-    b->uniform_len = uniform_len;
-    b->levels = levels;
-    b->max_isz = max_isz;
+    b->max_len = m.max_len;
+    b->uniform_len = m.uniform_len;
+    b->levels = m.levels;
+    b->max_isz = m.max_isz;
+    b->seq_off = seq_off_ready;
+    const uint32_t max_len = m.max_len;
     const size_t n = b->n;
-    const uint64_t base0 = n ? reads->seq_off[0] : 0;
-    const uint64_t nseq = n ? reads->seq_off[n] - base0 : 0;
+    const uint64_t nseq = m.nseq;
     // every read reserves PG_RESERVE slots (one atomic per claim of reads); lists longer than their share allocate more
     b->pool_shard_cap = (uint32_t)std::min<uint64_t>(((PG_RESERVE + 2ull) * n) / PG_POOL_SHARDS + 512ull, 0x7fffffffull / PG_POOL_SHARDS);
     if (env().tiny_pool) b->pool_shard_cap = 1;      // tests: force the overflow/regrow path
@@ -775,6 +801,7 @@ int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint
         if (e != hipSuccess) return drop(fail(ctx, PG_E_DEVICE, std::string("clearing the batch outputs: ") + hipGetErrorString(e)));
     } else {
         for (size_t k = 0; k < n_items; k++) {
+            if (*items[k].p) continue;                    // (seq_off_ready)
             hipError_t e = hipMalloc(items[k].p, items[k].bytes);
             // the delivery's scan / gather trusts the counts: a failed memset must not go unnoticed
             if (e == hipSuccess && k >= first_zero) e = hipMemset(*items[k].p, 0, items[k].bytes);
@@ -783,24 +810,66 @@ int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint
                                  std::string("batch buffers: ") + hipGetErrorString(e)));
         }
     }
-    if (copy && n) {
-        hipError_t e = hipSuccess;
-        if (nseq) e = hipMemcpy(b->seq, reads->seq + base0, (size_t)nseq, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(b->seq_off, off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(b->strand, reads->anchor_strand, n, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(b->pos, reads->anchor_pos, n * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(b->isz, reads->insert_size, n * sizeof(int16_t), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(b->chr, reads->chr_id, n * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return drop(fail(ctx, PG_E_DEVICE, std::string("input upload: ") + hipGetErrorString(e)));
-    }
-    // the pack's view of the inputs for launches that pack in place (launch_range replaces it when the windows or the parameters
-    // change); on the ctx stream, which every launch of the batch is ordered behind
+    *out = b;
+    return PG_OK;
+}
+
+// Copies the inputs of a batch into its buffers, all with blocking copies of `kind`: from host arrays (off = the offsets rebased
+// to 0) or from the caller's device arrays (off = null: the measurement kernel has written the batch's seq_off already).
+// seq points at the batch's first base.
+int copy_batch_inputs(pg_ctx *ctx, pg_device_batch *b, const pg_read_batch *reads, const uint8_t *seq, uint64_t nseq,
+                      const uint64_t *off, hipMemcpyKind kind)
+{
+    const size_t n = b->n;
+    if (!n) return PG_OK;
+    hipError_t e = hipSuccess;
+    if (nseq) e = hipMemcpy(b->seq, seq, (size_t)nseq, kind);
+    if (e == hipSuccess && off) e = hipMemcpy(b->seq_off, off, (n + 1) * sizeof(uint64_t), kind);
+    if (e == hipSuccess) e = hipMemcpy(b->strand, reads->anchor_strand, n, kind);
+    if (e == hipSuccess) e = hipMemcpy(b->pos, reads->anchor_pos, n * sizeof(int32_t), kind);
+    if (e == hipSuccess) e = hipMemcpy(b->isz, reads->insert_size, n * sizeof(int16_t), kind);
+    if (e == hipSuccess) e = hipMemcpy(b->chr, reads->chr_id, n * sizeof(int32_t), kind);
+    // (a device-to-device copy may return before it has run: the caller may release its buffers when the entry returns)
+    if (e == hipSuccess && kind == hipMemcpyDeviceToDevice) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) return fail(ctx, PG_E_DEVICE, std::string("input upload: ") + hipGetErrorString(e));
+    return PG_OK;
+}
+
+// The pack's view of the inputs for launches that pack in place (launch_range replaces it when the windows or the parameters
+// change); on the ctx stream, which every launch of the batch is ordered behind.
+int publish_soa(pg_ctx *ctx, pg_device_batch *b)
+{
     b->h_soa = soa_in(ctx, b);
-    {
-        hipError_t e = hipMemcpyAsync(b->d_soa, &b->h_soa, sizeof b->h_soa, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return drop(fail(ctx, PG_E_DEVICE, std::string("input upload: ") + hipGetErrorString(e)));
-    }
+    hipError_t e = hipMemcpyAsync(b->d_soa, &b->h_soa, sizeof b->h_soa, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return fail(ctx, PG_E_DEVICE, std::string("input upload: ") + hipGetErrorString(e));
     b->soa_uploaded = true;
+    return PG_OK;
+}
+
+// Validates the batch and allocates its device buffers.  copy = true also copies the inputs
+// (synchronously); otherwise the caller streams them in (search_host).  off = read offsets rebased to 0.
+// use_arena: carve the buffers out of the ctx arena (host-path calls: the batch dies with the call).
+// plan (search_host; needs use_arena): the arena gets room for the delivery buffers the caller takes behind the batch, and
+// `off` room for the one-copy upload (pg_host_plan.h).
+int alloc_batch(pg_ctx *ctx, const pg_read_batch *reads, bool copy, HostBuf<uint64_t> &off, pg_device_batch **out,
+                bool use_arena = false, const PgHostPlan *plan = nullptr)
+{
+    BatchMeasure m;
+    if (!off.resize(plan ? plan->off_words : (reads ? reads->n_reads : 0) + (size_t)1)) return fail(ctx, PG_E_NOMEM, "host memory for the read offsets");
+    int rc = validate_and_measure(ctx, reads, &m.max_len, &m.levels, &m.max_isz, off.data(), &m.uniform_len);
+    if (rc) return rc;
+    m.n = reads->n_reads;
+    const uint64_t base0 = m.n ? reads->seq_off[0] : 0;
+    m.nseq = m.n ? reads->seq_off[m.n] - base0 : 0;
+    pg_device_batch *b = nullptr;
+    if ((rc = alloc_batch_buffers(ctx, m, &b, use_arena, plan))) return rc;
+    if (copy) rc = copy_batch_inputs(ctx, b, reads, m.nseq ? reads->seq + base0 : nullptr, m.nseq, off.data(), hipMemcpyHostToDevice);
+    if (!rc) rc = publish_soa(ctx, b);
+    if (rc) {
+        free_batch_buffers(b);
+        delete b;
+        return rc;
+    }
     *out = b;
     return PG_OK;
 }
@@ -1066,10 +1135,75 @@ struct DevTemps {
     }
 };
 
-// Results of a searched batch to the host: the delivery kernels of the host path (pg_deliver_chunk) over the whole batch, in
-// two passes, so that the run buffers can be sized from the batch's totals and only the compact CSR crosses PCIe (pinned host
-// buffers).  Pass 1 scans every chunk -- per-read summaries, local sums, each chunk's base and run counts; pass 2 gathers the runs
-// in read order and writes the 64-bit offsets.
+// The two passes of a whole-batch delivery (n > 0), shared by the download to the host and the one into the caller's device
+// buffers: the delivery kernels of the host path (pg_deliver_chunk) over the whole batch.  Pass 1 scans every chunk -- per-read
+// summaries into the batch's own arrays, local sums, each chunk's base and run counts -- and brings the per-chunk info to the host,
+// which sizes (or checks) the run buffers from the totals; pass 2 gathers the runs in read order and writes the 64-bit offsets,
+// straight into whatever device buffers the caller names.  Each pass is queued on the ctx stream and waited for separately, so
+// that the caller's own copies travel in between.
+struct DeliveryPasses {
+    pg_ctx *ctx;
+    pg_device_batch *b;
+    const size_t n, chunk, n_chunks, chunk_blks;
+    DevTemps tmp;
+    uint2 *local = nullptr, *blk = nullptr;
+    unsigned long long *d_info = nullptr;
+    HostBuf<unsigned long long> info;
+    unsigned long long tot[2] = { 0, 0 };                  // close / far runs of the batch (wait_totals)
+    DeliveryPasses(pg_ctx *c, pg_device_batch *batch)
+        : ctx(c), b(batch), n(batch->n), chunk(download_chunk()), n_chunks((n + chunk - 1) / chunk), chunk_blks((chunk + 255) / 256),
+          tmp(c, batch) {}
+    const unsigned long long *d_last_info() const { return d_info + 8 * (n_chunks - 1); }
+    int queue_scan()
+    {
+        local = (uint2 *)tmp.take(n * 8);
+        blk = (uint2 *)tmp.take(n_chunks * chunk_blks * 8);
+        d_info = (unsigned long long *)tmp.take(n_chunks * 64);
+        if (!local || !blk || !d_info) return fail(ctx, PG_E_NOMEM, "device memory for the download's scans");
+        if (!info.resize(n_chunks * 8)) return fail(ctx, PG_E_NOMEM, "pinned host memory");
+        // (search_host's fallback: its deliveries have advanced the running totals)
+        HIP_TRY(ctx, hipMemsetAsync(b->run_tot, 0, 2 * sizeof(unsigned long long), ctx->stream));
+        for (size_t k = 0, lo = 0; k < n_chunks; k++, lo += chunk)
+            HIP_TRY(ctx, (hipError_t)pg_deliver_scan(b->out_rec + lo, (uint32_t)std::min(chunk, n - lo), b->rc_flag + lo, b->close_last + lo,
+                                                     b->close_max + lo, local + lo, blk + k * chunk_blks, b->run_tot, d_info + 8 * k,
+                                                     b->pool_used, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(info.data(), d_info, n_chunks * 64, hipMemcpyDeviceToHost, ctx->stream));
+        return PG_OK;
+    }
+    // the totals: the last chunk's base + its runs
+    int wait_totals()
+    {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const unsigned long long *last = info.data() + 8 * (n_chunks - 1);
+        tot[0] = last[0] + last[2];
+        tot[1] = last[1] + last[3];
+        return PG_OK;
+    }
+    // d_runs[k]: room for tot[k] runs; a list without a run needs no buffer -- its null pointer is never written through (a null
+    // far buffer makes the gather place the far runs behind the close runs: there are none to place).  d_off[k]: n offsets.
+    int queue_gather(pg_run *const d_runs[2], unsigned long long *const d_off[2])
+    {
+        const unsigned long long pool_runs = (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS;
+        for (size_t k = 0, lo = 0; k < n_chunks; k++, lo += chunk)
+            HIP_TRY(ctx, (hipError_t)pg_deliver_gather_runs(b->out_rec + lo, (uint32_t)std::min(chunk, n - lo), local + lo, blk + k * chunk_blks,
+                                                            d_info + 8 * k, b->pool, pool_runs, tot[0] ? d_runs[0] : nullptr,
+                                                            tot[1] ? d_runs[1] : nullptr, std::max(tot[0], tot[1]),
+                                                            d_off[0] + lo, d_off[1] + lo, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(info.data(), d_info, n_chunks * 64, hipMemcpyDeviceToHost, ctx->stream));
+        return PG_OK;
+    }
+    int wait_gather()
+    {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        // the buffers hold the totals exactly and the search has checked its pool: a gather that ran out of either is a bug
+        for (size_t k = 0; k < n_chunks; k++)
+            if (info[8 * k + 5]) return fail(ctx, PG_E_DEVICE, "download: the gather of chunk " + std::to_string(k) + " found a run list out of bounds");
+        return PG_OK;
+    }
+};
+
+// Results of a searched batch to the host: the two passes, with temporaries for the gathered runs and offsets, so that the run
+// buffers can be sized from the batch's totals and only the compact CSR crosses PCIe (pinned host buffers).
 // summaries = false (pg_search_batch_table, between its two launches): the per-read close-end summaries stay on the device
 int download(pg_ctx *ctx, pg_device_batch *b, pg_result *r, bool summaries = true)
 {
@@ -1084,43 +1218,24 @@ int download(pg_ctx *ctx, pg_device_batch *b, pg_result *r, bool summaries = tru
         r->close_off[0] = r->far_off[0] = 0;
         return PG_OK;
     }
-    const size_t chunk = download_chunk(), n_chunks = (n + chunk - 1) / chunk, chunk_blks = (chunk + 255) / 256;
-    DevTemps tmp(ctx, b);
-    uint2 *local = (uint2 *)tmp.take(n * 8), *blk = (uint2 *)tmp.take(n_chunks * chunk_blks * 8);
-    unsigned long long *d_info = (unsigned long long *)tmp.take(n_chunks * 64), *d_off[2];
-    d_off[0] = (unsigned long long *)tmp.take(n * 8);
-    d_off[1] = (unsigned long long *)tmp.take(n * 8);
-    HostBuf<unsigned long long> info;
-    if (!local || !blk || !d_info || !d_off[0] || !d_off[1]) return fail(ctx, PG_E_NOMEM, "device memory for the download's scans");
-    if (!info.resize(n_chunks * 8)) return fail(ctx, PG_E_NOMEM, "pinned host memory");
-    // (search_host's fallback: its deliveries have advanced the running totals)
-    HIP_TRY(ctx, hipMemsetAsync(b->run_tot, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    for (size_t k = 0, lo = 0; k < n_chunks; k++, lo += chunk)
-        HIP_TRY(ctx, (hipError_t)pg_deliver_scan(b->out_rec + lo, (uint32_t)std::min(chunk, n - lo), b->rc_flag + lo, b->close_last + lo,
-                                                 b->close_max + lo, local + lo, blk + k * chunk_blks, b->run_tot, d_info + 8 * k,
-                                                 b->pool_used, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(info.data(), d_info, n_chunks * 64, hipMemcpyDeviceToHost, ctx->stream));
+    DeliveryPasses p(ctx, b);
+    if (int rc = p.queue_scan()) return rc;
+    unsigned long long *d_off[2] = { (unsigned long long *)p.tmp.take(n * 8), (unsigned long long *)p.tmp.take(n * 8) };
+    if (!d_off[0] || !d_off[1]) return fail(ctx, PG_E_NOMEM, "device memory for the download's scans");
     // (the per-read summaries travel while the host sizes the run buffers)
     if (summaries) {
         HIP_TRY(ctx, hipMemcpyAsync(r->rc_flag.data(), b->rc_flag, n, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(r->close_last.data(), b->close_last, n * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(r->close_max.data(), b->close_max, n * 2, hipMemcpyDeviceToHost, ctx->stream));
     }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    // the totals: the last chunk's base + its runs.  A list without a run gets no buffer -- its null pointer is never written
-    // through (a null far buffer makes the gather place the far runs behind the close runs: there are none to place)
-    const unsigned long long *last = info.data() + 8 * (n_chunks - 1), tot[2] = { last[0] + last[2], last[1] + last[3] };
+    if (int rc = p.wait_totals()) return rc;
+    const unsigned long long *tot = p.tot;
     pg_run *d_runs[2] = { nullptr, nullptr };
     if (!r->close_runs.resize((size_t)tot[0]) || !r->far_runs.resize((size_t)tot[1]))
         return fail(ctx, PG_E_NOMEM, "pinned host memory for the runs");
     for (int k = 0; k < 2; k++)
-        if (tot[k] && !(d_runs[k] = (pg_run *)tmp.take((size_t)tot[k] * sizeof(pg_run)))) return fail(ctx, PG_E_NOMEM, "gathered runs");
-    const unsigned long long pool_runs = (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS;
-    for (size_t k = 0, lo = 0; k < n_chunks; k++, lo += chunk)
-        HIP_TRY(ctx, (hipError_t)pg_deliver_gather_runs(b->out_rec + lo, (uint32_t)std::min(chunk, n - lo), local + lo, blk + k * chunk_blks,
-                                                        d_info + 8 * k, b->pool, pool_runs, d_runs[0], d_runs[1], std::max(tot[0], tot[1]),
-                                                        d_off[0] + lo, d_off[1] + lo, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(info.data(), d_info, n_chunks * 64, hipMemcpyDeviceToHost, ctx->stream));
+        if (tot[k] && !(d_runs[k] = (pg_run *)p.tmp.take((size_t)tot[k] * sizeof(pg_run)))) return fail(ctx, PG_E_NOMEM, "gathered runs");
+    if (int rc = p.queue_gather(d_runs, d_off)) return rc;
     HostBuf<uint64_t> *off[2] = { &r->close_off, &r->far_off };
     HostBuf<pg_run> *runs[2] = { &r->close_runs, &r->far_runs };
     for (int k = 0; k < 2; k++)
@@ -1132,12 +1247,55 @@ int download(pg_ctx *ctx, pg_device_batch *b, pg_result *r, bool summaries = tru
     // the far-end seams has no close run)
     for (int k = 0; k < 2; k++)
         if (!tot[k]) std::memset(off[k]->data(), 0, n * 8);
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = p.wait_gather()) return rc;
     r->close_off[n] = tot[0];
     r->far_off[n] = tot[1];
-    // the buffers hold the totals exactly and the search has checked its pool: a gather that ran out of either is a bug
-    for (size_t k = 0; k < n_chunks; k++)
-        if (info[8 * k + 5]) return fail(ctx, PG_E_DEVICE, "download: the gather of chunk " + std::to_string(k) + " found a run list out of bounds");
+    return PG_OK;
+}
+
+// ... and into the caller's device buffers (pg_device_batch_download_device; the pointers have been checked): the gather writes
+// the runs and offsets there, the summaries are device-to-device copies, off[n] is stored by a kernel from the last chunk's info.
+// Only the per-chunk info crosses to the host.  Nothing is written when a capacity is below its total.
+int download_device(pg_ctx *ctx, pg_device_batch *b, const pg_device_result *dst)
+{
+    const size_t n = b->n;
+    if (!n) {                                            // offsets [0]; nothing is launched
+        HIP_TRY(ctx, hipMemsetAsync(dst->close_off, 0, 8, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(dst->far_off, 0, 8, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return PG_OK;
+    }
+    DeliveryPasses p(ctx, b);
+    int rc = p.queue_scan();
+    if (!rc) rc = p.wait_totals();
+    if (rc) return rc;
+    if (p.tot[0] > dst->close_cap || p.tot[1] > dst->far_cap)
+        return fail(ctx, PG_E_INVALID, "pg_device_result: " + std::string(p.tot[0] > dst->close_cap ? "close_cap" : "far_cap") +
+                                           " is below the batch's number of runs (pg_device_batch_result_sizes)");
+    if ((rc = check_device_ptr(ctx, dst->close_runs, (size_t)p.tot[0] * sizeof(pg_run), 4, "pg_device_result.close_runs")) ||
+        (rc = check_device_ptr(ctx, dst->far_runs, (size_t)p.tot[1] * sizeof(pg_run), 4, "pg_device_result.far_runs")))
+        return rc;
+    pg_run *d_runs[2] = { dst->close_runs, dst->far_runs };
+    unsigned long long *d_off[2] = { (unsigned long long *)dst->close_off, (unsigned long long *)dst->far_off };
+    if ((rc = p.queue_gather(d_runs, d_off))) return rc;
+    HIP_TRY(ctx, (hipError_t)pg_devio_store_totals(p.d_last_info(), d_off[0] + n, d_off[1] + n, ctx->stream));
+    if (dst->rc_flag) HIP_TRY(ctx, hipMemcpyAsync(dst->rc_flag, b->rc_flag, n, hipMemcpyDeviceToDevice, ctx->stream));
+    if (dst->close_last) HIP_TRY(ctx, hipMemcpyAsync(dst->close_last, b->close_last, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    if (dst->close_max) HIP_TRY(ctx, hipMemcpyAsync(dst->close_max, b->close_max, n * 2, hipMemcpyDeviceToDevice, ctx->stream));
+    return p.wait_gather();
+}
+
+// Pass 1 alone: the batch's two totals (pg_device_batch_result_sizes).
+int result_sizes(pg_ctx *ctx, pg_device_batch *b, uint64_t *n_close, uint64_t *n_far)
+{
+    *n_close = *n_far = 0;
+    if (!b->n) return PG_OK;
+    DeliveryPasses p(ctx, b);
+    int rc = p.queue_scan();
+    if (!rc) rc = p.wait_totals();
+    if (rc) return rc;
+    *n_close = p.tot[0];
+    *n_far = p.tot[1];
     return PG_OK;
 }
 
@@ -1410,6 +1568,178 @@ int upload_reference(pg_ctx *ctx)
         free_reference(ctx);
         return rc;
     }
+    ctx->plane_words = ctx->h_lo.size();
+    ctx->mirror_ok = true;
+    return PG_OK;
+}
+
+// The host mirror of the planes, for the two entries that read it: after pg_load_reference_device it is filled here, on first
+// use, with one device-to-host copy per plane.
+int host_mirror(const pg_ctx *ctx)
+{
+    if (ctx->mirror_ok) return PG_OK;
+    use_device(ctx);
+    try {
+        ctx->h_lo.resize(ctx->plane_words);
+        ctx->h_hi.resize(ctx->plane_words);
+        ctx->h_nn.resize(ctx->plane_words);
+    } catch (...) {
+        ctx->h_lo.clear();
+        ctx->h_hi.clear();
+        ctx->h_nn.clear();
+        return PG_E_NOMEM;
+    }
+    const size_t bytes = (size_t)ctx->plane_words * sizeof(uint32_t);
+    if (hipMemcpy(ctx->h_lo.data(), ctx->d_lo, bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(ctx->h_hi.data(), ctx->d_hi, bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(ctx->h_nn.data(), ctx->d_nn, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        return PG_E_DEVICE;
+    ctx->mirror_ok = true;
+    return PG_OK;
+}
+
+// A pointer a device entry was handed: device memory of the context's own GPU, aligned for its element type, with the `bytes`
+// the library will read or write inside its allocation.  Checked before anything is launched: a host pointer must end in a
+// status code, never in a fault.  bytes = 0: nothing will be touched, nothing is checked.
+int check_device_ptr(pg_ctx *ctx, const void *p, size_t bytes, size_t align, const char *what)
+{
+    if (!bytes) return PG_OK;
+    if (!p) return fail(ctx, PG_E_INVALID, std::string(what) + ": null pointer");
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();                         // (a pointer the runtime does not know: plain host memory)
+        return fail(ctx, PG_E_INVALID, std::string(what) + ": not device memory");
+    }
+    if (at.type != hipMemoryTypeDevice) return fail(ctx, PG_E_INVALID, std::string(what) + ": not device memory");
+    if (at.device != ctx->prm.device) return fail(ctx, PG_E_INVALID, std::string(what) + ": memory of another GPU than the context's");
+    if ((uintptr_t)p % align) return fail(ctx, PG_E_INVALID, std::string(what) + ": misaligned for its element type");
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, PG_E_INVALID, std::string(what) + ": not inside a device allocation");
+    }
+    const uintptr_t lo = (uintptr_t)base, at_p = (uintptr_t)p;
+    if (at_p < lo || at_p - lo > size || bytes > size - (at_p - lo))
+        return fail(ctx, PG_E_INVALID, std::string(what) + ": reaches past the end of its device allocation");
+    return PG_OK;
+}
+
+// pg_device_batch_upload_device: the batch's arrays are in device memory.  The measurement kernel (pg_devio.hip) is the
+// device twin of validate_and_measure; only its 40-byte record comes to the host, which reports, sizes and allocates as the
+// host upload does (alloc_batch_buffers), copies device-to-device and packs.
+int upload_batch_device(pg_ctx *ctx, const pg_read_batch *d, pg_device_batch **out)
+{
+    if (!d || (d->n_reads && (!d->seq_off || !d->anchor_strand || !d->anchor_pos || !d->insert_size || !d->chr_id)))
+        return fail(ctx, PG_E_INVALID, "null array in pg_read_batch");
+    if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
+    const size_t n = d->n_reads;
+    BatchMeasure m;
+    m.n = d->n_reads;
+    uint64_t *d_off = nullptr;                           // becomes the batch's seq_off
+    uint64_t off0 = 0;
+    int rc = PG_OK;
+    if (n) {                                             // (nothing is checked or launched for an empty batch)
+        if ((rc = check_device_ptr(ctx, d->seq_off, (n + 1) * 8, 8, "pg_read_batch.seq_off")) ||
+            (rc = check_device_ptr(ctx, d->anchor_strand, n, 1, "pg_read_batch.anchor_strand")) ||
+            (rc = check_device_ptr(ctx, d->anchor_pos, n * 4, 4, "pg_read_batch.anchor_pos")) ||
+            (rc = check_device_ptr(ctx, d->insert_size, n * 2, 2, "pg_read_batch.insert_size")) ||
+            (rc = check_device_ptr(ctx, d->chr_id, n * 4, 4, "pg_read_batch.chr_id")))
+            return rc;
+        PgReadMeasure h, *d_rec = nullptr;
+        std::memset(&h, 0, sizeof h);
+        h.first_bad = PG_MEASURE_NONE;
+        h.len_min = 0xffffffffu;
+        HIP_TRY(ctx, hipMalloc((void **)&d_off, pg_input_layout(n).a[PG_IN_SEQ_OFF].bytes));
+        hipError_t e = hipMalloc((void **)&d_rec, sizeof h);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_rec, &h, sizeof h, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess)
+            e = (hipError_t)pg_devio_measure_reads((const unsigned long long *)d->seq_off, d->anchor_pos, d->insert_size, d->chr_id,
+                                                   d->n_reads, ctx->d_chr_size, (int32_t)ctx->names.size(), ctx->prm.spacer,
+                                                   (unsigned long long *)d_off, d_rec, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&h, d_rec, sizeof h, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (d_rec) (void)hipFree(d_rec);
+        if (e != hipSuccess) rc = fail(ctx, e == hipErrorOutOfMemory ? PG_E_NOMEM : PG_E_DEVICE, std::string("read measurement: ") + hipGetErrorString(e));
+        // the host upload's order: a missing seq, then the first bad read's code
+        else if (!d->seq && h.offn > h.off0) rc = fail(ctx, PG_E_INVALID, "null seq in pg_read_batch");
+        else if (h.first_bad != PG_MEASURE_NONE) rc = validation_failure(ctx, (int)(h.first_bad & 0xffu));
+        else rc = check_device_ptr(ctx, d->seq ? d->seq + h.off0 : nullptr, (size_t)(h.offn - h.off0), 1, "pg_read_batch.seq");
+        if (rc) {
+            (void)hipFree(d_off);
+            return rc;
+        }
+        off0 = h.off0;
+        m.nseq = h.offn - h.off0;
+        m.max_len = std::max<uint32_t>(h.len_max, 1u);
+        m.max_isz = h.isz_max;
+        m.uniform_len = h.len_min == h.len_max ? h.len_max : 0u;
+    }
+    if ((rc = batch_levels(ctx, m.max_len, &m.levels))) {
+        if (d_off) (void)hipFree(d_off);
+        return rc;
+    }
+    pg_device_batch *b = nullptr;
+    if ((rc = alloc_batch_buffers(ctx, m, &b, false, nullptr, d_off))) return rc;
+    rc = copy_batch_inputs(ctx, b, d, m.nseq ? d->seq + off0 : nullptr, m.nseq, nullptr, hipMemcpyDeviceToDevice);
+    if (!rc) rc = publish_soa(ctx, b);
+    if (!rc) rc = pack_reads(ctx, b, 0, b->n);
+    if (rc) {
+        free_batch_buffers(b);
+        delete b;
+        return rc;
+    }
+    *out = b;
+    return PG_OK;
+}
+
+// pg_load_reference_device: the planes are built in HBM from the caller's ASCII bases (pg_devio.hip), bit for bit what
+// pg_load_reference packs on host threads; the host mirror stays empty until somebody asks (host_mirror).
+int load_reference_device(pg_ctx *ctx, int32_t n_chr, const char *const *names, const uint8_t *const *d_seq, const uint64_t *len_padded)
+{
+    uint64_t total_words = 0;
+    std::vector<uint64_t> word_off;
+    for (int c = 0; c < n_chr; c++) {
+        if (len_padded[c] > PG_MAX_CHR_PADDED) return fail(ctx, PG_E_UNSUPPORTED, "chromosome of 2^31 bases or more (positions are signed 32-bit on the device)");
+        if (len_padded[c] < 2ull * ctx->prm.spacer) return fail(ctx, PG_E_INVALID, "chromosome shorter than its spacers");
+        total_words += PG_GUARD_WORDS;
+        word_off.push_back(total_words);
+        total_words += (len_padded[c] + 31) / 32 + PG_GUARD_WORDS;
+    }
+    total_words += 8;
+    for (int c = 0; c < n_chr; c++)
+        if (int rc = check_device_ptr(ctx, d_seq[c], (size_t)len_padded[c], 1, "d_seq_padded")) return rc;
+    free_reference(ctx);
+    for (int c = 0; c < n_chr; c++) {
+        ctx->names.push_back(names && names[c] ? names[c] : "");
+        ctx->comp_size.push_back(len_padded[c]);
+    }
+    ctx->word_off = word_off;
+    ctx->plane_words = total_words;
+    std::vector<uint32_t> sizes(ctx->comp_size.size());
+    for (size_t c = 0; c < sizes.size(); c++) sizes[c] = (uint32_t)ctx->comp_size[c];
+    const size_t bytes = (size_t)total_words * sizeof(uint32_t);
+    int rc;
+    if ((rc = dev_alloc(ctx, &ctx->d_lo, total_words)) || (rc = dev_alloc(ctx, &ctx->d_hi, total_words)) ||
+        (rc = dev_alloc(ctx, &ctx->d_nn, total_words)) ||
+        (rc = dev_upload(ctx, &ctx->d_word_off, ctx->word_off.data(), ctx->word_off.size())) ||
+        (rc = dev_upload(ctx, &ctx->d_chr_size, sizes.data(), sizes.size()))) {
+        free_reference(ctx);
+        return rc;
+    }
+    // guards, tails and the 8 trailing words are N; the kernel writes every word of every chromosome
+    hipError_t e = hipMemsetAsync(ctx->d_lo, 0, bytes, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_hi, 0, bytes, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_nn, 0xff, bytes, ctx->stream);
+    for (int c = 0; c < n_chr && e == hipSuccess; c++)
+        e = (hipError_t)pg_devio_pack_reference(d_seq[c], len_padded[c], ctx->d_lo + word_off[c], ctx->d_hi + word_off[c],
+                                                ctx->d_nn + word_off[c], ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        free_reference(ctx);
+        return fail(ctx, PG_E_DEVICE, std::string("reference pack: ") + hipGetErrorString(e));
+    }
     return PG_OK;
 }
 
@@ -1655,6 +1985,15 @@ int pg_load_reference(pg_ctx *ctx, int32_t n_chr, const char *const *names,
     return upload_reference(ctx);
 }
 
+int pg_load_reference_device(pg_ctx *ctx, int32_t n_chr, const char *const *names,
+                             const uint8_t *const *d_seq_padded, const uint64_t *len_padded)
+{
+    use_device(ctx);
+    if (!ctx || n_chr <= 0 || !d_seq_padded || !len_padded) return fail(ctx, PG_E_INVALID, "bad reference arguments");
+    if (n_chr > 32767) return fail(ctx, PG_E_UNSUPPORTED, "more than 32767 chromosomes");
+    return load_reference_device(ctx, n_chr, names, d_seq_padded, len_padded);
+}
+
 // ---- packed reference on disk: the bit planes exactly as they sit in HBM, so a
 // genome is packed from FASTA once (Genome::loadChromosome semantics, pg_load_fasta) and mapped back
 // in seconds.  Layout: magic, spacer, n_chr, per chromosome {name length, name, padded size, word
@@ -1665,6 +2004,7 @@ int pg_reference_save_packed(const pg_ctx *ctx, const char *path)
 {
     if (!ctx || !path) return PG_E_INVALID;
     if (ctx->names.empty()) return PG_E_NO_REFERENCE;
+    if (int rc = host_mirror(ctx)) return rc;
     FILE *f = fopen(path, "wb");
     if (!f) return PG_E_INVALID;
     bool ok = fwrite(PG_REF_MAGIC, 1, 8, f) == 8;
@@ -1798,6 +2138,7 @@ int pg_reference_fetch(const pg_ctx *ctx, int32_t c, uint64_t start, uint64_t n,
 {
     if (!ctx || !out || c < 0 || c >= (int)ctx->names.size()) return PG_E_INVALID;
     if (start + n > ctx->comp_size[c]) return PG_E_INVALID;
+    if (int rc = host_mirror(ctx)) return rc;
     const uint32_t *lo = &ctx->h_lo[ctx->word_off[c]], *hi = &ctx->h_hi[ctx->word_off[c]],
                    *nn = &ctx->h_nn[ctx->word_off[c]];
     for (uint64_t k = 0; k < n; k++) {
@@ -1875,6 +2216,41 @@ int pg_device_batch_download(pg_ctx *ctx, pg_device_batch *b, pg_result **out)
     }
     *out = r;
     return PG_OK;
+}
+
+// ---- device buffers in and out
+int pg_device_batch_upload_device(pg_ctx *ctx, const pg_read_batch *d_reads, pg_device_batch **out)
+{
+    use_device(ctx);
+    if (!ctx || !out) return PG_E_INVALID;
+    *out = nullptr;
+    int rc = upload_batch_device(ctx, d_reads, out);
+    if (rc) return rc;
+    return read_exact_count(ctx, *out);
+}
+
+int pg_device_batch_result_sizes(pg_ctx *ctx, pg_device_batch *b, uint64_t *n_close_runs, uint64_t *n_far_runs)
+{
+    use_device(ctx);
+    if (!ctx || !b || !n_close_runs || !n_far_runs) return PG_E_INVALID;
+    return result_sizes(ctx, b, n_close_runs, n_far_runs);
+}
+
+int pg_device_batch_download_device(pg_ctx *ctx, pg_device_batch *b, const pg_device_result *dst)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (!dst) return fail(ctx, PG_E_INVALID, "null pg_device_result");
+    const size_t n = b->n;
+    int rc;
+    // (the run buffers are checked once the totals are known: a list without a run needs none)
+    if ((rc = check_device_ptr(ctx, dst->close_off, (n + 1) * 8, 8, "pg_device_result.close_off")) ||
+        (rc = check_device_ptr(ctx, dst->far_off, (n + 1) * 8, 8, "pg_device_result.far_off")) ||
+        (dst->rc_flag && (rc = check_device_ptr(ctx, dst->rc_flag, n, 1, "pg_device_result.rc_flag"))) ||
+        (dst->close_last && (rc = check_device_ptr(ctx, dst->close_last, n * 4, 4, "pg_device_result.close_last"))) ||
+        (dst->close_max && (rc = check_device_ptr(ctx, dst->close_max, n * 2, 2, "pg_device_result.close_max"))))
+        return rc;
+    return download_device(ctx, b, dst);
 }
 
 void pg_device_batch_free(pg_ctx *ctx, pg_device_batch *b)

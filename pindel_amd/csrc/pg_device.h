@@ -374,6 +374,25 @@ int pg_deliver_scan(const PgOutRec *out, uint32_t cnt, uint8_t *rc_flag, uint32_
 int pg_deliver_gather_runs(const PgOutRec *out, uint32_t cnt, const void *local, const void *blk, unsigned long long *info,
                            const pg_run *pool, unsigned long long pool_runs, pg_run *close_runs, pg_run *far_runs /* null: behind the close runs */,
                            unsigned long long cap, unsigned long long *close_off, unsigned long long *far_off, void *stream);
+// The device-buffer entries (pg_devio.hip).  Every pointer is device memory the host has already checked.
+// What one pass over a batch's arrays in device memory yields (pg_devio_measure_reads): the host initialises it -- first_bad =
+// PG_MEASURE_NONE, len_max = 0, len_min = ~0, isz_max = 0 -- and reads it back, 40 bytes.
+#define PG_MEASURE_NONE (~0ull)
+struct PgReadMeasure {
+    unsigned long long first_bad;      // (read index << 8) | code of the bad read with the lowest index (codes: validate_and_measure)
+    unsigned long long off0, offn;     // seq_off[0], seq_off[n]
+    uint32_t len_max, len_min;         // over the good reads: equal when the batch has ONE read length
+    int32_t isz_max;                   // largest insert size (at least 0)
+    uint32_t reserved;
+};
+// words [0, (len + 31) / 32) of a chromosome's planes (lo / hi / nn point at its first word) from its len ASCII bases
+int pg_devio_pack_reference(const uint8_t *d_seq, unsigned long long len, uint32_t *lo, uint32_t *hi, uint32_t *nn, void *stream);
+// off_out: n + 1 offsets rebased to 0; n = 0 launches nothing
+int pg_devio_measure_reads(const unsigned long long *seq_off, const int32_t *pos, const int16_t *isz, const int32_t *chr, uint32_t n,
+                           const uint32_t *chr_size, int32_t n_chr, uint32_t spacer, unsigned long long *off_out,
+                           struct PgReadMeasure *rec, void *stream);
+// *close_end / *far_end = the batch's run totals, from the 8 info values pg_deliver_scan left for its last chunk
+int pg_devio_store_totals(const unsigned long long *info, unsigned long long *close_end, unsigned long long *far_end, void *stream);
 #ifdef __cplusplus
 }
 #endif
