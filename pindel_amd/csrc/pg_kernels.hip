@@ -50,6 +50,7 @@
 
 #include "pg_device.h"
 #include "pg_lane_masks.h"
+#include "pg_eval_masks.h"
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -241,6 +242,20 @@ constexpr bool pg_short_masks()
     if (!DEF || EXACT) return false;
     return !((NB == 4 && NS == 3 && mode == PG_MODE_FAR) || (NB == 8 && NS == 3 && mode == PG_MODE_CLOSE));
 }
+// The evaluation and the emission of the runs (evaluate, count_kept, emit_runs) have a short form too (pg_eval_masks.h and the comment
+// at evaluate): scalar and literal masks for per-lane ones, and nothing for what the masks already in hand imply.  It rests on
+// mm_of's contract alone, so any kernel could take it.  The fixed-length kernels do (the same registers, no spill, fewer
+// instructions).  Of the default-parameter kernels for any length only the few below: every other one came out with more SGPR spill
+// slots or VGPR spills on the short form (profiles/r10/README.md lists both figures) and keeps the long one.  The generic and the
+// exact kernels are compiled from the long form as before.  SE, a template parameter of the three functions, carries the choice
+// down from search_read.
+template <int NB, int NS, typename Id, int mode, bool DEF, bool EXACT, int LEN>
+constexpr bool pg_short_eval()
+{
+    if (!DEF || EXACT) return false;
+    if (LEN > 0) return true;
+    return (NB == 3 && mode == PG_MODE_FAR) || (NB == 4 && NS == 4 && mode == PG_MODE_BOTH) || (NB == 8 && mode == PG_MODE_CLOSE);
+}
 // bits of a (wave-uniform) mask below the calling lane
 __device__ __forceinline__ int count_below(u64 m)
 {
@@ -426,9 +441,22 @@ struct Search {
 #endif
 #ifdef PG_DIAG
     u32 dg;              // diagnostics build: fills | seed-filter runs << 8 | candidate passes << 16 | evaluations << 24
+#endif
+    // -DPG_DIAG=2: the census of the evaluations instead (scripts/diag_counts.py), a nibble each: close-end evaluations | far-end ones
+    // << 4 | evaluations without a point << 8 | rounds run << 12 | of those without a point << 16 | emit_runs calls << 20 | quarter
+    // merges through LDS << 24 (reads of up to 128 bases: no nibble overflows)
+#if defined(PG_DIAG) && PG_DIAG == 2
+#define PG_DG(S, sh) ((void)0)
+#define PG_DC(S, sh) ((S).dg += 1u << (sh))
+#define PG_DC_IF(S, cond, sh) ((S).dg += (cond) ? 1u << (sh) : 0u)
+#elif defined(PG_DIAG)
 #define PG_DG(S, sh) ((S).dg += 1u << (sh))
+#define PG_DC(S, sh) ((void)0)
+#define PG_DC_IF(S, cond, sh) ((void)0)
 #else
 #define PG_DG(S, sh) ((void)0)
+#define PG_DC(S, sh) ((void)0)
+#define PG_DC_IF(S, cond, sh) ((void)0)
 #endif
     int cap_state;       // state-dependent relevance bound for seeds (see evaluate); T - 1 = none
     // bits of one word (a wave-uniform bool costs two scalar registers):
@@ -1638,9 +1666,21 @@ __device__ __forceinline__ u32 mm_of(const Search &S, int L)
 // reduction itself is not modified.
 // qmask: the tier A quarters that belong to the state (bit q; all four unless the pass kept the rings of the nested
 // far-end ranges apart, see Rings).
-template <int NB, typename Id>
+// SE: the short form (pg_short_eval, pg_eval_masks.h) -- the same Eval, from fewer instructions:
+//   * vm, the round's valid lanes, is low_bits(len - r0) in scalar code (a literal in the fixed-length kernels), not the ballot of a
+//     per-lane add and compare;
+//   * no ballot of "m1 <= M": cm only keeps valid lanes below the first abort, that is lanes with lo <= mmL.  mmL = g_maxMismatch[L]
+//     <= M for every valid L (mm_of's contract: the table is monotone and L < len; pg_create checks the baked rows of the
+//     fixed-length kernels), and lo = min(m1, M + 1): lo <= mmL <= M rules out lo = M + 1, so m1 = lo <= M on every lane of cm;
+//   * "L >= bps + m1" is "lane >= m1" in round 0 and holds on every lane of cm in the rounds after it: m1 <= M <= PG_MM_BREAKS < 64
+//     <= L - bps (pg_em_reach);
+//   * a round without a point (cm == 0, wave-uniform) is not run-length encoded: startm = cm & ~samem = 0 and brkm = startm | ~cm
+//     = ~0 are what the round's entry was initialised with, and id / lo are only ever read under a bit of kept, a subset of startm
+//     (count_kept, emit_runs).
+template <int NB, typename Id, bool SE>
 __device__ __forceinline__ void evaluate(Search &S, const Acc<NB, Id> &A, Eval<NB, Id> &E, int lane, int qmask = 15)
 {
+    static_assert(PG_MM_BREAKS < 64, "the short form's reach rule: no level of a point reaches 64");
     const u32 mm0 = mm_of<NB>(S, S.bps + lane);       // (one LDS read per evaluation; a VGPR per phase otherwise: the register budget of six and seven waves per SIMD)
     E.n_runs = 0;
     E.max_len = 0;
@@ -1654,6 +1694,7 @@ __device__ __forceinline__ void evaluate(Search &S, const Acc<NB, Id> &A, Eval<N
         Id aid = 0;
         if (lane < 16) { a1 = A.a1; a2 = A.a2; aok = A.aok; aid = A.aid; }
         if (qmask != 1) {                                     // uniform (quarter 0 alone: nothing to fetch)
+            PG_DC(S, 24);
             S.bufA[lane] = make_uint4(A.a1, A.a2 | (A.aok << 16), (u32)A.aid, (u32)((u64)A.aid >> 32));
             PG_SYNC();
             if (lane < 16) {
@@ -1708,11 +1749,24 @@ __device__ __forceinline__ void evaluate(Search &S, const Acc<NB, Id> &A, Eval<N
             }
         }
         const u32 lo = m1 <= (u32)S.M ? m1 : (u32)S.M + 1u;
-        const u64 vm = ballot64(valid);
+        // (SE: the valid lanes from scalar code -- the ballot is that of "L <= len - 1")
+        const u64 vm = SE ? pg_em_valid(S.len, r0) : ballot64(valid);
         const u64 ab = vm & ballot64(lo > mmL);
         // a point at L: below the first abort, lowest level <= M and alone up to + ADDITIONAL_MISMATCH, L >= bps + level, CheckMismatches
-        const u64 cm = vm & (~ab & (ab - 1ull)) & ballot64(m1 <= (u32)S.M) & ballot64(m2 > m1 + (u32)S.add_mm) &
-                       ballot64((u32)L >= (u32)S.bps + m1) & ballot64(ok != 0u);
+        // (SE: without the two compares that the masks before them imply, see above)
+        u64 cm;
+        if (SE) {
+            cm = vm & (~ab & (ab - 1ull)) & ballot64(m2 > m1 + (u32)S.add_mm) & ballot64(ok != 0u);
+            if (pg_em_reach_needs_compare(r)) cm &= ballot64((u32)lane >= m1);
+        } else
+            cm = vm & (~ab & (ab - 1ull)) & ballot64(m1 <= (u32)S.M) & ballot64(m2 > m1 + (u32)S.add_mm) &
+                 ballot64((u32)L >= (u32)S.bps + m1) & ballot64(ok != 0u);
+        PG_DC(S, 12);
+        PG_DC_IF(S, cm == 0ull, 16);
+        if (SE && cm == 0ull) {                           // uniform: no point in this round, nothing to encode
+            if (ab) aborted = 1u;
+            continue;
+        }
         // run-length encode consecutive points of the same candidate / level (a run never spans two rounds)
         const u32 lok = lane_bit(cm) ? lo + 1u : 0u;       // 0 = no point here
         const u32 plok = wave_shr1(lok);                   // lane 0 gets 0
@@ -1730,13 +1784,16 @@ __device__ __forceinline__ void evaluate(Search &S, const Acc<NB, Id> &A, Eval<N
         }
         if (ab) aborted = 1u;
     }
+    PG_DC_IF(S, E.max_len == 0, 8);
 }
 
 // Writes the runs of the evaluation to out[0..): all of them (far end), or those of the candidate of the
 // last point (close end: CleanUniquePoints, pindel.cpp:2904-2941, keeps the points whose implied read
 // terminal equals the last point's = the runs of the last run's candidate).  kept = masks of the run starts
 // that are written.
-template <int NB, typename Id>
+// (SE: for symmetry with evaluate and emit_runs alone -- count_kept has one form; the popcounts it shares with emit_runs are scalar
+// instructions of one inlined body, which the compiler already merges.)
+template <int NB, typename Id, bool SE>
 __device__ __forceinline__ int count_kept(const Eval<NB, Id> &E, bool only_last, u64 *kept)
 {
     int n = 0;
@@ -1749,7 +1806,7 @@ __device__ __forceinline__ int count_kept(const Eval<NB, Id> &E, bool only_last,
     return n;
 }
 
-template <int NB, typename Id>
+template <int NB, typename Id, bool SE>
 __device__ __forceinline__ void emit_runs(const Search &S, bool antiF, bool antiB, int chr0, int origin0,
                                           const pg_window *bd, const Eval<NB, Id> &E, const u64 *kept,
                                           pg_run *out, int lane)
@@ -1761,7 +1818,7 @@ __device__ __forceinline__ void emit_runs(const Search &S, bool antiF, bool anti
         if (kept[r] == 0ull) continue;                    // uniform
         if ((kept[r] >> lane) & 1ull) {
             const int L = S.bps + 64 * r + lane;
-            const u64 higher = E.brkm[r] & ~low_bits_lane(lane + 1);
+            const u64 higher = E.brkm[r] & (SE ? pg_em_above(lane) : ~low_bits_lane(lane + 1));
             const int end_lane = higher ? __ffsll((long long)higher) - 2 : WAVE - 1;
             const u64 id = (u64)E.id[r];
             const u32 rel = (u32)(id & ((1ull << F::RB) - 1ull));
@@ -1879,6 +1936,7 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
     S.min_perfect = PRM(min_perfect, PG_DEF_MIN_PERFECT);
     static_assert(PG_DEF_MIN_PERFECT <= PG_DEF_MIN_CLOSE && PG_DEF_MIN_PERFECT <= 10, "the short masks need min_perfect <= bps at both ends");
     constexpr bool SM = pg_short_masks<NB, NS, mode, DEF, EXACT, LEN>();
+    constexpr bool SE = pg_short_eval<NB, NS, Id, mode, DEF, EXACT, LEN>();
     S.depth = rb[0];
     S.jmask[0] = rb[1];
     S.jmask[1] = 0u;                                        // (the wide depth's mask comes with the far end's part of the record)
@@ -2066,19 +2124,21 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                 if (S.nsurv != nsurv_eval) {
                     nsurv_eval = S.nsurv;
                     Eval<NB, Id> E;
-                    evaluate<NB, Id>(S, A, E, PG_LANE);
+                    PG_DC(S, 0);
+                    evaluate<NB, Id, SE>(S, A, E, PG_LANE);
                     PG_STOP_AT_V(S, 20, true);
                     close_max = uni(E.max_len);
                     if (uni(E.n_runs) > 0) {
                         u64 kept[NB];
-                        n_close = uni(count_kept<NB, Id>(E, true, kept));
+                        n_close = uni(count_kept<NB, Id, SE>(E, true, kept));
                         // the read's reserved slots, or (a list longer than that) an allocation of its own
                         if (n_close <= (int)PG_RES_CLOSE) {
                             close_base = res_base;
                             fits = res_fits;
                         } else
                             close_base = pool_alloc(B, n_close, lane, fits);
-                        if (fits) emit_runs<NB, Id>(S, true, false, chr, w1s, nullptr, E, kept, KA(B, pool) + close_base, PG_LANE);
+                        PG_DC(S, 20);
+                        if (fits) emit_runs<NB, Id, SE>(S, true, false, chr, w1s, nullptr, E, kept, KA(B, pool) + close_base, PG_LANE);
                         // AbsLoc of the last point (getLastAbsLocCloseEnd)
                         const u64 idl = (u64)E.id_last;
                         const int pl = w1s + (int)(u32)(idl & ((1ull << IdFmt<Id>::RB) - 1ull));
@@ -2165,7 +2225,8 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
             // a search window's result replaces UP_Far if its MaxLen is >= (NewUPFarIsBetter, farend_searcher.cpp:30-44)
             auto far_update = [&](int origin, const pg_window *bdw, int qmask) {
                 Eval<NB, Id> E;
-                evaluate<NB, Id>(S, A, E, PG_LANE, qmask);
+                PG_DC(S, 4);
+                evaluate<NB, Id, SE>(S, A, E, PG_LANE, qmask);
                 const int mx = uni(E.max_len);
                 if (mx >= far_max) {
                     far_max = mx;
@@ -2173,7 +2234,7 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                     far_base = 0;
                     if (n_far > 0) {
                         u64 kept[NB];
-                        (void)count_kept<NB, Id>(E, false, kept);
+                        (void)count_kept<NB, Id, SE>(E, false, kept);
                         if (n_far <= (int)PG_RES_FAR) {          // (a later range's result overwrites an earlier one's slots)
                             far_base = res_base + PG_RES_CLOSE;
                             fits &= res_fits;
@@ -2182,7 +2243,8 @@ __device__ __forceinline__ void search_read(const PgDevRef &ref, const PgDevPara
                             far_base = pool_alloc(B, n_far, lane, f2);
                             fits &= f2;
                         }
-                        if (fits) emit_runs<NB, Id>(S, false, true, chr, origin, bdw, E, kept, KA(B, pool) + far_base, PG_LANE);
+                        PG_DC(S, 20);
+                        if (fits) emit_runs<NB, Id, SE>(S, false, true, chr, origin, bdw, E, kept, KA(B, pool) + far_base, PG_LANE);
                     }
                 }
             };

@@ -1,5 +1,6 @@
 """Diagnostics: per-read event counts of a -DPG_DIAG build (LDS fills, seed-filter runs, candidate passes, evaluations)
-on the bench workload:  python scripts/diag_counts.py <lib.so> [reads] (PG_X=<n> selects -x n, PG_LEN the read length)"""
+on the bench workload:  python scripts/diag_counts.py <lib.so> [reads] (PG_X=<n> selects -x n, PG_LEN the read length;
+PG_DIAG_LAYOUT=2 for a -DPG_DIAG=2 build: the census of the evaluations)"""
 import ctypes as C
 import os
 import sys
@@ -27,9 +28,20 @@ L = binding.lib()
 L.pg_debug_read_reserved.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
 out = np.zeros(n, dtype=np.uint32)
 assert L.pg_debug_read_reserved(eng._h, db, out.ctypes.data, n) == 0
-names = ["LDS fills", "seed-filter runs", "candidate passes", "evaluations"]
-for k, nm in enumerate(names):
-    f = (out >> (8 * k)) & 0xff
-    hist = np.bincount(f, minlength=8)
-    print(f"{nm:18s} mean {f.mean():6.3f}  histogram 0..9: {(hist[:10] / n).round(3).tolist()}")
+if os.environ.get("PG_DIAG_LAYOUT") == "2":
+    # a -DPG_DIAG=2 build: the census of the evaluations, a nibble per count (Search::dg, pg_kernels.hip)
+    names = ["close-end evaluations", "far-end evaluations", "evaluations, no point", "rounds run", "rounds without a point",
+             "emit_runs calls", "quarter merges via LDS"]
+    for k, nm in enumerate(names):
+        f = (out >> (4 * k)) & 0xf
+        hist = np.bincount(f, minlength=16)
+        print(f"{nm:24s} mean {f.mean():6.3f}  histogram 0..15: {(hist[:16] / n).round(3).tolist()}")
+    ev = ((out & 0xf) + ((out >> 4) & 0xf)).astype(np.int64)
+    print(f"{'evaluations':24s} mean {ev.mean():6.3f}; rounds per evaluation {((out >> 12) & 0xf).sum() / max(int(ev.sum()), 1):.3f}")
+else:
+    names = ["LDS fills", "seed-filter runs", "candidate passes", "evaluations"]
+    for k, nm in enumerate(names):
+        f = (out >> (8 * k)) & 0xff
+        hist = np.bincount(f, minlength=8)
+        print(f"{nm:18s} mean {f.mean():6.3f}  histogram 0..9: {(hist[:10] / n).round(3).tolist()}")
 print("kernel ms", round(eng.last_stats()[0], 2))
