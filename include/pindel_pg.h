@@ -316,6 +316,36 @@ int  pg_device_batch_result_sizes(pg_ctx *ctx, pg_device_batch *b, uint64_t *n_c
  * downloadable, by either download. */
 int  pg_device_batch_download_device(pg_ctx *ctx, pg_device_batch *b, const pg_device_result *dst);
 
+/* ---- device classifier: deletion and short-insertion candidates per read ---------------------------------
+ * The per-read stage of SearchVariant::Search (src/search_variant.cpp:104-240) for its two kinds -- 0 = deletions
+ * (searchdeletions.cpp), 1 = short insertions (searchshortinsertions.cpp) -- on a searched device batch: for every read and
+ * kind the first PG_VARIANT_CANDS distinct (close point, far point) pairs that pass the mismatch, direction and geometry
+ * tests, in the order the reference's loops first visit them (mismatch budget, then close points ascending for a '+' anchor
+ * and descending for a '-' anchor, then far points from the highest index down), each with the fields the loop has computed
+ * when it reaches readTransgressesBinBoundaries.  The window-dependent tests (bin boundary, region, box) stay with the caller. */
+#define PG_VARIANT_CANDS 4
+#define PG_VARIANT_MORE 0x80u        /* count byte: qualifying pairs exist beyond the ones listed */
+#define PG_VARIANT_REF_END 0x1u      /* pg_variant_cand::flags: BPLeft or BPRight lies beyond the chromosome string (the loop marks
+                                      * the read Used and stops); the other fields are as they stood before the alignment */
+typedef struct {
+    uint32_t bp_left, bp_right;      /* BPLeft, BPRight after the left alignment's shift            */
+    int32_t  left, right;            /* Left, Right                                                 */
+    uint32_t indel_size;             /* IndelSize                                                   */
+    int32_t  nt_rot;                 /* kind 1: NT_str is the read's substring rotated LEFT by nt_rot places (negative: right), the
+                                      * net effect of GetRealStart4Insertion; reduce it modulo the string's length.  0 for kind 0 */
+    int16_t  bp;                     /* BP after the shift                                          */
+    uint16_t close_idx, far_idx;     /* the pair: indices of the expanded points in UP_Close / UP_Far */
+    uint8_t  flags;                  /* PG_VARIANT_*                                                */
+    uint8_t  reserved;               /* 0                                                           */
+} pg_variant_cand;
+/* cands: n_reads x 2 kinds x PG_VARIANT_CANDS records (unused ones zeroed); counts: n_reads x 2 bytes, the number listed in the
+ * low bits and PG_VARIANT_MORE.  A read without a far end, with its far end on another chromosome than its anchor, or with an
+ * anchor strand other than '+' / '-' gets count 0.  ReadLength, MAX_SNP_ERROR and the bases are those GetCloseEnd left (rc_flag).
+ * The batch must have been searched (PG_E_INVALID otherwise).  Synchronous; pg_last_search_stats then reports the kernel's
+ * HIP-event time.  The _device entry writes into device buffers of the caller under the rules of "device buffers in and out". */
+int  pg_device_batch_variant_candidates(pg_ctx *ctx, pg_device_batch *b, pg_variant_cand *cands, uint8_t *counts);
+int  pg_device_batch_variant_candidates_device(pg_ctx *ctx, pg_device_batch *b, pg_variant_cand *d_cands, uint8_t *d_counts);
+
 /* -q (dispersed duplications): per item i, contains_subseq_any_strand(query_i, window_i, 15) of Pindel's MEI search
  * (src/search_MEI_util.cpp:188-351, bit-exact), where query_i = query[query_off[i] .. query_off[i+1]) (at most
  * PG_MAX_READ_LEN bases) and window_i = the loaded chromosome chr_id[i] at padded (AbsLoc) positions

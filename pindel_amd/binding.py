@@ -71,6 +71,14 @@ POINT_DTYPE = np.dtype([("abs_loc", "<u4"), ("length", "<i2"), ("mismatches", "<
                         ("chr_id", "<i2"), ("direction", "S1"), ("strand", "S1")], align=True)
 WINDOW_DTYPE = np.dtype([("chr_id", "<i4"), ("start", "<i4"), ("end", "<i4")], align=True)
 assert RUN_DTYPE.itemsize == 12 and POINT_DTYPE.itemsize == 12 and WINDOW_DTYPE.itemsize == 12
+# pg_variant_cand: one candidate of the device classifier (Engine.variant_candidates); PG_VARIANT_CANDS per read and kind
+VARIANT_CANDS = 4
+VARIANT_MORE = 0x80
+VARIANT_REF_END = 1
+VARIANT_CAND_DTYPE = np.dtype([("bp_left", "<u4"), ("bp_right", "<u4"), ("left", "<i4"), ("right", "<i4"), ("indel_size", "<u4"),
+                               ("nt_rot", "<i4"), ("bp", "<i2"), ("close_idx", "<u2"), ("far_idx", "<u2"), ("flags", "u1"),
+                               ("reserved", "u1")], align=True)
+assert VARIANT_CAND_DTYPE.itemsize == 32
 
 # one record of the library's launch log (PgLaunchRec, pg_device.h); it keeps the first LAUNCH_LOG_CAP (pg_ctx::PG_LAUNCH_LOG_CAP)
 LaunchRec = namedtuple("LaunchRec", "kernel blocks ns id_bits mode default in_place")
@@ -86,7 +94,8 @@ EXPORTS = [
     "pg_device_batch_upload", "pg_device_batch_set_windows", "pg_device_batch_search", "pg_device_batch_download",
     "pg_device_batch_free", "pg_last_search_stats", "pg_device_batch_algorithmic_bytes",
     "pg_device_batch_candidates", "pg_device_batch_repack", "pg_device_batch_pack_search", "pg_dd_contains_batch",
-    "pg_load_reference_device", "pg_device_batch_upload_device", "pg_device_batch_result_sizes", "pg_device_batch_download_device"]
+    "pg_load_reference_device", "pg_device_batch_upload_device", "pg_device_batch_result_sizes", "pg_device_batch_download_device",
+    "pg_device_batch_variant_candidates", "pg_device_batch_variant_candidates_device"]
 
 
 def build(force: bool = False) -> str:
@@ -178,6 +187,8 @@ def lib():
     L.pg_device_batch_upload_device.argtypes = [vp, C.POINTER(PgReadBatch), C.POINTER(vp)]
     L.pg_device_batch_result_sizes.argtypes = [vp, vp, C.POINTER(u64), C.POINTER(u64)]
     L.pg_device_batch_download_device.argtypes = [vp, vp, C.POINTER(PgDeviceResult)]
+    L.pg_device_batch_variant_candidates.argtypes = [vp, vp, vp, vp]
+    L.pg_device_batch_variant_candidates_device.argtypes = [vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -351,6 +362,12 @@ def runs_from_tensor(t) -> np.ndarray:
     """The uint8[n_runs, 12] tensor of download_tensors as a RUN_DTYPE array (a CPU copy)."""
     a = np.ascontiguousarray(t.detach().cpu().numpy())
     return a.reshape(-1).view(RUN_DTYPE)
+
+
+def variant_cands_from_tensor(t) -> np.ndarray:
+    """The uint8[n, 256] tensor of variant_candidates_tensors as a VARIANT_CAND_DTYPE[n, 2, VARIANT_CANDS] array (a CPU copy)."""
+    a = np.ascontiguousarray(t.detach().cpu().numpy())
+    return a.reshape(-1).view(VARIANT_CAND_DTYPE).reshape(-1, 2, VARIANT_CANDS)
 
 
 class Engine:
@@ -587,6 +604,39 @@ class Engine:
             out.update(rc_flag=torch.empty(n, dtype=torch.uint8, device=dev), close_last=torch.empty(n, dtype=torch.int32, device=dev),
                        close_max=torch.empty(n, dtype=torch.int16, device=dev))
         self.download_into(dbatch, **out)
+        return out
+
+    def variant_candidates(self, dbatch):
+        """The device classifier on a searched device batch (pg_device_batch_variant_candidates): per read the first VARIANT_CANDS
+        deletion (kind 0) and short-insertion (kind 1) candidates in the order Pindel's loops first visit them.  Returns (cands,
+        counts): VARIANT_CAND_DTYPE[n, 2, VARIANT_CANDS] and uint8[n, 2] (low bits: pairs listed, VARIANT_MORE: more exist).
+        last_stats()[0] is then the kernel's HIP-event time."""
+        n = self._batch_n[dbatch.value]
+        cands = np.zeros((n, 2, VARIANT_CANDS), dtype=VARIANT_CAND_DTYPE)
+        counts = np.zeros((n, 2), dtype=np.uint8)
+        self._check(self._L.pg_device_batch_variant_candidates(self._h, dbatch, cands.ctypes.data if n else None,
+                                                               counts.ctypes.data if n else None))
+        return cands, counts
+
+    def variant_candidates_into(self, dbatch, cands, counts):
+        """pg_device_batch_variant_candidates_device into tensors of the caller's on this engine's GPU: cands uint8[n, 2 *
+        VARIANT_CANDS * 32] (the records' bytes), counts uint8[n, 2]."""
+        _, dev = self._torch_ready()
+        n = self._batch_n[dbatch.value]
+        for name, t, width in (("cands", cands, 2 * VARIANT_CANDS * 32), ("counts", counts, 2)):
+            if str(t.dtype) != "torch.uint8" or t.dim() != 2 or tuple(t.shape) != (n, width) or not t.is_contiguous() or str(t.device) != dev:
+                raise ValueError(f"{name}: a contiguous uint8[{n}, {width}] tensor on {dev} is expected")
+        self._check(self._L.pg_device_batch_variant_candidates_device(self._h, dbatch, cands.data_ptr() if n else None,
+                                                                      counts.data_ptr() if n else None))
+
+    def variant_candidates_tensors(self, dbatch):
+        """variant_candidates with the lists staying on the GPU: a dict of tensors on this engine's device -- cands uint8[n, 256]
+        (variant_cands_from_tensor views a CPU copy as VARIANT_CAND_DTYPE[n, 2, VARIANT_CANDS]) and counts uint8[n, 2]."""
+        torch, dev = self._torch_ready()
+        n = self._batch_n[dbatch.value]
+        out = dict(cands=torch.empty((n, 2 * VARIANT_CANDS * 32), dtype=torch.uint8, device=dev),
+                   counts=torch.empty((n, 2), dtype=torch.uint8, device=dev))
+        self.variant_candidates_into(dbatch, **out)
         return out
 
     def set_windows(self, dbatch, bd=None, bd_off=None):

@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdio>
 #include <fstream>
+#include <mutex>
 #include <sstream>
 #include <thread>
 
@@ -477,23 +478,10 @@ void Caller::note_close_mapped_all(std::vector<SplitRead> &reads)
     }
 }
 
-// GetRealStart4Insertion, src/pindel.cpp:2134-2162
-static void real_start_insertion(const std::string &chr, unsigned spacer, std::string &ins, unsigned &rs,
-                                 unsigned &re)
+VariantListStats &variant_list_stats()
 {
-    if (chr.size() < rs || chr.size() < re) return;
-    unsigned after = re + spacer;
-    while (chr[after] == ins[0] && chr[after] != 'N') {
-        ins = ins.substr(1) + ins[0];
-        after++;
-    }
-    re = after - spacer;
-    unsigned before = after - 1;
-    while (chr[before] == ins[ins.size() - 1] && chr[before] != 'N') {
-        ins = ins[ins.size() - 1] + ins.substr(0, ins.size() - 1);
-        before--;
-    }
-    rs = before - spacer;
+    static VariantListStats s;
+    return s;
 }
 
 // ---------------------------------------------------------------------------------
@@ -859,13 +847,51 @@ void Caller::search_variant(Ctx &c, int kind)
         printf("Reads already used: %u\nFar ends already mapped %u\nChecksum of far ends: %u\n", used, far, bp_sum);
     }
 
+    // The window-dependent tail of the loop body for one qualifying pair: the read takes the pair's values, then
+    // readTransgressesBinBoundaries, the region and the box decide whether it is Used
+    auto tail = [&](SplitRead &r, unsigned ri, const VariantPair &p, BoxSink &sink) {
+        apply_variant_pair(r, p);
+        if (p.c.flags & PG_VARIANT_REF_END) {
+            r.Used = true;
+        } else if (transgresses(r, c.win_end)) {
+            r.Used = true;      // saveReadForNextCycle: the copy is cleared before reuse
+        } else if (r.BPLeft + 1 >= c.region_start && r.BPLeft + 1 <= c.region_end) {
+            unsigned box = (unsigned)((int)r.BPLeft / (int)BoxSize);
+            if (box < c.NumBoxes) {
+                sink[box].push_back(ri);
+                r.Used = true;
+            }
+        }
+    };
+    VariantListStats &stats = variant_list_stats();
+    std::mutex stats_mu;
     classify_reads(reads.size(), boxes, [&](unsigned lo_, unsigned hi_, BoxSink &sink) {
+    uint64_t fallbacks = 0;
+    std::vector<uint32_t> visits;
+    VariantPair pair;
     for (unsigned ri = lo_; ri < hi_; ri++) {
         SplitRead &r = reads[ri];
         if (r.FragName != r.FarFragName) continue;
         if (r.Used || r.UP_Far.empty()) continue;
         const bool plus = r.MatchedD == '+';
         if (!plus && r.MatchedD != '-') continue;
+        if (r.VarCands) {
+            // the pairs come from the device classifier's list, in the loop's first-visit order; the pair search below runs
+            // only for a read whose list ends, with more pairs behind it, before one of them has made the read Used
+            if (stats.log_visits) {
+                const uint32_t v[7] = { r.VarIndex, (uint32_t)kind, c.win_end, c.region_start, c.region_end, c.NumBoxes, BoxSize };
+                visits.insert(visits.end(), v, v + 7);
+            }
+            const uint8_t count = r.VarCounts[kind];
+            const unsigned n_listed = std::min<unsigned>(count & ~PG_VARIANT_MORE, PG_VARIANT_CANDS);
+            bool listed_ok = true;
+            for (unsigned j = 0; j < n_listed && !r.Used && listed_ok; j++) {
+                listed_ok = variant_pair_from_cand(r, kind, r.VarCands[kind * PG_VARIANT_CANDS + j], pair);
+                if (listed_ok) tail(r, ri, pair, sink);
+            }
+            if (r.Used || (listed_ok && !(count & PG_VARIANT_MORE))) continue;
+            fallbacks++;
+        }
         const FarByLength by_len(r);
         const FarByLoc by_loc(r);
         for (short budget = 0; budget <= r.MAX_SNP_ERROR && !r.Used; budget++) {
@@ -894,66 +920,16 @@ void Caller::search_variant(Ctx &c, int kind)
                     const UniquePoint &fp = r.UP_Far[fi];
                     if (fp.Mismatches > budget) continue;
                     if (fp.Mismatches + cp.Mismatches > budget) continue;
-                    if (fp.Direction != (plus ? '-' : '+')) continue;
-                    bool ok;
-                    if (kind == 0) {
-                        ok = plus ? (fp.LengthStr + cp.LengthStr == r.getReadLength() && fp.AbsLoc > cp.AbsLoc + 1)
-                                  : (cp.LengthStr + fp.LengthStr == r.getReadLength() && cp.AbsLoc > fp.AbsLoc + 1);
-                    } else {
-                        ok = plus ? (fp.AbsLoc == cp.AbsLoc + 1 && cp.LengthStr + fp.LengthStr < r.getReadLength())
-                                  : (cp.AbsLoc == fp.AbsLoc + 1 && fp.LengthStr + cp.LengthStr < r.getReadLength());
-                    }
-                    if (!ok) continue;
-                    if (plus) {
-                        r.Left = (int)(cp.AbsLoc - cp.LengthStr + 1);
-                        r.Right = (int)(fp.AbsLoc + fp.LengthStr - 1);
-                        r.BP = (short)(cp.LengthStr - 1);
-                    } else {
-                        r.Left = (int)(fp.AbsLoc - fp.LengthStr + 1);
-                        r.Right = (int)(cp.AbsLoc + cp.LengthStr - 1);
-                        r.BP = (short)(fp.LengthStr - 1);
-                    }
-                    if (kind == 0) {
-                        r.IndelSize = (unsigned)((r.Right - r.Left) - r.getReadLengthMinus());
-                        r.NT_str = "";
-                    } else {
-                        r.IndelSize = (unsigned)(r.getReadLengthMinus() - (r.Right - r.Left));
-                        r.NT_str = plus ? sub(reverse_complement(r.UnmatchedSeq), r.BP + 1, r.IndelSize)
-                                        : sub(r.UnmatchedSeq, r.BP + 1, r.IndelSize);
-                    }
-                    if (plus) {
-                        r.BPLeft = cp.AbsLoc - S.spacer;
-                        r.BPRight = fp.AbsLoc - S.spacer;
-                    } else {
-                        r.BPLeft = fp.AbsLoc - S.spacer;
-                        r.BPRight = cp.AbsLoc - S.spacer;
-                    }
-                    unsigned real_l = r.BPLeft, real_r = r.BPRight;
-                    if (ref.size() < real_l || ref.size() < real_r) {
-                        r.Used = true;
-                        break;
-                    }
-                    if (!r.NT_str.empty()) real_start_insertion(ref, S.spacer, r.NT_str, real_l, real_r);
-                    else real_start_deletion(ref, S.spacer, real_l, real_r);
-                    short diff = (short)(r.BPLeft - real_l);
-                    diff = !((r.BP - 1) < diff) ? diff : (short)(r.BP - 1);
-                    if (diff > 0) {
-                        r.BP -= diff;
-                        r.BPLeft -= diff;
-                        r.BPRight -= diff;
-                    }
-                    if (transgresses(r, c.win_end)) {
-                        r.Used = true;      // saveReadForNextCycle: the copy is cleared before reuse
-                    } else if (r.BPLeft + 1 >= c.region_start && r.BPLeft + 1 <= c.region_end) {
-                        unsigned box = (unsigned)((int)r.BPLeft / (int)BoxSize);
-                        if (box < c.NumBoxes) {
-                            sink[box].push_back(ri);
-                            r.Used = true;
-                        }
-                    }
+                    if (!variant_pair(r, kind, ci, fi, ref, S.spacer, pair)) continue;
+                    tail(r, ri, pair, sink);
                 }
             }
         }
+    }
+    if (fallbacks || !visits.empty()) {
+        std::lock_guard<std::mutex> lk(stats_mu);
+        stats.fallbacks += fallbacks;
+        stats.visits.insert(stats.visits.end(), visits.begin(), visits.end());
     }
     });
     if (kind == 0) sort_output_d(c, boxes);

@@ -73,6 +73,11 @@ struct SplitRead {                // the SPLIT_READ fields used downstream, src/
     int LeftMostPos = 0;
     int chr_id = -1;
     std::map<std::string, unsigned> SampleName2Number;
+    // The device classifier's lists for this read (pg_variant_cand, pindel_pg.h): 2 kinds x PG_VARIANT_CANDS records and the 2 count
+    // bytes; VarIndex = the read's index in the caller's arrays.  Null: SearchVariant's stage searches the pairs itself.
+    const pg_variant_cand *VarCands = nullptr;
+    const uint8_t *VarCounts = nullptr;
+    uint32_t VarIndex = 0;
     short getReadLength() const { return ReadLength; }
     short getReadLengthMinus() const { return (short)(ReadLength - 1); }
 };
@@ -190,6 +195,17 @@ int load_pindel_inputs(const std::string &config, const std::string &reads_path,
                        std::vector<SplitRead> &out, std::string &err);
 
 std::string reverse_complement(const std::string &s);
+
+// SearchVariant's stage fed from candidate lists (SplitRead::VarCands): what the last run did with them.
+//   fallbacks   reads whose list was exhausted without making them Used and carried PG_VARIANT_MORE: the pair search ran for them
+//   visits      with log_visits set, seven values per (read, kind) whose list was consulted: VarIndex, kind, and what the
+//               window-dependent tests compare against -- win_end, region_start, region_end, NumBoxes, BoxSize
+struct VariantListStats {
+    uint64_t fallbacks = 0;
+    bool log_visits = false;
+    std::vector<uint32_t> visits;
+};
+VariantListStats &variant_list_stats();      // (reset by the caller before a run; filled under a lock)
 
 // MergeInterChr (src/pindel.cpp:1514-1579): the calls of int_path (the lines of <prefix>_INT) paired within 10 bp on
 // both sides, or alone with support >= 4, written to final_path (created empty when there is no call)

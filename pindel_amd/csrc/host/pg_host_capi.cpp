@@ -22,6 +22,7 @@
 #include "pindel_pg.h"
 
 using namespace pgh;
+using namespace pgh::detail;
 
 static std::string g_err;
 
@@ -66,10 +67,11 @@ static std::string str_or_empty(const char *s) { return s ? s : ""; }
  * repairs: int-pairs, depth-mapq and bed0 act as on the command line; inv-pairs, with normal_samples and
  * bam_config, discovers the discordant read pairs of every window in those BAMs (-A 0) for the inversion filter.
  */
-int pgh_call_from_points(const char *fasta_path, const char *reads_path, const char *out_prefix,
-                         const pgh_settings *st, uint32_t n_reads,
-                         const uint64_t *close_off, const pg_point *close_pts,
-                         const uint64_t *far_off, const pg_point *far_pts, const uint8_t *rc_flag)
+static int call_from_points(const char *fasta_path, const char *reads_path, const char *out_prefix,
+                            const pgh_settings *st, uint32_t n_reads,
+                            const uint64_t *close_off, const pg_point *close_pts,
+                            const uint64_t *far_off, const pg_point *far_pts, const uint8_t *rc_flag,
+                            const pg_variant_cand *var_cands, const uint8_t *var_counts)
 {
     std::vector<Chromosome> genome;
     if (load_fasta(fasta_path, genome, st->spacer, g_err)) return -1;
@@ -133,10 +135,132 @@ int pgh_call_from_points(const char *fasta_path, const char *reads_path, const c
             }
             for (uint64_t q = close_off[i]; q < close_off[i + 1]; q++) r.UP_Close.push_back(to_unique_point(close_pts[q]));
             for (uint64_t q = far_off[i]; q < far_off[i + 1]; q++) r.UP_Far.push_back(to_unique_point(far_pts[q]));
+            if (var_cands) {
+                r.VarCands = var_cands + (size_t)i * 2 * PG_VARIANT_CANDS;
+                r.VarCounts = var_counts + (size_t)i * 2;
+                r.VarIndex = i;
+            }
         }
         return 0;
     };
+    VariantListStats &vs = variant_list_stats();
+    vs.fallbacks = 0;
+    vs.visits.clear();
+    vs.log_visits = var_cands != nullptr;
     return run_pipeline(genome, plan, all, S, out_prefix, attach, pgh::NoFarSearch(), g_err, nullptr, pairs_of);
+}
+
+int pgh_call_from_points(const char *fasta_path, const char *reads_path, const char *out_prefix,
+                         const pgh_settings *st, uint32_t n_reads,
+                         const uint64_t *close_off, const pg_point *close_pts,
+                         const uint64_t *far_off, const pg_point *far_pts, const uint8_t *rc_flag)
+{
+    return call_from_points(fasta_path, reads_path, out_prefix, st, n_reads, close_off, close_pts, far_off, far_pts, rc_flag, nullptr, nullptr);
+}
+
+/*
+ * pgh_call_from_points with the per-read stage of the deletion and short-insertion classifiers fed from candidate lists
+ * (pg_variant_cand, pindel_pg.h; what pg_device_batch_variant_candidates or pgh_variant_candidates yield): var_cands holds
+ * n_reads x 2 kinds x PG_VARIANT_CANDS records, var_counts n_reads x 2 count bytes.  Each classifier takes a read's pairs
+ * from its list, in order, and applies the window-dependent tests to them; a read whose list is exhausted, with
+ * PG_VARIANT_MORE set, before a pair has made it Used goes through the pair search instead (pgh_last_variant_fallbacks
+ * counts those).  The reports are the bytes pgh_call_from_points writes.
+ */
+int pgh_call_from_points_candidates(const char *fasta_path, const char *reads_path, const char *out_prefix,
+                                    const pgh_settings *st, uint32_t n_reads,
+                                    const uint64_t *close_off, const pg_point *close_pts,
+                                    const uint64_t *far_off, const pg_point *far_pts, const uint8_t *rc_flag,
+                                    const pg_variant_cand *var_cands, const uint8_t *var_counts)
+{
+    if (!var_cands || !var_counts) {
+        g_err = "pgh_call_from_points_candidates: null candidate arrays";
+        return -1;
+    }
+    return call_from_points(fasta_path, reads_path, out_prefix, st, n_reads, close_off, close_pts, far_off, far_pts, rc_flag, var_cands, var_counts);
+}
+
+/* reads of the last pgh_call_from_points_candidates that went through the pair search after their list (both kinds, all windows) */
+uint64_t pgh_last_variant_fallbacks(void) { return variant_list_stats().fallbacks; }
+
+/*
+ * Test hook: every consultation of a list in the last pgh_call_from_points_candidates, seven values each -- read index, kind,
+ * and what the window-dependent tests compared against: the window's end, the region's start and end, the number of boxes and
+ * the box size.  Returns the number of consultations (only cap are written); their order is not defined.
+ */
+uint64_t pgh_last_variant_visits(uint32_t *out, uint64_t cap)
+{
+    const std::vector<uint32_t> &v = variant_list_stats().visits;
+    const uint64_t n = v.size() / 7;
+    if (out) std::copy(v.begin(), v.begin() + (size_t)std::min(n, cap) * 7, out);
+    return n;
+}
+
+/*
+ * The per-read stage of SearchVariant::Search as candidate lists (pg_variant_cand, pindel_pg.h), on the host: for every read and
+ * both kinds the first PG_VARIANT_CANDS distinct qualifying pairs in the order the loops first visit them, and PG_VARIANT_MORE
+ * when there are more.  Written as those loops -- mismatch budget, close points, every far point from the highest index down --
+ * around the function the classifier itself uses for a pair: the reference the device classifier is tested against.
+ * chr_seq[c]: the padded chromosome (spacer N's on both sides), chr_len[c] its length.  The reads come as they were handed to the
+ * search (seq, seq_off, strand, chr_id) with its rc flags and the expanded points (CSR); ReadLength and MAX_SNP_ERROR are taken
+ * from the read as rc_flag applications of setUnmatchedSeq(ReverseComplement()) leave it.  mm500 = g_maxMismatch.
+ * cands: n_reads x 2 x PG_VARIANT_CANDS records (unused ones zeroed), counts: n_reads x 2.
+ */
+int pgh_variant_candidates(int32_t n_chr, const char *const *chr_seq, const uint64_t *chr_len, uint32_t spacer, uint32_t n_reads,
+                           const uint8_t *seq, const uint64_t *seq_off, const uint8_t *strand, const int32_t *chr_id, const uint8_t *rc_flag,
+                           const uint64_t *close_off, const pg_point *close_pts, const uint64_t *far_off, const pg_point *far_pts,
+                           const uint32_t *mm500, pg_variant_cand *cands, uint8_t *counts)
+{
+    std::vector<std::string> ref((size_t)std::max(n_chr, 0));
+    for (int32_t c = 0; c < n_chr; c++) ref[(size_t)c].assign(chr_seq[c], (size_t)chr_len[c]);
+    memset(cands, 0, (size_t)n_reads * 2 * PG_VARIANT_CANDS * sizeof(pg_variant_cand));
+    memset(counts, 0, (size_t)n_reads * 2);
+    pg_adapter::parallel_ranges(n_reads, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; i++) {
+            if (far_off[i + 1] == far_off[i] || close_off[i + 1] == close_off[i]) continue;
+            if (strand[i] != '+' && strand[i] != '-') continue;
+            if (chr_id[i] < 0 || chr_id[i] >= n_chr) continue;
+            if (far_pts[far_off[i]].chr_id != chr_id[i]) continue;           // FragName != FarFragName (UpdateFarFragName: the first far point's)
+            SplitRead r;
+            r.UnmatchedSeq.assign((const char *)seq + seq_off[i], (size_t)(seq_off[i + 1] - seq_off[i]));
+            pg_adapter::apply_rc_flag(r, rc_flag[i]);
+            r.ReadLength = (short)r.UnmatchedSeq.size();
+            r.MAX_SNP_ERROR = (short)mm500[std::min<int>(r.ReadLength, 499)];
+            r.MatchedD = (char)strand[i];
+            for (uint64_t q = close_off[i]; q < close_off[i + 1]; q++) r.UP_Close.push_back(to_unique_point(close_pts[q]));
+            for (uint64_t q = far_off[i]; q < far_off[i + 1]; q++) r.UP_Far.push_back(to_unique_point(far_pts[q]));
+            const bool plus = r.MatchedD == '+';
+            const int nc = (int)r.UP_Close.size(), nf = (int)r.UP_Far.size();
+            for (int kind = 0; kind < 2; kind++) {
+                pg_variant_cand *list = cands + (i * 2 + (size_t)kind) * PG_VARIANT_CANDS;
+                std::vector<std::pair<int, int>> seen;                       // pairs listed so far (a pair comes round again at every higher budget)
+                unsigned n_listed = 0;
+                bool more = false, stop = false;
+                VariantPair pair;
+                for (short budget = 0; budget <= r.MAX_SNP_ERROR && !stop; budget++)
+                    for (int k = 0; k < nc && !stop; k++) {
+                        const int ci = plus ? k : nc - 1 - k;
+                        const UniquePoint &cp = r.UP_Close[ci];
+                        if (cp.Mismatches > budget) continue;
+                        for (int fi = nf - 1; fi >= 0 && !stop; fi--) {
+                            const UniquePoint &fp = r.UP_Far[fi];
+                            if (fp.Mismatches > budget) continue;
+                            if (fp.Mismatches + cp.Mismatches > budget) continue;
+                            if (std::find(seen.begin(), seen.end(), std::make_pair(ci, fi)) != seen.end()) continue;
+                            if (!variant_pair(r, kind, ci, fi, ref[(size_t)chr_id[i]], spacer, pair)) continue;
+                            if (n_listed == PG_VARIANT_CANDS) {
+                                more = stop = true;
+                                break;
+                            }
+                            seen.push_back(std::make_pair(ci, fi));
+                            list[n_listed++] = pair.c;
+                            if (pair.c.flags & PG_VARIANT_REF_END) stop = true;   // the loop marks the read Used: no later pair is tried
+                        }
+                    }
+                counts[i * 2 + (size_t)kind] = (uint8_t)(n_listed | (more ? PG_VARIANT_MORE : 0u));
+            }
+        }
+    });
+    return 0;
 }
 
 /* "int-pairs,depth-mapq" / "all" -> the bits of pgh_settings.repairs; -1 = an unknown name or an empty list (pgh_last_error) */

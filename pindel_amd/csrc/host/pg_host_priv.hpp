@@ -95,6 +95,137 @@ inline void real_start_deletion(const std::string &chr, unsigned spacer, unsigne
     re = pos - spacer;
 }
 
+// GetRealStart4Insertion, src/pindel.cpp:2134-2162
+inline void real_start_insertion(const std::string &chr, unsigned spacer, std::string &ins, unsigned &rs, unsigned &re)
+{
+    if (chr.size() < rs || chr.size() < re) return;
+    unsigned after = re + spacer;
+    while (chr[after] == ins[0] && chr[after] != 'N') {
+        ins = ins.substr(1) + ins[0];
+        after++;
+    }
+    re = after - spacer;
+    unsigned before = after - 1;
+    while (chr[before] == ins[ins.size() - 1] && chr[before] != 'N') {
+        ins = ins[ins.size() - 1] + ins.substr(0, ins.size() - 1);
+        before--;
+    }
+    rs = before - spacer;
+}
+
+// One (close point, far point) pair of SearchVariant::Search (src/search_variant.cpp:120-214; kind 0 = deletions, 1 = short
+// insertions): the direction and geometry tests, then everything the loop computes for the pair before
+// readTransgressesBinBoundaries -- Left, Right, BP, IndelSize, NT_str, BPLeft / BPRight left-aligned against the reference and
+// the `diff` shift -- as a pg_variant_cand (pindel_pg.h) plus the string.  false: the pair does not qualify.  With
+// PG_VARIANT_REF_END set the loop marks the read Used and stops; the fields are then those before the alignment.
+struct VariantPair {
+    pg_variant_cand c;
+    std::string nt;               // NT_str as the alignment left it
+};
+inline bool variant_pair(const SplitRead &r, int kind, int ci, int fi, const std::string &ref, unsigned spacer, VariantPair &out)
+{
+    const bool plus = r.MatchedD == '+';
+    const UniquePoint &cp = r.UP_Close[ci], &fp = r.UP_Far[fi];
+    if (fp.Direction != (plus ? '-' : '+')) return false;
+    bool ok;
+    if (kind == 0) {
+        ok = plus ? (fp.LengthStr + cp.LengthStr == r.getReadLength() && fp.AbsLoc > cp.AbsLoc + 1)
+                  : (cp.LengthStr + fp.LengthStr == r.getReadLength() && cp.AbsLoc > fp.AbsLoc + 1);
+    } else {
+        ok = plus ? (fp.AbsLoc == cp.AbsLoc + 1 && cp.LengthStr + fp.LengthStr < r.getReadLength())
+                  : (cp.AbsLoc == fp.AbsLoc + 1 && fp.LengthStr + cp.LengthStr < r.getReadLength());
+    }
+    if (!ok) return false;
+    int Left, Right;
+    short BP;
+    if (plus) {
+        Left = (int)(cp.AbsLoc - cp.LengthStr + 1);
+        Right = (int)(fp.AbsLoc + fp.LengthStr - 1);
+        BP = (short)(cp.LengthStr - 1);
+    } else {
+        Left = (int)(fp.AbsLoc - fp.LengthStr + 1);
+        Right = (int)(cp.AbsLoc + cp.LengthStr - 1);
+        BP = (short)(fp.LengthStr - 1);
+    }
+    unsigned IndelSize;
+    if (kind == 0) {
+        IndelSize = (unsigned)((Right - Left) - r.getReadLengthMinus());
+        out.nt.clear();
+    } else {
+        IndelSize = (unsigned)(r.getReadLengthMinus() - (Right - Left));
+        out.nt = plus ? sub(reverse_complement(r.UnmatchedSeq), BP + 1, IndelSize) : sub(r.UnmatchedSeq, BP + 1, IndelSize);
+    }
+    unsigned BPLeft, BPRight;
+    if (plus) {
+        BPLeft = cp.AbsLoc - spacer;
+        BPRight = fp.AbsLoc - spacer;
+    } else {
+        BPLeft = fp.AbsLoc - spacer;
+        BPRight = cp.AbsLoc - spacer;
+    }
+    pg_variant_cand &c = out.c;
+    c = pg_variant_cand();
+    c.close_idx = (uint16_t)ci;
+    c.far_idx = (uint16_t)fi;
+    c.left = Left;
+    c.right = Right;
+    c.indel_size = IndelSize;
+    unsigned real_l = BPLeft, real_r = BPRight;
+    if (ref.size() < real_l || ref.size() < real_r) {
+        c.flags = PG_VARIANT_REF_END;
+    } else {
+        if (!out.nt.empty()) {
+            real_start_insertion(ref, spacer, out.nt, real_l, real_r);
+            // left rotations = how far the right end moved; right rotations = the distance the second loop walked back from it
+            c.nt_rot = (int32_t)(real_r - BPRight) - (int32_t)(real_r - 1 - real_l);
+        } else {
+            real_start_deletion(ref, spacer, real_l, real_r);
+        }
+        short diff = (short)(BPLeft - real_l);
+        diff = !((BP - 1) < diff) ? diff : (short)(BP - 1);
+        if (diff > 0) {
+            BP -= diff;
+            BPLeft -= diff;
+            BPRight -= diff;
+        }
+    }
+    c.bp = BP;
+    c.bp_left = BPLeft;
+    c.bp_right = BPRight;
+    return true;
+}
+
+// A listed candidate back to what variant_pair yields: NT_str is rebuilt from the read (cut as the loop cuts it, then rotated).
+// false: the record does not fit the read (indices outside its point lists).
+inline bool variant_pair_from_cand(const SplitRead &r, int kind, const pg_variant_cand &c, VariantPair &out)
+{
+    if (c.close_idx >= r.UP_Close.size() || c.far_idx >= r.UP_Far.size()) return false;
+    out.c = c;
+    out.nt.clear();
+    if (kind == 1) {
+        const bool plus = r.MatchedD == '+';
+        const short bp0 = (short)((plus ? r.UP_Close[c.close_idx].LengthStr : r.UP_Far[c.far_idx].LengthStr) - 1);
+        out.nt = plus ? sub(reverse_complement(r.UnmatchedSeq), bp0 + 1, c.indel_size) : sub(r.UnmatchedSeq, bp0 + 1, c.indel_size);
+        const long len = (long)out.nt.size();
+        if (len > 1) {
+            const long rot = (((long)c.nt_rot % len) + len) % len;
+            std::rotate(out.nt.begin(), out.nt.begin() + rot, out.nt.end());
+        }
+    }
+    return true;
+}
+
+inline void apply_variant_pair(SplitRead &r, const VariantPair &p)
+{
+    r.Left = p.c.left;
+    r.Right = p.c.right;
+    r.BP = p.c.bp;
+    r.IndelSize = p.c.indel_size;
+    r.NT_str = p.nt;
+    r.BPLeft = p.c.bp_left;
+    r.BPRight = p.c.bp_right;
+}
+
 // ReportEvent, src/pindel.cpp:2059-2093 (Min_Filter_Ratio = 0.5)
 inline bool report_event(const std::vector<SplitRead> &g, unsigned s, unsigned e)
 {

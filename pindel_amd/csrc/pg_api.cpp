@@ -296,6 +296,7 @@ struct pg_device_batch {
     PgSoaIn h_soa;                     // ... and what was copied there last (the source of an asynchronous copy)
     bool soa_uploaded = false;
     long long exact_n = -1;            // host copy of the counter; -1: not read back (the exact kernel is launched regardless)
+    bool searched = false;             // close end + far end have run on the batch: its output records and run pool hold a result
 };
 
 struct pg_result {
@@ -1096,6 +1097,7 @@ int run_search(pg_ctx *ctx, pg_device_batch *b, int mode, bool pack = false)
         if (worst <= b->pool_shard_cap) {
             ctx->last_ms = ms;
             ctx->last_runs = total;
+            if (mode == PG_MODE_BOTH) b->searched = true;
             return PG_OK;
         }
         // overflow: grow the pool and redo the launch
@@ -2251,6 +2253,63 @@ int pg_device_batch_download_device(pg_ctx *ctx, pg_device_batch *b, const pg_de
         (dst->close_max && (rc = check_device_ptr(ctx, dst->close_max, n * 2, 2, "pg_device_result.close_max"))))
         return rc;
     return download_device(ctx, b, dst);
+}
+
+// ---- the device classifier (pg_variant.hip): deletion and short-insertion candidates of a searched batch
+// d_cands / d_counts: device memory (checked by the caller where it is the user's).  The launch is recorded in the launch log and
+// timed with HIP events like a search's.
+static int variant_candidates(pg_ctx *ctx, pg_device_batch *b, pg_variant_cand *d_cands, uint8_t *d_counts)
+{
+    if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
+    if (int rc = stale_batch(ctx, b)) return rc;
+    ctx->last_ms = 0.0;
+    if (!b->n) return PG_OK;                                  // nothing is launched for an empty batch
+    if (!b->searched) return fail(ctx, PG_E_INVALID, "the batch has not been searched: no close and far ends to classify");
+    const PgDevRef ref = dev_ref(ctx);
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if (pg_variant_launch(&ref, b->out_rec, b->pool, (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS, b->seq, b->seq_off, b->strand,
+                          b->chr, ctx->d_mm, ctx->prm.spacer, b->n, d_cands, d_counts, ctx->stream))
+        return fail(ctx, PG_E_DEVICE, "launching the variant-candidate kernel failed");
+    PgLaunchRec rec{};
+    rec.kernel = PG_KERNEL_VARIANT;
+    rec.blocks = 4;                                           // reads (waves) per workgroup
+    log_launch(ctx, rec);
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->last_ms = ms;
+    return PG_OK;
+}
+
+int pg_device_batch_variant_candidates_device(pg_ctx *ctx, pg_device_batch *b, pg_variant_cand *d_cands, uint8_t *d_counts)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    const size_t n = b->n;
+    int rc;
+    if ((rc = check_device_ptr(ctx, d_cands, n * 2 * PG_VARIANT_CANDS * sizeof(pg_variant_cand), 4, "variant candidates: cands")) ||
+        (rc = check_device_ptr(ctx, d_counts, n * 2, 1, "variant candidates: counts")))
+        return rc;
+    return variant_candidates(ctx, b, d_cands, d_counts);
+}
+
+int pg_device_batch_variant_candidates(pg_ctx *ctx, pg_device_batch *b, pg_variant_cand *cands, uint8_t *counts)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    const size_t n = b->n;
+    if (n && (!cands || !counts)) return fail(ctx, PG_E_INVALID, "variant candidates: null output array");
+    if (!n || !b->searched) return variant_candidates(ctx, b, nullptr, nullptr);      // (nothing to do, or the refusal)
+    DevTemps tmp(ctx, b);
+    const size_t cand_bytes = n * 2 * PG_VARIANT_CANDS * sizeof(pg_variant_cand);
+    pg_variant_cand *d_cands = (pg_variant_cand *)tmp.take(cand_bytes);
+    uint8_t *d_counts = (uint8_t *)tmp.take(n * 2);
+    if (!d_cands || !d_counts) return fail(ctx, PG_E_NOMEM, "device memory for the variant candidates");
+    if (int rc = variant_candidates(ctx, b, d_cands, d_counts)) return rc;
+    HIP_TRY(ctx, hipMemcpy(cands, d_cands, cand_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(counts, d_counts, n * 2, hipMemcpyDeviceToHost));
+    return PG_OK;
 }
 
 void pg_device_batch_free(pg_ctx *ctx, pg_device_batch *b)

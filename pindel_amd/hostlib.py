@@ -80,6 +80,12 @@ def lib():
         L.pgh_call_from_points.argtypes = [
             C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(HostSettings), C.c_uint32,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pgh_call_from_points_candidates.argtypes = L.pgh_call_from_points.argtypes + [C.c_void_p, C.c_void_p]
+        L.pgh_last_variant_fallbacks.restype = C.c_uint64
+        L.pgh_last_variant_fallbacks.argtypes = []
+        L.pgh_last_variant_visits.restype = C.c_uint64
+        L.pgh_last_variant_visits.argtypes = [C.c_void_p, C.c_uint64]
+        L.pgh_variant_candidates.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32] + [C.c_void_p] * 12
         L.pgh_region_depth.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.POINTER(C.c_double)]
         L.pgh_region_depth_mapq.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.c_uint32, C.POINTER(C.c_double)]
         L.pgh_depth_ratio_mapq.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_uint32,
@@ -205,9 +211,69 @@ def depth_rule_td(ratios):
     return bool(lib().pgh_depth_rule_td(len(ratios), arr))
 
 
+# pg_variant_cand (include/pindel_pg.h): one candidate of the deletion / short-insertion classifiers
+VARIANT_CANDS = 4
+VARIANT_MORE = 0x80
+VARIANT_REF_END = 1
+VARIANT_CAND_DTYPE = np.dtype([("bp_left", "<u4"), ("bp_right", "<u4"), ("left", "<i4"), ("right", "<i4"), ("indel_size", "<u4"),
+                               ("nt_rot", "<i4"), ("bp", "<i2"), ("close_idx", "<u2"), ("far_idx", "<u2"), ("flags", "u1"),
+                               ("reserved", "u1")], align=True)
+assert VARIANT_CAND_DTYPE.itemsize == 32
+
+
+def variant_candidates(chroms, seq, seq_off, anchor_strand, chr_id, rc_flag, close_off, close_pts, far_off, far_pts, max_mismatch,
+                       spacer=100000):
+    """The per-read stage of the deletion and short-insertion classifiers as candidate lists, computed on the host with the
+    classifier's own loops (pgh_variant_candidates): the reference the device classifier (Engine.variant_candidates) is compared
+    with.  chroms: [(name, padded bytes)] as hostio.load_fasta returns; the reads as they were handed to the search, the search's
+    rc flags and its expanded points (CSR, 12-byte pg_point records); max_mismatch: g_maxMismatch (500 entries).
+    Returns (cands, counts): VARIANT_CAND_DTYPE[n, 2, VARIANT_CANDS] and uint8[n, 2] (low bits: pairs listed, VARIANT_MORE: more exist)."""
+    L = lib()
+    n = len(seq_off) - 1
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    strand = np.ascontiguousarray(anchor_strand, dtype=np.uint8)
+    chr_id = np.ascontiguousarray(chr_id, dtype=np.int32)
+    rc_flag = np.ascontiguousarray(rc_flag, dtype=np.uint8)
+    close_off = np.ascontiguousarray(close_off, dtype=np.uint64)
+    far_off = np.ascontiguousarray(far_off, dtype=np.uint64)
+    close_pts = np.ascontiguousarray(close_pts)
+    far_pts = np.ascontiguousarray(far_pts)
+    assert close_pts.dtype.itemsize == 12 and far_pts.dtype.itemsize == 12
+    mm = np.ascontiguousarray(max_mismatch, dtype=np.uint32)
+    assert len(mm) >= 500 and len(strand) == n and len(chr_id) == n and len(rc_flag) == n
+    bufs = [bytes(s) for _, s in chroms]
+    ptrs = (C.c_char_p * len(bufs))(*bufs)
+    lens = (C.c_uint64 * len(bufs))(*[len(b) for b in bufs])
+    cands = np.zeros((n, 2, VARIANT_CANDS), dtype=VARIANT_CAND_DTYPE)
+    counts = np.zeros((n, 2), dtype=np.uint8)
+    rc = L.pgh_variant_candidates(len(bufs), ptrs, lens, int(spacer), n, seq.ctypes.data, seq_off.ctypes.data, strand.ctypes.data,
+                                  chr_id.ctypes.data, rc_flag.ctypes.data, close_off.ctypes.data, close_pts.ctypes.data,
+                                  far_off.ctypes.data, far_pts.ctypes.data, mm.ctypes.data, cands.ctypes.data, counts.ctypes.data)
+    if rc:
+        raise RuntimeError("pgh_variant_candidates: " + (L.pgh_last_error() or b"").decode())
+    return cands, counts
+
+
+def last_variant_fallbacks():
+    """Reads of the last call_from_points(variant_candidates=...) whose list ran out, with VARIANT_MORE set, before one of its
+    pairs had made the read Used: they went through the classifier's own pair search."""
+    return int(lib().pgh_last_variant_fallbacks())
+
+
+def last_variant_visits():
+    """Test hook: the list consultations of the last call_from_points(variant_candidates=...), a uint32[k, 7] array of (read
+    index, kind, window end, region start, region end, number of boxes, box size) in no particular order."""
+    L = lib()
+    k = int(L.pgh_last_variant_visits(None, 0))
+    out = np.zeros((max(k, 1), 7), dtype=np.uint32)
+    L.pgh_last_variant_visits(out.ctypes.data, k)
+    return out[:k]
+
+
 def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pts, far_off, far_pts,
                      rc_flag, region=None, include_bed=None, exclude_bed=None, reads_config=None, normal_samples=None,
-                     bam_config=None, repairs=None):
+                     bam_config=None, repairs=None, variant_candidates=None):
     """Classify + report (_D, _SI, _TD, _INV) from per-read UP_Close / UP_Far points (CSR over
     all reads of the file, 12-byte pg_point records).  settings.analyze_li / settings.report_close_mapped
     add <out_prefix>_LI / <out_prefix>_CloseEndMapped, settings.report_interchromosomal <out_prefix>_INT and
@@ -220,7 +286,9 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
     -N changes nothing (text input).  Both override the settings' fields when given.  repairs (--repair; see repairs_mask):
     opt-in fixes of reference defects, replacing the settings' field when given: int-pairs, depth-mapq and bed0 as on the
     command line; inv-pairs, with normal_samples and bam_config, discovers the discordant read pairs of every window in those
-    BAMs for the inversion filter."""
+    BAMs for the inversion filter.  variant_candidates: (cands, counts) as variant_candidates() or Engine.variant_candidates
+    return them, for the same reads -- the deletion and short-insertion classifiers then take each read's pairs from its list
+    and search only where a list runs out (last_variant_fallbacks); the reports are the same bytes."""
     L = lib()
     tmp_cfg = None
     if reads_config is not None and not isinstance(reads_config, (str, bytes, os.PathLike)):
@@ -243,11 +311,18 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
     far_pts = np.ascontiguousarray(far_pts)
     rc_flag = np.ascontiguousarray(rc_flag, dtype=np.uint8)
     assert close_pts.dtype.itemsize == 12 and far_pts.dtype.itemsize == 12
+    args = (str(fasta).encode(), _enc(reads_txt), str(out_prefix).encode(), C.byref(settings), len(close_off) - 1,
+            close_off.ctypes.data, close_pts.ctypes.data, far_off.ctypes.data, far_pts.ctypes.data, rc_flag.ctypes.data)
     try:
-        rc = L.pgh_call_from_points(str(fasta).encode(), _enc(reads_txt), str(out_prefix).encode(),
-                                    C.byref(settings), len(close_off) - 1, close_off.ctypes.data,
-                                    close_pts.ctypes.data, far_off.ctypes.data, far_pts.ctypes.data,
-                                    rc_flag.ctypes.data)
+        if variant_candidates is None:
+            rc = L.pgh_call_from_points(*args)
+        else:
+            n = len(close_off) - 1
+            cands = np.ascontiguousarray(variant_candidates[0], dtype=VARIANT_CAND_DTYPE)
+            counts = np.ascontiguousarray(variant_candidates[1], dtype=np.uint8)
+            if cands.size != n * 2 * VARIANT_CANDS or counts.size != n * 2:
+                raise ValueError(f"variant_candidates: {cands.size} records and {counts.size} counts for {n} reads")
+            rc = L.pgh_call_from_points_candidates(*args, cands.ctypes.data, counts.ctypes.data)
     finally:
         if tmp_cfg:
             os.unlink(tmp_cfg)
