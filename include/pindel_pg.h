@@ -346,6 +346,38 @@ typedef struct {
 int  pg_device_batch_variant_candidates(pg_ctx *ctx, pg_device_batch *b, pg_variant_cand *cands, uint8_t *counts);
 int  pg_device_batch_variant_candidates_device(pg_ctx *ctx, pg_device_batch *b, pg_variant_cand *d_cands, uint8_t *d_counts);
 
+/* ---- device classifier: DI, tandem-duplication and inversion candidates per read ---------------------------
+ * The per-read stage of the five other classifiers process_window runs, on a searched device batch.  The kinds continue
+ * the numbering of 0 and 1; the record is pg_variant_cand with the fields the classifier has assigned when it reaches the
+ * window-dependent tail (bin boundary, region, box), which stays with the caller:
+ *   PG_SV_DI     searchIndels (src/search_deletions_nt.cpp): one pair, UP_Close.back() and UP_Far.back()
+ *   PG_SV_TD     searchTandemDuplications: the first PG_VARIANT_CANDS pairs in first-visit order (budget, close points ascending
+ *                for a '+' anchor and descending for '-', far points from the highest index down for '+' and from the lowest up
+ *                for '-') after LeftMostTD; a pair with BPLeft == 0 is not listed
+ *   PG_SV_TD_NT  searchTandemDuplicationsNT: one pair
+ *   PG_SV_INV    searchInversions: the first PG_VARIANT_CANDS pairs (geometries 0 and 2: close points descending, far points
+ *                ascending; 1 and 3: the reverse) after LeftMostINV
+ *   PG_SV_INV_NT searchInversionsNT: one pair
+ * nt_rot carries NT_size for the three kinds with non-template bases (0 for TD and INV); NT_str is cut from the read by the
+ * host.  flags: PG_VARIANT_REF_END = LeftMostTD / LeftMostINV took their out-of-range branch (the record then carries BPLeft =
+ * BPRight = BP = 1, the read is Used and the box test still runs); bits 4-5 = the inversion geometry of PG_SV_INV and
+ * PG_SV_INV_NT (0: '+' anchor, far end right; 1: '+', far end left; 2: '-', far end left; 3: '-', far end right). */
+enum { PG_SV_DI = 2, PG_SV_TD = 3, PG_SV_TD_NT = 4, PG_SV_INV = 5, PG_SV_INV_NT = 6 };
+#define PG_SV_KINDS 5                /* count bytes per read: DI, TD, TD_NT, INV, INV_NT */
+#define PG_SV_SLOTS 11               /* records per read: DI, TD x 4, TD_NT, INV x 4, INV_NT */
+#define PG_SV_GEO_SHIFT 4            /* pg_variant_cand::flags bits 4-5: the inversion geometry */
+#define PG_SV_MAX_INVERSION_SIZE (1 << 30)
+typedef struct {
+    double  seq_error_rate;          /* -e */
+    int32_t min_num_matched_bases;   /* -d */
+    int32_t min_inversion_size;      /* -v: used as unsigned; negative or above PG_SV_MAX_INVERSION_SIZE is PG_E_INVALID */
+} pg_sv_params;
+/* cands: n_reads x PG_SV_SLOTS records (unused ones zeroed); counts: n_reads x PG_SV_KINDS bytes as for the kinds 0 and 1.
+ * Same rules as pg_device_batch_variant_candidates: a searched batch, synchronous, the HIP-event time in pg_last_search_stats. */
+int  pg_device_batch_sv_candidates(pg_ctx *ctx, pg_device_batch *b, const pg_sv_params *p, pg_variant_cand *cands, uint8_t *counts);
+int  pg_device_batch_sv_candidates_device(pg_ctx *ctx, pg_device_batch *b, const pg_sv_params *p, pg_variant_cand *d_cands,
+                                          uint8_t *d_counts);
+
 /* -q (dispersed duplications): per item i, contains_subseq_any_strand(query_i, window_i, 15) of Pindel's MEI search
  * (src/search_MEI_util.cpp:188-351, bit-exact), where query_i = query[query_off[i] .. query_off[i+1]) (at most
  * PG_MAX_READ_LEN bases) and window_i = the loaded chromosome chr_id[i] at padded (AbsLoc) positions

@@ -79,6 +79,32 @@ VARIANT_CAND_DTYPE = np.dtype([("bp_left", "<u4"), ("bp_right", "<u4"), ("left",
                                ("nt_rot", "<i4"), ("bp", "<i2"), ("close_idx", "<u2"), ("far_idx", "<u2"), ("flags", "u1"),
                                ("reserved", "u1")], align=True)
 assert VARIANT_CAND_DTYPE.itemsize == 32
+# the five other classifiers (Engine.sv_candidates): kinds PG_SV_*, SV_KINDS count bytes and SV_SLOTS records per read --
+# DI, TD x VARIANT_CANDS, TD_NT, INV x VARIANT_CANDS, INV_NT; SV_SLOT[kind] = the kind's first record, SV_COUNT[kind] its count byte
+SV_DI, SV_TD, SV_TD_NT, SV_INV, SV_INV_NT = 2, 3, 4, 5, 6
+SV_KINDS = 5
+SV_SLOTS = 3 + 2 * VARIANT_CANDS
+SV_SLOT = {SV_DI: 0, SV_TD: 1, SV_TD_NT: 1 + VARIANT_CANDS, SV_INV: 2 + VARIANT_CANDS, SV_INV_NT: 2 + 2 * VARIANT_CANDS}
+SV_COUNT = {k: k - SV_DI for k in SV_SLOT}
+SV_GEO_SHIFT = 4                        # flags bits 4-5: the inversion geometry of SV_INV / SV_INV_NT records
+SV_MAX_INVERSION_SIZE = 1 << 30
+
+
+class SvParams(C.Structure):
+    """pg_sv_params: the settings the five classifiers read (-e, -d, -v)"""
+    _fields_ = [("seq_error_rate", C.c_double), ("min_num_matched_bases", C.c_int32), ("min_inversion_size", C.c_int32)]
+
+
+def sv_params(settings=None):
+    """A pg_sv_params from None (Pindel's defaults), a (rate, -d, -v) tuple, an SvParams, or anything with the attributes
+    seq_error_rate, min_num_matched_bases and min_inversion_size (hostlib.HostSettings)."""
+    if settings is None:
+        return SvParams(0.01, 30, 50)
+    if isinstance(settings, SvParams):
+        return settings
+    if isinstance(settings, (tuple, list)):
+        return SvParams(float(settings[0]), int(settings[1]), int(settings[2]))
+    return SvParams(float(settings.seq_error_rate), int(settings.min_num_matched_bases), int(settings.min_inversion_size))
 
 # one record of the library's launch log (PgLaunchRec, pg_device.h); it keeps the first LAUNCH_LOG_CAP (pg_ctx::PG_LAUNCH_LOG_CAP)
 LaunchRec = namedtuple("LaunchRec", "kernel blocks ns id_bits mode default in_place")
@@ -95,7 +121,8 @@ EXPORTS = [
     "pg_device_batch_free", "pg_last_search_stats", "pg_device_batch_algorithmic_bytes",
     "pg_device_batch_candidates", "pg_device_batch_repack", "pg_device_batch_pack_search", "pg_dd_contains_batch",
     "pg_load_reference_device", "pg_device_batch_upload_device", "pg_device_batch_result_sizes", "pg_device_batch_download_device",
-    "pg_device_batch_variant_candidates", "pg_device_batch_variant_candidates_device"]
+    "pg_device_batch_variant_candidates", "pg_device_batch_variant_candidates_device",
+    "pg_device_batch_sv_candidates", "pg_device_batch_sv_candidates_device"]
 
 
 def build(force: bool = False) -> str:
@@ -189,6 +216,8 @@ def lib():
     L.pg_device_batch_download_device.argtypes = [vp, vp, C.POINTER(PgDeviceResult)]
     L.pg_device_batch_variant_candidates.argtypes = [vp, vp, vp, vp]
     L.pg_device_batch_variant_candidates_device.argtypes = [vp, vp, vp, vp]
+    L.pg_device_batch_sv_candidates.argtypes = [vp, vp, vp, vp, vp]
+    L.pg_device_batch_sv_candidates_device.argtypes = [vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -362,6 +391,12 @@ def runs_from_tensor(t) -> np.ndarray:
     """The uint8[n_runs, 12] tensor of download_tensors as a RUN_DTYPE array (a CPU copy)."""
     a = np.ascontiguousarray(t.detach().cpu().numpy())
     return a.reshape(-1).view(RUN_DTYPE)
+
+
+def sv_cands_from_tensor(t) -> np.ndarray:
+    """The uint8[n, SV_SLOTS * 32] tensor of sv_candidates_tensors as a VARIANT_CAND_DTYPE[n, SV_SLOTS] array (a CPU copy)."""
+    a = np.ascontiguousarray(t.cpu().numpy())
+    return a.reshape(-1).view(VARIANT_CAND_DTYPE).reshape(-1, SV_SLOTS)
 
 
 def variant_cands_from_tensor(t) -> np.ndarray:
@@ -637,6 +672,41 @@ class Engine:
         out = dict(cands=torch.empty((n, 2 * VARIANT_CANDS * 32), dtype=torch.uint8, device=dev),
                    counts=torch.empty((n, 2), dtype=torch.uint8, device=dev))
         self.variant_candidates_into(dbatch, **out)
+        return out
+
+    def sv_candidates(self, dbatch, settings=None):
+        """The device classifier of the five other kinds on a searched device batch (pg_device_batch_sv_candidates): per read the
+        DI, TD_NT and INV_NT candidate and the first VARIANT_CANDS tandem-duplication and inversion candidates in the order Pindel's
+        loops first visit them.  settings: see sv_params().  Returns (cands, counts): VARIANT_CAND_DTYPE[n, SV_SLOTS] (SV_SLOT[kind] =
+        the kind's first record) and uint8[n, SV_KINDS] (SV_COUNT[kind]; low bits: pairs listed, VARIANT_MORE: more exist)."""
+        n = self._batch_n[dbatch.value]
+        prm = sv_params(settings)
+        cands = np.zeros((n, SV_SLOTS), dtype=VARIANT_CAND_DTYPE)
+        counts = np.zeros((n, SV_KINDS), dtype=np.uint8)
+        self._check(self._L.pg_device_batch_sv_candidates(self._h, dbatch, C.addressof(prm), cands.ctypes.data if n else None,
+                                                          counts.ctypes.data if n else None))
+        return cands, counts
+
+    def sv_candidates_into(self, dbatch, cands, counts, settings=None):
+        """pg_device_batch_sv_candidates_device into tensors of the caller's on this engine's GPU: cands uint8[n, SV_SLOTS * 32]
+        (the records' bytes), counts uint8[n, SV_KINDS]."""
+        _, dev = self._torch_ready()
+        n = self._batch_n[dbatch.value]
+        prm = sv_params(settings)
+        for name, t, width in (("cands", cands, SV_SLOTS * 32), ("counts", counts, SV_KINDS)):
+            if str(t.dtype) != "torch.uint8" or t.dim() != 2 or tuple(t.shape) != (n, width) or not t.is_contiguous() or str(t.device) != dev:
+                raise ValueError(f"{name}: a contiguous uint8[{n}, {width}] tensor on {dev} is expected")
+        self._check(self._L.pg_device_batch_sv_candidates_device(self._h, dbatch, C.addressof(prm), cands.data_ptr() if n else None,
+                                                                 counts.data_ptr() if n else None))
+
+    def sv_candidates_tensors(self, dbatch, settings=None):
+        """sv_candidates with the lists staying on the GPU: a dict of tensors on this engine's device -- cands uint8[n, SV_SLOTS *
+        32] (sv_cands_from_tensor views a CPU copy as VARIANT_CAND_DTYPE[n, SV_SLOTS]) and counts uint8[n, SV_KINDS]."""
+        torch, dev = self._torch_ready()
+        n = self._batch_n[dbatch.value]
+        out = dict(cands=torch.empty((n, SV_SLOTS * 32), dtype=torch.uint8, device=dev),
+                   counts=torch.empty((n, SV_KINDS), dtype=torch.uint8, device=dev))
+        self.sv_candidates_into(dbatch, settings=settings, **out)
         return out
 
     def set_windows(self, dbatch, bd=None, bd_off=None):

@@ -941,50 +941,35 @@ void Caller::search_indels(Ctx &c)
 {
     std::vector<SplitRead> &reads = *c.reads;
     std::vector<std::vector<unsigned>> boxes(c.NumBoxes);
+    const pg_sv_params prm = { S.Seq_Error_Rate, S.Min_Num_Matched_Bases, S.MIN_IndelSize_Inversion };
+    std::mutex stats_mu;
     classify_reads(reads.size(), boxes, [&](unsigned lo_, unsigned hi_, BoxSink &sink) {
+    ListLog log;
+    VariantPair pair;
     for (unsigned ri = lo_; ri < hi_; ri++) {
         SplitRead &r = reads[ri];
         if (r.Used || r.UP_Far.empty() || r.FragName != r.FarFragName) continue;
-        const UniquePoint &cp = r.UP_Close.back();
-        const UniquePoint &fp = r.UP_Far.back();
-        if (fp.Mismatches + cp.Mismatches > (short)(1 + S.Seq_Error_Rate * (fp.LengthStr + cp.LengthStr))) continue;
-        const bool plus = r.MatchedD == '+';
-        if (!plus && r.MatchedD != '-') continue;
-        if (fp.Direction != (plus ? '-' : '+')) continue;
-        if (!(fp.LengthStr + cp.LengthStr < r.getReadLength() &&
-              fp.LengthStr + cp.LengthStr >= S.Min_Num_Matched_Bases))
-            continue;
-        if (plus) {
-            if (!(fp.AbsLoc > cp.AbsLoc + 1)) continue;
-            r.Left = (int)(cp.AbsLoc - cp.LengthStr + 1);
-            r.Right = (int)(fp.AbsLoc + fp.LengthStr - 1);
-            r.BP = (short)(cp.LengthStr - 1);
-            r.NT_size = (unsigned short)(r.getReadLength() - fp.LengthStr - cp.LengthStr);
-            r.NT_str = sub(reverse_complement(r.UnmatchedSeq), r.BP + 1, r.NT_size);
-            r.IndelSize = (unsigned)((r.Right - r.Left) + r.NT_size - r.getReadLengthMinus());
-            r.BPLeft = cp.AbsLoc - S.spacer;
-            r.BPRight = fp.AbsLoc - S.spacer;
-        } else {
-            if (!(cp.AbsLoc > fp.AbsLoc + 1)) continue;
-            r.Left = (int)(fp.AbsLoc - fp.LengthStr + 1);
-            r.Right = (int)(cp.AbsLoc + cp.LengthStr - 1);
-            r.BP = (short)(fp.LengthStr - 1);
-            r.NT_size = (unsigned short)(r.getReadLength() - cp.LengthStr - fp.LengthStr);
-            r.NT_str = sub(r.UnmatchedSeq, r.BP + 1, r.NT_size);
-            r.IndelSize = (unsigned)((r.Right - r.Left) - r.getReadLengthMinus() + r.NT_size);
-            r.BPLeft = fp.AbsLoc - S.spacer;
-            r.BPRight = cp.AbsLoc - S.spacer;
-        }
-        if (transgresses(r, c.win_end)) {
-            r.Used = true;
-        } else if (r.BPLeft + 1 >= c.region_start && r.BPLeft + 1 <= c.region_end) {
-            unsigned box = (unsigned)((int)r.BPLeft / (int)BoxSize);
-            if (box < c.NumBoxes) {
-                sink[box].push_back(ri);
+        auto tail = [&](const VariantPair &) {
+            if (transgresses(r, c.win_end)) {
                 r.Used = true;
+            } else if (r.BPLeft + 1 >= c.region_start && r.BPLeft + 1 <= c.region_end) {
+                unsigned box = (unsigned)((int)r.BPLeft / (int)BoxSize);
+                if (box < c.NumBoxes) {
+                    sink[box].push_back(ri);
+                    r.Used = true;
+                }
             }
+        };
+        if (r.SvCands) {
+            log.visit(r.VarIndex, PG_SV_DI, c.win_end, c.region_start, c.region_end, c.NumBoxes, BoxSize);
+            if (!sv_consult_list(r, PG_SV_DI, pair, tail)) continue;
+            log.fallbacks++;
         }
+        if (!sv_pair_di(r, prm, S.spacer, pair)) continue;
+        apply_sv_pair(r, PG_SV_DI, pair);
+        tail(pair);
     }
+    log.flush(stats_mu);
     });
     sort_output_di(c, boxes);
 }

@@ -78,6 +78,10 @@ struct SplitRead {                // the SPLIT_READ fields used downstream, src/
     const pg_variant_cand *VarCands = nullptr;
     const uint8_t *VarCounts = nullptr;
     uint32_t VarIndex = 0;
+    // ... and its lists for the five other classifiers: PG_SV_SLOTS records and PG_SV_KINDS count bytes.  Null:
+    // those classifiers search the pairs themselves.
+    const pg_variant_cand *SvCands = nullptr;
+    const uint8_t *SvCounts = nullptr;
     short getReadLength() const { return ReadLength; }
     short getReadLengthMinus() const { return (short)(ReadLength - 1); }
 };

@@ -71,7 +71,8 @@ static int call_from_points(const char *fasta_path, const char *reads_path, cons
                             const pgh_settings *st, uint32_t n_reads,
                             const uint64_t *close_off, const pg_point *close_pts,
                             const uint64_t *far_off, const pg_point *far_pts, const uint8_t *rc_flag,
-                            const pg_variant_cand *var_cands, const uint8_t *var_counts)
+                            const pg_variant_cand *var_cands, const uint8_t *var_counts,
+                            const pg_variant_cand *sv_cands = nullptr, const uint8_t *sv_counts = nullptr)
 {
     std::vector<Chromosome> genome;
     if (load_fasta(fasta_path, genome, st->spacer, g_err)) return -1;
@@ -138,15 +139,19 @@ static int call_from_points(const char *fasta_path, const char *reads_path, cons
             if (var_cands) {
                 r.VarCands = var_cands + (size_t)i * 2 * PG_VARIANT_CANDS;
                 r.VarCounts = var_counts + (size_t)i * 2;
-                r.VarIndex = i;
             }
+            if (sv_cands) {
+                r.SvCands = sv_cands + (size_t)i * PG_SV_SLOTS;
+                r.SvCounts = sv_counts + (size_t)i * PG_SV_KINDS;
+            }
+            r.VarIndex = i;
         }
         return 0;
     };
     VariantListStats &vs = variant_list_stats();
     vs.fallbacks = 0;
     vs.visits.clear();
-    vs.log_visits = var_cands != nullptr;
+    vs.log_visits = var_cands != nullptr || sv_cands != nullptr;
     return run_pipeline(genome, plan, all, S, out_prefix, attach, pgh::NoFarSearch(), g_err, nullptr, pairs_of);
 }
 
@@ -177,6 +182,25 @@ int pgh_call_from_points_candidates(const char *fasta_path, const char *reads_pa
         return -1;
     }
     return call_from_points(fasta_path, reads_path, out_prefix, st, n_reads, close_off, close_pts, far_off, far_pts, rc_flag, var_cands, var_counts);
+}
+
+/*
+ * ... with the lists of the five other classifiers as well (what pg_device_batch_sv_candidates or pgh_sv_candidates
+ * yield): sv_cands holds n_reads x PG_SV_SLOTS records, sv_counts n_reads x PG_SV_KINDS count bytes.  Either pair of arrays may be
+ * null: those classifiers then search the pairs themselves.  With a -v outside [0, PG_SV_MAX_INVERSION_SIZE] the inversion
+ * classifiers do not consult their lists.  The fallback counter and the visit hook cover all seven kinds.
+ */
+int pgh_call_from_points_lists(const char *fasta_path, const char *reads_path, const char *out_prefix, const pgh_settings *st,
+                               uint32_t n_reads, const uint64_t *close_off, const pg_point *close_pts, const uint64_t *far_off,
+                               const pg_point *far_pts, const uint8_t *rc_flag, const pg_variant_cand *var_cands, const uint8_t *var_counts,
+                               const pg_variant_cand *sv_cands, const uint8_t *sv_counts)
+{
+    if ((var_cands == nullptr) != (var_counts == nullptr) || (sv_cands == nullptr) != (sv_counts == nullptr) || (!var_cands && !sv_cands)) {
+        g_err = "pgh_call_from_points_lists: candidate arrays come in pairs, and at least one pair";
+        return -1;
+    }
+    return call_from_points(fasta_path, reads_path, out_prefix, st, n_reads, close_off, close_pts, far_off, far_pts, rc_flag, var_cands, var_counts,
+                            sv_cands, sv_counts);
 }
 
 /* reads of the last pgh_call_from_points_candidates that went through the pair search after their list (both kinds, all windows) */
@@ -257,6 +281,99 @@ int pgh_variant_candidates(int32_t n_chr, const char *const *chr_seq, const uint
                         }
                     }
                 counts[i * 2 + (size_t)kind] = (uint8_t)(n_listed | (more ? PG_VARIANT_MORE : 0u));
+            }
+        }
+    });
+    return 0;
+}
+
+/*
+ * The per-read stage of the five other classifiers as candidate lists, on the host: plain loops over mismatch
+ * budget, close points and every far point in the classifier's own order around the functions the classifiers use for a pair
+ * (pg_host_priv.hpp) -- the reference the device classifier (pg_sv_kernel) is tested against.  Inputs as pgh_variant_candidates,
+ * plus prm.  cands: n_reads x PG_SV_SLOTS records (unused ones zeroed), counts: n_reads x PG_SV_KINDS.  -1: prm is refused.
+ */
+int pgh_sv_candidates(int32_t n_chr, const char *const *chr_seq, const uint64_t *chr_len, uint32_t spacer, uint32_t n_reads,
+                      const uint8_t *seq, const uint64_t *seq_off, const uint8_t *strand, const int32_t *chr_id, const uint8_t *rc_flag,
+                      const uint64_t *close_off, const pg_point *close_pts, const uint64_t *far_off, const pg_point *far_pts,
+                      const uint32_t *mm500, const pg_sv_params *prm, pg_variant_cand *cands, uint8_t *counts)
+{
+    if (!prm || prm->min_inversion_size < 0 || prm->min_inversion_size > PG_SV_MAX_INVERSION_SIZE) {
+        g_err = "pgh_sv_candidates: the minimum inversion size must lie in [0, 2^30]";
+        return -1;
+    }
+    std::vector<std::string> ref((size_t)std::max(n_chr, 0));
+    for (int32_t c = 0; c < n_chr; c++) ref[(size_t)c].assign(chr_seq[c], (size_t)chr_len[c]);
+    memset(cands, 0, (size_t)n_reads * PG_SV_SLOTS * sizeof(pg_variant_cand));
+    memset(counts, 0, (size_t)n_reads * PG_SV_KINDS);
+    const unsigned MIN = (unsigned)prm->min_inversion_size;
+    pg_adapter::parallel_ranges(n_reads, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; i++) {
+            if (far_off[i + 1] == far_off[i] || close_off[i + 1] == close_off[i]) continue;
+            if (strand[i] != '+' && strand[i] != '-') continue;
+            if (chr_id[i] < 0 || chr_id[i] >= n_chr) continue;
+            if (far_pts[far_off[i]].chr_id != chr_id[i]) continue;           // FragName != FarFragName
+            SplitRead r;
+            r.UnmatchedSeq.assign((const char *)seq + seq_off[i], (size_t)(seq_off[i + 1] - seq_off[i]));
+            pg_adapter::apply_rc_flag(r, rc_flag[i]);
+            r.ReadLength = (short)r.UnmatchedSeq.size();
+            r.MAX_SNP_ERROR = (short)mm500[std::min<int>(r.ReadLength, 499)];
+            r.MatchedD = (char)strand[i];
+            for (uint64_t q = close_off[i]; q < close_off[i + 1]; q++) r.UP_Close.push_back(to_unique_point(close_pts[q]));
+            for (uint64_t q = far_off[i]; q < far_off[i + 1]; q++) r.UP_Far.push_back(to_unique_point(far_pts[q]));
+            const std::string &chr = ref[(size_t)chr_id[i]];
+            const bool plus = r.MatchedD == '+';
+            const int nc = (int)r.UP_Close.size(), nf = (int)r.UP_Far.size();
+            pg_variant_cand *rec = cands + i * PG_SV_SLOTS;
+            uint8_t *cnt = counts + i * PG_SV_KINDS;
+            VariantPair pair;
+            if (sv_pair_di(r, *prm, spacer, pair)) {
+                rec[sv_slot_base()[0]] = pair.c;
+                cnt[0] = 1;
+            }
+            if (sv_pair_td_nt(r, *prm, spacer, pair)) {
+                rec[sv_slot_base()[2]] = pair.c;
+                cnt[2] = 1;
+            }
+            if (sv_inv_nt_read_ok(r, *prm))
+                for (int which = 0; which < 2 && !cnt[4]; which++)
+                    if (sv_pair_inv_nt(r, *prm, which, spacer, pair)) {
+                        rec[sv_slot_base()[4]] = pair.c;
+                        cnt[4] = 1;
+                    }
+            // the two kinds with loops: first visits of distinct pairs, in the loops' order
+            const int geo = sv_inv_read_ok(r) ? sv_inv_geometry(r, MIN) : -1;
+            for (int kind : { (int)PG_SV_TD, (int)PG_SV_INV }) {
+                if (kind == PG_SV_INV && geo < 0) continue;
+                const bool close_asc = kind == PG_SV_TD ? plus : (geo == 1 || geo == 3);
+                const bool far_asc = kind == PG_SV_TD ? !plus : (geo == 0 || geo == 2);
+                pg_variant_cand *list = rec + sv_slot_base()[kind - PG_SV_DI];
+                std::vector<std::pair<int, int>> seen;
+                unsigned n_listed = 0;
+                bool more = false, stop = false;
+                for (short budget = 0; budget <= r.MAX_SNP_ERROR && !stop; budget++)
+                    for (int k = 0; k < nc && !stop; k++) {
+                        const int ci = close_asc ? k : nc - 1 - k;
+                        const UniquePoint &cp = r.UP_Close[ci];
+                        if (cp.Mismatches > budget) continue;
+                        for (int j = 0; j < nf && !stop; j++) {
+                            const int fi = far_asc ? j : nf - 1 - j;
+                            const UniquePoint &fp = r.UP_Far[fi];
+                            if (fp.Mismatches > budget) continue;
+                            if (fp.Mismatches + cp.Mismatches > budget) continue;
+                            if (std::find(seen.begin(), seen.end(), std::make_pair(ci, fi)) != seen.end()) continue;
+                            if (!(kind == PG_SV_TD ? sv_pair_td(r, ci, fi, chr, spacer, pair) : sv_pair_inv(r, geo, ci, fi, MIN, chr, spacer, pair)))
+                                continue;
+                            if (n_listed == PG_VARIANT_CANDS) {
+                                more = stop = true;
+                                break;
+                            }
+                            seen.push_back(std::make_pair(ci, fi));
+                            list[n_listed++] = pair.c;
+                            if (pair.c.flags & PG_VARIANT_REF_END) stop = true;   // the read is Used: no later pair is tried
+                        }
+                    }
+                cnt[kind - PG_SV_DI] = (uint8_t)(n_listed | (more ? PG_VARIANT_MORE : 0u));
             }
         }
     });

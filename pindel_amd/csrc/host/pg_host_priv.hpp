@@ -9,6 +9,7 @@
 #include <unordered_set>
 #include <utility>
 #include <cstdlib>
+#include <mutex>
 #include <thread>
 #include <utility>
 #include <vector>
@@ -225,6 +226,398 @@ inline void apply_variant_pair(SplitRead &r, const VariantPair &p)
     r.BPLeft = p.c.bp_left;
     r.BPRight = p.c.bp_right;
 }
+
+// ---- the five other classifiers: one function per (close point, far point) pair, used by the classifiers'
+// loops (pg_host.cpp, pg_host_sv.cpp) and by pgh_sv_candidates.  Each yields a pg_variant_cand with what the classifier has
+// assigned when it reaches the window-dependent tail, and NT_str where the kind has one.  false: the pair does not qualify.
+
+// LeftMostTD, src/search_tandem_duplications.cpp:194-222, on the values.  true: the out-of-range branch (the read is Used)
+inline bool left_most_td(const std::string &ref, unsigned spacer, unsigned &BPLeft, unsigned &BPRight, short &BP)
+{
+    unsigned pos = BPLeft + spacer, orig = pos, end = BPRight + spacer - 1;
+    unsigned n = (unsigned)ref.size();
+    if (pos >= n || end >= n) {
+        BPLeft = 1;
+        BPRight = 1;
+        BP = 1;
+        return true;
+    }
+    while (ref[pos] == ref[end]) {
+        --pos;
+        --end;
+    }
+    int diff = (int)(orig - pos);
+    if (diff > 0) {
+        if (diff >= BP) diff = BP - 1;
+        BPLeft -= diff;
+        BPRight -= diff;
+        BP -= (short)diff;
+    }
+    return false;
+}
+
+// LeftMostINV, src/search_inversions.cpp:285-318, on the values
+inline bool left_most_inv(const std::string &ref, unsigned spacer, bool plus, short read_length, unsigned &BPLeft, unsigned &BPRight, short &BP)
+{
+    unsigned n = (unsigned)ref.size();
+    unsigned pos = BPLeft + spacer + 1, orig = pos, end = BPRight + spacer - 1;
+    if (n <= pos + spacer || n <= orig + spacer) {
+        BPLeft = 1;
+        BPRight = 1;
+        BP = 1;
+        return true;
+    }
+    while (ref[pos] == rc4n(ref[end])) {
+        ++pos;
+        --end;
+    }
+    short diff = (short)(pos - orig);
+    if (diff > 0) {
+        if (plus) {
+            if (diff >= BP) diff = (short)(BP - 1);
+        } else {
+            if (diff + BP >= read_length) diff = (short)(read_length - BP - 1);
+            BPLeft += diff;
+            BPRight -= diff;
+            BP += diff;
+        }
+    }
+    return false;
+}
+
+// the mismatch budget of the kinds with non-template bases: (short)(1 + Seq_Error_Rate * length sum), the product rounded on its own
+inline short sv_nt_budget(double rate, int len_sum)
+{
+    volatile double prod = rate * len_sum;
+    return (short)(1 + prod);
+}
+
+// -v as the lists take it: used as unsigned, so a negative value or one above 2^30 lets the unsigned sums wrap and the two
+// distance tests of searchInversionsNT overlap; no list is made or consulted then
+inline bool sv_list_usable(const Settings &S) { return S.MIN_IndelSize_Inversion >= 0 && S.MIN_IndelSize_Inversion <= PG_SV_MAX_INVERSION_SIZE; }
+
+inline const int *sv_slot_base()
+{
+    static const int base[PG_SV_KINDS] = { 0, 1, 1 + PG_VARIANT_CANDS, 2 + PG_VARIANT_CANDS, 2 + 2 * PG_VARIANT_CANDS };
+    return base;
+}
+
+// searchIndels, src/search_deletions_nt.cpp:40-120: UP_Close.back() with UP_Far.back()
+inline bool sv_pair_di(const SplitRead &r, const pg_sv_params &prm, unsigned spacer, VariantPair &out)
+{
+    const UniquePoint &cp = r.UP_Close.back();
+    const UniquePoint &fp = r.UP_Far.back();
+    if (fp.Mismatches + cp.Mismatches > sv_nt_budget(prm.seq_error_rate, fp.LengthStr + cp.LengthStr)) return false;
+    const bool plus = r.MatchedD == '+';
+    if (!plus && r.MatchedD != '-') return false;
+    if (fp.Direction != (plus ? '-' : '+')) return false;
+    if (!(fp.LengthStr + cp.LengthStr < r.getReadLength() && fp.LengthStr + cp.LengthStr >= prm.min_num_matched_bases)) return false;
+    pg_variant_cand &c = out.c;
+    c = pg_variant_cand();
+    unsigned short NT_size;
+    if (plus) {
+        if (!(fp.AbsLoc > cp.AbsLoc + 1)) return false;
+        c.left = (int)(cp.AbsLoc - cp.LengthStr + 1);
+        c.right = (int)(fp.AbsLoc + fp.LengthStr - 1);
+        c.bp = (short)(cp.LengthStr - 1);
+        NT_size = (unsigned short)(r.getReadLength() - fp.LengthStr - cp.LengthStr);
+        out.nt = sub(reverse_complement(r.UnmatchedSeq), c.bp + 1, NT_size);
+        c.indel_size = (unsigned)((c.right - c.left) + NT_size - r.getReadLengthMinus());
+        c.bp_left = cp.AbsLoc - spacer;
+        c.bp_right = fp.AbsLoc - spacer;
+    } else {
+        if (!(cp.AbsLoc > fp.AbsLoc + 1)) return false;
+        c.left = (int)(fp.AbsLoc - fp.LengthStr + 1);
+        c.right = (int)(cp.AbsLoc + cp.LengthStr - 1);
+        c.bp = (short)(fp.LengthStr - 1);
+        NT_size = (unsigned short)(r.getReadLength() - cp.LengthStr - fp.LengthStr);
+        out.nt = sub(r.UnmatchedSeq, c.bp + 1, NT_size);
+        c.indel_size = (unsigned)((c.right - c.left) - r.getReadLengthMinus() + NT_size);
+        c.bp_left = fp.AbsLoc - spacer;
+        c.bp_right = cp.AbsLoc - spacer;
+    }
+    c.nt_rot = NT_size;
+    c.close_idx = (uint16_t)(r.UP_Close.size() - 1);
+    c.far_idx = (uint16_t)(r.UP_Far.size() - 1);
+    return true;
+}
+
+// searchTandemDuplications, src/search_tandem_duplications.cpp:60-180, one pair.  *assigned (nullable): the loop assigned the
+// read's fields for this pair although it then skipped it (BPLeft == 0); out.c holds them
+inline bool sv_pair_td(const SplitRead &r, int ci, int fi, const std::string &ref, unsigned spacer, VariantPair &out, bool *assigned = nullptr)
+{
+    const bool plus = r.MatchedD == '+';
+    const UniquePoint &cp = r.UP_Close[ci], &fp = r.UP_Far[fi];
+    if (assigned) *assigned = false;
+    pg_variant_cand &c = out.c;
+    c = pg_variant_cand();
+    out.nt.clear();
+    if (plus) {
+        if (fp.Direction != '-') return false;
+        if (!(fp.LengthStr + cp.LengthStr == r.getReadLength() && fp.AbsLoc + fp.LengthStr < cp.AbsLoc && fp.AbsLoc + cp.LengthStr < cp.AbsLoc))
+            return false;
+        c.right = (int)(cp.AbsLoc - cp.LengthStr + 1);
+        c.left = (int)(fp.AbsLoc + fp.LengthStr - 1);
+        c.bp = (short)(cp.LengthStr - 1);
+        c.indel_size = cp.AbsLoc - fp.AbsLoc + 1;
+        c.bp_right = cp.AbsLoc - spacer;
+        c.bp_left = fp.AbsLoc - spacer;
+    } else {
+        if (fp.Direction != '+') return false;
+        if (!(cp.LengthStr + fp.LengthStr == r.getReadLength() && cp.AbsLoc + cp.LengthStr < fp.AbsLoc && cp.AbsLoc + fp.LengthStr < fp.AbsLoc))
+            return false;
+        c.right = (int)(fp.AbsLoc - fp.LengthStr + 1);
+        c.left = (int)(cp.AbsLoc + cp.LengthStr - 1);
+        c.bp = (short)(fp.LengthStr - 1);
+        c.indel_size = fp.AbsLoc - cp.AbsLoc + 1;
+        c.bp_right = fp.AbsLoc - spacer;
+        c.bp_left = cp.AbsLoc - spacer;
+    }
+    c.close_idx = (uint16_t)ci;
+    c.far_idx = (uint16_t)fi;
+    if (c.bp_left == 0) {
+        if (assigned) *assigned = true;
+        return false;
+    }
+    unsigned bl = c.bp_left, br = c.bp_right;
+    short bp = c.bp;
+    if (left_most_td(ref, spacer, bl, br, bp)) c.flags = PG_VARIANT_REF_END;
+    c.bp_left = bl;
+    c.bp_right = br;
+    c.bp = bp;
+    return true;
+}
+
+// searchTandemDuplicationsNT, src/search_tandem_duplications_nt.cpp:40-125
+inline bool sv_pair_td_nt(const SplitRead &r, const pg_sv_params &prm, unsigned spacer, VariantPair &out)
+{
+    const UniquePoint &cp = r.UP_Close.back();
+    const UniquePoint &fp = r.UP_Far.back();
+    if (fp.LengthStr + cp.LengthStr >= r.getReadLength()) return false;
+    if (fp.Mismatches + cp.Mismatches > sv_nt_budget(prm.seq_error_rate, fp.LengthStr + cp.LengthStr)) return false;
+    pg_variant_cand &c = out.c;
+    c = pg_variant_cand();
+    unsigned short NT_size;
+    if (r.MatchedD == '+') {
+        if (fp.Direction != '-') return false;
+        if (!(fp.AbsLoc + fp.LengthStr < cp.AbsLoc && fp.AbsLoc + cp.LengthStr < cp.AbsLoc &&
+              fp.LengthStr + cp.LengthStr > prm.min_num_matched_bases))
+            return false;
+        c.right = (int)(cp.AbsLoc - cp.LengthStr + 1);
+        c.left = (int)(fp.AbsLoc + fp.LengthStr - 1);
+        c.bp = (short)(cp.LengthStr - 1);
+        c.indel_size = cp.AbsLoc - fp.AbsLoc + 1;
+        NT_size = (unsigned short)(r.getReadLength() - cp.LengthStr - fp.LengthStr);
+        out.nt = sub(reverse_complement(r.UnmatchedSeq), c.bp + 1, NT_size);
+        c.bp_right = cp.AbsLoc - spacer;
+        c.bp_left = fp.AbsLoc - spacer;
+    } else if (r.MatchedD == '-') {
+        if (fp.Direction != '+') return false;
+        if (!(cp.AbsLoc + cp.LengthStr < fp.AbsLoc && cp.AbsLoc + fp.LengthStr < fp.AbsLoc &&
+              fp.LengthStr + cp.LengthStr > prm.min_num_matched_bases))
+            return false;
+        c.right = (int)(fp.AbsLoc - fp.LengthStr + 1);
+        c.left = (int)(cp.AbsLoc + cp.LengthStr - 1);
+        c.bp = (short)(fp.LengthStr - 1);
+        c.indel_size = fp.AbsLoc - cp.AbsLoc + 1;
+        NT_size = (unsigned short)(r.getReadLength() - cp.LengthStr - fp.LengthStr);
+        out.nt = sub(r.UnmatchedSeq, c.bp + 1, NT_size);
+        c.bp_right = fp.AbsLoc - spacer;
+        c.bp_left = cp.AbsLoc - spacer;
+    } else {
+        return false;
+    }
+    c.nt_rot = NT_size;
+    c.close_idx = (uint16_t)(r.UP_Close.size() - 1);
+    c.far_idx = (uint16_t)(r.UP_Far.size() - 1);
+    return true;
+}
+
+// The read-level tests of both inversion classifiers: strand differs and direction is equal between the first points
+inline bool sv_inv_read_ok(const SplitRead &r)
+{
+    return r.UP_Close[0].Strand != r.UP_Far[0].Strand && r.UP_Close[0].Direction == r.UP_Far[0].Direction;
+}
+// ... and which geometry searchInversions takes for the read (src/search_inversions.cpp:53, 118, 186, 245); -1: none
+inline int sv_inv_geometry(const SplitRead &r, unsigned MIN)
+{
+    if (r.MatchedD == '+') {
+        if (r.UP_Far[0].AbsLoc > r.UP_Close.back().AbsLoc + MIN) return 0;
+        if (r.UP_Far.back().AbsLoc + MIN < r.UP_Close[0].AbsLoc) return 1;
+    } else if (r.MatchedD == '-') {
+        if (r.UP_Close.back().AbsLoc > r.UP_Far[0].AbsLoc + MIN) return 2;
+        if (r.UP_Close[0].AbsLoc + MIN < r.UP_Far.back().AbsLoc) return 3;
+    }
+    return -1;
+}
+
+// The fields the four geometries assign (shared by searchInversions and searchInversionsNT); RL = the read's length
+inline void sv_inv_fields(int geo, const UniquePoint &cp, const UniquePoint &fp, short RL, unsigned spacer, pg_variant_cand &c)
+{
+    if (geo == 0) {
+        c.left = (int)((cp.AbsLoc + 1) - cp.LengthStr);
+        c.right = (int)(fp.AbsLoc - fp.LengthStr + RL);
+        c.bp = (short)(cp.LengthStr - 1);
+        c.indel_size = fp.AbsLoc - cp.AbsLoc;
+        c.bp_left = cp.AbsLoc + 1 - spacer;
+        c.bp_right = fp.AbsLoc - spacer;
+    } else if (geo == 1) {
+        c.right = (int)(cp.AbsLoc - cp.LengthStr + RL);
+        c.left = (int)(fp.AbsLoc - fp.LengthStr + 1);
+        c.bp = (short)(fp.LengthStr - 1);
+        c.indel_size = cp.AbsLoc - fp.AbsLoc;
+        c.bp_right = cp.AbsLoc - spacer;
+        c.bp_left = (fp.AbsLoc + 1) - spacer;
+    } else if (geo == 2) {
+        c.left = (int)(fp.AbsLoc + fp.LengthStr - RL);
+        c.right = (int)(cp.AbsLoc + cp.LengthStr - 1);
+        c.bp = (short)(fp.LengthStr - 1);
+        c.indel_size = cp.AbsLoc - fp.AbsLoc;
+        c.bp_left = fp.AbsLoc - spacer;
+        c.bp_right = cp.AbsLoc - 1 - spacer;
+    } else {
+        c.right = (int)(fp.AbsLoc + fp.LengthStr - 1);
+        c.left = (int)(cp.AbsLoc + cp.LengthStr - RL);
+        c.bp = (short)(cp.LengthStr - 1);
+        c.indel_size = fp.AbsLoc - cp.AbsLoc;
+        c.bp_left = cp.AbsLoc - spacer;
+        c.bp_right = fp.AbsLoc - 1 - spacer;
+    }
+    c.flags = (uint8_t)(geo << PG_SV_GEO_SHIFT);
+}
+inline bool sv_inv_distance_ok(int geo, const UniquePoint &cp, const UniquePoint &fp, unsigned MIN)
+{
+    switch (geo) {
+    case 0: return fp.AbsLoc > cp.AbsLoc + MIN;
+    case 1: return fp.AbsLoc + MIN < cp.AbsLoc;
+    case 2: return cp.AbsLoc > fp.AbsLoc + MIN;
+    default: return cp.AbsLoc + MIN < fp.AbsLoc;
+    }
+}
+
+// searchInversions, src/search_inversions.cpp:40-280, one pair of a read of geometry geo
+inline bool sv_pair_inv(const SplitRead &r, int geo, int ci, int fi, unsigned MIN, const std::string &ref, unsigned spacer, VariantPair &out)
+{
+    const bool plus = r.MatchedD == '+';
+    const UniquePoint &cp = r.UP_Close[ci], &fp = r.UP_Far[fi];
+    if (fp.Direction != (plus ? '+' : '-')) return false;
+    if (fp.LengthStr + cp.LengthStr != r.getReadLength()) return false;
+    if (!sv_inv_distance_ok(geo, cp, fp, MIN)) return false;
+    pg_variant_cand &c = out.c;
+    c = pg_variant_cand();
+    out.nt.clear();
+    sv_inv_fields(geo, cp, fp, r.getReadLength(), spacer, c);
+    c.close_idx = (uint16_t)ci;
+    c.far_idx = (uint16_t)fi;
+    unsigned bl = c.bp_left, br = c.bp_right;
+    short bp = c.bp;
+    if (left_most_inv(ref, spacer, plus, r.getReadLength(), bl, br, bp)) c.flags |= PG_VARIANT_REF_END;
+    c.bp_left = bl;
+    c.bp_right = br;
+    c.bp = bp;
+    return true;
+}
+
+// searchInversionsNT, src/search_inversions_nt.cpp:40-195: UP_Close.back() with UP_Far.back().  which = 0 / 1: the first / second
+// distance test of the anchor's strand (geometries 0, 1 for '+' and 2, 3 for '-').  The tests before them are sv_inv_nt_read_ok's.
+inline bool sv_inv_nt_read_ok(const SplitRead &r, const pg_sv_params &prm)
+{
+    const UniquePoint &cp = r.UP_Close.back();
+    const UniquePoint &fp = r.UP_Far.back();
+    if (fp.Mismatches + cp.Mismatches > sv_nt_budget(prm.seq_error_rate, fp.LengthStr + cp.LengthStr)) return false;
+    if (!sv_inv_read_ok(r)) return false;
+    if (!(fp.LengthStr + cp.LengthStr < r.getReadLength() && fp.LengthStr + cp.LengthStr >= prm.min_num_matched_bases)) return false;
+    const bool plus = r.MatchedD == '+';
+    if (!plus && r.MatchedD != '-') return false;
+    return fp.Direction == (plus ? '+' : '-');
+}
+inline bool sv_pair_inv_nt(const SplitRead &r, const pg_sv_params &prm, int which, unsigned spacer, VariantPair &out)
+{
+    const UniquePoint &cp = r.UP_Close.back();
+    const UniquePoint &fp = r.UP_Far.back();
+    const int geo = (r.MatchedD == '+' ? 0 : 2) + which;
+    if (!sv_inv_distance_ok(geo, cp, fp, (unsigned)prm.min_inversion_size)) return false;
+    pg_variant_cand &c = out.c;
+    c = pg_variant_cand();
+    sv_inv_fields(geo, cp, fp, r.getReadLength(), spacer, c);
+    const unsigned short NT_size = (unsigned short)(r.getReadLength() - fp.LengthStr - cp.LengthStr);
+    out.nt = (geo == 0 || geo == 3) ? sub(reverse_complement(r.UnmatchedSeq), c.bp + 1, NT_size) : sub(r.UnmatchedSeq, c.bp + 1, NT_size);
+    c.nt_rot = NT_size;
+    c.close_idx = (uint16_t)(r.UP_Close.size() - 1);
+    c.far_idx = (uint16_t)(r.UP_Far.size() - 1);
+    return true;
+}
+
+// A listed record of kind PG_SV_* back to what the pair function yields: NT_str is cut from the read again.  false: the record
+// does not fit the read.
+inline bool sv_pair_from_cand(const SplitRead &r, int kind, const pg_variant_cand &c, VariantPair &out)
+{
+    if (c.close_idx >= r.UP_Close.size() || c.far_idx >= r.UP_Far.size()) return false;
+    out.c = c;
+    out.nt.clear();
+    if (kind == PG_SV_TD || kind == PG_SV_INV) return true;
+    const int geo = (c.flags >> PG_SV_GEO_SHIFT) & 3;
+    const bool from_rc = kind == PG_SV_INV_NT ? (geo == 0 || geo == 3) : r.MatchedD == '+';
+    out.nt = from_rc ? sub(reverse_complement(r.UnmatchedSeq), c.bp + 1, (unsigned short)c.nt_rot) : sub(r.UnmatchedSeq, c.bp + 1, (unsigned short)c.nt_rot);
+    return true;
+}
+
+// The read takes a pair's values: exactly the fields the kind's classifier assigns (searchTandemDuplications leaves NT_size and
+// NT_str alone).  With PG_VARIANT_REF_END the read is Used, and the box test still runs.
+inline void apply_sv_pair(SplitRead &r, int kind, const VariantPair &p)
+{
+    r.Left = p.c.left;
+    r.Right = p.c.right;
+    r.BP = p.c.bp;
+    r.IndelSize = p.c.indel_size;
+    r.BPLeft = p.c.bp_left;
+    r.BPRight = p.c.bp_right;
+    if (kind != PG_SV_TD) {
+        r.NT_size = (unsigned short)p.c.nt_rot;
+        r.NT_str = p.nt;
+    }
+    if (p.c.flags & PG_VARIANT_REF_END) r.Used = true;
+}
+
+// The list of one kind consulted for a read: every listed pair, in order, through tail(pair) until one makes the read Used.
+// true: the classifier's own search must still run (the list was cut short with PG_VARIANT_MORE, or did not fit the read).
+template <class Tail>
+inline bool sv_consult_list(SplitRead &r, int kind, VariantPair &pair, Tail tail)
+{
+    const uint8_t count = r.SvCounts[kind - PG_SV_DI];
+    const unsigned cap = (kind == PG_SV_TD || kind == PG_SV_INV) ? PG_VARIANT_CANDS : 1u;
+    const unsigned n_listed = std::min<unsigned>(count & ~PG_VARIANT_MORE, cap);
+    const pg_variant_cand *list = r.SvCands + sv_slot_base()[kind - PG_SV_DI];
+    bool listed_ok = true;
+    for (unsigned j = 0; j < n_listed && !r.Used && listed_ok; j++) {
+        listed_ok = sv_pair_from_cand(r, kind, list[j], pair);
+        if (listed_ok) {
+            apply_sv_pair(r, kind, pair);
+            tail(pair);
+        }
+    }
+    return !(r.Used || (listed_ok && !(count & PG_VARIANT_MORE)));
+}
+
+// What one thread of a classifier did with the lists, added to variant_list_stats() when its range of reads is done
+struct ListLog {
+    uint64_t fallbacks = 0;
+    std::vector<uint32_t> visits;
+    void visit(uint32_t index, int kind, unsigned win_end, unsigned region_start, unsigned region_end, unsigned n_boxes, unsigned box_size)
+    {
+        if (!variant_list_stats().log_visits) return;
+        const uint32_t v[7] = { index, (uint32_t)kind, win_end, region_start, region_end, n_boxes, box_size };
+        visits.insert(visits.end(), v, v + 7);
+    }
+    void flush(std::mutex &mu)
+    {
+        if (!fallbacks && visits.empty()) return;
+        std::lock_guard<std::mutex> lk(mu);
+        VariantListStats &stats = variant_list_stats();
+        stats.fallbacks += fallbacks;
+        stats.visits.insert(stats.visits.end(), visits.begin(), visits.end());
+    }
+};
 
 // ReportEvent, src/pindel.cpp:2059-2093 (Min_Filter_Ratio = 0.5)
 inline bool report_event(const std::vector<SplitRead> &g, unsigned s, unsigned e)

@@ -29,48 +29,35 @@ using namespace detail;
         }                                                                                    \
     } while (0)
 
-// LeftMostTD, src/search_tandem_duplications.cpp:194-222
-static void left_most_td(const std::string &ref, unsigned spacer, SplitRead &r)
-{
-    unsigned pos = r.BPLeft + spacer, orig = pos, end = r.BPRight + spacer - 1;
-    unsigned n = (unsigned)ref.size();
-    if (pos >= n || end >= n) {
-        r.BPLeft = 1;
-        r.BPRight = 1;
-        r.BP = 1;
-        r.Used = true;
-        return;
-    }
-    while (ref[pos] == ref[end]) {
-        --pos;
-        --end;
-    }
-    int diff = (int)(orig - pos);
-    if (diff > 0) {
-        if (diff >= r.BP) diff = r.BP - 1;
-        r.BPLeft -= diff;
-        r.BPRight -= diff;
-        r.BP -= (short)diff;
-    }
-}
+// (LeftMostTD and LeftMostINV, and the body of every classifier for one pair: pg_host_priv.hpp)
 
 void Caller::search_tandem_dup(Ctx &c)
 {
     std::vector<SplitRead> &reads = *c.reads;
     const std::string &ref = c.chrom->seq;
     std::vector<std::vector<unsigned>> boxes(c.NumBoxes);
+    std::mutex stats_mu;
     classify_reads(reads.size(), boxes, [&](unsigned lo_, unsigned hi_, BoxSink &sink) {
+    ListLog log;
+    VariantPair pair;
     for (unsigned ri = lo_; ri < hi_; ri++) {
         SplitRead &r = reads[ri];
         if (r.Used || r.UP_Far.empty() || r.FragName != r.FarFragName) continue;
         const bool plus = r.MatchedD == '+';
         if (!plus && r.MatchedD != '-') continue;
+        auto tail = [&](const VariantPair &) { PGH_BOX_READ(r, ri, sink, true); };
+        if (r.SvCands) {
+            log.visit(r.VarIndex, PG_SV_TD, c.win_end, c.region_start, c.region_end, c.NumBoxes, BoxSize);
+            if (!sv_consult_list(r, PG_SV_TD, pair, tail)) continue;
+            log.fallbacks++;
+        }
         const int nc = (int)r.UP_Close.size(), nf = (int)r.UP_Far.size();
         const FarByLength by_len(r);
         for (short budget = 0; budget <= r.MAX_SNP_ERROR; budget++) {
             for (int k = 0; k < nc; k++) {
                 if (r.Used) break;
-                const UniquePoint &cp = r.UP_Close[plus ? k : nc - 1 - k];
+                const int ci = plus ? k : nc - 1 - k;
+                const UniquePoint &cp = r.UP_Close[ci];
                 if (cp.Mismatches > budget) continue;
                 // only the far point of length ReadLength - LengthStr(close) can pass the tests below
                 int fi_first, fi_last;
@@ -82,39 +69,19 @@ void Caller::search_tandem_dup(Ctx &c)
                 }
                 for (int j = j_first; j <= j_last; j++) {
                     if (r.Used) break;
-                    const UniquePoint &fp = r.UP_Far[plus ? nf - 1 - j : j];
+                    const int fi = plus ? nf - 1 - j : j;
+                    const UniquePoint &fp = r.UP_Far[fi];
                     if (fp.Mismatches > budget) continue;
                     if (fp.Mismatches + cp.Mismatches > budget) continue;
-                    if (plus) {
-                        if (fp.Direction != '-') continue;
-                        if (!(fp.LengthStr + cp.LengthStr == r.getReadLength() &&
-                              fp.AbsLoc + fp.LengthStr < cp.AbsLoc && fp.AbsLoc + cp.LengthStr < cp.AbsLoc))
-                            continue;
-                        r.Right = (int)(cp.AbsLoc - cp.LengthStr + 1);
-                        r.Left = (int)(fp.AbsLoc + fp.LengthStr - 1);
-                        r.BP = (short)(cp.LengthStr - 1);
-                        r.IndelSize = cp.AbsLoc - fp.AbsLoc + 1;
-                        r.BPRight = cp.AbsLoc - S.spacer;
-                        r.BPLeft = fp.AbsLoc - S.spacer;
-                    } else {
-                        if (fp.Direction != '+') continue;
-                        if (!(cp.LengthStr + fp.LengthStr == r.getReadLength() &&
-                              cp.AbsLoc + cp.LengthStr < fp.AbsLoc && cp.AbsLoc + fp.LengthStr < fp.AbsLoc))
-                            continue;
-                        r.Right = (int)(fp.AbsLoc - fp.LengthStr + 1);
-                        r.Left = (int)(cp.AbsLoc + cp.LengthStr - 1);
-                        r.BP = (short)(fp.LengthStr - 1);
-                        r.IndelSize = fp.AbsLoc - cp.AbsLoc + 1;
-                        r.BPRight = fp.AbsLoc - S.spacer;
-                        r.BPLeft = cp.AbsLoc - S.spacer;
-                    }
-                    if (r.BPLeft == 0) continue;
-                    left_most_td(ref, S.spacer, r);
-                    PGH_BOX_READ(r, ri, sink, true);
+                    bool assigned;
+                    const bool ok = sv_pair_td(r, ci, fi, ref, S.spacer, pair, &assigned);
+                    if (ok || assigned) apply_sv_pair(r, PG_SV_TD, pair);     // (a pair with BPLeft == 0 is assigned, then skipped)
+                    if (ok) tail(pair);
                 }
             }
         }
     }
+    log.flush(stats_mu);
     });
     sort_output_td(c, boxes, false);
 }
@@ -123,45 +90,25 @@ void Caller::search_tandem_dup_nt(Ctx &c)
 {
     std::vector<SplitRead> &reads = *c.reads;
     std::vector<std::vector<unsigned>> boxes(c.NumBoxes);
+    const pg_sv_params prm = { S.Seq_Error_Rate, S.Min_Num_Matched_Bases, S.MIN_IndelSize_Inversion };
+    std::mutex stats_mu;
     classify_reads(reads.size(), boxes, [&](unsigned lo_, unsigned hi_, BoxSink &sink) {
+    ListLog log;
+    VariantPair pair;
     for (unsigned ri = lo_; ri < hi_; ri++) {
         SplitRead &r = reads[ri];
         if (r.Used || r.UP_Far.empty() || r.FragName != r.FarFragName) continue;
-        const UniquePoint &cp = r.UP_Close.back();
-        const UniquePoint &fp = r.UP_Far.back();
-        if (fp.LengthStr + cp.LengthStr >= r.getReadLength()) continue;
-        if (fp.Mismatches + cp.Mismatches > (short)(1 + S.Seq_Error_Rate * (fp.LengthStr + cp.LengthStr))) continue;
-        if (r.MatchedD == '+') {
-            if (fp.Direction != '-') continue;
-            if (!(fp.AbsLoc + fp.LengthStr < cp.AbsLoc && fp.AbsLoc + cp.LengthStr < cp.AbsLoc &&
-                  fp.LengthStr + cp.LengthStr > S.Min_Num_Matched_Bases))
-                continue;
-            r.Right = (int)(cp.AbsLoc - cp.LengthStr + 1);
-            r.Left = (int)(fp.AbsLoc + fp.LengthStr - 1);
-            r.BP = (short)(cp.LengthStr - 1);
-            r.IndelSize = cp.AbsLoc - fp.AbsLoc + 1;
-            r.NT_size = (unsigned short)(r.getReadLength() - cp.LengthStr - fp.LengthStr);
-            r.NT_str = sub(reverse_complement(r.UnmatchedSeq), r.BP + 1, r.NT_size);
-            r.BPRight = cp.AbsLoc - S.spacer;
-            r.BPLeft = fp.AbsLoc - S.spacer;
-        } else if (r.MatchedD == '-') {
-            if (fp.Direction != '+') continue;
-            if (!(cp.AbsLoc + cp.LengthStr < fp.AbsLoc && cp.AbsLoc + fp.LengthStr < fp.AbsLoc &&
-                  fp.LengthStr + cp.LengthStr > S.Min_Num_Matched_Bases))
-                continue;
-            r.Right = (int)(fp.AbsLoc - fp.LengthStr + 1);
-            r.Left = (int)(cp.AbsLoc + cp.LengthStr - 1);
-            r.BP = (short)(fp.LengthStr - 1);
-            r.IndelSize = fp.AbsLoc - cp.AbsLoc + 1;
-            r.NT_size = (unsigned short)(r.getReadLength() - cp.LengthStr - fp.LengthStr);
-            r.NT_str = sub(r.UnmatchedSeq, r.BP + 1, r.NT_size);
-            r.BPRight = fp.AbsLoc - S.spacer;
-            r.BPLeft = cp.AbsLoc - S.spacer;
-        } else {
-            continue;
+        auto tail = [&](const VariantPair &) { PGH_BOX_READ(r, ri, sink, true); };
+        if (r.SvCands) {
+            log.visit(r.VarIndex, PG_SV_TD_NT, c.win_end, c.region_start, c.region_end, c.NumBoxes, BoxSize);
+            if (!sv_consult_list(r, PG_SV_TD_NT, pair, tail)) continue;
+            log.fallbacks++;
         }
-        PGH_BOX_READ(r, ri, sink, true);
+        if (!sv_pair_td_nt(r, prm, S.spacer, pair)) continue;
+        apply_sv_pair(r, PG_SV_TD_NT, pair);
+        tail(pair);
     }
+    log.flush(stats_mu);
     });
     sort_output_td(c, boxes, true);
 }
@@ -243,115 +190,53 @@ void Caller::sort_output_td(Ctx &c, std::vector<std::vector<unsigned>> &boxes, b
 }
 
 // ------------------------------------------------------------------------------ inversions
-// LeftMostINV, src/search_inversions.cpp:285-318
-static void left_most_inv(const std::string &ref, unsigned spacer, SplitRead &r)
-{
-    unsigned n = (unsigned)ref.size();
-    unsigned pos = r.BPLeft + spacer + 1, orig = pos, end = r.BPRight + spacer - 1;
-    if (n <= pos + spacer || n <= orig + spacer) {
-        r.BPLeft = 1;
-        r.BPRight = 1;
-        r.BP = 1;
-        r.Used = true;
-        return;
-    }
-    while (ref[pos] == rc4n(ref[end])) {
-        ++pos;
-        --end;
-    }
-    short diff = (short)(pos - orig);
-    if (diff > 0) {
-        if (r.MatchedD == '+') {
-            if (diff >= r.BP) diff = (short)(r.BP - 1);
-        } else {
-            if (diff + r.BP >= r.getReadLength()) diff = (short)(r.getReadLength() - r.BP - 1);
-            r.BPLeft += diff;
-            r.BPRight -= diff;
-            r.BP += diff;
-        }
-    }
-}
-
 void Caller::search_inversions(Ctx &c)
 {
     std::vector<SplitRead> &reads = *c.reads;
     const std::string &ref = c.chrom->seq;
     std::vector<std::vector<unsigned>> boxes(c.NumBoxes);
     const unsigned MIN = (unsigned)S.MIN_IndelSize_Inversion;
+    std::mutex stats_mu;
     classify_reads(reads.size(), boxes, [&](unsigned lo_, unsigned hi_, BoxSink &sink) {
+    ListLog log;
+    VariantPair pair;
     for (unsigned ri = lo_; ri < hi_; ri++) {
         SplitRead &r = reads[ri];
         if (r.Used || r.UP_Far.empty() || r.FragName != r.FarFragName) continue;
-        if (!(r.UP_Close[0].Strand != r.UP_Far[0].Strand && r.UP_Close[0].Direction == r.UP_Far[0].Direction))
-            continue;
+        if (!sv_inv_read_ok(r)) continue;
         const int nc = (int)r.UP_Close.size(), nf = (int)r.UP_Far.size();
         const bool plus = r.MatchedD == '+';
         if (!plus && r.MatchedD != '-') continue;
-        // which of the two geometries (search_inversions.cpp:53, 118, 186, 245)
-        int geo;
-        if (plus) {
-            if (r.UP_Far[0].AbsLoc > r.UP_Close.back().AbsLoc + MIN) geo = 0;
-            else if (r.UP_Far.back().AbsLoc + MIN < r.UP_Close[0].AbsLoc) geo = 1;
-            else continue;
-        } else {
-            if (r.UP_Close.back().AbsLoc > r.UP_Far[0].AbsLoc + MIN) geo = 2;
-            else if (r.UP_Close[0].AbsLoc + MIN < r.UP_Far.back().AbsLoc) geo = 3;
-            else continue;
+        auto tail = [&](const VariantPair &) { PGH_BOX_READ(r, ri, sink, plus); };   // the '-' branches skip the bin-border test
+        if (r.SvCands && sv_list_usable(S)) {
+            log.visit(r.VarIndex, PG_SV_INV, c.win_end, c.region_start, c.region_end, c.NumBoxes, BoxSize);
+            if (!sv_consult_list(r, PG_SV_INV, pair, tail)) continue;
+            log.fallbacks++;
         }
+        // which of the two geometries (search_inversions.cpp:53, 118, 186, 245)
+        const int geo = sv_inv_geometry(r, MIN);
+        if (geo < 0) continue;
         const bool close_desc = (geo == 0 || geo == 2);   // CloseIndex from the back, FarIndex ascending
         for (short budget = 0; budget <= r.MAX_SNP_ERROR; budget++) {
             for (int k = 0; k < nc; k++) {
                 if (r.Used) break;
-                const UniquePoint &cp = r.UP_Close[close_desc ? nc - 1 - k : k];
+                const int ci = close_desc ? nc - 1 - k : k;
+                const UniquePoint &cp = r.UP_Close[ci];
                 if (cp.Mismatches > budget) continue;
                 for (int j = 0; j < nf; j++) {
                     if (r.Used) break;
-                    const UniquePoint &fp = r.UP_Far[close_desc ? j : nf - 1 - j];
+                    const int fi = close_desc ? j : nf - 1 - j;
+                    const UniquePoint &fp = r.UP_Far[fi];
                     if (fp.Mismatches > budget) continue;
                     if (fp.Mismatches + cp.Mismatches > budget) continue;
-                    if (fp.Direction != (plus ? '+' : '-')) continue;
-                    if (fp.LengthStr + cp.LengthStr != r.getReadLength()) continue;
-                    if (geo == 0) {
-                        if (!(fp.AbsLoc > cp.AbsLoc + MIN)) continue;
-                        r.Left = (int)((cp.AbsLoc + 1) - cp.LengthStr);
-                        r.Right = (int)(fp.AbsLoc - fp.LengthStr + r.getReadLength());
-                        r.BP = (short)(cp.LengthStr - 1);
-                        r.IndelSize = fp.AbsLoc - cp.AbsLoc;
-                        r.BPLeft = cp.AbsLoc + 1 - S.spacer;
-                        r.BPRight = fp.AbsLoc - S.spacer;
-                    } else if (geo == 1) {
-                        if (!(fp.AbsLoc + MIN < cp.AbsLoc)) continue;
-                        r.Right = (int)(cp.AbsLoc - cp.LengthStr + r.getReadLength());
-                        r.Left = (int)(fp.AbsLoc - fp.LengthStr + 1);
-                        r.BP = (short)(fp.LengthStr - 1);
-                        r.IndelSize = cp.AbsLoc - fp.AbsLoc;
-                        r.BPRight = cp.AbsLoc - S.spacer;
-                        r.BPLeft = (fp.AbsLoc + 1) - S.spacer;
-                    } else if (geo == 2) {
-                        if (!(cp.AbsLoc > fp.AbsLoc + MIN)) continue;
-                        r.Left = (int)(fp.AbsLoc + fp.LengthStr - r.getReadLength());
-                        r.Right = (int)(cp.AbsLoc + cp.LengthStr - 1);
-                        r.BP = (short)(fp.LengthStr - 1);
-                        r.IndelSize = cp.AbsLoc - fp.AbsLoc;
-                        r.BPLeft = fp.AbsLoc - S.spacer;
-                        r.BPRight = cp.AbsLoc - 1 - S.spacer;
-                    } else {
-                        if (!(cp.AbsLoc + MIN < fp.AbsLoc)) continue;
-                        r.Right = (int)(fp.AbsLoc + fp.LengthStr - 1);
-                        r.Left = (int)(cp.AbsLoc + cp.LengthStr - r.getReadLength());
-                        r.BP = (short)(cp.LengthStr - 1);
-                        r.IndelSize = fp.AbsLoc - cp.AbsLoc;
-                        r.BPLeft = cp.AbsLoc - S.spacer;
-                        r.BPRight = fp.AbsLoc - 1 - S.spacer;
-                    }
-                    r.NT_str = "";
-                    r.NT_size = 0;
-                    left_most_inv(ref, S.spacer, r);
-                    PGH_BOX_READ(r, ri, sink, plus);   // the '-' branches skip the bin-border test
+                    if (!sv_pair_inv(r, geo, ci, fi, MIN, ref, S.spacer, pair)) continue;
+                    apply_sv_pair(r, PG_SV_INV, pair);
+                    tail(pair);
                 }
             }
         }
     }
+    log.flush(stats_mu);
     });
     sort_output_inv(c, boxes, false);
 }
@@ -360,70 +245,28 @@ void Caller::search_inversions_nt(Ctx &c)
 {
     std::vector<SplitRead> &reads = *c.reads;
     std::vector<std::vector<unsigned>> boxes(c.NumBoxes);
-    const unsigned MIN = (unsigned)S.MIN_IndelSize_Inversion;
+    const pg_sv_params prm = { S.Seq_Error_Rate, S.Min_Num_Matched_Bases, S.MIN_IndelSize_Inversion };
+    std::mutex stats_mu;
     classify_reads(reads.size(), boxes, [&](unsigned lo_, unsigned hi_, BoxSink &sink) {
+    ListLog log;
+    VariantPair pair;
     for (unsigned ri = lo_; ri < hi_; ri++) {
         SplitRead &r = reads[ri];
         if (r.Used || r.UP_Far.empty() || r.FragName != r.FarFragName) continue;
-        const UniquePoint &cp = r.UP_Close.back();
-        const UniquePoint &fp = r.UP_Far.back();
-        if (fp.Mismatches + cp.Mismatches > (short)(1 + S.Seq_Error_Rate * (fp.LengthStr + cp.LengthStr))) continue;
-        if (!(r.UP_Close[0].Strand != r.UP_Far[0].Strand && r.UP_Close[0].Direction == r.UP_Far[0].Direction))
-            continue;
-        const bool short_enough = fp.LengthStr + cp.LengthStr < r.getReadLength() &&
-                                  fp.LengthStr + cp.LengthStr >= S.Min_Num_Matched_Bases;
-        if (!short_enough) continue;
-        const unsigned short nt = (unsigned short)(r.getReadLength() - fp.LengthStr - cp.LengthStr);
-        if (r.MatchedD == '+') {
-            if (fp.Direction != '+') continue;
-            if (fp.AbsLoc > cp.AbsLoc + MIN) {
-                r.Left = (int)((cp.AbsLoc + 1) - cp.LengthStr);
-                r.Right = (int)(fp.AbsLoc - fp.LengthStr + r.getReadLength());
-                r.BP = (short)(cp.LengthStr - 1);
-                r.IndelSize = fp.AbsLoc - cp.AbsLoc;
-                r.NT_size = nt;
-                r.NT_str = sub(reverse_complement(r.UnmatchedSeq), r.BP + 1, r.NT_size);
-                r.BPLeft = cp.AbsLoc + 1 - S.spacer;
-                r.BPRight = fp.AbsLoc - S.spacer;
-                PGH_BOX_READ(r, ri, sink, true);
-            }
-            if (fp.AbsLoc + MIN < cp.AbsLoc) {
-                r.Right = (int)(cp.AbsLoc - cp.LengthStr + r.getReadLength());
-                r.Left = (int)(fp.AbsLoc - fp.LengthStr + 1);
-                r.BP = (short)(fp.LengthStr - 1);
-                r.IndelSize = cp.AbsLoc - fp.AbsLoc;
-                r.NT_size = nt;
-                r.NT_str = sub(r.UnmatchedSeq, r.BP + 1, r.NT_size);
-                r.BPRight = cp.AbsLoc - S.spacer;
-                r.BPLeft = (fp.AbsLoc + 1) - S.spacer;
-                PGH_BOX_READ(r, ri, sink, true);
-            }
-        } else if (r.MatchedD == '-') {
-            if (fp.Direction != '-') continue;
-            if (cp.AbsLoc > fp.AbsLoc + MIN) {
-                r.Left = (int)(fp.AbsLoc + fp.LengthStr - r.getReadLength());
-                r.Right = (int)(cp.AbsLoc + cp.LengthStr - 1);
-                r.BP = (short)(fp.LengthStr - 1);
-                r.IndelSize = cp.AbsLoc - fp.AbsLoc;
-                r.NT_size = nt;
-                r.NT_str = sub(r.UnmatchedSeq, r.BP + 1, r.NT_size);
-                r.BPLeft = fp.AbsLoc - S.spacer;
-                r.BPRight = cp.AbsLoc - 1 - S.spacer;
-                PGH_BOX_READ(r, ri, sink, true);
-            }
-            if (cp.AbsLoc + MIN < fp.AbsLoc) {
-                r.Right = (int)(fp.AbsLoc + fp.LengthStr - 1);
-                r.Left = (int)(cp.AbsLoc + cp.LengthStr - r.getReadLength());
-                r.BP = (short)(cp.LengthStr - 1);
-                r.IndelSize = fp.AbsLoc - cp.AbsLoc;
-                r.NT_size = nt;
-                r.NT_str = sub(reverse_complement(r.UnmatchedSeq), r.BP + 1, r.NT_size);
-                r.BPLeft = cp.AbsLoc - S.spacer;
-                r.BPRight = fp.AbsLoc - 1 - S.spacer;
-                PGH_BOX_READ(r, ri, sink, true);
-            }
+        auto tail = [&](const VariantPair &) { PGH_BOX_READ(r, ri, sink, true); };
+        if (r.SvCands && sv_list_usable(S)) {
+            log.visit(r.VarIndex, PG_SV_INV_NT, c.win_end, c.region_start, c.region_end, c.NumBoxes, BoxSize);
+            if (!sv_consult_list(r, PG_SV_INV_NT, pair, tail)) continue;
+            log.fallbacks++;
+        }
+        if (!sv_inv_nt_read_ok(r, prm)) continue;
+        for (int which = 0; which < 2; which++) {          // (both distance tests run, the second also after the first has boxed the read)
+            if (!sv_pair_inv_nt(r, prm, which, S.spacer, pair)) continue;
+            apply_sv_pair(r, PG_SV_INV_NT, pair);
+            tail(pair);
         }
     }
+    log.flush(stats_mu);
     });
     sort_output_inv(c, boxes, true);
 }

@@ -209,6 +209,8 @@ struct pg_ctx {
     uint16_t thr[512]{};
     uint16_t *d_thr = nullptr;
     uint32_t *d_mm = nullptr;
+    int32_t *d_sv_budget = nullptr;    // [PG_SV_BUDGET_N] the NT kinds' mismatch budget by length sum (pg_sv.hip), for sv_budget_rate
+    double sv_budget_rate = 0.0;
     PgLenRec *d_len_tab = nullptr;     // [512] pg_len_rec of every read length under this context's parameters (the pack's per-length fields)
     hipStream_t stream = nullptr, copy_stream = nullptr;   // kernels / host-to-device input copies
     hipStream_t dl_stream = nullptr;                       // device-to-host result copies of the chunked host path
@@ -1901,6 +1903,7 @@ void pg_destroy(pg_ctx *ctx)
     if (ctx->arena.base) (void)hipFree(ctx->arena.base);
     if (ctx->d_thr) (void)hipFree(ctx->d_thr);
     if (ctx->d_mm) (void)hipFree(ctx->d_mm);
+    if (ctx->d_sv_budget) (void)hipFree(ctx->d_sv_budget);
     if (ctx->d_len_tab) (void)hipFree(ctx->d_len_tab);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -2309,6 +2312,92 @@ int pg_device_batch_variant_candidates(pg_ctx *ctx, pg_device_batch *b, pg_varia
     if (int rc = variant_candidates(ctx, b, d_cands, d_counts)) return rc;
     HIP_TRY(ctx, hipMemcpy(cands, d_cands, cand_bytes, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(counts, d_counts, n * 2, hipMemcpyDeviceToHost));
+    return PG_OK;
+}
+
+// ---- ... of the five other kinds (pg_sv.hip): DI, tandem-duplication and inversion candidates
+// (short)(1 + Seq_Error_Rate * length sum) for every length sum, as the host classifiers compute it: the product is stored before
+// the add, so that no compiler fuses the two
+static int sv_budget_table(pg_ctx *ctx, double rate)
+{
+    if (ctx->d_sv_budget && std::memcmp(&ctx->sv_budget_rate, &rate, sizeof rate) == 0) return PG_OK;
+    std::vector<int32_t> t(PG_SV_BUDGET_N);
+    for (int len = 0; len < PG_SV_BUDGET_N; len++) {
+        volatile double prod = rate * len;
+        const double v = 1 + prod;
+        t[(size_t)len] = v >= -32768.0 && v < 32768.0 ? (int32_t)(short)v : 32767;      // (NaN or out of a short's range: undefined on the host)
+    }
+    if (ctx->d_sv_budget) {
+        HIP_TRY(ctx, hipMemcpy(ctx->d_sv_budget, t.data(), t.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    } else if (int rc = dev_upload(ctx, &ctx->d_sv_budget, t.data(), t.size())) {
+        return rc;
+    }
+    ctx->sv_budget_rate = rate;
+    return PG_OK;
+}
+
+static int sv_params_ok(pg_ctx *ctx, const pg_sv_params *p)
+{
+    if (!p) return fail(ctx, PG_E_INVALID, "sv candidates: null pg_sv_params");
+    if (p->min_inversion_size < 0 || p->min_inversion_size > PG_SV_MAX_INVERSION_SIZE)
+        return fail(ctx, PG_E_INVALID, "sv candidates: the minimum inversion size (-v) must lie in [0, 2^30]");
+    return PG_OK;
+}
+
+static int sv_candidates(pg_ctx *ctx, pg_device_batch *b, const pg_sv_params *p, pg_variant_cand *d_cands, uint8_t *d_counts)
+{
+    if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
+    if (int rc = stale_batch(ctx, b)) return rc;
+    ctx->last_ms = 0.0;
+    if (int rc = sv_params_ok(ctx, p)) return rc;
+    if (!b->n) return PG_OK;                                  // nothing is launched for an empty batch
+    if (!b->searched) return fail(ctx, PG_E_INVALID, "the batch has not been searched: no close and far ends to classify");
+    if (int rc = sv_budget_table(ctx, p->seq_error_rate)) return rc;
+    const PgDevRef ref = dev_ref(ctx);
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if (pg_sv_launch(&ref, b->out_rec, b->pool, (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS, b->seq, b->seq_off, b->strand, b->chr,
+                     ctx->d_mm, ctx->d_sv_budget, p->min_num_matched_bases, (uint32_t)p->min_inversion_size, ctx->prm.spacer, b->n, d_cands,
+                     d_counts, ctx->stream))
+        return fail(ctx, PG_E_DEVICE, "launching the sv-candidate kernel failed");
+    PgLaunchRec rec{};
+    rec.kernel = PG_KERNEL_SV;
+    rec.blocks = 4;                                           // reads (waves) per workgroup
+    log_launch(ctx, rec);
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->last_ms = ms;
+    return PG_OK;
+}
+
+int pg_device_batch_sv_candidates_device(pg_ctx *ctx, pg_device_batch *b, const pg_sv_params *p, pg_variant_cand *d_cands, uint8_t *d_counts)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    const size_t n = b->n;
+    int rc;
+    if ((rc = check_device_ptr(ctx, d_cands, n * PG_SV_SLOTS * sizeof(pg_variant_cand), 4, "sv candidates: cands")) ||
+        (rc = check_device_ptr(ctx, d_counts, n * PG_SV_KINDS, 1, "sv candidates: counts")))
+        return rc;
+    return sv_candidates(ctx, b, p, d_cands, d_counts);
+}
+
+int pg_device_batch_sv_candidates(pg_ctx *ctx, pg_device_batch *b, const pg_sv_params *p, pg_variant_cand *cands, uint8_t *counts)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    const size_t n = b->n;
+    if (n && (!cands || !counts)) return fail(ctx, PG_E_INVALID, "sv candidates: null output array");
+    if (!n || !b->searched || sv_params_ok(ctx, p)) return sv_candidates(ctx, b, p, nullptr, nullptr);      // (nothing to do, or the refusal)
+    DevTemps tmp(ctx, b);
+    const size_t cand_bytes = n * PG_SV_SLOTS * sizeof(pg_variant_cand);
+    pg_variant_cand *d_cands = (pg_variant_cand *)tmp.take(cand_bytes);
+    uint8_t *d_counts = (uint8_t *)tmp.take(n * PG_SV_KINDS);
+    if (!d_cands || !d_counts) return fail(ctx, PG_E_NOMEM, "device memory for the sv candidates");
+    if (int rc = sv_candidates(ctx, b, p, d_cands, d_counts)) return rc;
+    HIP_TRY(ctx, hipMemcpy(cands, d_cands, cand_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(counts, d_counts, n * PG_SV_KINDS, hipMemcpyDeviceToHost));
     return PG_OK;
 }
 

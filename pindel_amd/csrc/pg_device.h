@@ -305,7 +305,7 @@ int pg_debug_kargs_check(const PgDevRef *ref, const PgDevParams *prm, const PgDe
                          uint32_t *scratch_dev, void *stream);
 // What one kernel launch on the search path ran (the launch log of pg_api.cpp, pg_debug_launch_log): the kernel and its
 // template arguments.  The launch functions below fill these when given somewhere to put them (null: nothing is recorded).
-enum PgKernelKind { PG_KERNEL_SEARCH = 1, PG_KERNEL_EXACT = 2, PG_KERNEL_PACK = 3, PG_KERNEL_VARIANT = 4 };
+enum PgKernelKind { PG_KERNEL_SEARCH = 1, PG_KERNEL_EXACT = 2, PG_KERNEL_PACK = 3, PG_KERNEL_VARIANT = 4, PG_KERNEL_SV = 5 };
 struct PgLaunchRec {
     int32_t kernel;                // PgKernelKind
     int32_t blocks;                // NB of pg_search_kernel, PB of pg_pack_kernel (0: pg_search_exact_kernel)
@@ -337,6 +337,13 @@ int pg_pack_in_place_ok(int mode, uint32_t max_len, int small_ids, uint32_t n_re
 int pg_variant_launch(const PgDevRef *ref, const PgOutRec *out, const pg_run *pool, unsigned long long pool_runs, const uint8_t *seq,
                       const uint64_t *seq_off, const uint8_t *strand, const int32_t *chr, const uint32_t *d_mm, uint32_t spacer,
                       uint32_t n, pg_variant_cand *d_cands, uint8_t *d_counts, void *stream);
+// The device classifier of the five other kinds (pg_sv.hip): the inputs of pg_variant_launch plus d_budget -- the
+// mismatch budget of the kinds with non-template bases by length sum, PG_SV_BUDGET_N entries made on the host -- and -d and -v;
+// d_cands: n x PG_SV_SLOTS records, d_counts: n x PG_SV_KINDS bytes.  n = 0 launches nothing.
+#define PG_SV_BUDGET_N 1024
+int pg_sv_launch(const PgDevRef *ref, const PgOutRec *out, const pg_run *pool, unsigned long long pool_runs, const uint8_t *seq,
+                 const uint64_t *seq_off, const uint8_t *strand, const int32_t *chr, const uint32_t *d_mm, const int32_t *d_budget,
+                 int32_t min_matched, uint32_t min_inv, uint32_t spacer, uint32_t n, pg_variant_cand *d_cands, uint8_t *d_counts, void *stream);
 // Position-keyed hint tables (pg_hints.hip): a pg_hint_table in device memory, its windows already split into pieces of at most
 // 2^26 - 1 positions, and per cluster the longest of its windows.  pg_hint_count_scan: the reads' window counts scanned into
 // bd_off (n + 1 offsets) -- blk: scratch of pg_hint_scan_blocks(n) words; info (4 dwords): the total (64 bits), the most windows

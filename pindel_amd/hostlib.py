@@ -81,6 +81,8 @@ def lib():
             C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(HostSettings), C.c_uint32,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pgh_call_from_points_candidates.argtypes = L.pgh_call_from_points.argtypes + [C.c_void_p, C.c_void_p]
+        L.pgh_call_from_points_lists.argtypes = L.pgh_call_from_points.argtypes + [C.c_void_p] * 4
+        L.pgh_sv_candidates.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32] + [C.c_void_p] * 13
         L.pgh_last_variant_fallbacks.restype = C.c_uint64
         L.pgh_last_variant_fallbacks.argtypes = []
         L.pgh_last_variant_visits.restype = C.c_uint64
@@ -255,6 +257,61 @@ def variant_candidates(chroms, seq, seq_off, anchor_strand, chr_id, rc_flag, clo
     return cands, counts
 
 
+# the five other classifiers (include/pindel_pg.h): kind -> name; SV_SLOTS records and SV_KINDS count bytes per read in
+# the order DI, TD x VARIANT_CANDS, TD_NT, INV x VARIANT_CANDS, INV_NT
+SV_KINDS = {2: "DI", 3: "TD", 4: "TD_NT", 5: "INV", 6: "INV_NT"}
+SV_SLOTS = 3 + 2 * VARIANT_CANDS
+SV_SLOT = {2: 0, 3: 1, 4: 1 + VARIANT_CANDS, 5: 2 + VARIANT_CANDS, 6: 2 + 2 * VARIANT_CANDS}
+SV_LIST_LEN = {2: 1, 3: VARIANT_CANDS, 4: 1, 5: VARIANT_CANDS, 6: 1}
+SV_GEO_SHIFT = 4
+
+
+class SvParams(C.Structure):
+    """pg_sv_params: -e, -d, -v"""
+    _fields_ = [("seq_error_rate", C.c_double), ("min_num_matched_bases", C.c_int32), ("min_inversion_size", C.c_int32)]
+
+
+def sv_candidates(chroms, seq, seq_off, anchor_strand, chr_id, rc_flag, close_off, close_pts, far_off, far_pts, max_mismatch,
+                  settings=None, spacer=100000):
+    """The per-read stage of the DI, tandem-duplication and inversion classifiers as candidate lists, computed on the host with
+    plain loops around the classifiers' own pair functions (pgh_sv_candidates): the reference the device classifier
+    (Engine.sv_candidates) is compared with.  Arguments as variant_candidates(); settings: None (Pindel's defaults), a (rate, -d,
+    -v) tuple or anything with seq_error_rate, min_num_matched_bases and min_inversion_size (HostSettings).  Raises ValueError for
+    a -v outside [0, 2^30].  Returns (cands, counts): VARIANT_CAND_DTYPE[n, SV_SLOTS] and uint8[n, 5]; kind k has its records
+    from SV_SLOT[k] on and count byte k - 2."""
+    L = lib()
+    n = len(seq_off) - 1
+    if settings is None:
+        prm = SvParams(0.01, 30, 50)
+    elif isinstance(settings, (tuple, list)):
+        prm = SvParams(float(settings[0]), int(settings[1]), int(settings[2]))
+    else:
+        prm = SvParams(float(settings.seq_error_rate), int(settings.min_num_matched_bases), int(settings.min_inversion_size))
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    strand = np.ascontiguousarray(anchor_strand, dtype=np.uint8)
+    chr_id = np.ascontiguousarray(chr_id, dtype=np.int32)
+    rc_flag = np.ascontiguousarray(rc_flag, dtype=np.uint8)
+    close_off = np.ascontiguousarray(close_off, dtype=np.uint64)
+    far_off = np.ascontiguousarray(far_off, dtype=np.uint64)
+    close_pts = np.ascontiguousarray(close_pts)
+    far_pts = np.ascontiguousarray(far_pts)
+    assert close_pts.dtype.itemsize == 12 and far_pts.dtype.itemsize == 12
+    mm = np.ascontiguousarray(max_mismatch, dtype=np.uint32)
+    assert len(mm) >= 500 and len(strand) == n and len(chr_id) == n and len(rc_flag) == n
+    bufs = [bytes(s) for _, s in chroms]
+    ptrs = (C.c_char_p * len(bufs))(*bufs)
+    lens = (C.c_uint64 * len(bufs))(*[len(b) for b in bufs])
+    cands = np.zeros((n, SV_SLOTS), dtype=VARIANT_CAND_DTYPE)
+    counts = np.zeros((n, len(SV_KINDS)), dtype=np.uint8)
+    rc = L.pgh_sv_candidates(len(bufs), ptrs, lens, int(spacer), n, seq.ctypes.data, seq_off.ctypes.data, strand.ctypes.data,
+                             chr_id.ctypes.data, rc_flag.ctypes.data, close_off.ctypes.data, close_pts.ctypes.data,
+                             far_off.ctypes.data, far_pts.ctypes.data, mm.ctypes.data, C.addressof(prm), cands.ctypes.data, counts.ctypes.data)
+    if rc:
+        raise ValueError("pgh_sv_candidates: " + (L.pgh_last_error() or b"").decode())
+    return cands, counts
+
+
 def last_variant_fallbacks():
     """Reads of the last call_from_points(variant_candidates=...) whose list ran out, with VARIANT_MORE set, before one of its
     pairs had made the read Used: they went through the classifier's own pair search."""
@@ -273,7 +330,7 @@ def last_variant_visits():
 
 def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pts, far_off, far_pts,
                      rc_flag, region=None, include_bed=None, exclude_bed=None, reads_config=None, normal_samples=None,
-                     bam_config=None, repairs=None, variant_candidates=None):
+                     bam_config=None, repairs=None, variant_candidates=None, sv_candidates=None):
     """Classify + report (_D, _SI, _TD, _INV) from per-read UP_Close / UP_Far points (CSR over
     all reads of the file, 12-byte pg_point records).  settings.analyze_li / settings.report_close_mapped
     add <out_prefix>_LI / <out_prefix>_CloseEndMapped, settings.report_interchromosomal <out_prefix>_INT and
@@ -288,7 +345,9 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
     command line; inv-pairs, with normal_samples and bam_config, discovers the discordant read pairs of every window in those
     BAMs for the inversion filter.  variant_candidates: (cands, counts) as variant_candidates() or Engine.variant_candidates
     return them, for the same reads -- the deletion and short-insertion classifiers then take each read's pairs from its list
-    and search only where a list runs out (last_variant_fallbacks); the reports are the same bytes."""
+    and search only where a list runs out (last_variant_fallbacks); the reports are the same bytes.  sv_candidates: (cands,
+    counts) as sv_candidates() or Engine.sv_candidates return them, made with these settings' -e, -d and -v -- the same for the
+    DI, tandem-duplication and inversion classifiers; with or without variant_candidates."""
     L = lib()
     tmp_cfg = None
     if reads_config is not None and not isinstance(reads_config, (str, bytes, os.PathLike)):
@@ -314,15 +373,25 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
     args = (str(fasta).encode(), _enc(reads_txt), str(out_prefix).encode(), C.byref(settings), len(close_off) - 1,
             close_off.ctypes.data, close_pts.ctypes.data, far_off.ctypes.data, far_pts.ctypes.data, rc_flag.ctypes.data)
     try:
-        if variant_candidates is None:
-            rc = L.pgh_call_from_points(*args)
-        else:
-            n = len(close_off) - 1
+        n = len(close_off) - 1
+        cands = counts = sv_c = sv_n = None
+        if variant_candidates is not None:
             cands = np.ascontiguousarray(variant_candidates[0], dtype=VARIANT_CAND_DTYPE)
             counts = np.ascontiguousarray(variant_candidates[1], dtype=np.uint8)
             if cands.size != n * 2 * VARIANT_CANDS or counts.size != n * 2:
                 raise ValueError(f"variant_candidates: {cands.size} records and {counts.size} counts for {n} reads")
+        if sv_candidates is not None:
+            sv_c = np.ascontiguousarray(sv_candidates[0], dtype=VARIANT_CAND_DTYPE)
+            sv_n = np.ascontiguousarray(sv_candidates[1], dtype=np.uint8)
+            if sv_c.size != n * SV_SLOTS or sv_n.size != n * len(SV_KINDS):
+                raise ValueError(f"sv_candidates: {sv_c.size} records and {sv_n.size} counts for {n} reads")
+        if variant_candidates is None and sv_candidates is None:
+            rc = L.pgh_call_from_points(*args)
+        elif sv_candidates is None:
             rc = L.pgh_call_from_points_candidates(*args, cands.ctypes.data, counts.ctypes.data)
+        else:
+            rc = L.pgh_call_from_points_lists(*args, cands.ctypes.data if cands is not None else None,
+                                              counts.ctypes.data if counts is not None else None, sv_c.ctypes.data, sv_n.ctypes.data)
     finally:
         if tmp_cfg:
             os.unlink(tmp_cfg)

@@ -1,8 +1,10 @@
-"""Measurement (one MI355X + its host): what the device classifier (pg_variant_kernel) costs and what it takes off
-the host.  On n synthetic 100-bp reads (all SV types, default parameters), searched on the GPU:
+"""Measurement (one MI355X + its host): what the device classifiers (pg_variant_kernel; pg_sv_kernel, 7l) cost and what
+they take off the host.  On n synthetic 100-bp reads (all SV types, default parameters), searched on the GPU:
   * the kernel's HIP-event time, per batch and per read;
   * the host's `deletions` and `short insertions` laps of call_from_points (PGH_TIMING=1: the per-read stage plus the
     kind's box sorting and reporting) without and with the candidate lists, next to the other classifiers' laps;
+  * pg_sv_kernel's HIP-event time beside it, and the five laps it feeds (`indels (DI)`, `tandem dup`, `tandem dup NT`, `inversions`,
+    `inversions NT`) with the lists of both kernels (column `sv`);
   * with --parent-lib: the same two laps of a libpindel_host.so built from the parent commit, on the same points.
 Prints a markdown block (profiles/variant/README.md quotes it).
 
@@ -21,7 +23,8 @@ import numpy as np
 
 from pindel_amd import hostlib
 
-ARRAYS = ("co", "cp", "fo", "fp", "rc_flag", "cands", "counts", "mm")
+ARRAYS = ("co", "cp", "fo", "fp", "rc_flag", "cands", "counts", "sv_cands", "sv_counts", "mm")
+SV_LAPS = ("indels (DI)", "tandem dup", "tandem dup NT", "inversions", "inversions NT")
 
 
 def child(mode, work, parent_lib):
@@ -33,12 +36,13 @@ def child(mode, work, parent_lib):
         L.pgh_call_from_points.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(hostlib.HostSettings), C.c_uint32] + [C.c_void_p] * 5
         hostlib._lib = L
     st = hostlib.default_settings(a["mm"])
-    lists = (a["cands"], a["counts"]) if mode == "lists" else None
+    lists = (a["cands"], a["counts"]) if mode in ("lists", "sv") else None
+    sv = (a["sv_cands"], a["sv_counts"]) if mode == "sv" else None
     t0 = time.time()
     hostlib.call_from_points(os.path.join(work, "ref.fa"), os.path.join(work, "reads.txt"), os.path.join(work, "out_" + mode), st,
-                             a["co"], a["cp"], a["fo"], a["fp"], a["rc_flag"], variant_candidates=lists)
+                             a["co"], a["cp"], a["fo"], a["fp"], a["rc_flag"], variant_candidates=lists, sv_candidates=sv)
     print(f"wall {time.time() - t0:.3f}")
-    if mode == "lists":
+    if mode in ("lists", "sv"):
         print(f"fallbacks {hostlib.last_variant_fallbacks()}")
 
 
@@ -105,6 +109,10 @@ def main():
     for _ in range(5):
         cands, counts = eng.variant_candidates(db)
         ms.append(eng.last_stats()[0])
+    sv_ms = []
+    for _ in range(5):
+        sv_cands, sv_counts = eng.sv_candidates(db)
+        sv_ms.append(eng.last_stats()[0])
     res = eng.download(db)
     eng.free_device_batch(db)
 
@@ -115,7 +123,8 @@ def main():
     note("expand and save the points")
     co, cp = csr(res.close_off, res.close_runs)
     fo, fp = csr(res.far_off, res.far_runs)
-    arrays = dict(co=co, cp=cp, fo=fo, fp=fp, rc_flag=np.asarray(res.rc_flag), cands=cands, counts=counts, mm=eng.max_mismatch_table())
+    arrays = dict(co=co, cp=cp, fo=fo, fp=fp, rc_flag=np.asarray(res.rc_flag), cands=cands, counts=counts, sv_cands=sv_cands, sv_counts=sv_counts,
+                  mm=eng.max_mismatch_table())
     for k in ARRAYS:
         np.save(os.path.join(a.dir, k + ".npy"), arrays[k])
     listed = counts & 0x7f
@@ -124,8 +133,13 @@ def main():
     print(f"- reads with a deletion candidate {(listed[:, 0] > 0).sum()}, with an insertion candidate {(listed[:, 1] > 0).sum()}, "
           f"lists with more pairs behind them {((counts & 0x80) != 0).sum()}")
     print(f"- search kernel {search_ms:.2f} ms; pg_variant_kernel {min(ms):.3f} ms (best of 5; all: {', '.join(f'{x:.3f}' for x in ms)}) = "
-          f"{min(ms) * 1e6 / n:.2f} ns per read\n", flush=True)
-    modes = ["plain", "lists"] + (["parent"] if a.parent_lib else [])
+          f"{min(ms) * 1e6 / n:.2f} ns per read")
+    sv_listed = sv_counts & 0x7f
+    print("- reads with a candidate of DI / TD / TD NT / INV / INV NT: " + " / ".join(str(int((sv_listed[:, k] > 0).sum())) for k in range(5)) +
+          f", lists with more pairs behind them {((sv_counts & 0x80) != 0).sum()}")
+    print(f"- pg_sv_kernel {min(sv_ms):.3f} ms (best of 5; all: {', '.join(f'{x:.3f}' for x in sv_ms)}) = {min(sv_ms) * 1e6 / n:.2f} ns per read\n",
+          flush=True)
+    modes = ["plain", "lists", "sv"] + (["parent"] if a.parent_lib else [])
     got = {}
     for m in modes:
         note(f"host run: {m}")
@@ -143,8 +157,13 @@ def main():
     print(f"\n- `deletions` + `short insertions` = {two:.3f} s of {total:.3f} s in laps ({100 * two / total:.1f} %); with the lists they "
           f"take {two - saved:.3f} s: the per-read stage was {saved:.3f} s ({100 * saved / total:.1f} % of the laps)")
     print(f"- reads that fell back to the pair search: {got['lists'][1].get('fallbacks')}")
-    same = all(open(os.path.join(a.dir, f"out_plain_{s}"), "rb").read() == open(os.path.join(a.dir, f"out_lists_{s}"), "rb").read()
-               for s in ("D", "SI", "TD", "INV"))
+    five = sum(p.get(k, 0.0) for k in SV_LAPS)
+    five_sv = sum(got["sv"][0].get(k, 0.0) for k in SV_LAPS)
+    print(f"- the five laps pg_sv_kernel feeds = {five:.3f} s of {total:.3f} s ({100 * five / total:.1f} %); with its lists they take {five_sv:.3f} s: "
+          f"their per-read stage was {five - five_sv:.3f} s ({100 * (five - five_sv) / total:.1f} % of the laps); fallbacks with all seven lists: "
+          f"{got['sv'][1].get('fallbacks')}")
+    same = all(open(os.path.join(a.dir, f"out_plain_{s}"), "rb").read() == open(os.path.join(a.dir, f"out_{m}_{s}"), "rb").read()
+               for s in ("D", "SI", "TD", "INV") for m in ("lists", "sv"))
     print(f"- reports with and without the lists byte-identical: {same}")
 
 
