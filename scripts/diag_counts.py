@@ -1,6 +1,7 @@
 """Diagnostics: per-read event counts of a -DPG_DIAG build (LDS fills, seed-filter runs, candidate passes, evaluations)
 on the bench workload:  python scripts/diag_counts.py <lib.so> [reads] (PG_X=<n> selects -x n, PG_LEN the read length;
-PG_DIAG_LAYOUT=2 for a -DPG_DIAG=2 build: the census of the evaluations)"""
+PG_DIAG_LAYOUT=2 for a -DPG_DIAG=2 build: the census of the evaluations; PG_DIAG_LAYOUT=3 for a -DPG_DIAG=3 build: the census of the
+fold's loops)"""
 import ctypes as C
 import os
 import sys
@@ -38,6 +39,15 @@ if os.environ.get("PG_DIAG_LAYOUT") == "2":
         print(f"{nm:24s} mean {f.mean():6.3f}  histogram 0..15: {(hist[:16] / n).round(3).tolist()}")
     ev = ((out & 0xf) + ((out >> 4) & 0xf)).astype(np.int64)
     print(f"{'evaluations':24s} mean {ev.mean():6.3f}; rounds per evaluation {((out >> 12) & 0xf).sum() / max(int(ev.sum()), 1):.3f}")
+elif os.environ.get("PG_DIAG_LAYOUT") == "3":
+    # a -DPG_DIAG=3 build: the census of the fold's loops (Search::dg, pg_kernels.hip); "full" = the share of reads whose field is at
+    # its highest value, a bound on the overflows into the next field
+    fields = [("tier A full iterations, no rings", 0, 6), ("tier A tail iterations, no rings", 6, 4), ("tier A iterations, rings", 10, 6),
+              ("tier B candidate-rounds, round 0", 16, 6), ("tier B candidate-rounds, rounds >= 1", 22, 5), ("AccB stores", 27, 4)]
+    for nm, sh, w in fields:
+        f = (out >> sh) & ((1 << w) - 1)
+        hist = np.bincount(f, minlength=10)
+        print(f"{nm:38s} mean {f.mean():7.3f}  full {(f == (1 << w) - 1).mean():.5f}  histogram 0..9: {(hist[:10] / n).round(3).tolist()}")
 else:
     names = ["LDS fills", "seed-filter runs", "candidate passes", "evaluations"]
     for k, nm in enumerate(names):
