@@ -378,6 +378,73 @@ int  pg_device_batch_sv_candidates(pg_ctx *ctx, pg_device_batch *b, const pg_sv_
 int  pg_device_batch_sv_candidates_device(pg_ctx *ctx, pg_device_batch *b, const pg_sv_params *p, pg_variant_cand *d_cands,
                                           uint8_t *d_counts);
 
+/* ---- device classifier: window tail, boxes and event tables -------------------------------------------------
+ * From the candidate lists of a searched batch and one window description to event tables on the GPU: the window-dependent
+ * tail of all seven classifiers in process_window's order (kind 0, DI, TD and TD_NT if analyze_td, INV and INV_NT if analyze_inv,
+ * kind 1 last) with the Used cascade between them, then -- for the four kinds whose reporters sort with bubblesortReads and
+ * markDuplicates: kind 0, kind 1, PG_SV_TD, PG_SV_TD_NT, "tables" 0..3 in this order -- the boxed reads in the order the sort leaves
+ * them, the duplicates marked, and the unique reads grouped into events.  A pure function of the lists, the reads of the batch, the
+ * window and the loaded reference; the lists are trusted (close_idx / far_idx are not checked against the points).  BoxSize and
+ * NumBoxes follow from the padded chromosome length as Caller::process_window computes them. */
+typedef struct {
+    int32_t  chr_id;                 /* reads with another chr_id are untouched                                    */
+    uint32_t win_end;                /* upper bound of readTransgressesBinBoundaries                              */
+    uint32_t region_start, region_end;   /* the region test is on BPLeft + 1, both ends included                  */
+    uint32_t min_support;            /* -M NumRead2ReportCutOff                                                    */
+    uint32_t balance_cutoff;         /* -B BalanceCutoff                                                           */
+    int32_t  analyze_td, analyze_inv;
+} pg_event_window;
+#define PG_EVENT_TABLES 4            /* kind 0, kind 1, PG_SV_TD, PG_SV_TD_NT */
+#define PG_EVR_BOXED      0x1u       /* pg_event_read::flags: the pair (kind, slot) put the read into a box         */
+#define PG_EVR_USED       0x2u       /* ... made it Used without a box (PG_VARIANT_REF_END, or it transgresses the window's end) */
+#define PG_EVR_UNRESOLVED 0x4u       /* the list of unresolved_kind ended with PG_VARIANT_MORE before a pair made the read Used: the
+                                      * read left the cascade there (on the host it goes to the pair search) and is in no event */
+#define PG_EVR_DUPLICATE  0x8u       /* markDuplicates: an earlier read of its box has the same (Left, Right, name)  */
+typedef struct {
+    uint8_t  kind;                   /* the kind whose pair made the read Used (valid with BOXED or USED)           */
+    uint8_t  slot;                   /* ... and the pair's place in that kind's list                                */
+    uint8_t  flags;                  /* PG_EVR_*; an untouched read is all zero                                     */
+    uint8_t  unresolved_kind;        /* valid with PG_EVR_UNRESOLVED                                                */
+    uint16_t nt_size;                /* NT_size as the cascade left it when the read was boxed (0 otherwise)        */
+    uint16_t reserved;
+} pg_event_read;
+#define PG_EV_SUPPORT 0x1u           /* pg_event::flags: n_reads >= -M                                              */
+#define PG_EV_RANGE   0x2u           /* kind 1: real_start < real_end; TD kinds: !(real_end < real_start || real_start == 0); kind 0: set */
+#define PG_EV_BALANCE 0x4u           /* the first member's IndelSize < -B, or ReportEvent over the members; kind 1: set */
+#define PG_EV_REPORT  0x8u           /* all three                                                                   */
+typedef struct {
+    uint32_t bp_left, bp_right, indel_size;   /* of the first member                                                */
+    uint32_t first, n_reads;         /* members [first, first + n_reads) of the kind's member list                  */
+    uint32_t n_plus;                 /* members with a '+' anchor                                                   */
+    uint32_t real_start, real_end;   /* GetRealStart4Deletion (GetRealStart4Insertion with the first member's NT_str for kind 1) */
+    uint32_t box_head;               /* member index of the first unique read of the event's box (GoodIndels[0])    */
+    uint16_t nt_size;                /* carried NT_size of the first member                                         */
+    uint8_t  kind;
+    uint8_t  flags;                  /* PG_EV_*                                                                     */
+} pg_event;
+typedef struct {
+    uint64_t members[PG_EVENT_TABLES];   /* unique boxed reads per table                                            */
+    uint64_t events[PG_EVENT_TABLES];
+    uint64_t unresolved;                 /* reads flagged PG_EVR_UNRESOLVED                                         */
+} pg_event_sizes;
+/* Builds the tables of the batch for one window and keeps them with the batch (a later build replaces them).  cands / counts and
+ * sv_cands / sv_counts: the lists as the two candidate entries yield them, host memory; either pair may be NULL (those kinds' lists
+ * then count as empty).  name_id: NULL (all names differ) or one uint32 per read, equal names having equal ids.  Refused with nothing
+ * launched: a batch that was not searched, a chr_id outside the reference, region_start > region_end.  n_reads == 0 and "nothing
+ * boxed" are valid.  Synchronous; pg_last_search_stats then reports the HIP-event time of the kernels.  The _device siblings take /
+ * fill device memory under the rules of "device buffers in and out".
+ * pg_device_batch_events_download: reads = n_reads records; members = the four member lists back to back (read indices, in table
+ * order); events = the four event lists back to back; sized by pg_device_batch_event_sizes.  Any of the three may be NULL. */
+int  pg_device_batch_events(pg_ctx *ctx, pg_device_batch *b, const pg_event_window *window, const pg_variant_cand *cands,
+                            const uint8_t *counts, const pg_variant_cand *sv_cands, const uint8_t *sv_counts, const uint32_t *name_id);
+int  pg_device_batch_events_device(pg_ctx *ctx, pg_device_batch *b, const pg_event_window *window, const pg_variant_cand *d_cands,
+                                   const uint8_t *d_counts, const pg_variant_cand *d_sv_cands, const uint8_t *d_sv_counts,
+                                   const uint32_t *d_name_id);
+int  pg_device_batch_event_sizes(pg_ctx *ctx, pg_device_batch *b, pg_event_sizes *sizes);
+int  pg_device_batch_events_download(pg_ctx *ctx, pg_device_batch *b, pg_event_read *reads, uint32_t *members, pg_event *events);
+int  pg_device_batch_events_download_device(pg_ctx *ctx, pg_device_batch *b, pg_event_read *d_reads, uint32_t *d_members,
+                                            pg_event *d_events);
+
 /* -q (dispersed duplications): per item i, contains_subseq_any_strand(query_i, window_i, 15) of Pindel's MEI search
  * (src/search_MEI_util.cpp:188-351, bit-exact), where query_i = query[query_off[i] .. query_off[i+1]) (at most
  * PG_MAX_READ_LEN bases) and window_i = the loaded chromosome chr_id[i] at padded (AbsLoc) positions

@@ -106,6 +106,44 @@ def sv_params(settings=None):
         return SvParams(float(settings[0]), int(settings[1]), int(settings[2]))
     return SvParams(float(settings.seq_error_rate), int(settings.min_num_matched_bases), int(settings.min_inversion_size))
 
+# event tables (Engine.events): pg_event_window, pg_event_read, pg_event, pg_event_sizes; tables 0..3 = the kinds
+# EVENT_KINDS (deletions, short insertions, TD, TD_NT)
+EVENT_TABLES = 4
+EVENT_KINDS = (0, 1, SV_TD, SV_TD_NT)
+EVR_BOXED, EVR_USED, EVR_UNRESOLVED, EVR_DUPLICATE = 1, 2, 4, 8
+EV_SUPPORT, EV_RANGE, EV_BALANCE, EV_REPORT = 1, 2, 4, 8
+KERNEL_EVENT_CASCADE, KERNEL_EVENT_SORT, KERNEL_EVENT_TABLES = 6, 7, 8      # launch-log ids after 4 (variant) and 5 (sv)
+EVENT_BLOCK = 256                       # PG_EV_BLOCK: the scan / sort block of the events kernels
+EVENT_READ_DTYPE = np.dtype([("kind", "u1"), ("slot", "u1"), ("flags", "u1"), ("unresolved_kind", "u1"), ("nt_size", "<u2"),
+                             ("reserved", "<u2")], align=True)
+EVENT_DTYPE = np.dtype([("bp_left", "<u4"), ("bp_right", "<u4"), ("indel_size", "<u4"), ("first", "<u4"), ("n_reads", "<u4"),
+                        ("n_plus", "<u4"), ("real_start", "<u4"), ("real_end", "<u4"), ("box_head", "<u4"), ("nt_size", "<u2"),
+                        ("kind", "u1"), ("flags", "u1")], align=True)
+assert EVENT_READ_DTYPE.itemsize == 8 and EVENT_DTYPE.itemsize == 40
+
+
+class EventWindow(C.Structure):
+    """pg_event_window"""
+    _fields_ = [("chr_id", C.c_int32), ("win_end", C.c_uint32), ("region_start", C.c_uint32), ("region_end", C.c_uint32),
+                ("min_support", C.c_uint32), ("balance_cutoff", C.c_uint32), ("analyze_td", C.c_int32), ("analyze_inv", C.c_int32)]
+
+
+class EventSizes(C.Structure):
+    """pg_event_sizes"""
+    _fields_ = [("members", C.c_uint64 * EVENT_TABLES), ("events", C.c_uint64 * EVENT_TABLES), ("unresolved", C.c_uint64)]
+
+
+def event_window(window):
+    """A pg_event_window from an EventWindow (of this module or hostlib's), a dict of its fields or a tuple in field order."""
+    if isinstance(window, EventWindow):
+        return window
+    if isinstance(window, dict):
+        return EventWindow(**{k: int(v) for k, v in window.items()})
+    if isinstance(window, (tuple, list)):
+        return EventWindow(*[int(v) for v in window])
+    return EventWindow(*[int(getattr(window, f)) for f, _ in EventWindow._fields_])
+
+
 # one record of the library's launch log (PgLaunchRec, pg_device.h); it keeps the first LAUNCH_LOG_CAP (pg_ctx::PG_LAUNCH_LOG_CAP)
 LaunchRec = namedtuple("LaunchRec", "kernel blocks ns id_bits mode default in_place")
 LAUNCH_LOG_CAP = 256
@@ -122,7 +160,9 @@ EXPORTS = [
     "pg_device_batch_candidates", "pg_device_batch_repack", "pg_device_batch_pack_search", "pg_dd_contains_batch",
     "pg_load_reference_device", "pg_device_batch_upload_device", "pg_device_batch_result_sizes", "pg_device_batch_download_device",
     "pg_device_batch_variant_candidates", "pg_device_batch_variant_candidates_device",
-    "pg_device_batch_sv_candidates", "pg_device_batch_sv_candidates_device"]
+    "pg_device_batch_sv_candidates", "pg_device_batch_sv_candidates_device",
+    "pg_device_batch_events", "pg_device_batch_events_device", "pg_device_batch_event_sizes",
+    "pg_device_batch_events_download", "pg_device_batch_events_download_device"]
 
 
 def build(force: bool = False) -> str:
@@ -218,6 +258,11 @@ def lib():
     L.pg_device_batch_variant_candidates_device.argtypes = [vp, vp, vp, vp]
     L.pg_device_batch_sv_candidates.argtypes = [vp, vp, vp, vp, vp]
     L.pg_device_batch_sv_candidates_device.argtypes = [vp, vp, vp, vp, vp]
+    L.pg_device_batch_events.argtypes = [vp] * 8
+    L.pg_device_batch_events_device.argtypes = [vp] * 8
+    L.pg_device_batch_event_sizes.argtypes = [vp, vp, vp]
+    L.pg_device_batch_events_download.argtypes = [vp] * 5
+    L.pg_device_batch_events_download_device.argtypes = [vp] * 5
     _lib = L
     return L
 
@@ -397,6 +442,22 @@ def sv_cands_from_tensor(t) -> np.ndarray:
     """The uint8[n, SV_SLOTS * 32] tensor of sv_candidates_tensors as a VARIANT_CAND_DTYPE[n, SV_SLOTS] array (a CPU copy)."""
     a = np.ascontiguousarray(t.cpu().numpy())
     return a.reshape(-1).view(VARIANT_CAND_DTYPE).reshape(-1, SV_SLOTS)
+
+
+def _event_tables(reads, members, events, nm, ne, unresolved):
+    mo = np.concatenate([[0], np.cumsum(nm)]).astype(np.int64)
+    eo = np.concatenate([[0], np.cumsum(ne)]).astype(np.int64)
+    return dict(reads=reads, members=[members[mo[t]:mo[t + 1]] for t in range(EVENT_TABLES)],
+                events=[events[eo[t]:eo[t + 1]] for t in range(EVENT_TABLES)], unresolved=int(unresolved),
+                members_flat=members, events_flat=events, n_members=list(nm), n_events=list(ne))
+
+
+def events_from_tensors(t) -> dict:
+    """The dict of events_tensors as the dict events returns (CPU copies)."""
+    reads = np.ascontiguousarray(t["reads"].cpu().numpy()).reshape(-1).view(EVENT_READ_DTYPE)
+    members = np.ascontiguousarray(t["members"].cpu().numpy()).view(np.uint32)
+    events = np.ascontiguousarray(t["events"].cpu().numpy()).reshape(-1).view(EVENT_DTYPE)
+    return _event_tables(reads, members, events, t["n_members"], t["n_events"], t["unresolved"])
 
 
 def variant_cands_from_tensor(t) -> np.ndarray:
@@ -707,6 +768,81 @@ class Engine:
         out = dict(cands=torch.empty((n, SV_SLOTS * 32), dtype=torch.uint8, device=dev),
                    counts=torch.empty((n, SV_KINDS), dtype=torch.uint8, device=dev))
         self.sv_candidates_into(dbatch, settings=settings, **out)
+        return out
+
+    def event_sizes(self, dbatch):
+        """pg_device_batch_event_sizes: (members per table, events per table, unresolved reads) of the tables built last."""
+        sz = EventSizes()
+        self._check(self._L.pg_device_batch_event_sizes(self._h, dbatch, C.addressof(sz)))
+        return [int(x) for x in sz.members], [int(x) for x in sz.events], int(sz.unresolved)
+
+    def events(self, dbatch, window, variant=None, sv=None, name_id=None):
+        """Event tables of a searched device batch for one window (pg_device_batch_events): the window-dependent tail
+        and Used cascade of all seven classifiers over the candidate lists, then the boxed reads of deletions, short insertions, TD
+        and TD_NT sorted, duplicates marked and grouped into events, all on the GPU.  window: see event_window(); variant / sv: the
+        (cands, counts) pairs variant_candidates / sv_candidates return, or None (empty lists); name_id: None (all names differ) or
+        uint32 per read.  Returns a dict: reads EVENT_READ_DTYPE[n]; members and events, lists of four arrays (uint32 read indices,
+        EVENT_DTYPE) in EVENT_KINDS order; unresolved; members_flat / events_flat (the four back to back, as downloaded)."""
+        n = self._batch_n[dbatch.value]
+        w = event_window(window)
+        keep = []
+
+        def ptr(a, dtype, size):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if a.size != size:
+                raise ValueError(f"events: an array of {size} {dtype} is expected, got {a.size}")
+            keep.append(a)
+            return a.ctypes.data if size else None
+        vc = vn = sc = sn = None
+        if variant is not None:
+            vc, vn = ptr(variant[0], VARIANT_CAND_DTYPE, n * 2 * VARIANT_CANDS), ptr(variant[1], np.uint8, n * 2)
+        if sv is not None:
+            sc, sn = ptr(sv[0], VARIANT_CAND_DTYPE, n * SV_SLOTS), ptr(sv[1], np.uint8, n * SV_KINDS)
+        nid = ptr(name_id, np.uint32, n)
+        self._check(self._L.pg_device_batch_events(self._h, dbatch, C.addressof(w), vc, vn, sc, sn, nid))
+        nm, ne, unresolved = self.event_sizes(dbatch)
+        reads = np.zeros(n, dtype=EVENT_READ_DTYPE)
+        members = np.zeros(sum(nm), dtype=np.uint32)
+        events = np.zeros(sum(ne), dtype=EVENT_DTYPE)
+        self._check(self._L.pg_device_batch_events_download(self._h, dbatch, reads.ctypes.data if n else None,
+                                                            members.ctypes.data if members.size else None,
+                                                            events.ctypes.data if events.size else None))
+        return _event_tables(reads, members, events, nm, ne, unresolved)
+
+    def events_tensors(self, dbatch, window, variant=None, sv=None, name_id=None):
+        """events with everything staying on the GPU (pg_device_batch_events_device and its download sibling): variant / sv are the
+        dicts variant_candidates_tensors / sv_candidates_tensors return (or (cands, counts) tensor pairs), name_id an int32 / uint32
+        tensor of n entries or None.  Returns a dict of tensors on this engine's device: reads uint8[n, 8], members int32[total],
+        events uint8[total, 40], plus n_members / n_events (lists of four) and unresolved."""
+        torch, dev = self._torch_ready()
+        n = self._batch_n[dbatch.value]
+        w = event_window(window)
+
+        def pair(x, widths):
+            if x is None:
+                return None, None
+            c, k = (x["cands"], x["counts"]) if isinstance(x, dict) else x
+            for name, t, width in (("cands", c, widths[0]), ("counts", k, widths[1])):
+                if str(t.dtype) != "torch.uint8" or tuple(t.shape) != (n, width) or not t.is_contiguous() or str(t.device) != dev:
+                    raise ValueError(f"events: {name}: a contiguous uint8[{n}, {width}] tensor on {dev} is expected")
+            return (c.data_ptr(), k.data_ptr()) if n else (None, None)
+        vc, vn = pair(variant, (2 * VARIANT_CANDS * 32, 2))
+        sc, sn = pair(sv, (SV_SLOTS * 32, SV_KINDS))
+        nid = None
+        if name_id is not None:
+            if name_id.numel() != n or name_id.element_size() != 4 or not name_id.is_contiguous() or str(name_id.device) != dev:
+                raise ValueError(f"events: name_id: a contiguous 32-bit tensor of {n} entries on {dev} is expected")
+            nid = name_id.data_ptr() if n else None
+        self._check(self._L.pg_device_batch_events_device(self._h, dbatch, C.addressof(w), vc, vn, sc, sn, nid))
+        nm, ne, unresolved = self.event_sizes(dbatch)
+        out = dict(reads=torch.empty((n, 8), dtype=torch.uint8, device=dev), members=torch.empty(sum(nm), dtype=torch.int32, device=dev),
+                   events=torch.empty((sum(ne), 40), dtype=torch.uint8, device=dev))
+        self._check(self._L.pg_device_batch_events_download_device(self._h, dbatch, out["reads"].data_ptr() if n else None,
+                                                                   out["members"].data_ptr() if sum(nm) else None,
+                                                                   out["events"].data_ptr() if sum(ne) else None))
+        out.update(n_members=nm, n_events=ne, unresolved=unresolved)
         return out
 
     def set_windows(self, dbatch, bd=None, bd_off=None):

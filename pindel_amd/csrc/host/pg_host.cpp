@@ -1014,6 +1014,28 @@ void Caller::process_window(const Chromosome &chrom, std::vector<SplitRead> &rea
         fprintf(stderr, "pgh timing: %-18s %.3f s (%zu reads)\n", what, t1 - t, reads.size());
         t = t1;
     };
+    if (S.use_events) {
+        EventPathStats &es = event_path_stats();
+        int chr_index = -1;
+        if (genome)
+            for (size_t k = 0; k < genome->size(); k++)
+                if (&(*genome)[k] == &chrom) chr_index = (int)k;
+        const uint32_t v[6] = { (uint32_t)chr_index, win_start, win_end, region_start, region_end, (uint32_t)reads.size() };
+        es.windows.insert(es.windows.end(), v, v + 6);
+        if (process_window_events(c)) {
+            es.table_windows++;
+            lap("event tables");
+            flush_reports();
+            if (S.Analyze_LI) {
+                const double t_li = now();
+                sort_output_li(c, win_start, win_end);
+                li_seconds += now() - t_li;
+            }
+            if (S.report_interchromosomal) report_interchr();
+            return;
+        }
+        es.fallback_windows++;
+    }
     search_variant(c, 0);
     lap("deletions");
     search_indels(c);

@@ -154,6 +154,18 @@ struct DiscordantPair {
 bool inv_pairs_good(const std::vector<DiscordantPair> &pairs, unsigned support, unsigned real_start, unsigned real_end,
                     unsigned *counts = nullptr);
 
+// Event tables of one window as pg_device_batch_events_download yields them, over ALL reads of the run (indexed by
+// SplitRead::VarIndex): n_reads records, the four member lists and the four event lists back to back.
+struct SuppliedEvents {
+    int chr = -1;
+    unsigned win_start = 0, win_end = 0;
+    uint32_t n_reads = 0;
+    const pg_event_read *reads = nullptr;
+    const uint32_t *members = nullptr;
+    const pg_event *events = nullptr;
+    pg_event_sizes sizes{};
+};
+
 struct Settings {                 // the flags the downstream steps read (src/fn_parameters.cpp)
     unsigned spacer = 100000;
     unsigned NumRead2ReportCutOff = 1;   // -M
@@ -177,7 +189,21 @@ struct Settings {                 // the flags the downstream steps read (src/fn
     bool germline_filter() const { return NormalSamples && germline; }
     uint32_t repairs = 0;                // --repair: REPAIR_* bits (default none: the reference's behaviour, defects included)
     bool repair(uint32_t bit) const { return (repairs & bit) != 0; }
+    // Opt-in: process_window builds event tables from the reads' candidate lists and writes deletions, short
+    // insertions and tandem duplications from them; supplied_events: tables a caller built elsewhere (on the device) for a window.
+    bool use_events = false;
+    std::vector<SuppliedEvents> supplied_events;
 };
+
+// What the events path of the last run did.  windows: six values per window process_window saw with use_events set -- chromosome
+// index, win_start, win_end, region_start, region_end, reads -- in order.
+struct EventPathStats {
+    uint64_t fallback_windows = 0;       // windows with an unresolved read (or without usable lists): the existing path ran
+    uint64_t table_windows = 0;          // windows written from tables
+    uint64_t supplied_windows = 0;       // ... of them, from supplied tables
+    std::vector<uint32_t> windows;
+};
+EventPathStats &event_path_stats();
 
 int load_fasta(const std::string &path, std::vector<Chromosome> &out, unsigned spacer, std::string &err);
 
@@ -331,6 +357,8 @@ private:
     // other reports (pindel.cpp:1940-1942)
     std::vector<SplitRead> interchr_;
     std::vector<DiscordantPair> inv_pairs_;
+    // the events path (pg_host_events.cpp): false = the window has to go through the existing path
+    bool process_window_events(Ctx &c);
     void collect_interchr(const std::vector<SplitRead> &reads);
     void report_interchr();
 };

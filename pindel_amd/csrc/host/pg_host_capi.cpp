@@ -8,6 +8,7 @@
 #include <sstream>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "pg_bam.hpp"
@@ -15,6 +16,7 @@
 #include "pg_dd.hpp"
 #include "pg_depth.hpp"
 #include "pg_host.hpp"
+#include "pg_host_events.hpp"
 #include "pg_host_priv.hpp"
 #include "pg_pipeline.hpp"
 #include "pg_rp.hpp"
@@ -72,7 +74,8 @@ static int call_from_points(const char *fasta_path, const char *reads_path, cons
                             const uint64_t *close_off, const pg_point *close_pts,
                             const uint64_t *far_off, const pg_point *far_pts, const uint8_t *rc_flag,
                             const pg_variant_cand *var_cands, const uint8_t *var_counts,
-                            const pg_variant_cand *sv_cands = nullptr, const uint8_t *sv_counts = nullptr)
+                            const pg_variant_cand *sv_cands = nullptr, const uint8_t *sv_counts = nullptr, bool use_events = false,
+                            const std::vector<SuppliedEvents> *supplied = nullptr)
 {
     std::vector<Chromosome> genome;
     if (load_fasta(fasta_path, genome, st->spacer, g_err)) return -1;
@@ -98,6 +101,9 @@ static int call_from_points(const char *fasta_path, const char *reads_path, cons
     memcpy(S.max_mismatch, st->max_mismatch, sizeof S.max_mismatch);
     S.NormalSamples = st->normal_samples != 0;
     S.repairs = st->repairs;
+    S.use_events = use_events;
+    if (supplied) S.supplied_events = *supplied;
+    event_path_stats() = EventPathStats();
     if (S.repairs & ~(uint32_t)REPAIR_ALL) {
         g_err = "unknown bits in the repairs field";
         return -1;
@@ -201,6 +207,60 @@ int pgh_call_from_points_lists(const char *fasta_path, const char *reads_path, c
     }
     return call_from_points(fasta_path, reads_path, out_prefix, st, n_reads, close_off, close_pts, far_off, far_pts, rc_flag, var_cands, var_counts,
                             sv_cands, sv_counts);
+}
+
+/*
+ * pgh_call_from_points_lists with the events path switched on: per window process_window builds the event tables
+ * from the lists (pgh_events_from_lists' function) and writes deletions, short insertions and tandem duplications from them; DI and
+ * the inversions take their boxes from the per-read records.  Both pairs of list arrays are needed.  A window with an unresolved
+ * read takes the existing path as a whole (pgh_last_event_fallback_windows).  supplied: n_supplied tables built elsewhere (on the
+ * device) for the window (chr, win_start, win_end) over all n_reads reads; a window without an entry uses the host builder.  The
+ * reports are the bytes pgh_call_from_points writes.
+ */
+struct pgh_supplied_events {
+    int32_t chr;
+    uint32_t win_start, win_end, reserved;
+    const pg_event_read *reads;
+    const uint32_t *members;
+    const pg_event *events;
+    pg_event_sizes sizes;
+};
+int pgh_call_from_points_events(const char *fasta_path, const char *reads_path, const char *out_prefix, const pgh_settings *st,
+                                uint32_t n_reads, const uint64_t *close_off, const pg_point *close_pts, const uint64_t *far_off,
+                                const pg_point *far_pts, const uint8_t *rc_flag, const pg_variant_cand *var_cands, const uint8_t *var_counts,
+                                const pg_variant_cand *sv_cands, const uint8_t *sv_counts, int32_t n_supplied, const pgh_supplied_events *sup)
+{
+    if (!var_cands || !var_counts || !sv_cands || !sv_counts) {
+        g_err = "pgh_call_from_points_events: the lists of both device classifiers are needed";
+        return -1;
+    }
+    std::vector<SuppliedEvents> supplied;
+    for (int32_t k = 0; k < n_supplied; k++) {
+        SuppliedEvents e;
+        e.chr = sup[k].chr;
+        e.win_start = sup[k].win_start;
+        e.win_end = sup[k].win_end;
+        e.n_reads = n_reads;
+        e.reads = sup[k].reads;
+        e.members = sup[k].members;
+        e.events = sup[k].events;
+        e.sizes = sup[k].sizes;
+        supplied.push_back(e);
+    }
+    return call_from_points(fasta_path, reads_path, out_prefix, st, n_reads, close_off, close_pts, far_off, far_pts, rc_flag, var_cands, var_counts,
+                            sv_cands, sv_counts, true, &supplied);
+}
+/* windows of the last run with the events path that took the existing path / were written from tables / ... from supplied tables */
+uint64_t pgh_last_event_fallback_windows(void) { return event_path_stats().fallback_windows; }
+uint64_t pgh_last_event_table_windows(void) { return event_path_stats().table_windows; }
+uint64_t pgh_last_event_supplied_windows(void) { return event_path_stats().supplied_windows; }
+/* the windows the events path saw, six values each: chromosome index, win_start, win_end, region_start, region_end, reads */
+uint64_t pgh_last_event_windows(uint32_t *out, uint64_t cap)
+{
+    const std::vector<uint32_t> &v = event_path_stats().windows;
+    const uint64_t n = v.size() / 6;
+    if (out) std::copy(v.begin(), v.begin() + (size_t)std::min(n, cap) * 6, out);
+    return n;
 }
 
 /* reads of the last pgh_call_from_points_candidates that went through the pair search after their list (both kinds, all windows) */
@@ -378,6 +438,94 @@ int pgh_sv_candidates(int32_t n_chr, const char *const *chr_seq, const uint64_t 
         }
     });
     return 0;
+}
+
+/*
+ * Event tables from candidate lists (pindel_pg.h "window tail, boxes and event tables"), on the host: the plain-loop
+ * statement (pg_host_events.hpp) the device entry pg_device_batch_events is compared with, byte for byte.  The reads and points as
+ * pgh_variant_candidates takes them, plus insert_size; either pair of list arrays and name_id may be null.  out_reads: n_reads
+ * records; out_members / out_events: room for n_reads entries each (a read is boxed at most once), filled table after table;
+ * sizes: what was filled.  -1: the window is refused (chr_id outside the reference, region_start > region_end).
+ */
+int pgh_events_from_lists(int32_t n_chr, const char *const *chr_seq, const uint64_t *chr_len, uint32_t spacer, uint32_t n_reads,
+                          const uint8_t *seq, const uint64_t *seq_off, const uint8_t *strand, const int32_t *chr_id, const uint8_t *rc_flag,
+                          const int16_t *insert_size, const uint64_t *close_off, const pg_point *close_pts, const uint64_t *far_off,
+                          const pg_point *far_pts, const pg_event_window *w, const pg_variant_cand *cands, const uint8_t *counts,
+                          const pg_variant_cand *sv_cands, const uint8_t *sv_counts, const uint32_t *name_id, pg_event_read *out_reads,
+                          uint32_t *out_members, pg_event *out_events, pg_event_sizes *sizes)
+{
+    if (!w || !sizes || w->chr_id < 0 || w->chr_id >= n_chr) {
+        g_err = "pgh_events_from_lists: the window's chr_id lies outside the reference";
+        return -1;
+    }
+    if (w->region_start > w->region_end) {
+        g_err = "pgh_events_from_lists: region_start > region_end";
+        return -1;
+    }
+    if ((cands == nullptr) != (counts == nullptr) || (sv_cands == nullptr) != (sv_counts == nullptr)) {
+        g_err = "pgh_events_from_lists: candidate arrays come in pairs";
+        return -1;
+    }
+    const std::string ref(chr_seq[w->chr_id], (size_t)chr_len[w->chr_id]);
+    auto post_state = [&](uint32_t i, SplitRead &r) {
+        r.UnmatchedSeq.assign((const char *)seq + seq_off[i], (size_t)(seq_off[i + 1] - seq_off[i]));
+        pg_adapter::apply_rc_flag(r, rc_flag[i]);
+        r.ReadLength = (short)r.UnmatchedSeq.size();
+        r.MatchedD = (char)strand[i];
+    };
+    std::vector<EventReadIn> in(n_reads);
+    pg_adapter::parallel_ranges(n_reads, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; i++) {
+            EventReadIn &e = in[i];
+            e.in_window = chr_id[i] == w->chr_id;
+            if (!e.in_window) continue;
+            SplitRead r;
+            post_state((uint32_t)i, r);
+            e.plus = strand[i] == '+';
+            e.insert_size = insert_size[i];
+            e.read_length = r.ReadLength;
+            e.name_id = name_id ? name_id[i] : (uint32_t)i;
+            if (cands) {
+                e.var = cands + i * 2 * PG_VARIANT_CANDS;
+                e.var_counts = counts + i * 2;
+            }
+            if (sv_cands) {
+                e.sv = sv_cands + i * PG_SV_SLOTS;
+                e.sv_counts = sv_counts + i * PG_SV_KINDS;
+            }
+        }
+    });
+    EventTables tabs;
+    events_from_lists(ref, spacer, *w, in, [&](uint32_t i, const pg_variant_cand &c) {
+        SplitRead r;
+        post_state(i, r);
+        for (uint64_t q = close_off[i]; q < close_off[i + 1]; q++) r.UP_Close.push_back(to_unique_point(close_pts[q]));
+        for (uint64_t q = far_off[i]; q < far_off[i + 1]; q++) r.UP_Far.push_back(to_unique_point(far_pts[q]));
+        VariantPair p;
+        if (!variant_pair_from_cand(r, 1, c, p)) return std::string();
+        return p.nt;
+    }, tabs);
+    if (n_reads) memcpy(out_reads, tabs.reads.data(), (size_t)n_reads * sizeof(pg_event_read));
+    size_t m = 0, e = 0;
+    for (int t = 0; t < PG_EVENT_TABLES; t++) {
+        sizes->members[t] = tabs.members[t].size();
+        sizes->events[t] = tabs.events[t].size();
+        if (!tabs.members[t].empty()) memcpy(out_members + m, tabs.members[t].data(), tabs.members[t].size() * sizeof(uint32_t));
+        if (!tabs.events[t].empty()) memcpy(out_events + e, tabs.events[t].data(), tabs.events[t].size() * sizeof(pg_event));
+        m += tabs.members[t].size();
+        e += tabs.events[t].size();
+    }
+    sizes->unresolved = tabs.unresolved;
+    return 0;
+}
+
+/* Numbers names by first occurrence: id[i] = the index of the first name equal to names[i] among the distinct ones (the name_id
+ * array of the events entries).  names: n NUL-terminated strings. */
+void pgh_name_ids(uint32_t n, const char *const *names, uint32_t *id)
+{
+    std::unordered_map<std::string, uint32_t> seen;
+    seen.reserve((size_t)n * 2);
+    for (uint32_t i = 0; i < n; i++) id[i] = seen.emplace(names[i], (uint32_t)seen.size()).first->second;
 }
 
 /* "int-pairs,depth-mapq" / "all" -> the bits of pgh_settings.repairs; -1 = an unknown name or an empty list (pgh_last_error) */

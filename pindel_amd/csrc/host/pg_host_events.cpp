@@ -1,0 +1,218 @@
+// pg_host_events.cpp -- the opt-in events path of Caller::process_window: the window's event tables are built
+// from the reads' candidate lists (pg_host_events.hpp) or taken from the caller (built on the device), and deletions, short
+// insertions and tandem duplications are written from them -- `good` from the member lists with the pairs' fields applied, the
+// reporters' output_* functions for the events flagged PG_EV_REPORT, in table order.  DI and the inversions take their boxes from
+// the per-read records and keep their own reporters (their exchange sorts are strict: no stable sort reproduces their tie order).
+// The reports must be the bytes of the existing path: that is what pins pg_host_events.hpp to the reference's gold reports.
+#include <unordered_map>
+
+#include "pg_depth.hpp"
+#include "pg_host_events.hpp"
+#include "pg_host_priv.hpp"
+
+namespace pgh {
+
+using namespace detail;
+
+EventPathStats &event_path_stats()
+{
+    static EventPathStats s;
+    return s;
+}
+
+bool Caller::process_window_events(Ctx &c)
+{
+    std::vector<SplitRead> &reads = *c.reads;
+    const std::string &ref = c.chrom->seq;
+    const size_t n = reads.size();
+    // the lists of both device classifiers for every read, and a -v the inversion lists are consulted with
+    if (!sv_list_usable(S)) return false;
+    for (const SplitRead &r : reads)
+        if (!r.VarCands || !r.SvCands) return false;
+    pg_event_window w;
+    w.chr_id = 0;
+    w.win_end = c.win_end;
+    w.region_start = c.region_start;
+    w.region_end = c.region_end;
+    w.min_support = S.NumRead2ReportCutOff;
+    w.balance_cutoff = S.BalanceCutoff;
+    w.analyze_td = S.Analyze_TD;
+    w.analyze_inv = S.Analyze_INV;
+    if (w.region_start > w.region_end) return false;
+
+    EventTables tabs;
+    const SuppliedEvents *sup = nullptr;
+    for (const SuppliedEvents &e : S.supplied_events)
+        if (genome && e.chr >= 0 && e.chr < (int)genome->size() && &(*genome)[e.chr] == c.chrom && e.win_start == c.win_start && e.win_end == c.win_end)
+            sup = &e;
+    bool from_supplied = false;
+    if (sup) {
+        // the supplied tables index the reads of the whole run: to the window's own indices.  Tables that touch a read the window
+        // does not hold (the device cascade sees every read of the chromosome) are not this window's: the host builds its own.
+        std::unordered_map<uint32_t, uint32_t> local;
+        local.reserve(n * 2);
+        for (size_t k = 0; k < n; k++) local[reads[k].VarIndex] = (uint32_t)k;
+        bool ok = true;
+        for (uint32_t i = 0; i < sup->n_reads && ok; i++)
+            if (sup->reads[i].flags) ok = local.count(i) != 0;
+        tabs.reads.assign(n, pg_event_read());
+        for (size_t k = 0; k < n && ok; k++) {
+            ok = reads[k].VarIndex < sup->n_reads;
+            if (ok) tabs.reads[k] = sup->reads[reads[k].VarIndex];
+        }
+        size_t m0 = 0, e0 = 0;
+        for (int t = 0; t < PG_EVENT_TABLES && ok; t++) {
+            for (uint64_t k = 0; k < sup->sizes.members[t] && ok; k++) {
+                auto it = local.find(sup->members[m0 + k]);
+                ok = it != local.end();
+                if (ok) tabs.members[t].push_back(it->second);
+            }
+            tabs.events[t].assign(sup->events + e0, sup->events + e0 + sup->sizes.events[t]);
+            for (const pg_event &ev : tabs.events[t])
+                ok = ok && (uint64_t)ev.first + ev.n_reads <= sup->sizes.members[t] && ev.box_head <= ev.first && ev.n_reads > 0;
+            m0 += sup->sizes.members[t];
+            e0 += sup->sizes.events[t];
+        }
+        tabs.unresolved = sup->sizes.unresolved;
+        from_supplied = ok;
+    }
+    if (!from_supplied) {
+        std::vector<EventReadIn> in(n);
+        std::unordered_map<std::string, uint32_t> names;
+        names.reserve(n * 2);
+        for (size_t k = 0; k < n; k++) {
+            const SplitRead &r = reads[k];
+            EventReadIn &e = in[k];
+            e.in_window = true;
+            e.plus = r.MatchedD == '+';
+            e.insert_size = r.InsertSize;
+            e.read_length = r.getReadLength();
+            e.name_id = names.emplace(r.Name, (uint32_t)names.size()).first->second;
+            e.var = r.VarCands;
+            e.var_counts = r.VarCounts;
+            e.sv = r.SvCands;
+            e.sv_counts = r.SvCounts;
+        }
+        tabs = EventTables();
+        events_from_lists(ref, S.spacer, w, in, [&](uint32_t k, const pg_variant_cand &cand) {
+            VariantPair p;
+            if (!variant_pair_from_cand(reads[k], 1, cand, p)) return std::string();
+            return p.nt;
+        }, tabs);
+    }
+    // A read whose list ran out goes to the pair search on the host; the tables do not replay that: the whole window takes the
+    // existing path.  So does a window whose records do not fit its reads' lists.
+    if (tabs.unresolved) return false;
+    for (size_t k = 0; k < n; k++) {
+        const pg_event_read &rec = tabs.reads[k];
+        if (!(rec.flags & (PG_EVR_BOXED | PG_EVR_USED))) continue;
+        const pg_variant_cand *list;
+        uint8_t count;
+        unsigned cap;
+        EventReadIn e;
+        e.var = reads[k].VarCands;
+        e.var_counts = reads[k].VarCounts;
+        e.sv = reads[k].SvCands;
+        e.sv_counts = reads[k].SvCounts;
+        if (rec.kind > PG_SV_INV_NT) return false;
+        event_list(e, rec.kind, list, count, cap);
+        if (rec.slot >= std::min<unsigned>(count & ~PG_VARIANT_MORE, cap)) return false;
+    }
+    if (from_supplied) event_path_stats().supplied_windows++;
+
+    auto cand_of = [&](size_t k) -> const pg_variant_cand & {
+        const pg_event_read &rec = tabs.reads[k];
+        return rec.kind < 2 ? reads[k].VarCands[rec.kind * PG_VARIANT_CANDS + rec.slot]
+                            : reads[k].SvCands[sv_slot_base()[rec.kind - PG_SV_DI] + rec.slot];
+    };
+    for (size_t k = 0; k < n; k++)
+        if (tabs.reads[k].flags & (PG_EVR_BOXED | PG_EVR_USED)) reads[k].Used = true;
+
+    // `good` of a table: the members with the pair's fields applied, the NT_size the cascade carried and the NT_str that goes with it
+    auto good_of = [&](int t, std::vector<SplitRead> &good) {
+        const int kind = event_kind_of(t);
+        good.clear();
+        good.reserve(tabs.members[t].size());
+        VariantPair p;
+        for (uint32_t k : tabs.members[t]) {
+            good.push_back(reads[k]);
+            SplitRead &g = good.back();
+            const pg_variant_cand &cand = cand_of(k);
+            if (kind < 2) {
+                variant_pair_from_cand(reads[k], kind, cand, p);
+                apply_variant_pair(g, p);
+            } else {
+                if (kind == PG_SV_TD) {
+                    // searchTandemDuplications leaves NT_str alone: it is DI's where DI listed a pair (applied, whatever the window
+                    // made of it), and empty otherwise (kind 0 assigns an empty one, a fresh read has none)
+                    g.NT_str.clear();
+                    if ((reads[k].SvCounts[0] & ~PG_VARIANT_MORE) >= 1 && sv_pair_from_cand(reads[k], PG_SV_DI, reads[k].SvCands[0], p)) g.NT_str = p.nt;
+                }
+                sv_pair_from_cand(reads[k], kind, cand, p);
+                apply_sv_pair(g, kind, p);
+            }
+            g.NT_size = tabs.reads[k].nt_size;
+            g.Used = true;
+        }
+    };
+    // one table written in table order: the order of the boxes, and of the events within each
+    auto write_table = [&](int t) {
+        const int kind = event_kind_of(t);
+        if (tabs.events[t].empty()) return;
+        bool any = false;
+        for (const pg_event &ev : tabs.events[t]) any = any || (ev.flags & PG_EV_REPORT);
+        if (!any) return;
+        std::vector<SplitRead> good;
+        good_of(t, good);
+        for_boxes(1, [&](unsigned) {
+            for (const pg_event &ev : tabs.events[t]) {
+                if (!(ev.flags & PG_EV_REPORT)) continue;
+                const unsigned s = ev.first, e = ev.first + ev.n_reads - 1;
+                if (kind == 0) output_deletion(c, good, s, e, ev.real_start, ev.real_end);
+                else if (kind == 1) output_si(c, good, s, e, ev.real_start, ev.real_end);
+                else {
+                    // IsGoodTD's -N test (sort_output_td), with GoodIndels[0] = the first unique read of the event's box
+                    if (S.germline_filter() && ev.real_end - ev.real_start >= (unsigned)(good[ev.box_head].getReadLength() * 2)) {
+                        std::set<std::string> tags;
+                        for (unsigned i = s; i <= e; i++) tags.insert(good[i].Tag);
+                        if (!S.germline->good_td(c.chrom->name, (int64_t)c.chrom->seq.size() - 2 * (int64_t)S.spacer, ev.real_start, ev.real_end, tags))
+                            continue;
+                    }
+                    output_td(c, good, s, e, ev.real_start, ev.real_end);
+                }
+            }
+        });
+    };
+    // the boxes of a kind that keeps its own reporter, from the per-read records: ascending read index, as the classifier pushes
+    auto boxes_of = [&](int kind, std::vector<std::vector<unsigned>> &boxes) {
+        boxes.assign(c.NumBoxes, std::vector<unsigned>());
+        VariantPair p;
+        for (size_t k = 0; k < n; k++) {
+            const pg_event_read &rec = tabs.reads[k];
+            if (!(rec.flags & PG_EVR_BOXED) || rec.kind != kind) continue;
+            const pg_variant_cand &cand = cand_of(k);
+            sv_pair_from_cand(reads[k], kind, cand, p);
+            apply_sv_pair(reads[k], kind, p);
+            const unsigned box = (unsigned)((int)cand.bp_left / (int)BoxSize);
+            if (box < c.NumBoxes) boxes[box].push_back((unsigned)k);
+        }
+    };
+    std::vector<std::vector<unsigned>> boxes;
+    write_table(0);
+    boxes_of(PG_SV_DI, boxes);
+    sort_output_di(c, boxes);
+    if (S.Analyze_TD) {
+        write_table(2);
+        write_table(3);
+    }
+    if (S.Analyze_INV) {
+        boxes_of(PG_SV_INV, boxes);
+        sort_output_inv(c, boxes, false);
+        boxes_of(PG_SV_INV_NT, boxes);
+        sort_output_inv(c, boxes, true);
+    }
+    write_table(1);
+    return true;
+}
+
+}  // namespace pgh

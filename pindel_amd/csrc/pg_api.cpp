@@ -299,6 +299,12 @@ struct pg_device_batch {
     bool soa_uploaded = false;
     long long exact_n = -1;            // host copy of the counter; -1: not read back (the exact kernel is launched regardless)
     bool searched = false;             // close end + far end have run on the batch: its output records and run pool hold a result
+    // the event tables of the last pg_device_batch_events (always allocations of their own; null: none built)
+    pg_event_read *ev_reads = nullptr;     // n
+    uint32_t *ev_members = nullptr;        // n: the four member lists back to back
+    pg_event *ev_events = nullptr;         // n: the four event lists back to back
+    pg_event_sizes ev_sizes{};
+    bool ev_built = false;
 };
 
 struct pg_result {
@@ -451,6 +457,12 @@ PgDevParams dev_params(const pg_ctx *ctx)
 
 void free_batch_buffers(pg_device_batch *b)
 {
+    for (void *p : { (void *)b->ev_reads, (void *)b->ev_members, (void *)b->ev_events })
+        if (p) (void)hipFree(p);
+    b->ev_reads = nullptr;
+    b->ev_members = nullptr;
+    b->ev_events = nullptr;
+    b->ev_built = false;
     if (b->in_arena) {
         if (b->pool_owned && b->pool) (void)hipFree(b->pool);
         if (b->bd_off) (void)hipFree(b->bd_off);          // window clusters are always allocated on their own
@@ -2399,6 +2411,229 @@ int pg_device_batch_sv_candidates(pg_ctx *ctx, pg_device_batch *b, const pg_sv_p
     HIP_TRY(ctx, hipMemcpy(cands, d_cands, cand_bytes, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(counts, d_counts, n * PG_SV_KINDS, hipMemcpyDeviceToHost));
     return PG_OK;
+}
+
+// ---- ... its third part (pg_events.hip): window tail, boxes and event tables
+namespace {
+struct EventTemps {                                           // device scratch of one build, released when it ends
+    std::vector<void *> owned;
+    ~EventTemps()
+    {
+        for (void *p : owned) (void)hipFree(p);
+    }
+    // n elements of elem bytes into *p (as dev_alloc: at least one)
+    int take(pg_ctx *ctx, void *p, size_t n, size_t elem)
+    {
+        uint8_t *q = nullptr;
+        if (int rc = dev_alloc(ctx, &q, std::max<size_t>(n, 1) * elem)) return rc;
+        owned.push_back(q);
+        *(void **)p = q;
+        return PG_OK;
+    }
+};
+#define EV_TAKE(tmp, ctx, p, n) (tmp).take(ctx, &(p), n, sizeof *(p))
+
+// the refusals of both build entries, before anything is launched or copied
+int events_refusal(pg_ctx *ctx, pg_device_batch *b, const pg_event_window *w, bool lists_null_mismatch)
+{
+    if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
+    if (int rc = stale_batch(ctx, b)) return rc;
+    ctx->last_ms = 0.0;
+    if (!w) return fail(ctx, PG_E_INVALID, "events: null pg_event_window");
+    if (lists_null_mismatch) return fail(ctx, PG_E_INVALID, "events: candidate arrays come in pairs (records and count bytes)");
+    if (w->chr_id < 0 || w->chr_id >= (int32_t)ctx->names.size()) return fail(ctx, PG_E_INVALID, "events: the window's chr_id lies outside the reference");
+    if (w->region_start > w->region_end) return fail(ctx, PG_E_INVALID, "events: region_start > region_end");
+    if (b->n && !b->searched) return fail(ctx, PG_E_INVALID, "the batch has not been searched: no close and far ends to classify");
+    return PG_OK;
+}
+
+// every list pointer is device memory (or null)
+int build_events(pg_ctx *ctx, pg_device_batch *b, const pg_event_window *w, const pg_variant_cand *d_cands, const uint8_t *d_counts,
+                 const pg_variant_cand *d_sv_cands, const uint8_t *d_sv_counts, const uint32_t *d_name_id)
+{
+    b->ev_built = false;
+    b->ev_sizes = pg_event_sizes{};
+    const size_t n = b->n;
+    if (!n) {                                                 // nothing is launched for an empty batch
+        b->ev_built = true;
+        return PG_OK;
+    }
+    int rc;
+    if (!b->ev_reads && ((rc = dev_alloc(ctx, &b->ev_reads, n)) || (rc = dev_alloc(ctx, &b->ev_members, n)) || (rc = dev_alloc(ctx, &b->ev_events, n))))
+        return rc;
+    EventTemps tmp;
+    PgEventArgs a{};
+    const size_t n_blk = n / PG_EV_BLOCK + 2;
+    if ((rc = EV_TAKE(tmp, ctx, a.rec_a, n)) || (rc = EV_TAKE(tmp, ctx, a.rec_b, n)) || (rc = EV_TAKE(tmp, ctx, a.flag, n)) ||
+        (rc = EV_TAKE(tmp, ctx, a.rank, n)) || (rc = EV_TAKE(tmp, ctx, a.blk, n_blk)) || (rc = EV_TAKE(tmp, ctx, a.midx, n)) ||
+        (rc = EV_TAKE(tmp, ctx, a.efirst, n + 1)) || (rc = EV_TAKE(tmp, ctx, a.digit_cnt, 256 * n_blk + 1)) || (rc = EV_TAKE(tmp, ctx, a.info, 1)))
+        return rc;
+    a.out = b->out_rec;
+    a.pool = b->pool;
+    a.pool_runs = (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS;
+    a.seq = b->seq;
+    a.seq_off = b->seq_off;
+    a.strand = b->strand;
+    a.chr = b->chr;
+    a.isz = b->isz;
+    a.spacer = ctx->prm.spacer;
+    a.n = b->n;
+    a.win = *w;
+    // BoxSize / NumBoxes from the padded chromosome length, as Caller::process_window computes them (pindel.cpp:1806-1810)
+    const uint64_t chr_len = ctx->comp_size[(size_t)w->chr_id];
+    a.box_size = (uint32_t)(chr_len / 30000);
+    if (a.box_size == 0) a.box_size = 1;
+    a.n_boxes = (uint32_t)(chr_len * 2 / a.box_size) + 1;
+    a.cands = d_cands;
+    a.counts = d_counts;
+    a.sv_cands = d_sv_cands;
+    a.sv_counts = d_sv_counts;
+    a.name_id = d_name_id;
+    a.reads = b->ev_reads;
+    a.members = b->ev_members;
+    a.events = b->ev_events;
+    const PgDevRef ref = dev_ref(ctx);
+    PgLaunchRec rec{};
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if (pg_events_cascade_launch(&a, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the event cascade kernels failed");
+    rec.kernel = PG_KERNEL_EVENT_CASCADE;
+    rec.blocks = (int32_t)PG_EV_BLOCK;
+    log_launch(ctx, rec);
+    PgEventInfo info;
+    HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (info.n_boxed > n) return fail(ctx, PG_E_DEVICE, "events: the boxed count exceeds the batch");
+    const PgEventRec *sorted = a.rec_b;
+    if (info.n_boxed) {                                       // (nothing boxed: nothing below indexes an empty array)
+        PgEventRec *src = a.rec_b, *dst = a.rec_a;
+        for (int pass = 0; pass < PG_EV_SORT_PASSES; pass++) {
+            const int word = pass >= 16 ? 4 : 3 - (pass >> 2), shift = pass >= 16 ? 0 : (pass & 3) * 8;
+            if ((((info.key_or[word] ^ info.key_and[word]) >> shift) & 0xffu) == 0u) continue;      // the byte is constant: no pass
+            if (pg_events_sort_pass_launch(&a, src, dst, info.n_boxed, pass, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching an event sort pass failed");
+            rec.kernel = PG_KERNEL_EVENT_SORT;
+            rec.blocks = pass;
+            log_launch(ctx, rec);
+            std::swap(src, dst);
+        }
+        sorted = src;
+        if (pg_events_tables_launch(&ref, &a, sorted, info.n_boxed, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the event table kernels failed");
+        rec.kernel = PG_KERNEL_EVENT_TABLES;
+        rec.blocks = (int32_t)PG_EV_BLOCK;
+        log_launch(ctx, rec);
+        HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->last_ms = ms;
+    if (info.n_boxed) {
+        if (info.n_members > info.n_boxed || info.n_events > info.n_members) return fail(ctx, PG_E_DEVICE, "events: inconsistent table sizes");
+        for (int t = 0; t < PG_EVENT_TABLES; t++) {
+            b->ev_sizes.members[t] = info.member_start[t + 1] - info.member_start[t];
+            b->ev_sizes.events[t] = info.event_start[t + 1] - info.event_start[t];
+        }
+    }
+    b->ev_sizes.unresolved = info.n_unresolved;
+    b->ev_built = true;
+    return PG_OK;
+}
+}  // namespace
+
+int pg_device_batch_events_device(pg_ctx *ctx, pg_device_batch *b, const pg_event_window *window, const pg_variant_cand *d_cands,
+                                  const uint8_t *d_counts, const pg_variant_cand *d_sv_cands, const uint8_t *d_sv_counts, const uint32_t *d_name_id)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (int rc = events_refusal(ctx, b, window, (d_cands == nullptr) != (d_counts == nullptr) || (d_sv_cands == nullptr) != (d_sv_counts == nullptr)))
+        return rc;
+    const size_t n = b->n;
+    int rc;
+    if ((d_cands && ((rc = check_device_ptr(ctx, d_cands, n * 2 * PG_VARIANT_CANDS * sizeof(pg_variant_cand), 4, "events: cands")) ||
+                     (rc = check_device_ptr(ctx, d_counts, n * 2, 1, "events: counts")))) ||
+        (d_sv_cands && ((rc = check_device_ptr(ctx, d_sv_cands, n * PG_SV_SLOTS * sizeof(pg_variant_cand), 4, "events: sv_cands")) ||
+                        (rc = check_device_ptr(ctx, d_sv_counts, n * PG_SV_KINDS, 1, "events: sv_counts")))) ||
+        (d_name_id && (rc = check_device_ptr(ctx, d_name_id, n * 4, 4, "events: name_id"))))
+        return rc;
+    return build_events(ctx, b, window, d_cands, d_counts, d_sv_cands, d_sv_counts, d_name_id);
+}
+
+int pg_device_batch_events(pg_ctx *ctx, pg_device_batch *b, const pg_event_window *window, const pg_variant_cand *cands, const uint8_t *counts,
+                           const pg_variant_cand *sv_cands, const uint8_t *sv_counts, const uint32_t *name_id)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (int rc = events_refusal(ctx, b, window, (cands == nullptr) != (counts == nullptr) || (sv_cands == nullptr) != (sv_counts == nullptr)))
+        return rc;
+    const size_t n = b->n;
+    EventTemps tmp;
+    pg_variant_cand *d_cands = nullptr, *d_sv = nullptr;
+    uint8_t *d_counts = nullptr, *d_svn = nullptr;
+    uint32_t *d_name = nullptr;
+    int rc;
+    if (n && cands) {
+        if ((rc = EV_TAKE(tmp, ctx, d_cands, n * 2 * PG_VARIANT_CANDS)) || (rc = EV_TAKE(tmp, ctx, d_counts, n * 2))) return rc;
+        HIP_TRY(ctx, hipMemcpy(d_cands, cands, n * 2 * PG_VARIANT_CANDS * sizeof(pg_variant_cand), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_counts, counts, n * 2, hipMemcpyHostToDevice));
+    }
+    if (n && sv_cands) {
+        if ((rc = EV_TAKE(tmp, ctx, d_sv, n * PG_SV_SLOTS)) || (rc = EV_TAKE(tmp, ctx, d_svn, n * PG_SV_KINDS))) return rc;
+        HIP_TRY(ctx, hipMemcpy(d_sv, sv_cands, n * PG_SV_SLOTS * sizeof(pg_variant_cand), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_svn, sv_counts, n * PG_SV_KINDS, hipMemcpyHostToDevice));
+    }
+    if (n && name_id) {
+        if ((rc = EV_TAKE(tmp, ctx, d_name, n))) return rc;
+        HIP_TRY(ctx, hipMemcpy(d_name, name_id, n * 4, hipMemcpyHostToDevice));
+    }
+    return build_events(ctx, b, window, d_cands, d_counts, d_sv, d_svn, d_name);
+}
+
+int pg_device_batch_event_sizes(pg_ctx *ctx, pg_device_batch *b, pg_event_sizes *sizes)
+{
+    use_device(ctx);
+    if (!ctx || !b || !sizes) return PG_E_INVALID;
+    if (!b->ev_built) return fail(ctx, PG_E_INVALID, "no event tables: pg_device_batch_events has not been run on this batch");
+    *sizes = b->ev_sizes;
+    return PG_OK;
+}
+
+static int events_download(pg_ctx *ctx, pg_device_batch *b, pg_event_read *reads, uint32_t *members, pg_event *events, hipMemcpyKind kind)
+{
+    if (!b->ev_built) return fail(ctx, PG_E_INVALID, "no event tables: pg_device_batch_events has not been run on this batch");
+    size_t nm = 0, ne = 0;
+    for (int t = 0; t < PG_EVENT_TABLES; t++) {
+        nm += b->ev_sizes.members[t];
+        ne += b->ev_sizes.events[t];
+    }
+    if (reads && b->n) HIP_TRY(ctx, hipMemcpy(reads, b->ev_reads, (size_t)b->n * sizeof(pg_event_read), kind));
+    if (members && nm) HIP_TRY(ctx, hipMemcpy(members, b->ev_members, nm * sizeof(uint32_t), kind));
+    if (events && ne) HIP_TRY(ctx, hipMemcpy(events, b->ev_events, ne * sizeof(pg_event), kind));
+    return PG_OK;
+}
+
+int pg_device_batch_events_download(pg_ctx *ctx, pg_device_batch *b, pg_event_read *reads, uint32_t *members, pg_event *events)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    return events_download(ctx, b, reads, members, events, hipMemcpyDeviceToHost);
+}
+
+int pg_device_batch_events_download_device(pg_ctx *ctx, pg_device_batch *b, pg_event_read *d_reads, uint32_t *d_members, pg_event *d_events)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (!b->ev_built) return fail(ctx, PG_E_INVALID, "no event tables: pg_device_batch_events has not been run on this batch");
+    size_t nm = 0, ne = 0;
+    for (int t = 0; t < PG_EVENT_TABLES; t++) {
+        nm += b->ev_sizes.members[t];
+        ne += b->ev_sizes.events[t];
+    }
+    int rc;
+    if ((d_reads && (rc = check_device_ptr(ctx, d_reads, (size_t)b->n * sizeof(pg_event_read), 2, "events download: reads"))) ||
+        (d_members && (rc = check_device_ptr(ctx, d_members, nm * sizeof(uint32_t), 4, "events download: members"))) ||
+        (d_events && (rc = check_device_ptr(ctx, d_events, ne * sizeof(pg_event), 4, "events download: events"))))
+        return rc;
+    return events_download(ctx, b, d_reads, d_members, d_events, hipMemcpyDeviceToDevice);
 }
 
 void pg_device_batch_free(pg_ctx *ctx, pg_device_batch *b)

@@ -305,7 +305,8 @@ int pg_debug_kargs_check(const PgDevRef *ref, const PgDevParams *prm, const PgDe
                          uint32_t *scratch_dev, void *stream);
 // What one kernel launch on the search path ran (the launch log of pg_api.cpp, pg_debug_launch_log): the kernel and its
 // template arguments.  The launch functions below fill these when given somewhere to put them (null: nothing is recorded).
-enum PgKernelKind { PG_KERNEL_SEARCH = 1, PG_KERNEL_EXACT = 2, PG_KERNEL_PACK = 3, PG_KERNEL_VARIANT = 4, PG_KERNEL_SV = 5 };
+enum PgKernelKind { PG_KERNEL_SEARCH = 1, PG_KERNEL_EXACT = 2, PG_KERNEL_PACK = 3, PG_KERNEL_VARIANT = 4, PG_KERNEL_SV = 5,
+                    PG_KERNEL_EVENT_CASCADE = 6, PG_KERNEL_EVENT_SORT = 7, PG_KERNEL_EVENT_TABLES = 8 };
 struct PgLaunchRec {
     int32_t kernel;                // PgKernelKind
     int32_t blocks;                // NB of pg_search_kernel, PB of pg_pack_kernel (0: pg_search_exact_kernel)
@@ -406,6 +407,52 @@ int pg_devio_measure_reads(const unsigned long long *seq_off, const int32_t *pos
                            struct PgReadMeasure *rec, void *stream);
 // *close_end / *far_end = the batch's run totals, from the 8 info values pg_deliver_scan left for its last chunk
 int pg_devio_store_totals(const unsigned long long *info, unsigned long long *close_end, unsigned long long *far_end, void *stream);
+// Event tables (pg_events.hip): the window tail and cascade per read, the order of the boxed reads of the four
+// sorted kinds, duplicates and events.  Every pointer is device memory of the library's own or one the host has checked.
+#define PG_EV_BLOCK 256u              // the scan / sort block: reads (records) per workgroup of the count, rank and scatter kernels
+#define PG_EV_SORT_PASSES 17          // one per key byte, least significant first: BP (2), NT_size (2), IndelSize, BPRight, BPLeft (4 each), table
+struct PgEventRec { uint32_t w[8]; }; // one boxed read: BPLeft, BPRight, IndelSize, NT_size << 16 | (BP ^ 0x8000), Left, Right, read, table | plus << 8 | ReadLength << 16
+struct PgEventInfo {                  // what the host reads back, 96 bytes
+    uint32_t n_boxed;                 // boxed reads of the four tables
+    uint32_t n_unresolved;
+    uint32_t key_or[5], key_and[5];   // over the boxed records' key words w[0..3] and the table: a byte equal in both is constant
+    uint32_t n_members, n_events;
+    uint32_t member_start[PG_EVENT_TABLES + 1], event_start[PG_EVENT_TABLES + 1];
+};
+struct PgEventArgs {
+    const PgOutRec *out;
+    const pg_run *pool;
+    unsigned long long pool_runs;
+    const uint8_t *seq;
+    const uint64_t *seq_off;
+    const uint8_t *strand;
+    const int32_t *chr;
+    const int16_t *isz;
+    uint32_t spacer, n;
+    pg_event_window win;
+    uint32_t box_size, n_boxes;
+    const pg_variant_cand *cands;     // n x 2 x PG_VARIANT_CANDS, or null
+    const uint8_t *counts;
+    const pg_variant_cand *sv_cands;  // n x PG_SV_SLOTS, or null
+    const uint8_t *sv_counts;
+    const uint32_t *name_id;          // or null
+    pg_event_read *reads;             // n
+    uint32_t *members;                // n
+    pg_event *events;                 // n
+    struct PgEventRec *rec_a, *rec_b; // n each
+    uint8_t *flag;                    // n
+    uint32_t *rank, *blk;             // n; n / PG_EV_BLOCK + 2
+    uint32_t *midx, *efirst;          // n; n + 1
+    uint32_t *digit_cnt;              // 256 x (n / PG_EV_BLOCK + 1)
+    struct PgEventInfo *info;
+};
+// stage A and the compaction of the boxed reads into rec_b (descending read index); info->n_boxed and the key masks are then valid
+int pg_events_cascade_launch(const struct PgEventArgs *a, void *stream);
+// one stable counting pass over key byte `pass` of src[0 .. n_boxed) into dst
+int pg_events_sort_pass_launch(const struct PgEventArgs *a, const struct PgEventRec *src, struct PgEventRec *dst, uint32_t n_boxed, int pass,
+                               void *stream);
+// stages C and D over the sorted records; fills members, events and the rest of info
+int pg_events_tables_launch(const PgDevRef *ref, const struct PgEventArgs *a, const struct PgEventRec *sorted, uint32_t n_boxed, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,14 @@ def lib():
         L.pgh_last_variant_visits.restype = C.c_uint64
         L.pgh_last_variant_visits.argtypes = [C.c_void_p, C.c_uint64]
         L.pgh_variant_candidates.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32] + [C.c_void_p] * 12
+        L.pgh_call_from_points_events.argtypes = L.pgh_call_from_points.argtypes + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]
+        for f in ("pgh_last_event_fallback_windows", "pgh_last_event_table_windows", "pgh_last_event_supplied_windows"):
+            getattr(L, f).restype = C.c_uint64
+            getattr(L, f).argtypes = []
+        L.pgh_last_event_windows.restype = C.c_uint64
+        L.pgh_last_event_windows.argtypes = [C.c_void_p, C.c_uint64]
+        L.pgh_name_ids.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p]
+        L.pgh_name_ids.restype = None
         L.pgh_region_depth.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.POINTER(C.c_double)]
         L.pgh_region_depth_mapq.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.c_uint32, C.POINTER(C.c_double)]
         L.pgh_depth_ratio_mapq.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_uint32,
@@ -312,6 +320,110 @@ def sv_candidates(chroms, seq, seq_off, anchor_strand, chr_id, rc_flag, close_of
     return cands, counts
 
 
+# event tables (include/pindel_pg.h): tables 0..3 = kind 0, kind 1, TD, TD_NT
+EVENT_TABLES = 4
+EVENT_KINDS = (0, 1, 3, 4)
+EVR_BOXED, EVR_USED, EVR_UNRESOLVED, EVR_DUPLICATE = 1, 2, 4, 8
+EV_SUPPORT, EV_RANGE, EV_BALANCE, EV_REPORT = 1, 2, 4, 8
+EVENT_READ_DTYPE = np.dtype([("kind", "u1"), ("slot", "u1"), ("flags", "u1"), ("unresolved_kind", "u1"), ("nt_size", "<u2"),
+                             ("reserved", "<u2")], align=True)
+EVENT_DTYPE = np.dtype([("bp_left", "<u4"), ("bp_right", "<u4"), ("indel_size", "<u4"), ("first", "<u4"), ("n_reads", "<u4"),
+                        ("n_plus", "<u4"), ("real_start", "<u4"), ("real_end", "<u4"), ("box_head", "<u4"), ("nt_size", "<u2"),
+                        ("kind", "u1"), ("flags", "u1")], align=True)
+assert EVENT_READ_DTYPE.itemsize == 8 and EVENT_DTYPE.itemsize == 40
+
+
+class EventWindow(C.Structure):
+    """pg_event_window"""
+    _fields_ = [("chr_id", C.c_int32), ("win_end", C.c_uint32), ("region_start", C.c_uint32), ("region_end", C.c_uint32),
+                ("min_support", C.c_uint32), ("balance_cutoff", C.c_uint32), ("analyze_td", C.c_int32), ("analyze_inv", C.c_int32)]
+
+
+class EventSizes(C.Structure):
+    """pg_event_sizes"""
+    _fields_ = [("members", C.c_uint64 * EVENT_TABLES), ("events", C.c_uint64 * EVENT_TABLES), ("unresolved", C.c_uint64)]
+
+
+def event_window(chr_id=0, win_end=0xffffffff, region_start=0, region_end=0xffffffff, min_support=1, balance_cutoff=100,
+                 analyze_td=True, analyze_inv=True):
+    """A pg_event_window; the defaults are one window over everything with Pindel's -M 1 and -B 100."""
+    return EventWindow(int(chr_id), int(win_end), int(region_start), int(region_end), int(min_support), int(balance_cutoff),
+                       int(bool(analyze_td)), int(bool(analyze_inv)))
+
+
+def event_tables(reads, members, events, sizes):
+    """The three flat outputs of an events entry as a dict: reads (EVENT_READ_DTYPE[n]), members / events (lists of the four
+    tables' arrays, in EVENT_KINDS order), unresolved, and the flat arrays themselves (members_flat, events_flat)."""
+    nm = [int(x) for x in sizes.members]
+    ne = [int(x) for x in sizes.events]
+    mo = np.concatenate([[0], np.cumsum(nm)]).astype(np.int64)
+    eo = np.concatenate([[0], np.cumsum(ne)]).astype(np.int64)
+    members = members[:mo[-1]]
+    events = events[:eo[-1]]
+    return dict(reads=reads, members=[members[mo[t]:mo[t + 1]] for t in range(EVENT_TABLES)],
+                events=[events[eo[t]:eo[t + 1]] for t in range(EVENT_TABLES)], unresolved=int(sizes.unresolved),
+                members_flat=members, events_flat=events, n_members=nm, n_events=ne)
+
+
+def name_ids(names):
+    """Numbers names by first occurrence (pgh_name_ids): the name_id array of the events entries, uint32 per read."""
+    L = lib()
+    enc = [n if isinstance(n, bytes) else str(n).encode() for n in names]
+    arr = (C.c_char_p * len(enc))(*enc)
+    out = np.zeros(len(enc), dtype=np.uint32)
+    L.pgh_name_ids(len(enc), arr, out.ctypes.data)
+    return out
+
+
+def events_from_lists(chroms, seq, seq_off, anchor_strand, chr_id, rc_flag, insert_size, close_off, close_pts, far_off, far_pts,
+                      window, variant=None, sv=None, name_id=None, spacer=100000):
+    """Event tables from candidate lists on the host (pgh_events_from_lists): the reference Engine.events is compared
+    with, byte for byte.  Reads and points as variant_candidates() takes them, plus insert_size; window: an EventWindow; variant /
+    sv: (cands, counts) pairs as the candidate entries return them, or None (empty lists); name_id: None (all names differ) or
+    uint32 per read.  Returns event_tables(...).  Raises ValueError for a refused window."""
+    L = lib()
+    n = len(seq_off) - 1
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    strand = np.ascontiguousarray(anchor_strand, dtype=np.uint8)
+    chr_id = np.ascontiguousarray(chr_id, dtype=np.int32)
+    rc_flag = np.ascontiguousarray(rc_flag, dtype=np.uint8)
+    isz = np.ascontiguousarray(insert_size, dtype=np.int16)
+    close_off = np.ascontiguousarray(close_off, dtype=np.uint64)
+    far_off = np.ascontiguousarray(far_off, dtype=np.uint64)
+    close_pts = np.ascontiguousarray(close_pts)
+    far_pts = np.ascontiguousarray(far_pts)
+    assert close_pts.dtype.itemsize == 12 and far_pts.dtype.itemsize == 12
+    assert len(strand) == n and len(chr_id) == n and len(rc_flag) == n and len(isz) == n
+    vc = vn = sc = sn = nid = None
+    if variant is not None:
+        vc = np.ascontiguousarray(variant[0], dtype=VARIANT_CAND_DTYPE)
+        vn = np.ascontiguousarray(variant[1], dtype=np.uint8)
+        assert vc.size == n * 2 * VARIANT_CANDS and vn.size == n * 2
+    if sv is not None:
+        sc = np.ascontiguousarray(sv[0], dtype=VARIANT_CAND_DTYPE)
+        sn = np.ascontiguousarray(sv[1], dtype=np.uint8)
+        assert sc.size == n * SV_SLOTS and sn.size == n * len(SV_KINDS)
+    if name_id is not None:
+        nid = np.ascontiguousarray(name_id, dtype=np.uint32)
+        assert len(nid) == n
+    bufs = [bytes(s) for _, s in chroms]
+    ptrs = (C.c_char_p * len(bufs))(*bufs)
+    lens = (C.c_uint64 * len(bufs))(*[len(b) for b in bufs])
+    reads = np.zeros(n, dtype=EVENT_READ_DTYPE)
+    members = np.zeros(max(n, 1), dtype=np.uint32)
+    events = np.zeros(max(n, 1), dtype=EVENT_DTYPE)
+    sizes = EventSizes()
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    L.pgh_events_from_lists.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32] + [C.c_void_p] * 20
+    rc = L.pgh_events_from_lists(len(bufs), ptrs, lens, int(spacer), n, ptr(seq), ptr(seq_off), ptr(strand), ptr(chr_id), ptr(rc_flag),
+                                 ptr(isz), ptr(close_off), ptr(close_pts), ptr(far_off), ptr(far_pts), C.addressof(window), ptr(vc), ptr(vn),
+                                 ptr(sc), ptr(sn), ptr(nid), ptr(reads), ptr(members), ptr(events), C.addressof(sizes))
+    if rc:
+        raise ValueError("pgh_events_from_lists: " + (L.pgh_last_error() or b"").decode())
+    return event_tables(reads, members, events, sizes)
+
+
 def last_variant_fallbacks():
     """Reads of the last call_from_points(variant_candidates=...) whose list ran out, with VARIANT_MORE set, before one of its
     pairs had made the read Used: they went through the classifier's own pair search."""
@@ -330,7 +442,7 @@ def last_variant_visits():
 
 def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pts, far_off, far_pts,
                      rc_flag, region=None, include_bed=None, exclude_bed=None, reads_config=None, normal_samples=None,
-                     bam_config=None, repairs=None, variant_candidates=None, sv_candidates=None):
+                     bam_config=None, repairs=None, variant_candidates=None, sv_candidates=None, events=None):
     """Classify + report (_D, _SI, _TD, _INV) from per-read UP_Close / UP_Far points (CSR over
     all reads of the file, 12-byte pg_point records).  settings.analyze_li / settings.report_close_mapped
     add <out_prefix>_LI / <out_prefix>_CloseEndMapped, settings.report_interchromosomal <out_prefix>_INT and
@@ -347,7 +459,12 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
     return them, for the same reads -- the deletion and short-insertion classifiers then take each read's pairs from its list
     and search only where a list runs out (last_variant_fallbacks); the reports are the same bytes.  sv_candidates: (cands,
     counts) as sv_candidates() or Engine.sv_candidates return them, made with these settings' -e, -d and -v -- the same for the
-    DI, tandem-duplication and inversion classifiers; with or without variant_candidates."""
+    DI, tandem-duplication and inversion classifiers; with or without variant_candidates.  events (needs both
+    lists): True -- per window the event tables are built from the lists (events_from_lists' function) and deletions, short
+    insertions and tandem duplications are written from them, DI and the inversions from the per-read records; a window with an
+    unresolved read takes the existing path (last_event_fallback_windows); the reports are the same bytes.  Or a dict {(chromosome
+    index or name, win_start, win_end): tables} of tables built elsewhere over all reads (what Engine.events returns): a window
+    without an entry uses the host builder (last_event_windows lists the windows of a run)."""
     L = lib()
     tmp_cfg = None
     if reads_config is not None and not isinstance(reads_config, (str, bytes, os.PathLike)):
@@ -385,7 +502,13 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
             sv_n = np.ascontiguousarray(sv_candidates[1], dtype=np.uint8)
             if sv_c.size != n * SV_SLOTS or sv_n.size != n * len(SV_KINDS):
                 raise ValueError(f"sv_candidates: {sv_c.size} records and {sv_n.size} counts for {n} reads")
-        if variant_candidates is None and sv_candidates is None:
+        if events:
+            if cands is None or sv_c is None:
+                raise ValueError("events: variant_candidates and sv_candidates are both needed")
+            sup, keep_ev = _supplied_events(events, fasta, n)
+            rc = L.pgh_call_from_points_events(*args, cands.ctypes.data, counts.ctypes.data, sv_c.ctypes.data, sv_n.ctypes.data,
+                                               len(sup) if sup is not None else 0, sup)
+        elif variant_candidates is None and sv_candidates is None:
             rc = L.pgh_call_from_points(*args)
         elif sv_candidates is None:
             rc = L.pgh_call_from_points_candidates(*args, cands.ctypes.data, counts.ctypes.data)
@@ -397,6 +520,55 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
             os.unlink(tmp_cfg)
     if rc:
         raise RuntimeError("pgh_call_from_points: " + (L.pgh_last_error() or b"").decode())
+
+
+class SuppliedEvents(C.Structure):
+    """pgh_supplied_events: the tables of one window, built elsewhere over all reads of the run"""
+    _fields_ = [("chr", C.c_int32), ("win_start", C.c_uint32), ("win_end", C.c_uint32), ("reserved", C.c_uint32),
+                ("reads", C.c_void_p), ("members", C.c_void_p), ("events", C.c_void_p), ("sizes", EventSizes)]
+
+
+def _supplied_events(events, fasta, n):
+    """the events argument of call_from_points -> (array of SuppliedEvents or None, what must stay alive)"""
+    if events is True or not isinstance(events, dict):
+        return None, []
+    names = _fasta_names(fasta)
+    arr = (SuppliedEvents * len(events))()
+    keep = []
+    for k, ((chrom, ws, we), t) in enumerate(events.items()):
+        reads = np.ascontiguousarray(t["reads"], dtype=EVENT_READ_DTYPE)
+        members = np.ascontiguousarray(t["members_flat"], dtype=np.uint32)
+        evs = np.ascontiguousarray(t["events_flat"], dtype=EVENT_DTYPE)
+        if len(reads) != n or len(members) != sum(t["n_members"]) or len(evs) != sum(t["n_events"]):
+            raise ValueError(f"events: the tables of window {(chrom, ws, we)} do not fit {n} reads and their own sizes")
+        keep += [reads, members, evs]
+        sz = EventSizes()
+        for q in range(EVENT_TABLES):
+            sz.members[q], sz.events[q] = int(t["n_members"][q]), int(t["n_events"][q])
+        sz.unresolved = int(t["unresolved"])
+        arr[k] = SuppliedEvents(names.index(chrom) if isinstance(chrom, str) else int(chrom), int(ws), int(we), 0, reads.ctypes.data,
+                                members.ctypes.data, evs.ctypes.data, sz)
+    return arr, keep
+
+
+def last_event_fallback_windows():
+    """Windows of the last call_from_points(events=...) that held an unresolved read and went through the existing path."""
+    return int(lib().pgh_last_event_fallback_windows())
+
+
+def last_event_table_windows():
+    """(windows written from tables, of them from supplied tables) of the last call_from_points(events=...)"""
+    return int(lib().pgh_last_event_table_windows()), int(lib().pgh_last_event_supplied_windows())
+
+
+def last_event_windows():
+    """The windows the last call_from_points(events=...) processed, in order: a uint32[k, 6] array of (chromosome index, win_start,
+    win_end, region_start, region_end, reads) -- what the window description of Engine.events takes for each."""
+    L = lib()
+    k = int(L.pgh_last_event_windows(None, 0))
+    out = np.zeros((max(k, 1), 6), dtype=np.uint32)
+    L.pgh_last_event_windows(out.ctypes.data, k)
+    return out[:k]
 
 
 def vcf_cli():

@@ -1,4 +1,5 @@
-"""Measurement (one MI355X + its host): what the device classifiers (pg_variant_kernel; pg_sv_kernel, 7l) cost and what
+"""Measurement (one MI355X + its host): what the device classifiers (pg_variant_kernel; pg_sv_kernel, 7l; the events entry,
+7m) cost and what
 they take off the host.  On n synthetic 100-bp reads (all SV types, default parameters), searched on the GPU:
   * the kernel's HIP-event time, per batch and per read;
   * the host's `deletions` and `short insertions` laps of call_from_points (PGH_TIMING=1: the per-read stage plus the
@@ -113,6 +114,16 @@ def main():
     for _ in range(5):
         sv_cands, sv_counts = eng.sv_candidates(db)
         sv_ms.append(eng.last_stats()[0])
+    # the events stage: one window over the whole chromosome, lists and tables in device memory
+    note("event tables on the GPU")
+    vt, svt = eng.variant_candidates_tensors(db), eng.sv_candidates_tensors(db)
+    ev_ms = []
+    for _ in range(5):
+        eng.clear_launch_log()
+        ev = eng.events_tensors(db, binding.EventWindow(0, 0xffffffff, 0, 0xffffffff, 1, 100, 1, 1), vt, svt)
+        ev_ms.append(eng.last_stats()[0])
+    ev_sorts = sum(1 for r in eng.launch_log() if r.kernel == binding.KERNEL_EVENT_SORT)
+    del vt, svt
     res = eng.download(db)
     eng.free_device_batch(db)
 
@@ -139,6 +150,9 @@ def main():
           f", lists with more pairs behind them {((sv_counts & 0x80) != 0).sum()}")
     print(f"- pg_sv_kernel {min(sv_ms):.3f} ms (best of 5; all: {', '.join(f'{x:.3f}' for x in sv_ms)}) = {min(sv_ms) * 1e6 / n:.2f} ns per read\n",
           flush=True)
+    print(f"- events entry (cascade, sort, duplicates, events; lists and tables in device memory) {min(ev_ms):.3f} ms (best of 5; all: "
+          f"{', '.join(f'{x:.3f}' for x in ev_ms)}) = {min(ev_ms) * 1e6 / n:.2f} ns per read; members per table {ev['n_members']}, events per table "
+          f"{ev['n_events']}, unresolved reads {ev['unresolved']}, sort passes launched (of 17 key bytes) {ev_sorts}\n", flush=True)
     modes = ["plain", "lists", "sv"] + (["parent"] if a.parent_lib else [])
     got = {}
     for m in modes:
@@ -162,6 +176,10 @@ def main():
     print(f"- the five laps pg_sv_kernel feeds = {five:.3f} s of {total:.3f} s ({100 * five / total:.1f} %); with its lists they take {five_sv:.3f} s: "
           f"their per-read stage was {five - five_sv:.3f} s ({100 * (five - five_sv) / total:.1f} % of the laps); fallbacks with all seven lists: "
           f"{got['sv'][1].get('fallbacks')}")
+    all_sv = sum(got["sv"][0].values())
+    print(f"- host time of the stages the events entry stands for (window tail, box sorting, duplicates, grouping -- and the report "
+          f"formatting, which stays on the host): all laps with the lists of both kernels = {all_sv:.3f} s, against {min(ev_ms) / 1e3:.4f} s "
+          f"on the device")
     same = all(open(os.path.join(a.dir, f"out_plain_{s}"), "rb").read() == open(os.path.join(a.dir, f"out_{m}_{s}"), "rb").read()
                for s in ("D", "SI", "TD", "INV") for m in ("lists", "sv"))
     print(f"- reports with and without the lists byte-identical: {same}")
