@@ -445,6 +445,50 @@ int  pg_device_batch_events_download(pg_ctx *ctx, pg_device_batch *b, pg_event_r
 int  pg_device_batch_events_download_device(pg_ctx *ctx, pg_device_batch *b, pg_event_read *d_reads, uint32_t *d_members,
                                             pg_event *d_events);
 
+/* ---- device classifier: DI and inversion event tables --------------------------------------------------------
+ * The three kinds pg_device_batch_events leaves at their per-read records -- PG_SV_DI, PG_SV_INV, PG_SV_INV_NT, "SV tables" 0..2 in
+ * this order -- as event tables.  Their reporters sort a box with a STRICT exchange sort (x > y swaps, equality does not), whose tie
+ * order depends on the order the box arrives in: ascending read index.  A pure function of the per-read records the events build
+ * left with the batch (kind, slot, flags, nt_size), the sv lists, the batch (anchor strand, post-state read length and bases, the
+ * last close point: LeftMostPos = AbsLoc + 1 - close_len for a '+' anchor, AbsLoc + close_len - ReadLength for '-'), that build's
+ * window (-M, -B), BoxSize and the loaded reference.  No name_id: these reporters do not call markDuplicates.
+ *   sort keys    DI: BPLeft, BPRight, carried NT_size, BP (signed).  INV / INV_NT: BPLeft + BPRight (uint32, wrapping), IndelSize
+ *                DESCENDING, BPLeft, BPRight, for INV_NT the carried NT_size, BP.
+ *   duplicates   a read of the sorted box is one if ANY earlier read of the box, unique or not, has an equal LeftMostPos or an equal
+ *                LeftMostPos + ReadLength, and the same anchor strand -- for DI an equal ReadLength as well.
+ *   DI           members = the unique reads in sorted order; an event = a maximal run with equal (BPLeft, IndelSize, (short)NT_size).
+ *                PG_EV_BALANCE as for the tables of 7m, PG_EV_SHORT_INV = the first member's IndelSize == NT_size and the reverse
+ *                complement of those reference bases at spacer + 1 + BPLeft is its NT_str (the reporter then writes a short
+ *                inversion); PG_EV_REPORT = SUPPORT and BALANCE.  real_start / real_end = bp_left / bp_right.
+ *   INV, INV_NT  members = ALL reads of the box in sorted order, a duplicate with PG_SVEV_MEMBER_DUP in its member word.  A run = a
+ *                maximal stretch with an equal BPLeft + BPRight; mx = its largest IndelSize; a member passes if NOT
+ *                (IndelSize / (float)mx < 0.95 || mx + 30 > (unsigned)(ReadLength + IndelSize)) and is then harmonised: diff =
+ *                (short)((mx - IndelSize) / 2), IndelSize = mx, BPLeft -= diff, BPRight += diff, BP moves by diff under the two
+ *                guards of the reporter.  A run with a failing member yields no event, and neither does any later run of its box
+ *                (dropped_runs counts them).  The event: bp_left / bp_right = the harmonised first member's, indel_size = mx,
+ *                real_start / real_end = the same -- but for the LAST run of a box the first member's values before harmonisation;
+ *                PG_EV_RANGE = !(real_end < real_start || real_start == 0); PG_EV_BALANCE over the harmonised members; PG_EV_REPORT
+ *                = all three.  A consumer recomputes a member's harmonised fields from indel_size.
+ * All events are listed, boxes below -M included (their events cannot reach PG_EV_SUPPORT). */
+#define PG_SV_EVENT_TABLES 3         /* PG_SV_DI, PG_SV_INV, PG_SV_INV_NT */
+#define PG_EV_SHORT_INV 0x10u        /* pg_event::flags of SV table 0: is_inversion of the first member                    */
+#define PG_SVEV_MEMBER_DUP 0x80000000u   /* member word of SV tables 1 and 2: the read is a duplicate                      */
+typedef struct {
+    uint64_t members[PG_SV_EVENT_TABLES];
+    uint64_t events[PG_SV_EVENT_TABLES];
+    uint64_t dropped_runs[PG_SV_EVENT_TABLES];   /* runs without an event: a failed harmonisation in or before them        */
+} pg_sv_event_sizes;
+/* Builds the SV tables of the batch and keeps them with it (an events build or a new sv build replaces them; freed with the batch).
+ * sv_cands / sv_counts: the lists the events build was given (host memory; the _device sibling: device memory).  Refused with
+ * nothing launched: no events build on this batch (PG_E_INVALID), null lists for a non-empty batch, 2^31 reads or more.  The
+ * window is that build's.  n_reads == 0 and "nothing boxed" are valid.  Synchronous; pg_last_search_stats then reports the
+ * HIP-event time.  download: members = the three member lists back to back, events likewise; either may be NULL. */
+int  pg_device_batch_sv_events(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *sv_cands, const uint8_t *sv_counts);
+int  pg_device_batch_sv_events_device(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *d_sv_cands, const uint8_t *d_sv_counts);
+int  pg_device_batch_sv_event_sizes(pg_ctx *ctx, pg_device_batch *b, pg_sv_event_sizes *sizes);
+int  pg_device_batch_sv_events_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *members, pg_event *events);
+int  pg_device_batch_sv_events_download_device(pg_ctx *ctx, pg_device_batch *b, uint32_t *d_members, pg_event *d_events);
+
 /* -q (dispersed duplications): per item i, contains_subseq_any_strand(query_i, window_i, 15) of Pindel's MEI search
  * (src/search_MEI_util.cpp:188-351, bit-exact), where query_i = query[query_off[i] .. query_off[i+1]) (at most
  * PG_MAX_READ_LEN bases) and window_i = the loaded chromosome chr_id[i] at padded (AbsLoc) positions

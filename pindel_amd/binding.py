@@ -120,6 +120,13 @@ EVENT_DTYPE = np.dtype([("bp_left", "<u4"), ("bp_right", "<u4"), ("indel_size", 
                         ("n_plus", "<u4"), ("real_start", "<u4"), ("real_end", "<u4"), ("box_head", "<u4"), ("nt_size", "<u2"),
                         ("kind", "u1"), ("flags", "u1")], align=True)
 assert EVENT_READ_DTYPE.itemsize == 8 and EVENT_DTYPE.itemsize == 40
+# SV event tables (Engine.sv_events): tables 0..2 = DI, INV, INV_NT; the events are EVENT_DTYPE records
+SV_EVENT_TABLES = 3
+SV_EVENT_KINDS = (SV_DI, SV_INV, SV_INV_NT)
+EV_SHORT_INV = 0x10                     # PG_EV_SHORT_INV: a DI event the reporter writes as a short inversion
+SVEV_MEMBER_DUP = 0x80000000            # PG_SVEV_MEMBER_DUP: bit 31 of an inversion member word
+KERNEL_SV_EVENTS = 9                    # launch-log id after the three of the events build
+SVEV_LDS_BOX = 640                      # PG_SVEV_LDS_BOX: reads of a box the order kernel keeps in LDS
 
 
 class EventWindow(C.Structure):
@@ -131,6 +138,12 @@ class EventWindow(C.Structure):
 class EventSizes(C.Structure):
     """pg_event_sizes"""
     _fields_ = [("members", C.c_uint64 * EVENT_TABLES), ("events", C.c_uint64 * EVENT_TABLES), ("unresolved", C.c_uint64)]
+
+
+class SvEventSizes(C.Structure):
+    """pg_sv_event_sizes"""
+    _fields_ = [("members", C.c_uint64 * SV_EVENT_TABLES), ("events", C.c_uint64 * SV_EVENT_TABLES),
+                ("dropped_runs", C.c_uint64 * SV_EVENT_TABLES)]
 
 
 def event_window(window):
@@ -162,7 +175,9 @@ EXPORTS = [
     "pg_device_batch_variant_candidates", "pg_device_batch_variant_candidates_device",
     "pg_device_batch_sv_candidates", "pg_device_batch_sv_candidates_device",
     "pg_device_batch_events", "pg_device_batch_events_device", "pg_device_batch_event_sizes",
-    "pg_device_batch_events_download", "pg_device_batch_events_download_device"]
+    "pg_device_batch_events_download", "pg_device_batch_events_download_device",
+    "pg_device_batch_sv_events", "pg_device_batch_sv_events_device", "pg_device_batch_sv_event_sizes",
+    "pg_device_batch_sv_events_download", "pg_device_batch_sv_events_download_device"]
 
 
 def build(force: bool = False) -> str:
@@ -263,6 +278,11 @@ def lib():
     L.pg_device_batch_event_sizes.argtypes = [vp, vp, vp]
     L.pg_device_batch_events_download.argtypes = [vp] * 5
     L.pg_device_batch_events_download_device.argtypes = [vp] * 5
+    L.pg_device_batch_sv_events.argtypes = [vp] * 4
+    L.pg_device_batch_sv_events_device.argtypes = [vp] * 4
+    L.pg_device_batch_sv_event_sizes.argtypes = [vp, vp, vp]
+    L.pg_device_batch_sv_events_download.argtypes = [vp] * 4
+    L.pg_device_batch_sv_events_download_device.argtypes = [vp] * 4
     _lib = L
     return L
 
@@ -450,6 +470,21 @@ def _event_tables(reads, members, events, nm, ne, unresolved):
     return dict(reads=reads, members=[members[mo[t]:mo[t + 1]] for t in range(EVENT_TABLES)],
                 events=[events[eo[t]:eo[t + 1]] for t in range(EVENT_TABLES)], unresolved=int(unresolved),
                 members_flat=members, events_flat=events, n_members=list(nm), n_events=list(ne))
+
+
+def _sv_event_tables(members, events, nm, ne, dropped):
+    mo = np.concatenate([[0], np.cumsum(nm)]).astype(np.int64)
+    eo = np.concatenate([[0], np.cumsum(ne)]).astype(np.int64)
+    return dict(members=[members[mo[t]:mo[t + 1]] for t in range(SV_EVENT_TABLES)],
+                events=[events[eo[t]:eo[t + 1]] for t in range(SV_EVENT_TABLES)], dropped_runs=list(dropped),
+                members_flat=members, events_flat=events, n_members=list(nm), n_events=list(ne))
+
+
+def sv_events_from_tensors(t) -> dict:
+    """The dict of sv_events_tensors as the dict sv_events returns (CPU copies)."""
+    members = np.ascontiguousarray(t["members"].cpu().numpy()).view(np.uint32)
+    events = np.ascontiguousarray(t["events"].cpu().numpy()).reshape(-1).view(EVENT_DTYPE)
+    return _sv_event_tables(members, events, t["n_members"], t["n_events"], t["dropped_runs"])
 
 
 def events_from_tensors(t) -> dict:
@@ -843,6 +878,49 @@ class Engine:
                                                                    out["members"].data_ptr() if sum(nm) else None,
                                                                    out["events"].data_ptr() if sum(ne) else None))
         out.update(n_members=nm, n_events=ne, unresolved=unresolved)
+        return out
+
+    def sv_event_sizes(self, dbatch):
+        """pg_device_batch_sv_event_sizes: (members, events, dropped runs) per SV table of the tables built last."""
+        sz = SvEventSizes()
+        self._check(self._L.pg_device_batch_sv_event_sizes(self._h, dbatch, C.addressof(sz)))
+        return [int(x) for x in sz.members], [int(x) for x in sz.events], [int(x) for x in sz.dropped_runs]
+
+    def sv_events(self, dbatch, sv):
+        """Event tables of DI, INV and INV_NT (pg_device_batch_sv_events) from the per-read records the last events()
+        of this batch left with it, for that build's window: each box in the order the reporters' strict exchange sorts leave,
+        duplicates, the inversions' runs harmonised, events -- all on the GPU.  sv: the (cands, counts) pair that build was given.
+        Returns a dict: members and events, lists of three arrays (uint32 member words -- read indices, SVEV_MEMBER_DUP marking an
+        inversion's duplicates -- and EVENT_DTYPE) in SV_EVENT_KINDS order; dropped_runs; members_flat / events_flat."""
+        n = self._batch_n[dbatch.value]
+        sc = np.ascontiguousarray(sv[0], dtype=VARIANT_CAND_DTYPE)
+        sn = np.ascontiguousarray(sv[1], dtype=np.uint8)
+        if sc.size != n * SV_SLOTS or sn.size != n * SV_KINDS:
+            raise ValueError(f"sv_events: {sc.size} records and {sn.size} counts for {n} reads")
+        self._check(self._L.pg_device_batch_sv_events(self._h, dbatch, sc.ctypes.data if n else None, sn.ctypes.data if n else None))
+        nm, ne, dropped = self.sv_event_sizes(dbatch)
+        members = np.zeros(sum(nm), dtype=np.uint32)
+        events = np.zeros(sum(ne), dtype=EVENT_DTYPE)
+        self._check(self._L.pg_device_batch_sv_events_download(self._h, dbatch, members.ctypes.data if members.size else None,
+                                                               events.ctypes.data if events.size else None))
+        return _sv_event_tables(members, events, nm, ne, dropped)
+
+    def sv_events_tensors(self, dbatch, sv):
+        """sv_events with everything staying on the GPU (pg_device_batch_sv_events_device and its download sibling): sv is the dict
+        sv_candidates_tensors returns (or a (cands, counts) tensor pair).  Returns a dict of tensors on this engine's device:
+        members int32[total], events uint8[total, 40], plus n_members / n_events / dropped_runs (lists of three)."""
+        torch, dev = self._torch_ready()
+        n = self._batch_n[dbatch.value]
+        c, k = (sv["cands"], sv["counts"]) if isinstance(sv, dict) else sv
+        for name, t, width in (("cands", c, SV_SLOTS * 32), ("counts", k, SV_KINDS)):
+            if str(t.dtype) != "torch.uint8" or tuple(t.shape) != (n, width) or not t.is_contiguous() or str(t.device) != dev:
+                raise ValueError(f"sv_events: {name}: a contiguous uint8[{n}, {width}] tensor on {dev} is expected")
+        self._check(self._L.pg_device_batch_sv_events_device(self._h, dbatch, c.data_ptr() if n else None, k.data_ptr() if n else None))
+        nm, ne, dropped = self.sv_event_sizes(dbatch)
+        out = dict(members=torch.empty(sum(nm), dtype=torch.int32, device=dev), events=torch.empty((sum(ne), 40), dtype=torch.uint8, device=dev))
+        self._check(self._L.pg_device_batch_sv_events_download_device(self._h, dbatch, out["members"].data_ptr() if sum(nm) else None,
+                                                                      out["events"].data_ptr() if sum(ne) else None))
+        out.update(n_members=nm, n_events=ne, dropped_runs=dropped)
         return out
 
     def set_windows(self, dbatch, bd=None, bd_off=None):

@@ -166,6 +166,16 @@ struct SuppliedEvents {
     pg_event_sizes sizes{};
 };
 
+// The SV tables of one window as pg_device_batch_sv_events_download yields them, over ALL reads of the run: the
+// three member lists and the three event lists back to back.  They go with the SuppliedEvents of the same window.
+struct SuppliedSvEvents {
+    int chr = -1;
+    unsigned win_start = 0, win_end = 0;
+    const uint32_t *members = nullptr;
+    const pg_event *events = nullptr;
+    pg_sv_event_sizes sizes{};
+};
+
 struct Settings {                 // the flags the downstream steps read (src/fn_parameters.cpp)
     unsigned spacer = 100000;
     unsigned NumRead2ReportCutOff = 1;   // -M
@@ -193,6 +203,10 @@ struct Settings {                 // the flags the downstream steps read (src/fn
     // insertions and tandem duplications from them; supplied_events: tables a caller built elsewhere (on the device) for a window.
     bool use_events = false;
     std::vector<SuppliedEvents> supplied_events;
+    // ... and writes DI and the inversions from the SV tables instead of through sort_output_di / sort_output_inv;
+    // supplied_sv_events: tables built elsewhere, used for a window whose event tables were supplied too.
+    bool use_sv_events = false;
+    std::vector<SuppliedSvEvents> supplied_sv_events;
 };
 
 // What the events path of the last run did.  windows: six values per window process_window saw with use_events set -- chromosome
@@ -201,6 +215,8 @@ struct EventPathStats {
     uint64_t fallback_windows = 0;       // windows with an unresolved read (or without usable lists): the existing path ran
     uint64_t table_windows = 0;          // windows written from tables
     uint64_t supplied_windows = 0;       // ... of them, from supplied tables
+    uint64_t sv_table_windows = 0;       // windows whose DI and inversion reports were written from SV tables
+    uint64_t sv_supplied_windows = 0;    // ... of them, from supplied SV tables
     std::vector<uint32_t> windows;
 };
 EventPathStats &event_path_stats();

@@ -17,6 +17,7 @@
 #include "pg_depth.hpp"
 #include "pg_host.hpp"
 #include "pg_host_events.hpp"
+#include "pg_host_sv_events.hpp"
 #include "pg_host_priv.hpp"
 #include "pg_pipeline.hpp"
 #include "pg_rp.hpp"
@@ -75,7 +76,8 @@ static int call_from_points(const char *fasta_path, const char *reads_path, cons
                             const uint64_t *far_off, const pg_point *far_pts, const uint8_t *rc_flag,
                             const pg_variant_cand *var_cands, const uint8_t *var_counts,
                             const pg_variant_cand *sv_cands = nullptr, const uint8_t *sv_counts = nullptr, bool use_events = false,
-                            const std::vector<SuppliedEvents> *supplied = nullptr)
+                            const std::vector<SuppliedEvents> *supplied = nullptr, bool use_sv_events = false,
+                            const std::vector<SuppliedSvEvents> *supplied_sv = nullptr)
 {
     std::vector<Chromosome> genome;
     if (load_fasta(fasta_path, genome, st->spacer, g_err)) return -1;
@@ -103,6 +105,8 @@ static int call_from_points(const char *fasta_path, const char *reads_path, cons
     S.repairs = st->repairs;
     S.use_events = use_events;
     if (supplied) S.supplied_events = *supplied;
+    S.use_sv_events = use_sv_events;
+    if (supplied_sv) S.supplied_sv_events = *supplied_sv;
     event_path_stats() = EventPathStats();
     if (S.repairs & ~(uint32_t)REPAIR_ALL) {
         g_err = "unknown bits in the repairs field";
@@ -250,6 +254,60 @@ int pgh_call_from_points_events(const char *fasta_path, const char *reads_path, 
     return call_from_points(fasta_path, reads_path, out_prefix, st, n_reads, close_off, close_pts, far_off, far_pts, rc_flag, var_cands, var_counts,
                             sv_cands, sv_counts, true, &supplied);
 }
+/*
+ * pgh_call_from_points_events with the sv_events path switched on as well: DI and the inversions are written from
+ * their SV tables -- built per window by pgh_sv_events_from_lists' function, or supplied (sv_sup: n_sv_supplied tables built on the
+ * device over all n_reads reads, each beside the entry of `sup` for the same window; tables that do not fit the window are
+ * replaced by the host's own) -- where the events path alone calls sort_output_di and sort_output_inv.  A window that falls back
+ * falls back as a whole.  The reports are the bytes pgh_call_from_points writes.
+ */
+struct pgh_supplied_sv_events {
+    int32_t chr;
+    uint32_t win_start, win_end, reserved;
+    const uint32_t *members;
+    const pg_event *events;
+    pg_sv_event_sizes sizes;
+};
+int pgh_call_from_points_sv_events(const char *fasta_path, const char *reads_path, const char *out_prefix, const pgh_settings *st,
+                                   uint32_t n_reads, const uint64_t *close_off, const pg_point *close_pts, const uint64_t *far_off,
+                                   const pg_point *far_pts, const uint8_t *rc_flag, const pg_variant_cand *var_cands, const uint8_t *var_counts,
+                                   const pg_variant_cand *sv_cands, const uint8_t *sv_counts, int32_t n_supplied, const pgh_supplied_events *sup,
+                                   int32_t n_sv_supplied, const pgh_supplied_sv_events *sv_sup)
+{
+    if (!var_cands || !var_counts || !sv_cands || !sv_counts) {
+        g_err = "pgh_call_from_points_sv_events: the lists of both device classifiers are needed";
+        return -1;
+    }
+    std::vector<SuppliedEvents> supplied;
+    for (int32_t k = 0; k < n_supplied; k++) {
+        SuppliedEvents e;
+        e.chr = sup[k].chr;
+        e.win_start = sup[k].win_start;
+        e.win_end = sup[k].win_end;
+        e.n_reads = n_reads;
+        e.reads = sup[k].reads;
+        e.members = sup[k].members;
+        e.events = sup[k].events;
+        e.sizes = sup[k].sizes;
+        supplied.push_back(e);
+    }
+    std::vector<SuppliedSvEvents> supplied_sv;
+    for (int32_t k = 0; k < n_sv_supplied; k++) {
+        SuppliedSvEvents e;
+        e.chr = sv_sup[k].chr;
+        e.win_start = sv_sup[k].win_start;
+        e.win_end = sv_sup[k].win_end;
+        e.members = sv_sup[k].members;
+        e.events = sv_sup[k].events;
+        e.sizes = sv_sup[k].sizes;
+        supplied_sv.push_back(e);
+    }
+    return call_from_points(fasta_path, reads_path, out_prefix, st, n_reads, close_off, close_pts, far_off, far_pts, rc_flag, var_cands, var_counts,
+                            sv_cands, sv_counts, true, &supplied, true, &supplied_sv);
+}
+/* windows of the last run whose DI and inversion reports came from SV tables / ... from supplied SV tables */
+uint64_t pgh_last_sv_event_table_windows(void) { return event_path_stats().sv_table_windows; }
+uint64_t pgh_last_sv_event_supplied_windows(void) { return event_path_stats().sv_supplied_windows; }
 /* windows of the last run with the events path that took the existing path / were written from tables / ... from supplied tables */
 uint64_t pgh_last_event_fallback_windows(void) { return event_path_stats().fallback_windows; }
 uint64_t pgh_last_event_table_windows(void) { return event_path_stats().table_windows; }
@@ -516,6 +574,74 @@ int pgh_events_from_lists(int32_t n_chr, const char *const *chr_seq, const uint6
         e += tabs.events[t].size();
     }
     sizes->unresolved = tabs.unresolved;
+    return 0;
+}
+
+/*
+ * The event tables of DI, INV and INV_NT from the per-read records of an events build (pindel_pg.h "DI and inversion
+ * event tables"), on the host: the plain-loop statement (pg_host_sv_events.hpp) the device entry pg_device_batch_sv_events is
+ * compared with, byte for byte.  The reads and close points as pgh_events_from_lists takes them; recs: n_reads records of that
+ * entry (or of the device's); sv_cands: the lists it was given; w: its window.  out_members / out_events: room for n_reads entries
+ * each, filled table after table; sizes: what was filled.  -1: the window's chr_id lies outside the reference.
+ */
+int pgh_sv_events_from_lists(int32_t n_chr, const char *const *chr_seq, const uint64_t *chr_len, uint32_t spacer, uint32_t n_reads,
+                             const uint8_t *seq, const uint64_t *seq_off, const uint8_t *strand, const uint8_t *rc_flag,
+                             const uint64_t *close_off, const pg_point *close_pts, const pg_event_window *w, const pg_event_read *recs,
+                             const pg_variant_cand *sv_cands, uint32_t *out_members, pg_event *out_events, pg_sv_event_sizes *sizes)
+{
+    if (!w || !sizes || w->chr_id < 0 || w->chr_id >= n_chr) {
+        g_err = "pgh_sv_events_from_lists: the window's chr_id lies outside the reference";
+        return -1;
+    }
+    if (n_reads && (!recs || !sv_cands)) {
+        g_err = "pgh_sv_events_from_lists: null records or sv candidate array";
+        return -1;
+    }
+    const std::string ref(chr_seq[w->chr_id], (size_t)chr_len[w->chr_id]);
+    auto post_state = [&](uint32_t i, SplitRead &r) {
+        r.UnmatchedSeq.assign((const char *)seq + seq_off[i], (size_t)(seq_off[i + 1] - seq_off[i]));
+        pg_adapter::apply_rc_flag(r, rc_flag[i]);
+        r.ReadLength = (short)r.UnmatchedSeq.size();
+        r.MatchedD = (char)strand[i];
+    };
+    std::vector<SvEventReadIn> in(n_reads);
+    pg_adapter::parallel_ranges(n_reads, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; i++) {
+            if (!(recs[i].flags & PG_EVR_BOXED)) continue;
+            SplitRead r;
+            post_state((uint32_t)i, r);
+            SvEventReadIn &e = in[i];
+            e.plus = strand[i] == '+';
+            e.read_length = r.ReadLength;
+            // LeftMostPos, Caller::note_close_mapped (a read without a close end is never boxed; its point counts as all zero)
+            UniquePoint last;
+            last.AbsLoc = 0;
+            last.LengthStr = 0;
+            if (close_off[i + 1] > close_off[i]) last = to_unique_point(close_pts[close_off[i + 1] - 1]);
+            const short close_len = last.LengthStr;
+            e.left_most = e.plus ? (int)(last.AbsLoc + 1 - close_len) : (int)(last.AbsLoc + close_len - r.getReadLength());
+        }
+    });
+    SvEventTables tabs;
+    auto cand_of = [&](size_t i, int kind, unsigned slot) -> const pg_variant_cand & {
+        return sv_cands[i * PG_SV_SLOTS + sv_slot_base()[kind - PG_SV_DI] + slot];
+    };
+    sv_events_from_lists(ref, spacer, *w, in, recs, cand_of, [&](uint32_t i, const pg_variant_cand &c) {
+        SplitRead r;
+        post_state(i, r);
+        return r.MatchedD == '+' ? sub(reverse_complement(r.UnmatchedSeq), c.bp + 1, (unsigned short)c.nt_rot)
+                                 : sub(r.UnmatchedSeq, c.bp + 1, (unsigned short)c.nt_rot);
+    }, tabs);
+    size_t m = 0, e = 0;
+    for (int t = 0; t < PG_SV_EVENT_TABLES; t++) {
+        sizes->members[t] = tabs.members[t].size();
+        sizes->events[t] = tabs.events[t].size();
+        sizes->dropped_runs[t] = tabs.dropped_runs[t];
+        if (!tabs.members[t].empty()) memcpy(out_members + m, tabs.members[t].data(), tabs.members[t].size() * sizeof(uint32_t));
+        if (!tabs.events[t].empty()) memcpy(out_events + e, tabs.events[t].data(), tabs.events[t].size() * sizeof(pg_event));
+        m += tabs.members[t].size();
+        e += tabs.events[t].size();
+    }
     return 0;
 }
 

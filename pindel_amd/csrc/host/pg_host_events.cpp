@@ -2,13 +2,15 @@
 // from the reads' candidate lists (pg_host_events.hpp) or taken from the caller (built on the device), and deletions, short
 // insertions and tandem duplications are written from them -- `good` from the member lists with the pairs' fields applied, the
 // reporters' output_* functions for the events flagged PG_EV_REPORT, in table order.  DI and the inversions take their boxes from
-// the per-read records and keep their own reporters (their exchange sorts are strict: no stable sort reproduces their tie order).
+// the per-read records and keep their own reporters (their exchange sorts are strict: no stable sort reproduces their tie order)
+// -- or, with Settings::use_sv_events, are written from their SV tables (pg_host_sv_events.hpp) in the same places.
 // The reports must be the bytes of the existing path: that is what pins pg_host_events.hpp to the reference's gold reports.
 #include <unordered_map>
 
 #include "pg_depth.hpp"
 #include "pg_host_events.hpp"
 #include "pg_host_priv.hpp"
+#include "pg_host_sv_events.hpp"
 
 namespace pgh {
 
@@ -18,6 +20,47 @@ EventPathStats &event_path_stats()
 {
     static EventPathStats s;
     return s;
+}
+
+// Supplied SV tables (over all reads of the run, beside the supplied event tables `sup` of the same window) to the window's own
+// read indices.  false: they do not fit this window's reads and records -- a member the window does not hold or that its record
+// did not box for the table's kind, a member list of another size than the records give, an event outside its member list.
+static bool sv_tables_from_supplied(const SuppliedSvEvents &e, const SuppliedEvents &sup, const std::vector<SplitRead> &reads,
+                                    const std::vector<pg_event_read> &recs, SvEventTables &out)
+{
+    std::unordered_map<uint32_t, uint32_t> local;
+    local.reserve(reads.size() * 2);
+    for (size_t k = 0; k < reads.size(); k++) local[reads[k].VarIndex] = (uint32_t)k;
+    out = SvEventTables();
+    size_t m0 = 0, e0 = 0;
+    for (int t = 0; t < PG_SV_EVENT_TABLES; t++) {
+        const int kind = sv_event_kind_of(t);
+        size_t boxed = 0;
+        for (const pg_event_read &r : recs) boxed += (r.flags & PG_EVR_BOXED) && r.kind == kind;
+        const uint64_t nm = e.sizes.members[t], ne = e.sizes.events[t];
+        if (kind == PG_SV_DI ? nm > boxed : nm != boxed) return false;
+        std::vector<char> taken(reads.size(), 0);
+        for (uint64_t k = 0; k < nm; k++) {
+            const uint32_t word = e.members[m0 + k], idx = word & ~PG_SVEV_MEMBER_DUP;
+            if (idx >= sup.n_reads || (kind == PG_SV_DI && (word & PG_SVEV_MEMBER_DUP))) return false;
+            auto it = local.find(idx);
+            if (it == local.end()) return false;
+            const pg_event_read &r = recs[it->second];
+            if (!(r.flags & PG_EVR_BOXED) || r.kind != kind || taken[it->second]) return false;
+            taken[it->second] = 1;
+            out.members[t].push_back(it->second | (word & PG_SVEV_MEMBER_DUP));
+        }
+        out.events[t].assign(e.events + e0, e.events + e0 + ne);
+        uint64_t next = 0;
+        for (const pg_event &ev : out.events[t]) {
+            if (ev.n_reads == 0 || ev.first < next || (uint64_t)ev.first + ev.n_reads > nm || ev.kind != kind) return false;
+            next = (uint64_t)ev.first + ev.n_reads;
+        }
+        out.dropped_runs[t] = e.sizes.dropped_runs[t];
+        m0 += nm;
+        e0 += ne;
+    }
+    return true;
 }
 
 bool Caller::process_window_events(Ctx &c)
@@ -198,18 +241,111 @@ bool Caller::process_window_events(Ctx &c)
         }
     };
     std::vector<std::vector<unsigned>> boxes;
+    // ---- the sv_events path: DI and the inversions from their SV tables, in the places of the two reporters
+    SvEventTables svt;
+    if (S.use_sv_events) {
+        bool sv_supplied = false;
+        if (from_supplied)
+            for (const SuppliedSvEvents &e : S.supplied_sv_events)
+                if (e.chr == sup->chr && e.win_start == c.win_start && e.win_end == c.win_end && sv_tables_from_supplied(e, *sup, reads, tabs.reads, svt))
+                    sv_supplied = true;
+        if (!sv_supplied) {
+            // supplied tables that do not fit (or none): the host statement over the window's own reads
+            std::vector<SvEventReadIn> in(n);
+            for (size_t k = 0; k < n; k++) {
+                in[k].plus = reads[k].MatchedD == '+';
+                in[k].read_length = reads[k].getReadLength();
+                in[k].left_most = reads[k].LeftMostPos;
+            }
+            svt = SvEventTables();
+            sv_events_from_lists(ref, S.spacer, w, in, tabs.reads.data(),
+                                 [&](size_t k, int kind, unsigned slot) -> const pg_variant_cand & { return reads[k].SvCands[sv_slot_base()[kind - PG_SV_DI] + slot]; },
+                                 [&](uint32_t k, const pg_variant_cand &cand) {
+                                     VariantPair p;
+                                     sv_pair_from_cand(reads[k], PG_SV_DI, cand, p);
+                                     return p.nt;
+                                 }, svt);
+        }
+        event_path_stats().sv_table_windows++;
+        if (sv_supplied) event_path_stats().sv_supplied_windows++;
+    }
+    // one SV table written: what sort_output_di / sort_output_inv leave of the kind -- the pairs applied to the window's reads, the
+    // duplicates of the boxes that reach -M marked -- and the reporters' output_* for the events flagged PG_EV_REPORT
+    auto write_sv_table = [&](int t) {
+        const int kind = sv_event_kind_of(t);
+        boxes_of(kind, boxes);
+        std::vector<char> dup(n, 0);
+        if (kind == PG_SV_DI) {
+            for (size_t k = 0; k < n; k++) dup[k] = (tabs.reads[k].flags & PG_EVR_BOXED) && tabs.reads[k].kind == kind;
+            for (uint32_t m : svt.members[t]) dup[m] = 0;
+        } else {
+            for (uint32_t m : svt.members[t])
+                if (m & PG_SVEV_MEMBER_DUP) dup[m & ~PG_SVEV_MEMBER_DUP] = 1;
+        }
+        for (const std::vector<unsigned> &box : boxes)
+            if (!box.empty() && box.size() >= S.NumRead2ReportCutOff)
+                for (unsigned k : box)
+                    if (dup[k]) reads[k].UniqueRead = false;
+        bool any = false;
+        for (const pg_event &ev : svt.events[t]) any = any || (ev.flags & PG_EV_REPORT);
+        if (!any) return;
+        std::vector<SplitRead> good;
+        good.reserve(svt.members[t].size());
+        for (uint32_t m : svt.members[t]) {
+            good.push_back(reads[m & ~PG_SVEV_MEMBER_DUP]);              // (the pair is applied, NT_size is the carried one)
+            good.back().NT_size = tabs.reads[m & ~PG_SVEV_MEMBER_DUP].nt_size;
+        }
+        for_boxes(1, [&](unsigned) {
+            for (const pg_event &ev : svt.events[t]) {
+                if (!(ev.flags & PG_EV_REPORT)) continue;
+                const unsigned s = ev.first, e = ev.first + ev.n_reads - 1;
+                if (kind == PG_SV_DI) {
+                    if (ev.flags & PG_EV_SHORT_INV) output_short_inv(c, good, s, e);
+                    else output_di(c, good, s, e);
+                    continue;
+                }
+                // the run harmonised from the event's IndelSize, as sort_output_inv's harmonise() leaves its members
+                for (unsigned i = s; i <= e; i++) {
+                    SplitRead &r = good[i];
+                    const unsigned mx = ev.indel_size;
+                    const short diff = (short)((mx - r.IndelSize) / 2);
+                    r.IndelSize = mx;
+                    r.BPLeft = r.BPLeft - diff;
+                    r.BPRight = r.BPRight + diff;
+                    if (r.MatchedD == '+') {
+                        if (r.BP > diff) r.BP = (short)(r.BP - diff);
+                    } else {
+                        if (r.BP + diff < r.getReadLengthMinus()) r.BP = (short)(r.BP + diff);
+                    }
+                }
+                // IsGoodINV's -N test (sort_output_inv)
+                if (S.germline_filter() && ev.real_end - ev.real_start >= (unsigned)good[s].getReadLength() * 2 &&
+                    !(S.repair(REPAIR_INV_PAIRS) && inv_pairs_good(inv_pairs_, ev.n_reads, ev.real_start, ev.real_end)))
+                    continue;
+                output_inv(c, good, s, e, ev.real_start, ev.real_end);
+            }
+        });
+    };
     write_table(0);
-    boxes_of(PG_SV_DI, boxes);
-    sort_output_di(c, boxes);
+    if (S.use_sv_events) write_sv_table(0);
+    else {
+        boxes_of(PG_SV_DI, boxes);
+        sort_output_di(c, boxes);
+    }
     if (S.Analyze_TD) {
         write_table(2);
         write_table(3);
     }
     if (S.Analyze_INV) {
-        boxes_of(PG_SV_INV, boxes);
-        sort_output_inv(c, boxes, false);
-        boxes_of(PG_SV_INV_NT, boxes);
-        sort_output_inv(c, boxes, true);
+        if (S.use_sv_events) {
+            write_sv_table(1);
+            write_sv_table(2);
+        } else {
+            boxes_of(PG_SV_INV, boxes);
+            sort_output_inv(c, boxes, false);
+            boxes_of(PG_SV_INV_NT, boxes);
+            sort_output_inv(c, boxes, true);
+        }
     }
     write_table(1);
     return true;

@@ -305,6 +305,13 @@ struct pg_device_batch {
     pg_event *ev_events = nullptr;         // n: the four event lists back to back
     pg_event_sizes ev_sizes{};
     bool ev_built = false;
+    pg_event_window ev_window{};           // ... and the window they were built for
+    // the SV tables of the last pg_device_batch_sv_events; an events build discards them
+    uint32_t *svev_members = nullptr;      // n: the three member lists back to back
+    pg_event *svev_events = nullptr;       // n: the three event lists back to back
+    uint32_t *svev_ws = nullptr;           // n: the order kernel's ranks of boxes beyond its LDS
+    pg_sv_event_sizes svev_sizes{};
+    bool svev_built = false;
 };
 
 struct pg_result {
@@ -457,8 +464,12 @@ PgDevParams dev_params(const pg_ctx *ctx)
 
 void free_batch_buffers(pg_device_batch *b)
 {
-    for (void *p : { (void *)b->ev_reads, (void *)b->ev_members, (void *)b->ev_events })
+    for (void *p : { (void *)b->ev_reads, (void *)b->ev_members, (void *)b->ev_events, (void *)b->svev_members, (void *)b->svev_events, (void *)b->svev_ws })
         if (p) (void)hipFree(p);
+    b->svev_members = nullptr;
+    b->svev_events = nullptr;
+    b->svev_ws = nullptr;
+    b->svev_built = false;
     b->ev_reads = nullptr;
     b->ev_members = nullptr;
     b->ev_events = nullptr;
@@ -2452,7 +2463,9 @@ int build_events(pg_ctx *ctx, pg_device_batch *b, const pg_event_window *w, cons
                  const pg_variant_cand *d_sv_cands, const uint8_t *d_sv_counts, const uint32_t *d_name_id)
 {
     b->ev_built = false;
+    b->svev_built = false;                                    // (the SV tables belong to the records of the build they were made from)
     b->ev_sizes = pg_event_sizes{};
+    b->ev_window = *w;
     const size_t n = b->n;
     if (!n) {                                                 // nothing is launched for an empty batch
         b->ev_built = true;
@@ -2634,6 +2647,189 @@ int pg_device_batch_events_download_device(pg_ctx *ctx, pg_device_batch *b, pg_e
         (d_events && (rc = check_device_ptr(ctx, d_events, ne * sizeof(pg_event), 4, "events download: events"))))
         return rc;
     return events_download(ctx, b, d_reads, d_members, d_events, hipMemcpyDeviceToDevice);
+}
+
+// ---- ... its fourth part (pg_sv_events.hip): the event tables of DI, INV and INV_NT
+namespace {
+int sv_events_refusal(pg_ctx *ctx, pg_device_batch *b, const void *sv_cands, const void *sv_counts)
+{
+    if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
+    if (int rc = stale_batch(ctx, b)) return rc;
+    ctx->last_ms = 0.0;
+    if (b->n && !b->searched) return fail(ctx, PG_E_INVALID, "the batch has not been searched: no close and far ends to classify");
+    if (!b->ev_built) return fail(ctx, PG_E_INVALID, "sv events: pg_device_batch_events has not been run on this batch");
+    if (b->n && (!sv_cands || !sv_counts)) return fail(ctx, PG_E_INVALID, "sv events: null sv candidate arrays");
+    if (b->n >= 0x80000000u) return fail(ctx, PG_E_INVALID, "sv events: 2^31 reads or more (bit 31 of a member word is PG_SVEV_MEMBER_DUP)");
+    return PG_OK;
+}
+
+// d_sv_cands is device memory
+int build_sv_events(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *d_sv_cands)
+{
+    b->svev_built = false;
+    b->svev_sizes = pg_sv_event_sizes{};
+    const size_t n = b->n;
+    if (!n) {                                                 // nothing is launched for an empty batch
+        b->svev_built = true;
+        return PG_OK;
+    }
+    int rc;
+    if (!b->svev_members && ((rc = dev_alloc(ctx, &b->svev_members, n)) || (rc = dev_alloc(ctx, &b->svev_events, n)) || (rc = dev_alloc(ctx, &b->svev_ws, n))))
+        return rc;
+    EventTemps tmp;
+    PgSvEventArgs a{};
+    const size_t n_blk = n / PG_EV_BLOCK + 2;
+    if ((rc = EV_TAKE(tmp, ctx, a.rec_a, n)) || (rc = EV_TAKE(tmp, ctx, a.rec, n)) || (rc = EV_TAKE(tmp, ctx, a.flag, n)) ||
+        (rc = EV_TAKE(tmp, ctx, a.dupf, n)) || (rc = EV_TAKE(tmp, ctx, a.rank, n)) || (rc = EV_TAKE(tmp, ctx, a.blk, n_blk)) ||
+        (rc = EV_TAKE(tmp, ctx, a.perm_a, n)) || (rc = EV_TAKE(tmp, ctx, a.perm_b, n)) || (rc = EV_TAKE(tmp, ctx, a.kperm_a, n)) ||
+        (rc = EV_TAKE(tmp, ctx, a.kperm_b, n)) || (rc = EV_TAKE(tmp, ctx, a.krank, n)) || (rc = EV_TAKE(tmp, ctx, a.seg_first, n + 1)) ||
+        (rc = EV_TAKE(tmp, ctx, a.midx, n)) || (rc = EV_TAKE(tmp, ctx, a.rfirst, n + 1)) || (rc = EV_TAKE(tmp, ctx, a.rmx, n)) ||
+        (rc = EV_TAKE(tmp, ctx, a.rfail, n)) || (rc = EV_TAKE(tmp, ctx, a.digit_cnt, 256 * n_blk + 1)) || (rc = EV_TAKE(tmp, ctx, a.info, 1)))
+        return rc;
+    a.out = b->out_rec;
+    a.seq = b->seq;
+    a.seq_off = b->seq_off;
+    a.strand = b->strand;
+    a.spacer = ctx->prm.spacer;
+    a.n = b->n;
+    a.win = b->ev_window;
+    const uint64_t chr_len = ctx->comp_size[(size_t)a.win.chr_id];
+    a.box_size = (uint32_t)(chr_len / 30000);
+    if (a.box_size == 0) a.box_size = 1;
+    a.sv_cands = d_sv_cands;
+    a.reads = b->ev_reads;
+    a.members = b->svev_members;
+    a.events = b->svev_events;
+    a.ws_rank = b->svev_ws;
+    const PgDevRef ref = dev_ref(ctx);
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if (pg_sv_events_gather_launch(&a, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the sv event gather kernels failed");
+    PgLaunchRec rec{};
+    rec.kernel = PG_KERNEL_SV_EVENTS;
+    rec.blocks = (int32_t)PG_EV_BLOCK;
+    log_launch(ctx, rec);
+    PgSvEventInfo info;
+    HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (info.n_boxed > n) return fail(ctx, PG_E_DEVICE, "sv events: the boxed count exceeds the batch");
+    if (info.n_boxed) {                                       // (nothing boxed: nothing below indexes an empty array)
+        // a pass over a byte that is constant over the boxed records changes nothing: skipped
+        auto sort = [&](uint32_t *&src, uint32_t *&dst, int pass, uint32_t vary) -> int {
+            if (!vary) return 0;
+            if (pg_sv_events_sort_pass_launch(&a, src, dst, info.n_boxed, pass, ctx->stream)) return -1;
+            std::swap(src, dst);
+            return 0;
+        };
+        uint32_t *perm = a.perm_a, *perm_t = a.perm_b, *kperm = a.kperm_a, *kperm_t = a.kperm_b;
+        const uint32_t seg_vary = info.seg_or ^ info.seg_and;
+        for (int k = 0; k < 4; k++)
+            if (sort(perm, perm_t, PG_SVEV_PASS_BOX + k, (seg_vary >> (8 * k)) & 0xffu)) return fail(ctx, PG_E_DEVICE, "launching an sv event sort pass failed");
+        for (int pass = 0; pass < PG_SVEV_PASS_TABLE; pass++) {
+            const int word = PG_SVEV_KEY_WORDS - 1 - (pass >> 2);
+            if (sort(kperm, kperm_t, pass, ((info.key_or[word] ^ info.key_and[word]) >> ((pass & 3) * 8)) & 0xffu))
+                return fail(ctx, PG_E_DEVICE, "launching an sv event sort pass failed");
+        }
+        if (sort(kperm, kperm_t, PG_SVEV_PASS_TABLE, seg_vary >> 24)) return fail(ctx, PG_E_DEVICE, "launching an sv event sort pass failed");
+        if (pg_sv_events_tables_launch(&ref, &a, perm, kperm, info.n_boxed, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the sv event table kernels failed");
+        HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->last_ms = ms;
+    if (info.n_boxed) {
+        uint64_t nm = 0, ne = 0;
+        for (int t = 0; t < PG_SV_EVENT_TABLES; t++) {
+            b->svev_sizes.members[t] = info.n_mem[t];
+            b->svev_sizes.events[t] = info.n_ev[t];
+            b->svev_sizes.dropped_runs[t] = info.dropped[t];
+            nm += info.n_mem[t];
+            ne += info.n_ev[t];
+        }
+        if (nm != info.n_members || nm > info.n_boxed || ne > info.n_runs || info.n_runs > nm) {
+            b->svev_sizes = pg_sv_event_sizes{};
+            return fail(ctx, PG_E_DEVICE, "sv events: inconsistent table sizes");
+        }
+    }
+    b->svev_built = true;
+    return PG_OK;
+}
+
+void sv_event_totals(const pg_device_batch *b, size_t *nm, size_t *ne)
+{
+    *nm = *ne = 0;
+    for (int t = 0; t < PG_SV_EVENT_TABLES; t++) {
+        *nm += b->svev_sizes.members[t];
+        *ne += b->svev_sizes.events[t];
+    }
+}
+const char *const NO_SV_TABLES = "no sv event tables: pg_device_batch_sv_events has not been run on this batch since its events build";
+}  // namespace
+
+int pg_device_batch_sv_events_device(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *d_sv_cands, const uint8_t *d_sv_counts)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (int rc = sv_events_refusal(ctx, b, d_sv_cands, d_sv_counts)) return rc;
+    const size_t n = b->n;
+    int rc;
+    if (n && ((rc = check_device_ptr(ctx, d_sv_cands, n * PG_SV_SLOTS * sizeof(pg_variant_cand), 4, "sv events: sv_cands")) ||
+              (rc = check_device_ptr(ctx, d_sv_counts, n * PG_SV_KINDS, 1, "sv events: sv_counts"))))
+        return rc;
+    return build_sv_events(ctx, b, d_sv_cands);
+}
+
+int pg_device_batch_sv_events(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *sv_cands, const uint8_t *sv_counts)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (int rc = sv_events_refusal(ctx, b, sv_cands, sv_counts)) return rc;
+    const size_t n = b->n;
+    EventTemps tmp;
+    pg_variant_cand *d_sv = nullptr;
+    if (n) {
+        if (int rc = EV_TAKE(tmp, ctx, d_sv, n * PG_SV_SLOTS)) return rc;
+        HIP_TRY(ctx, hipMemcpy(d_sv, sv_cands, n * PG_SV_SLOTS * sizeof(pg_variant_cand), hipMemcpyHostToDevice));
+    }
+    return build_sv_events(ctx, b, d_sv);
+}
+
+int pg_device_batch_sv_event_sizes(pg_ctx *ctx, pg_device_batch *b, pg_sv_event_sizes *sizes)
+{
+    use_device(ctx);
+    if (!ctx || !b || !sizes) return PG_E_INVALID;
+    if (!b->svev_built) return fail(ctx, PG_E_INVALID, NO_SV_TABLES);
+    *sizes = b->svev_sizes;
+    return PG_OK;
+}
+
+int pg_device_batch_sv_events_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *members, pg_event *events)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (!b->svev_built) return fail(ctx, PG_E_INVALID, NO_SV_TABLES);
+    size_t nm, ne;
+    sv_event_totals(b, &nm, &ne);
+    if (members && nm) HIP_TRY(ctx, hipMemcpy(members, b->svev_members, nm * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (events && ne) HIP_TRY(ctx, hipMemcpy(events, b->svev_events, ne * sizeof(pg_event), hipMemcpyDeviceToHost));
+    return PG_OK;
+}
+
+int pg_device_batch_sv_events_download_device(pg_ctx *ctx, pg_device_batch *b, uint32_t *d_members, pg_event *d_events)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (!b->svev_built) return fail(ctx, PG_E_INVALID, NO_SV_TABLES);
+    size_t nm, ne;
+    sv_event_totals(b, &nm, &ne);
+    int rc;
+    if ((d_members && (rc = check_device_ptr(ctx, d_members, nm * sizeof(uint32_t), 4, "sv events download: members"))) ||
+        (d_events && (rc = check_device_ptr(ctx, d_events, ne * sizeof(pg_event), 4, "sv events download: events"))))
+        return rc;
+    if (d_members && nm) HIP_TRY(ctx, hipMemcpy(d_members, b->svev_members, nm * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+    if (d_events && ne) HIP_TRY(ctx, hipMemcpy(d_events, b->svev_events, ne * sizeof(pg_event), hipMemcpyDeviceToDevice));
+    return PG_OK;
 }
 
 void pg_device_batch_free(pg_ctx *ctx, pg_device_batch *b)

@@ -306,7 +306,7 @@ int pg_debug_kargs_check(const PgDevRef *ref, const PgDevParams *prm, const PgDe
 // What one kernel launch on the search path ran (the launch log of pg_api.cpp, pg_debug_launch_log): the kernel and its
 // template arguments.  The launch functions below fill these when given somewhere to put them (null: nothing is recorded).
 enum PgKernelKind { PG_KERNEL_SEARCH = 1, PG_KERNEL_EXACT = 2, PG_KERNEL_PACK = 3, PG_KERNEL_VARIANT = 4, PG_KERNEL_SV = 5,
-                    PG_KERNEL_EVENT_CASCADE = 6, PG_KERNEL_EVENT_SORT = 7, PG_KERNEL_EVENT_TABLES = 8 };
+                    PG_KERNEL_EVENT_CASCADE = 6, PG_KERNEL_EVENT_SORT = 7, PG_KERNEL_EVENT_TABLES = 8, PG_KERNEL_SV_EVENTS = 9 };
 struct PgLaunchRec {
     int32_t kernel;                // PgKernelKind
     int32_t blocks;                // NB of pg_search_kernel, PB of pg_pack_kernel (0: pg_search_exact_kernel)
@@ -453,6 +453,54 @@ int pg_events_sort_pass_launch(const struct PgEventArgs *a, const struct PgEvent
                                void *stream);
 // stages C and D over the sorted records; fills members, events and the rest of info
 int pg_events_tables_launch(const PgDevRef *ref, const struct PgEventArgs *a, const struct PgEventRec *sorted, uint32_t n_boxed, void *stream);
+// SV event tables (pg_sv_events.hip): DI, INV and INV_NT from the per-read records of the events build.  The boxed
+// records stay where the compaction put them (ascending read index); what is sorted are permutations of their places.
+#define PG_SVEV_LDS_BOX 640u          // reads of a box the order kernel keeps in LDS (rank + place: 8 bytes each, 4 granules of 1280 bytes)
+#define PG_SVEV_KEY_WORDS 5           // DI: BPLeft, BPRight, NT_size << 16 | BP biased, 0, 0.  INV / INV_NT: BPLeft + BPRight, ~IndelSize, BPLeft,
+                                      // BPRight, (NT_size << 16 for INV_NT) | BP biased
+#define PG_SVEV_PASS_TABLE 20         // sort passes: 0 .. 19 the key bytes, least significant first; 20 the table (key sort);
+#define PG_SVEV_PASS_BOX 21           // 21 .. 23 the bytes of the box, 24 the table (segment sort)
+#define PG_SVEV_PASS_SEG_TABLE 24
+// one boxed read: BPLeft, BPRight, IndelSize, NT_size << 16 | (BP ^ 0x8000), read, table | plus << 8 | ReadLength << 16, LeftMostPos, box | table << 24
+struct PgSvEventRec { uint32_t w[8]; };
+struct PgSvEventInfo {                // what the host reads back
+    uint32_t n_boxed, n_segs, n_members, n_runs;
+    uint32_t n_mem[PG_SV_EVENT_TABLES], n_ev[PG_SV_EVENT_TABLES], dropped[PG_SV_EVENT_TABLES];
+    uint32_t seg_or, seg_and;         // over w[7] of the boxed records: a byte equal in both is constant
+    uint32_t key_or[PG_SVEV_KEY_WORDS], key_and[PG_SVEV_KEY_WORDS];
+};
+struct PgSvEventArgs {
+    const PgOutRec *out;
+    const uint8_t *seq;
+    const uint64_t *seq_off;
+    const uint8_t *strand;
+    uint32_t spacer, n;
+    pg_event_window win;              // the events build's
+    uint32_t box_size;
+    const pg_variant_cand *sv_cands;  // n x PG_SV_SLOTS
+    const pg_event_read *reads;       // n: the events build's records
+    uint32_t *members;                // n
+    pg_event *events;                 // n
+    uint32_t *ws_rank;                // n: the ranks of boxes above PG_SVEV_LDS_BOX (kept with the batch)
+    struct PgSvEventRec *rec_a, *rec; // n each: by read; compacted in ascending read index
+    uint8_t *flag, *dupf;             // n each
+    uint32_t *rank, *blk;             // n; n / PG_EV_BLOCK + 2
+    uint32_t *perm_a, *perm_b;        // n each: places in (table, box) segments, arrival order within a segment
+    uint32_t *kperm_a, *kperm_b;      // n each: places by (table, key)
+    uint32_t *krank;                  // n: dense rank of a place's key within its table
+    uint32_t *seg_first, *midx, *rfirst;   // n + 1; n; n + 1
+    uint32_t *rmx;                    // n: a run's largest IndelSize
+    uint8_t *rfail;                   // n: a member of the run fails the harmonisation test
+    uint32_t *digit_cnt;              // 256 x (n / PG_EV_BLOCK + 2) + 1
+    struct PgSvEventInfo *info;
+};
+// the boxed reads of the three kinds compacted into rec, the identity in perm_a and kperm_a; info->n_boxed and the masks are then valid
+int pg_sv_events_gather_launch(const struct PgSvEventArgs *a, void *stream);
+// one stable counting pass of the places src[0 .. n_boxed) over digit `pass` of their records into dst
+int pg_sv_events_sort_pass_launch(const struct PgSvEventArgs *a, const uint32_t *src, uint32_t *dst, uint32_t n_boxed, int pass, void *stream);
+// ranks, segments, the record-shift passes per box (perm is permuted in place), duplicates, members, runs and events
+int pg_sv_events_tables_launch(const PgDevRef *ref, const struct PgSvEventArgs *a, uint32_t *perm, const uint32_t *kperm, uint32_t n_boxed,
+                               void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -89,7 +89,9 @@ def lib():
         L.pgh_last_variant_visits.argtypes = [C.c_void_p, C.c_uint64]
         L.pgh_variant_candidates.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32] + [C.c_void_p] * 12
         L.pgh_call_from_points_events.argtypes = L.pgh_call_from_points.argtypes + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]
-        for f in ("pgh_last_event_fallback_windows", "pgh_last_event_table_windows", "pgh_last_event_supplied_windows"):
+        L.pgh_call_from_points_sv_events.argtypes = L.pgh_call_from_points_events.argtypes + [C.c_int32, C.c_void_p]
+        for f in ("pgh_last_event_fallback_windows", "pgh_last_event_table_windows", "pgh_last_event_supplied_windows",
+                  "pgh_last_sv_event_table_windows", "pgh_last_sv_event_supplied_windows"):
             getattr(L, f).restype = C.c_uint64
             getattr(L, f).argtypes = []
         L.pgh_last_event_windows.restype = C.c_uint64
@@ -424,6 +426,65 @@ def events_from_lists(chroms, seq, seq_off, anchor_strand, chr_id, rc_flag, inse
     return event_tables(reads, members, events, sizes)
 
 
+# SV event tables (include/pindel_pg.h): tables 0..2 = DI, INV, INV_NT; the events are EVENT_DTYPE records
+SV_EVENT_TABLES = 3
+SV_EVENT_KINDS = (2, 5, 6)
+EV_SHORT_INV = 0x10
+SVEV_MEMBER_DUP = 0x80000000
+
+
+class SvEventSizes(C.Structure):
+    """pg_sv_event_sizes"""
+    _fields_ = [("members", C.c_uint64 * SV_EVENT_TABLES), ("events", C.c_uint64 * SV_EVENT_TABLES),
+                ("dropped_runs", C.c_uint64 * SV_EVENT_TABLES)]
+
+
+def sv_event_tables(members, events, sizes):
+    """The flat outputs of an sv events entry as a dict: members / events (lists of the three tables' arrays, in SV_EVENT_KINDS
+    order), dropped_runs, and the flat arrays themselves (members_flat, events_flat)."""
+    nm = [int(x) for x in sizes.members]
+    ne = [int(x) for x in sizes.events]
+    mo = np.concatenate([[0], np.cumsum(nm)]).astype(np.int64)
+    eo = np.concatenate([[0], np.cumsum(ne)]).astype(np.int64)
+    members = members[:mo[-1]]
+    events = events[:eo[-1]]
+    return dict(members=[members[mo[t]:mo[t + 1]] for t in range(SV_EVENT_TABLES)],
+                events=[events[eo[t]:eo[t + 1]] for t in range(SV_EVENT_TABLES)], dropped_runs=[int(x) for x in sizes.dropped_runs],
+                members_flat=members, events_flat=events, n_members=nm, n_events=ne)
+
+
+def sv_events_from_lists(chroms, seq, seq_off, anchor_strand, rc_flag, close_off, close_pts, window, reads, sv, spacer=100000):
+    """The event tables of DI, INV and INV_NT on the host (pgh_sv_events_from_lists): the reference Engine.sv_events
+    is compared with, byte for byte -- the literal exchange sort, the literal duplicate walk and the sequential `whether` of the
+    reporters.  Reads and close points as events_from_lists takes them; window: that build's EventWindow; reads: its per-read
+    records (EVENT_READ_DTYPE[n]); sv: the (cands, counts) pair it was given.  Returns sv_event_tables(...)."""
+    L = lib()
+    n = len(seq_off) - 1
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    strand = np.ascontiguousarray(anchor_strand, dtype=np.uint8)
+    rc_flag = np.ascontiguousarray(rc_flag, dtype=np.uint8)
+    close_off = np.ascontiguousarray(close_off, dtype=np.uint64)
+    close_pts = np.ascontiguousarray(close_pts)
+    recs = np.ascontiguousarray(reads, dtype=EVENT_READ_DTYPE)
+    sc = np.ascontiguousarray(sv[0], dtype=VARIANT_CAND_DTYPE)
+    assert close_pts.dtype.itemsize == 12
+    assert len(strand) == n and len(rc_flag) == n and len(close_off) == n + 1 and len(recs) == n and sc.size == n * SV_SLOTS
+    bufs = [bytes(s) for _, s in chroms]
+    ptrs = (C.c_char_p * len(bufs))(*bufs)
+    lens = (C.c_uint64 * len(bufs))(*[len(b) for b in bufs])
+    members = np.zeros(max(n, 1), dtype=np.uint32)
+    events = np.zeros(max(n, 1), dtype=EVENT_DTYPE)
+    sizes = SvEventSizes()
+    L.pgh_sv_events_from_lists.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32] + [C.c_void_p] * 12
+    rc = L.pgh_sv_events_from_lists(len(bufs), ptrs, lens, int(spacer), n, seq.ctypes.data, seq_off.ctypes.data, strand.ctypes.data,
+                                    rc_flag.ctypes.data, close_off.ctypes.data, close_pts.ctypes.data, C.addressof(window),
+                                    recs.ctypes.data, sc.ctypes.data, members.ctypes.data, events.ctypes.data, C.addressof(sizes))
+    if rc:
+        raise ValueError("pgh_sv_events_from_lists: " + (L.pgh_last_error() or b"").decode())
+    return sv_event_tables(members, events, sizes)
+
+
 def last_variant_fallbacks():
     """Reads of the last call_from_points(variant_candidates=...) whose list ran out, with VARIANT_MORE set, before one of its
     pairs had made the read Used: they went through the classifier's own pair search."""
@@ -442,7 +503,7 @@ def last_variant_visits():
 
 def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pts, far_off, far_pts,
                      rc_flag, region=None, include_bed=None, exclude_bed=None, reads_config=None, normal_samples=None,
-                     bam_config=None, repairs=None, variant_candidates=None, sv_candidates=None, events=None):
+                     bam_config=None, repairs=None, variant_candidates=None, sv_candidates=None, events=None, sv_events=None):
     """Classify + report (_D, _SI, _TD, _INV) from per-read UP_Close / UP_Far points (CSR over
     all reads of the file, 12-byte pg_point records).  settings.analyze_li / settings.report_close_mapped
     add <out_prefix>_LI / <out_prefix>_CloseEndMapped, settings.report_interchromosomal <out_prefix>_INT and
@@ -464,7 +525,11 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
     insertions and tandem duplications are written from them, DI and the inversions from the per-read records; a window with an
     unresolved read takes the existing path (last_event_fallback_windows); the reports are the same bytes.  Or a dict {(chromosome
     index or name, win_start, win_end): tables} of tables built elsewhere over all reads (what Engine.events returns): a window
-    without an entry uses the host builder (last_event_windows lists the windows of a run)."""
+    without an entry uses the host builder (last_event_windows lists the windows of a run).  sv_events (needs
+    events): True -- DI and the inversions are written from their SV tables (sv_events_from_lists' function) instead of through
+    the reporters' own quadratic sorts; the reports are the same bytes.  Or a dict {window: tables} of SV tables built elsewhere
+    (what Engine.sv_events returns), used for the windows whose event tables are supplied too; tables that do not fit a window
+    are replaced by the host's own (last_sv_event_table_windows)."""
     L = lib()
     tmp_cfg = None
     if reads_config is not None and not isinstance(reads_config, (str, bytes, os.PathLike)):
@@ -506,8 +571,15 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
             if cands is None or sv_c is None:
                 raise ValueError("events: variant_candidates and sv_candidates are both needed")
             sup, keep_ev = _supplied_events(events, fasta, n)
-            rc = L.pgh_call_from_points_events(*args, cands.ctypes.data, counts.ctypes.data, sv_c.ctypes.data, sv_n.ctypes.data,
-                                               len(sup) if sup is not None else 0, sup)
+            if sv_events:
+                sv_sup, keep_sv = _supplied_sv_events(sv_events, fasta)
+                rc = L.pgh_call_from_points_sv_events(*args, cands.ctypes.data, counts.ctypes.data, sv_c.ctypes.data, sv_n.ctypes.data,
+                                                      len(sup) if sup is not None else 0, sup, len(sv_sup) if sv_sup is not None else 0, sv_sup)
+            else:
+                rc = L.pgh_call_from_points_events(*args, cands.ctypes.data, counts.ctypes.data, sv_c.ctypes.data, sv_n.ctypes.data,
+                                                   len(sup) if sup is not None else 0, sup)
+        elif sv_events:
+            raise ValueError("sv_events: the events path is needed (events=True or supplied tables)")
         elif variant_candidates is None and sv_candidates is None:
             rc = L.pgh_call_from_points(*args)
         elif sv_candidates is None:
@@ -549,6 +621,39 @@ def _supplied_events(events, fasta, n):
         arr[k] = SuppliedEvents(names.index(chrom) if isinstance(chrom, str) else int(chrom), int(ws), int(we), 0, reads.ctypes.data,
                                 members.ctypes.data, evs.ctypes.data, sz)
     return arr, keep
+
+
+class SuppliedSvEvents(C.Structure):
+    """pgh_supplied_sv_events: the SV tables of one window, built elsewhere over all reads of the run"""
+    _fields_ = [("chr", C.c_int32), ("win_start", C.c_uint32), ("win_end", C.c_uint32), ("reserved", C.c_uint32),
+                ("members", C.c_void_p), ("events", C.c_void_p), ("sizes", SvEventSizes)]
+
+
+def _supplied_sv_events(sv_events, fasta):
+    """the sv_events argument of call_from_points -> (array of SuppliedSvEvents or None, what must stay alive)"""
+    if sv_events is True or not isinstance(sv_events, dict):
+        return None, []
+    names = _fasta_names(fasta)
+    arr = (SuppliedSvEvents * len(sv_events))()
+    keep = []
+    for k, ((chrom, ws, we), t) in enumerate(sv_events.items()):
+        members = np.ascontiguousarray(t["members_flat"], dtype=np.uint32)
+        evs = np.ascontiguousarray(t["events_flat"], dtype=EVENT_DTYPE)
+        if len(members) != sum(t["n_members"]) or len(evs) != sum(t["n_events"]):
+            raise ValueError(f"sv_events: the tables of window {(chrom, ws, we)} do not fit their own sizes")
+        keep += [members, evs]
+        sz = SvEventSizes()
+        for q in range(SV_EVENT_TABLES):
+            sz.members[q], sz.events[q], sz.dropped_runs[q] = int(t["n_members"][q]), int(t["n_events"][q]), int(t["dropped_runs"][q])
+        arr[k] = SuppliedSvEvents(names.index(chrom) if isinstance(chrom, str) else int(chrom), int(ws), int(we), 0, members.ctypes.data,
+                                  evs.ctypes.data, sz)
+    return arr, keep
+
+
+def last_sv_event_table_windows():
+    """(windows whose DI and inversion reports were written from SV tables, of them from supplied tables) of the last
+    call_from_points(sv_events=...)"""
+    return int(lib().pgh_last_sv_event_table_windows()), int(lib().pgh_last_sv_event_supplied_windows())
 
 
 def last_event_fallback_windows():

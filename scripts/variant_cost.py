@@ -1,5 +1,5 @@
 """Measurement (one MI355X + its host): what the device classifiers (pg_variant_kernel; pg_sv_kernel, 7l; the events entry,
-7m) cost and what
+7m; the sv events entry, 7n) cost and what
 they take off the host.  On n synthetic 100-bp reads (all SV types, default parameters), searched on the GPU:
   * the kernel's HIP-event time, per batch and per read;
   * the host's `deletions` and `short insertions` laps of call_from_points (PGH_TIMING=1: the per-read stage plus the
@@ -10,6 +10,7 @@ they take off the host.  On n synthetic 100-bp reads (all SV types, default para
 Prints a markdown block (profiles/variant/README.md quotes it).
 
     python scripts/variant_cost.py [--reads 2000000] [--chr-len 40000000] [--parent-lib path/to/libpindel_host.so] [--dir /tmp/variant_cost]
+                                   [--device-only]      (the device stages alone: no host runs)
 """
 import argparse
 import ctypes as C
@@ -71,6 +72,7 @@ def main():
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--dir", default="/tmp/variant_cost")
     ap.add_argument("--child", default=None)
+    ap.add_argument("--device-only", action="store_true")
     a = ap.parse_args()
     if a.child:
         return child(a.child, a.dir, a.parent_lib)
@@ -123,6 +125,13 @@ def main():
         ev = eng.events_tensors(db, binding.EventWindow(0, 0xffffffff, 0, 0xffffffff, 1, 100, 1, 1), vt, svt)
         ev_ms.append(eng.last_stats()[0])
     ev_sorts = sum(1 for r in eng.launch_log() if r.kernel == binding.KERNEL_EVENT_SORT)
+    # the sv events stage over the records of that build: DI, INV and INV_NT
+    note("sv event tables on the GPU")
+    svev_ms = []
+    for _ in range(5):
+        svev = eng.sv_events_tensors(db, svt)
+        svev_ms.append(eng.last_stats()[0])
+    ev_reads = binding.events_from_tensors(ev)["reads"]
     del vt, svt
     res = eng.download(db)
     eng.free_device_batch(db)
@@ -153,6 +162,21 @@ def main():
     print(f"- events entry (cascade, sort, duplicates, events; lists and tables in device memory) {min(ev_ms):.3f} ms (best of 5; all: "
           f"{', '.join(f'{x:.3f}' for x in ev_ms)}) = {min(ev_ms) * 1e6 / n:.2f} ns per read; members per table {ev['n_members']}, events per table "
           f"{ev['n_events']}, unresolved reads {ev['unresolved']}, sort passes launched (of 17 key bytes) {ev_sorts}\n", flush=True)
+    # the largest box of the three kinds, from the records of the events build: what the sequential passes of one wave see
+    recs = ev_reads
+    sv_flat = np.asarray(sv_cands).reshape(n, binding.SV_SLOTS)
+    box = 0
+    for kind in binding.SV_EVENT_KINDS:
+        idx = np.nonzero(((recs["flags"] & binding.EVR_BOXED) != 0) & (recs["kind"] == kind))[0]
+        if len(idx):
+            left = sv_flat["bp_left"][idx, binding.SV_SLOT[kind] + recs["slot"][idx].astype(np.int64)]
+            box = max(box, int(np.bincount(left // max(len(ref) // 30000, 1)).max()))
+    print(f"- sv events entry (DI, INV, INV_NT: gather, segment and key sorts, record-shift passes per box, duplicates, runs, events; lists "
+          f"and tables in device memory) {min(svev_ms):.3f} ms (best of 5; all: {', '.join(f'{x:.3f}' for x in svev_ms)}) = "
+          f"{min(svev_ms) * 1e6 / n:.2f} ns per read, beside the events entry's {min(ev_ms):.3f} ms of the same run; members per table "
+          f"{svev['n_members']}, events per table {svev['n_events']}, dropped runs {svev['dropped_runs']}, largest box {box} reads\n", flush=True)
+    if a.device_only:
+        return
     modes = ["plain", "lists", "sv"] + (["parent"] if a.parent_lib else [])
     got = {}
     for m in modes:
