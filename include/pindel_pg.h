@@ -489,6 +489,74 @@ int  pg_device_batch_sv_event_sizes(pg_ctx *ctx, pg_device_batch *b, pg_sv_event
 int  pg_device_batch_sv_events_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *members, pg_event *events);
 int  pg_device_batch_sv_events_download_device(pg_ctx *ctx, pg_device_batch *b, uint32_t *d_members, pg_event *d_events);
 
+/* ---- device classifier: report records --------------------------------------------------------------------------
+ * What a report writer takes from the candidate lists and the points, per table member and per read, so that a caller who writes
+ * reports from the tables downloads neither.  A pure function of the two table builds the batch holds, the lists they were given
+ * and the batch's run lists.
+ *   pg_report_read     one per member of the seven member lists, in order: tables 0..3 of the events build, then SV tables 0..2 of
+ *                      the sv build; record i belongs to member i.
+ *   pg_report_summary  one per read of the batch: what the pipeline and process_window read of the points for every read. */
+#define PG_RR_DUP 0x1u               /* pg_report_read::flags: the member word carries PG_SVEV_MEMBER_DUP (SV tables 1 and 2)   */
+#define PG_RR_DI  0x2u               /* ... table 2 (TD): the read's DI list holds a pair; di_bp / di_nt_rot are that pair's    */
+typedef struct {
+    uint32_t read;                   /* the member: a read index of the batch                                                  */
+    pg_variant_cand cand;            /* the pair (kind, slot) the read's pg_event_read names, copied from the lists            */
+    uint16_t nt_size;                /* the carried NT_size (pg_event_read::nt_size)                                           */
+    uint8_t  table;                  /* 0..3: the events build's tables; 4..6: SV tables 0..2                                  */
+    uint8_t  flags;                  /* PG_RR_*                                                                                */
+    int16_t  bp0;                    /* table 1: (short)(LengthStr - 1) of close point cand.close_idx for a '+' anchor, of far
+                                      * point cand.far_idx otherwise: NT_str is cut from the read behind it.  0 for other tables */
+    int16_t  di_bp;                  /* with PG_RR_DI: bp and nt_rot of the DI pair (TD's NT_str is DI's); 0 otherwise         */
+    int32_t  di_nt_rot;
+} pg_report_read;                    /* 48 bytes, no padding                                                                   */
+#define PG_RS_CLOSE          0x1u    /* pg_report_summary::flags: the read has a close end                                     */
+#define PG_RS_FAR            0x2u    /* ... a far end                                                                          */
+#define PG_RS_FAR_ANTISENSE  0x4u    /* ... whose first point (UP_Far[0]) has Strand ANTISENSE                                 */
+#define PG_RS_CLOSE_LEFT     0x8u    /* both ends: UP_Close[0].AbsLoc < UP_Far[0].AbsLoc (the inversion writer orients the read by it) */
+#define PG_RS_CLOSE_RIGHT    0x10u   /* both ends: UP_Close[0].AbsLoc > UP_Far[0].AbsLoc                                       */
+typedef struct {
+    uint32_t close_abs;              /* UP_Close.back().AbsLoc (0 without a close end)                                         */
+    int16_t  close_len;              /* UP_Close.back().LengthStr (0 without)                                                  */
+    int16_t  far_chr;                /* UP_Far[0]'s chromosome (0 without a far end)                                           */
+    uint8_t  flags;                  /* PG_RS_*                                                                                */
+    uint8_t  rc_flag;                /* pg_result_view::rc_flag                                                                */
+    uint16_t reserved;               /* 0                                                                                      */
+} pg_report_summary;                 /* 12 bytes                                                                               */
+typedef struct {
+    uint64_t records;                /* pg_report_read records: the members of all seven tables                                */
+    uint64_t reads;                  /* pg_report_summary records: the reads of the batch                                      */
+} pg_report_sizes;
+/* Builds both and keeps them with the batch (a new events or sv events build drops them; freed with the batch).  cands / counts and
+ * sv_cands / sv_counts: the lists the two table builds were given (host memory; the _device sibling: device memory under the rules
+ * of "device buffers in and out").  Refused with nothing launched (PG_E_INVALID): a batch that holds no events build or no sv events
+ * build, a null list array for a non-empty batch.  n_reads == 0 and "no members" are valid.  A member whose read, kind or slot lies
+ * outside the batch or its lists gets a zeroed record.  Synchronous; pg_last_search_stats then reports the HIP-event time.
+ * download: records = pg_report_sizes::records records, summaries = n_reads; either may be NULL. */
+int  pg_device_batch_report_reads(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *cands, const uint8_t *counts,
+                                  const pg_variant_cand *sv_cands, const uint8_t *sv_counts);
+int  pg_device_batch_report_reads_device(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *d_cands, const uint8_t *d_counts,
+                                         const pg_variant_cand *d_sv_cands, const uint8_t *d_sv_counts);
+int  pg_device_batch_report_sizes(pg_ctx *ctx, pg_device_batch *b, pg_report_sizes *sizes);
+int  pg_device_batch_report_download(pg_ctx *ctx, pg_device_batch *b, pg_report_read *records, pg_report_summary *summaries);
+int  pg_device_batch_report_download_device(pg_ctx *ctx, pg_device_batch *b, pg_report_read *d_records, pg_report_summary *d_summaries);
+
+/* One call per window on a searched batch: the two candidate kernels, the events build, the sv events build and the report records.
+ * The candidate lists stay in device memory owned by the batch (a later classify of the batch overwrites them; freed with it): no
+ * list crosses to the host.  The tables, records and summaries are then delivered by the size and download entries above.
+ *   max_listed  0..PG_VARIANT_CANDS.  Below PG_VARIANT_CANDS every list with more than max_listed pairs is cut: its count byte
+ *               becomes max_listed | PG_VARIANT_MORE (the records behind stay; nothing reads them).  A read whose cut list did not
+ *               make it Used is then PG_EVR_UNRESOLVED: with 0, every read that reaches a list with a pair.
+ * name_id: host memory, NULL or one uint32 per read as for pg_device_batch_events.  The refusals are those of the five stages,
+ * checked before anything is launched.  pg_last_search_stats then reports the sum of the stages' HIP-event times, the cut's
+ * included.  The launch log gets the stages' own records; the cut is logged as the report kernels' id with `blocks` 0. */
+typedef struct {
+    pg_event_window window;
+    pg_sv_params    sv;
+    int32_t         max_listed;      /* PG_VARIANT_CANDS: no cut                                                               */
+    int32_t         reserved;        /* 0                                                                                      */
+} pg_classify_params;
+int  pg_device_batch_classify(pg_ctx *ctx, pg_device_batch *b, const pg_classify_params *p, const uint32_t *name_id);
+
 /* -q (dispersed duplications): per item i, contains_subseq_any_strand(query_i, window_i, 15) of Pindel's MEI search
  * (src/search_MEI_util.cpp:188-351, bit-exact), where query_i = query[query_off[i] .. query_off[i+1]) (at most
  * PG_MAX_READ_LEN bases) and window_i = the loaded chromosome chr_id[i] at padded (AbsLoc) positions

@@ -129,6 +129,24 @@ KERNEL_SV_EVENTS = 9                    # launch-log id after the three of the e
 SVEV_LDS_BOX = 640                      # PG_SVEV_LDS_BOX: reads of a box the order kernel keeps in LDS
 
 
+# report records (Engine.report_reads): pg_report_read per member of the seven member lists (tables 0..3 of the
+# events build, then SV tables 0..2), pg_report_summary per read
+REPORT_TABLES = EVENT_TABLES + SV_EVENT_TABLES
+RR_DUP, RR_DI = 1, 2
+RS_CLOSE, RS_FAR, RS_FAR_ANTISENSE, RS_CLOSE_LEFT, RS_CLOSE_RIGHT = 1, 2, 4, 8, 16
+KERNEL_REPORT = 10                      # launch-log id of the report kernels (blocks 0: the list cut of classify)
+REPORT_READ_DTYPE = np.dtype([("read", "<u4"), ("cand", VARIANT_CAND_DTYPE), ("nt_size", "<u2"), ("table", "u1"), ("flags", "u1"),
+                              ("bp0", "<i2"), ("di_bp", "<i2"), ("di_nt_rot", "<i4")], align=True)
+REPORT_SUMMARY_DTYPE = np.dtype([("close_abs", "<u4"), ("close_len", "<i2"), ("far_chr", "<i2"), ("flags", "u1"), ("rc_flag", "u1"),
+                                 ("reserved", "<u2")], align=True)
+assert REPORT_READ_DTYPE.itemsize == 48 and REPORT_SUMMARY_DTYPE.itemsize == 12
+
+
+class ReportSizes(C.Structure):
+    """pg_report_sizes"""
+    _fields_ = [("records", C.c_uint64), ("reads", C.c_uint64)]
+
+
 class EventWindow(C.Structure):
     """pg_event_window"""
     _fields_ = [("chr_id", C.c_int32), ("win_end", C.c_uint32), ("region_start", C.c_uint32), ("region_end", C.c_uint32),
@@ -144,6 +162,11 @@ class SvEventSizes(C.Structure):
     """pg_sv_event_sizes"""
     _fields_ = [("members", C.c_uint64 * SV_EVENT_TABLES), ("events", C.c_uint64 * SV_EVENT_TABLES),
                 ("dropped_runs", C.c_uint64 * SV_EVENT_TABLES)]
+
+
+class ClassifyParams(C.Structure):
+    """pg_classify_params"""
+    _fields_ = [("window", EventWindow), ("sv", SvParams), ("max_listed", C.c_int32), ("reserved", C.c_int32)]
 
 
 def event_window(window):
@@ -177,7 +200,9 @@ EXPORTS = [
     "pg_device_batch_events", "pg_device_batch_events_device", "pg_device_batch_event_sizes",
     "pg_device_batch_events_download", "pg_device_batch_events_download_device",
     "pg_device_batch_sv_events", "pg_device_batch_sv_events_device", "pg_device_batch_sv_event_sizes",
-    "pg_device_batch_sv_events_download", "pg_device_batch_sv_events_download_device"]
+    "pg_device_batch_sv_events_download", "pg_device_batch_sv_events_download_device",
+    "pg_device_batch_report_reads", "pg_device_batch_report_reads_device", "pg_device_batch_report_sizes",
+    "pg_device_batch_report_download", "pg_device_batch_report_download_device", "pg_device_batch_classify"]
 
 
 def build(force: bool = False) -> str:
@@ -283,6 +308,12 @@ def lib():
     L.pg_device_batch_sv_event_sizes.argtypes = [vp, vp, vp]
     L.pg_device_batch_sv_events_download.argtypes = [vp] * 4
     L.pg_device_batch_sv_events_download_device.argtypes = [vp] * 4
+    L.pg_device_batch_report_reads.argtypes = [vp] * 6
+    L.pg_device_batch_report_reads_device.argtypes = [vp] * 6
+    L.pg_device_batch_report_sizes.argtypes = [vp, vp, vp]
+    L.pg_device_batch_report_download.argtypes = [vp] * 4
+    L.pg_device_batch_report_download_device.argtypes = [vp] * 4
+    L.pg_device_batch_classify.argtypes = [vp] * 4
     _lib = L
     return L
 
@@ -922,6 +953,99 @@ class Engine:
                                                                       out["events"].data_ptr() if sum(ne) else None))
         out.update(n_members=nm, n_events=ne, dropped_runs=dropped)
         return out
+
+    def report_sizes(self, dbatch):
+        """pg_device_batch_report_sizes: (report records, reads) of the records built last."""
+        sz = ReportSizes()
+        self._check(self._L.pg_device_batch_report_sizes(self._h, dbatch, C.addressof(sz)))
+        return int(sz.records), int(sz.reads)
+
+    def report_download(self, dbatch):
+        """pg_device_batch_report_download: (records, summaries) -- REPORT_READ_DTYPE per member of the seven member lists in order
+        (tables 0..3 of the events build, then SV tables 0..2), REPORT_SUMMARY_DTYPE per read."""
+        nr, n = self.report_sizes(dbatch)
+        records = np.zeros(nr, dtype=REPORT_READ_DTYPE)
+        summaries = np.zeros(n, dtype=REPORT_SUMMARY_DTYPE)
+        self._check(self._L.pg_device_batch_report_download(self._h, dbatch, records.ctypes.data if nr else None,
+                                                            summaries.ctypes.data if n else None))
+        return records, summaries
+
+    def report_reads(self, dbatch, variant, sv):
+        """Report records of a batch that holds an events build and an sv events build (pg_device_batch_report_reads):
+        per table member the pair its read's record names, the carried NT_size and the few point-derived values the report writers
+        need; per read a summary of its close and far end.  variant / sv: the (cands, counts) pairs the two builds were given.
+        Returns report_download(dbatch)."""
+        n = self._batch_n[dbatch.value]
+        vc = np.ascontiguousarray(variant[0], dtype=VARIANT_CAND_DTYPE)
+        vn = np.ascontiguousarray(variant[1], dtype=np.uint8)
+        sc = np.ascontiguousarray(sv[0], dtype=VARIANT_CAND_DTYPE)
+        sn = np.ascontiguousarray(sv[1], dtype=np.uint8)
+        if vc.size != n * 2 * VARIANT_CANDS or vn.size != n * 2 or sc.size != n * SV_SLOTS or sn.size != n * SV_KINDS:
+            raise ValueError(f"report_reads: lists of another size than {n} reads give")
+        self._check(self._L.pg_device_batch_report_reads(self._h, dbatch, vc.ctypes.data if n else None, vn.ctypes.data if n else None,
+                                                         sc.ctypes.data if n else None, sn.ctypes.data if n else None))
+        return self.report_download(dbatch)
+
+    def report_tensors(self, dbatch):
+        """report_download into tensors on this engine's device (pg_device_batch_report_download_device): records uint8[total, 48],
+        summaries uint8[n, 12]."""
+        torch, dev = self._torch_ready()
+        nr, n = self.report_sizes(dbatch)
+        out = dict(records=torch.empty((nr, 48), dtype=torch.uint8, device=dev), summaries=torch.empty((n, 12), dtype=torch.uint8, device=dev))
+        self._check(self._L.pg_device_batch_report_download_device(self._h, dbatch, out["records"].data_ptr() if nr else None,
+                                                                   out["summaries"].data_ptr() if n else None))
+        return out
+
+    def report_reads_tensors(self, dbatch, variant, sv):
+        """report_reads with everything staying on the GPU (pg_device_batch_report_reads_device and its download sibling): variant /
+        sv are the dicts variant_candidates_tensors / sv_candidates_tensors return (or (cands, counts) tensor pairs).  Returns
+        report_tensors(dbatch)."""
+        _, dev = self._torch_ready()
+        n = self._batch_n[dbatch.value]
+        ptrs = []
+        for x, widths in ((variant, (2 * VARIANT_CANDS * 32, 2)), (sv, (SV_SLOTS * 32, SV_KINDS))):
+            c, k = (x["cands"], x["counts"]) if isinstance(x, dict) else x
+            for name, t, width in (("cands", c, widths[0]), ("counts", k, widths[1])):
+                if str(t.dtype) != "torch.uint8" or tuple(t.shape) != (n, width) or not t.is_contiguous() or str(t.device) != dev:
+                    raise ValueError(f"report_reads: {name}: a contiguous uint8[{n}, {width}] tensor on {dev} is expected")
+                ptrs.append(t.data_ptr() if n else None)
+        self._check(self._L.pg_device_batch_report_reads_device(self._h, dbatch, *ptrs))
+        return self.report_tensors(dbatch)
+
+    def classify(self, dbatch, window, settings=None, max_listed=VARIANT_CANDS, name_id=None):
+        """One call per window on a searched device batch (pg_device_batch_classify): both candidate kernels, the events build, the
+        sv events build and the report records; the candidate lists stay on the GPU.  window: see event_window(); settings: see
+        sv_params(); max_listed: lists longer than this are cut and marked VARIANT_MORE; name_id: None or uint32 per read.
+        The tables and records are then delivered by events_download / sv_events_download / report_download."""
+        n = self._batch_n[dbatch.value]
+        prm = ClassifyParams(event_window(window), sv_params(settings), int(max_listed), 0)
+        nid = None
+        if name_id is not None:
+            nid = np.ascontiguousarray(name_id, dtype=np.uint32)
+            if nid.size != n:
+                raise ValueError(f"classify: name_id: {n} entries are expected, got {nid.size}")
+        self._check(self._L.pg_device_batch_classify(self._h, dbatch, C.addressof(prm), nid.ctypes.data if nid is not None and n else None))
+
+    def events_download(self, dbatch):
+        """The event tables the batch holds (pg_device_batch_event_sizes / _events_download) as the dict events() returns."""
+        n = self._batch_n[dbatch.value]
+        nm, ne, unresolved = self.event_sizes(dbatch)
+        reads = np.zeros(n, dtype=EVENT_READ_DTYPE)
+        members = np.zeros(sum(nm), dtype=np.uint32)
+        events = np.zeros(sum(ne), dtype=EVENT_DTYPE)
+        self._check(self._L.pg_device_batch_events_download(self._h, dbatch, reads.ctypes.data if n else None,
+                                                            members.ctypes.data if members.size else None,
+                                                            events.ctypes.data if events.size else None))
+        return _event_tables(reads, members, events, nm, ne, unresolved)
+
+    def sv_events_download(self, dbatch):
+        """The SV tables the batch holds (pg_device_batch_sv_event_sizes / _sv_events_download) as the dict sv_events() returns."""
+        nm, ne, dropped = self.sv_event_sizes(dbatch)
+        members = np.zeros(sum(nm), dtype=np.uint32)
+        events = np.zeros(sum(ne), dtype=EVENT_DTYPE)
+        self._check(self._L.pg_device_batch_sv_events_download(self._h, dbatch, members.ctypes.data if members.size else None,
+                                                               events.ctypes.data if events.size else None))
+        return _sv_event_tables(members, events, nm, ne, dropped)
 
     def set_windows(self, dbatch, bd=None, bd_off=None):
         """Per-read BreakDancer window clusters for a device-resident batch (None detaches them)."""

@@ -30,6 +30,8 @@ struct CliOptions {
     bool detect_dd = false;                // -q
     std::string gpu_list;                  // -G as typed
     std::vector<int> devices;              // ... and as parsed; without -G, prm.device alone
+    bool device_classifier = false;        // --device-classifier: windows are classified on the device and written from tables
+    int device_classifier_listed = -1;     // --device-classifier-listed 0..4: pg_classify_params::max_listed (-1: not given, no cut)
 };
 
 // A flag's word as the parser hands it to the row: as typed, as a number (kinds i and f), as a switch's state (kind u)
@@ -123,7 +125,34 @@ static const CliFlag CLI_FLAGS[] = {
     { "", "--MIN_DD_MAP_DISTANCE", 'i', PG_CLI_SET(o.dd.min_map_distance = (int)a.i) },
     { "", "--DD_REPORT_DUPLICATION_READS", 'u', PG_CLI_SET(o.dd.report_dup_reads = a.on) },
 };
+// The flags of the device classifier, a table of their own that parse_cli walks when no row of CLI_FLAGS matches
+static const CliFlag CLI_DEVICE_FLAGS[] = {
+    { "", "--device-classifier", 'u', PG_CLI_SET(o.device_classifier = a.on) },
+    { "", "--device-classifier-listed", 'i', [](CliOptions &o, const CliArg &a, std::string &err) {
+         if (a.i < 0 || a.i > PG_VARIANT_CANDS) {
+             err = "--device-classifier-listed takes a number of pairs from 0 to 4";
+             return false;
+         }
+         o.device_classifier_listed = (int)a.i;
+         return true;
+     } },
+};
 #undef PG_CLI_SET
+
+// What --device-classifier does not deliver yet: "" or the refusal, looked at after the last flag
+inline std::string device_classifier_refusal(const CliOptions &o)
+{
+    if (!o.device_classifier)
+        return o.device_classifier_listed >= 0 ? "--device-classifier-listed needs --device-classifier" : "";
+    const char *with = o.S.Analyze_LI ? "-l" : o.S.report_close_mapped ? "-s" : o.S.only_close_mapped ? "-S" : o.S.report_interchromosomal ? "-I"
+                     : o.detect_dd ? "-q" : o.S.NormalSamples ? "-N" : nullptr;
+    if (with) return std::string("--device-classifier cannot be combined with ") + with + ": its report needs points or pairs this path does not deliver";
+    if (o.use_bd) return "--device-classifier cannot be combined with --bd-hints on: window hints are not searched on this path";
+    if (!o.bam_config.empty() && o.search_rp)
+        return "--device-classifier with BAM input needs -R false: read-pair window hints are not searched on this path";
+    if (o.devices.size() > 1) return "--device-classifier runs on one device: give -G a single device";
+    return "";
+}
 
 // -G 0,1,...: numbers >= 0 separated by single commas; one comma may end the list.  false: not such a list, or empty
 inline bool parse_device_list(const std::string &list, std::vector<int> &devices)
@@ -148,6 +177,9 @@ inline int parse_cli(int argc, char **argv, CliOptions &o, std::string &err)
         const CliFlag *fl = nullptr;
         for (const CliFlag &x : CLI_FLAGS)
             if ((x.sh[0] && f == x.sh) || f == x.lg) fl = &x;
+        if (!fl)
+            for (const CliFlag &x : CLI_DEVICE_FLAGS)
+                if (f == x.lg) fl = &x;
         if (!fl) {
             err = "unknown argument: " + f;
             return 2;
@@ -188,6 +220,8 @@ inline int parse_cli(int argc, char **argv, CliOptions &o, std::string &err)
         err = "bad device list " + o.gpu_list;
         return 2;
     }
+    err = device_classifier_refusal(o);
+    if (!err.empty()) return 2;
     return 0;
 }
 

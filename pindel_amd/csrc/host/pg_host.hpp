@@ -71,6 +71,9 @@ struct SplitRead {                // the SPLIT_READ fields used downstream, src/
     unsigned short NT_size_2 = 0;
     bool UniqueRead = false, Used = false;
     int LeftMostPos = 0;
+    // the tables path, whose reads have no points: the sign of UP_Close[0].AbsLoc - UP_Far[0].AbsLoc, from the
+    // read's pg_report_summary (OutputInversions orients the read by it)
+    signed char CloseVsFar = 0;
     int chr_id = -1;
     std::map<std::string, unsigned> SampleName2Number;
     // The device classifier's lists for this read (pg_variant_cand, pindel_pg.h): 2 kinds x PG_VARIANT_CANDS records and the 2 count
@@ -207,6 +210,10 @@ struct Settings {                 // the flags the downstream steps read (src/fn
     // supplied_sv_events: tables built elsewhere, used for a window whose event tables were supplied too.
     bool use_sv_events = false;
     std::vector<SuppliedSvEvents> supplied_sv_events;
+    // ... and, with both of the above: builds the report records and summaries of the window, replaces its reads by
+    // copies without points, lists and pair fields, and writes the reports from tables, records and summaries alone
+    // (Caller::process_window_tables).
+    bool use_report_reads = false;
 };
 
 // What the events path of the last run did.  windows: six values per window process_window saw with use_events set -- chromosome
@@ -217,6 +224,8 @@ struct EventPathStats {
     uint64_t supplied_windows = 0;       // ... of them, from supplied tables
     uint64_t sv_table_windows = 0;       // windows whose DI and inversion reports were written from SV tables
     uint64_t sv_supplied_windows = 0;    // ... of them, from supplied SV tables
+    uint64_t report_windows = 0;         // windows written by process_window_tables, from records and summaries
+    uint64_t report_records = 0;         // ... and the records they took
     std::vector<uint32_t> windows;
 };
 EventPathStats &event_path_stats();
@@ -300,6 +309,18 @@ public:
     // --repair inv-pairs: the same-chromosome discordant pairs of the window that process_window is called for next
     // (all BAMs of the run); the inversion reporter's verdict is a function of the event and this list alone
     void set_window_pairs(std::vector<DiscordantPair> pairs) { inv_pairs_ = std::move(pairs); }
+    // The tables path for a caller whose window was classified on the device: `reads` are ALL reads of the window as
+    // loaded, in the order of the device batch -- no points, no lists, no pair field set.
+    //   apply_summaries             per read: rc_flag applied to UnmatchedSeq (read_length_follows: ReadLength becomes its length, as
+    //                               the BAM pipeline does), then what note_close_mapped and UpdateFarFragName take from the points
+    //   process_window_from_tables  process_window's frame around process_window_tables: the tables as the download entries yield
+    //                               them (members per table in n_members, events back to back in table order), the report records
+    //                               and the summaries.  summaries_applied: apply_summaries has been called on these reads already.
+    void apply_summaries(std::vector<SplitRead> &reads, const pg_report_summary *summaries, bool read_length_follows);
+    void process_window_from_tables(const Chromosome &chrom, std::vector<SplitRead> &reads, unsigned win_start, unsigned win_end,
+                                    unsigned region_start, unsigned region_end, const pg_event_read *recs, const pg_event_sizes &sizes,
+                                    const pg_event *events, const pg_sv_event_sizes &sv_sizes, const pg_event *sv_events,
+                                    const pg_report_read *records, const pg_report_summary *summaries, bool summaries_applied);
     ~Caller();
 
 private:
@@ -375,6 +396,18 @@ private:
     std::vector<DiscordantPair> inv_pairs_;
     // the events path (pg_host_events.cpp): false = the window has to go through the existing path
     bool process_window_events(Ctx &c);
+    // one table / one SV table written in table order, shared by the events path and the tables path: make_good fills `good` -- the
+    // table's members with their pairs applied -- and is called only if an event is flagged PG_EV_REPORT
+    typedef std::function<void(std::vector<SplitRead> &)> MakeGood;
+    void write_event_table(Ctx &c, int t, const std::vector<pg_event> &events, const MakeGood &make_good);
+    void write_sv_event_table(Ctx &c, int t, const std::vector<pg_event> &events, const MakeGood &make_good);
+    // the tables path: the window's reads as loaded -- no points, no lists, no pair field set -- and the event tables
+    // (recs: per read; n_members: the seven member lists' sizes; events / sv_events: per table), the report records (one per
+    // member, in order) and the summaries (per read; rc_flag is applied to the read here).  What note_close_mapped_all, the
+    // UpdateFarFragName loop and process_window_events do, from those inputs alone, with the same output_* calls in the same order.
+    void process_window_tables(Ctx &c, const pg_event_read *recs, const uint64_t *n_members, const std::vector<pg_event> *events,
+                               const std::vector<pg_event> *sv_events, const pg_report_read *records, const pg_report_summary *summaries,
+                               bool summaries_applied = false);
     void collect_interchr(const std::vector<SplitRead> &reads);
     void report_interchr();
 };

@@ -17,6 +17,7 @@
 #include "pg_depth.hpp"
 #include "pg_host.hpp"
 #include "pg_host_events.hpp"
+#include "pg_host_report.hpp"
 #include "pg_host_sv_events.hpp"
 #include "pg_host_priv.hpp"
 #include "pg_pipeline.hpp"
@@ -77,7 +78,7 @@ static int call_from_points(const char *fasta_path, const char *reads_path, cons
                             const pg_variant_cand *var_cands, const uint8_t *var_counts,
                             const pg_variant_cand *sv_cands = nullptr, const uint8_t *sv_counts = nullptr, bool use_events = false,
                             const std::vector<SuppliedEvents> *supplied = nullptr, bool use_sv_events = false,
-                            const std::vector<SuppliedSvEvents> *supplied_sv = nullptr)
+                            const std::vector<SuppliedSvEvents> *supplied_sv = nullptr, bool use_report_reads = false)
 {
     std::vector<Chromosome> genome;
     if (load_fasta(fasta_path, genome, st->spacer, g_err)) return -1;
@@ -107,6 +108,7 @@ static int call_from_points(const char *fasta_path, const char *reads_path, cons
     if (supplied) S.supplied_events = *supplied;
     S.use_sv_events = use_sv_events;
     if (supplied_sv) S.supplied_sv_events = *supplied_sv;
+    S.use_report_reads = use_report_reads;
     event_path_stats() = EventPathStats();
     if (S.repairs & ~(uint32_t)REPAIR_ALL) {
         g_err = "unknown bits in the repairs field";
@@ -305,6 +307,27 @@ int pgh_call_from_points_sv_events(const char *fasta_path, const char *reads_pat
     return call_from_points(fasta_path, reads_path, out_prefix, st, n_reads, close_off, close_pts, far_off, far_pts, rc_flag, var_cands, var_counts,
                             sv_cands, sv_counts, true, &supplied, true, &supplied_sv);
 }
+/*
+ * pgh_call_from_points_sv_events with the tables path switched on: per window the host statements build lists ->
+ * tables -> report records -> summaries, the window's reads are replaced by copies without points, lists and pair fields, and
+ * Caller::process_window_tables writes the reports from tables, records and summaries alone.  A window with an unresolved read, or
+ * whose tables do not fit, takes the existing path and is counted, as before.  The reports are the bytes pgh_call_from_points writes.
+ */
+int pgh_call_from_points_report_reads(const char *fasta_path, const char *reads_path, const char *out_prefix, const pgh_settings *st,
+                                      uint32_t n_reads, const uint64_t *close_off, const pg_point *close_pts, const uint64_t *far_off,
+                                      const pg_point *far_pts, const uint8_t *rc_flag, const pg_variant_cand *var_cands, const uint8_t *var_counts,
+                                      const pg_variant_cand *sv_cands, const uint8_t *sv_counts)
+{
+    if (!var_cands || !var_counts || !sv_cands || !sv_counts) {
+        g_err = "pgh_call_from_points_report_reads: the lists of both device classifiers are needed";
+        return -1;
+    }
+    return call_from_points(fasta_path, reads_path, out_prefix, st, n_reads, close_off, close_pts, far_off, far_pts, rc_flag, var_cands, var_counts,
+                            sv_cands, sv_counts, true, nullptr, true, nullptr, true);
+}
+/* windows of the last run written by process_window_tables, and the report records they took */
+uint64_t pgh_last_report_windows(void) { return event_path_stats().report_windows; }
+uint64_t pgh_last_report_records(void) { return event_path_stats().report_records; }
 /* windows of the last run whose DI and inversion reports came from SV tables / ... from supplied SV tables */
 uint64_t pgh_last_sv_event_table_windows(void) { return event_path_stats().sv_table_windows; }
 uint64_t pgh_last_sv_event_supplied_windows(void) { return event_path_stats().sv_supplied_windows; }
@@ -642,6 +665,60 @@ int pgh_sv_events_from_lists(int32_t n_chr, const char *const *chr_seq, const ui
         m += tabs.members[t].size();
         e += tabs.events[t].size();
     }
+    return 0;
+}
+
+/*
+ * Report records from tables, lists and points (pindel_pg.h "report records"), on the host: the plain-loop statement
+ * (pg_host_report.hpp) the device entry pg_device_batch_report_reads is compared with, byte for byte.  strand, rc_flag and the
+ * points as pgh_events_from_lists takes them; recs, ev_members / ev_sizes and sv_members / sv_sizes: the per-read records and the
+ * member lists of the two table builds, back to back as they are downloaded; cands, sv_cands, sv_counts: the lists they were given.
+ * out_records: room for every member of the seven lists; out_summaries: n_reads; sizes: what was filled.  -1: a null array.
+ */
+int pgh_report_reads_from_lists(uint32_t n_reads, const uint8_t *strand, const uint8_t *rc_flag, const uint64_t *close_off,
+                                const pg_point *close_pts, const uint64_t *far_off, const pg_point *far_pts, const pg_event_read *recs,
+                                const uint32_t *ev_members, const pg_event_sizes *ev_sizes, const uint32_t *sv_members,
+                                const pg_sv_event_sizes *sv_sizes, const pg_variant_cand *cands, const pg_variant_cand *sv_cands,
+                                const uint8_t *sv_counts, pg_report_read *out_records, pg_report_summary *out_summaries, pg_report_sizes *sizes)
+{
+    if (!ev_sizes || !sv_sizes || !sizes || (n_reads && (!strand || !rc_flag || !close_off || !far_off || !recs || !cands || !sv_cands || !sv_counts))) {
+        g_err = "pgh_report_reads_from_lists: null array";
+        return -1;
+    }
+    std::vector<UniquePoint> close(n_reads ? (size_t)close_off[n_reads] : 0), far(n_reads ? (size_t)far_off[n_reads] : 0);
+    for (size_t q = 0; q < close.size(); q++) close[q] = to_unique_point(close_pts[q]);
+    for (size_t q = 0; q < far.size(); q++) far[q] = to_unique_point(far_pts[q]);
+    std::vector<ReportReadIn> in(n_reads);
+    for (uint32_t i = 0; i < n_reads; i++) {
+        ReportReadIn &r = in[i];
+        r.plus = strand[i] == '+';
+        r.rc_flag = rc_flag[i];
+        r.close = close.data() + close_off[i];
+        r.n_close = (size_t)(close_off[i + 1] - close_off[i]);
+        r.far = far.data() + far_off[i];
+        r.n_far = (size_t)(far_off[i + 1] - far_off[i]);
+        r.var = cands + (size_t)i * 2 * PG_VARIANT_CANDS;
+        r.sv = sv_cands + (size_t)i * PG_SV_SLOTS;
+        r.sv_counts = sv_counts + (size_t)i * PG_SV_KINDS;
+    }
+    std::vector<uint32_t> evm[PG_EVENT_TABLES], svm[PG_SV_EVENT_TABLES];
+    size_t m = 0;
+    for (int t = 0; t < PG_EVENT_TABLES; t++) {
+        if (ev_sizes->members[t]) evm[t].assign(ev_members + m, ev_members + m + ev_sizes->members[t]);
+        m += ev_sizes->members[t];
+    }
+    m = 0;
+    for (int t = 0; t < PG_SV_EVENT_TABLES; t++) {
+        if (sv_sizes->members[t]) svm[t].assign(sv_members + m, sv_members + m + sv_sizes->members[t]);
+        m += sv_sizes->members[t];
+    }
+    std::vector<pg_report_read> records;
+    std::vector<pg_report_summary> summaries;
+    report_reads_from_lists(in, recs, evm, svm, records, summaries);
+    if (!records.empty()) memcpy(out_records, records.data(), records.size() * sizeof(pg_report_read));
+    if (n_reads) memcpy(out_summaries, summaries.data(), (size_t)n_reads * sizeof(pg_report_summary));
+    sizes->records = records.size();
+    sizes->reads = n_reads;
     return 0;
 }
 

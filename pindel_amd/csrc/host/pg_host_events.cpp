@@ -5,11 +5,13 @@
 // the per-read records and keep their own reporters (their exchange sorts are strict: no stable sort reproduces their tie order)
 // -- or, with Settings::use_sv_events, are written from their SV tables (pg_host_sv_events.hpp) in the same places.
 // The reports must be the bytes of the existing path: that is what pins pg_host_events.hpp to the reference's gold reports.
+#include <cctype>
 #include <unordered_map>
 
 #include "pg_depth.hpp"
 #include "pg_host_events.hpp"
 #include "pg_host_priv.hpp"
+#include "pg_host_report.hpp"
 #include "pg_host_sv_events.hpp"
 
 namespace pgh {
@@ -61,6 +63,218 @@ static bool sv_tables_from_supplied(const SuppliedSvEvents &e, const SuppliedEve
         e0 += ne;
     }
     return true;
+}
+
+// one table written in table order: the order of the boxes, and of the events within each
+void Caller::write_event_table(Ctx &c, int t, const std::vector<pg_event> &events, const MakeGood &make_good)
+{
+    const int kind = event_kind_of(t);
+    bool any = false;
+    for (const pg_event &ev : events) any = any || (ev.flags & PG_EV_REPORT);
+    if (!any) return;
+    std::vector<SplitRead> good;
+    make_good(good);
+    for_boxes(1, [&](unsigned) {
+        for (const pg_event &ev : events) {
+            if (!(ev.flags & PG_EV_REPORT)) continue;
+            const unsigned s = ev.first, e = ev.first + ev.n_reads - 1;
+            if (kind == 0) output_deletion(c, good, s, e, ev.real_start, ev.real_end);
+            else if (kind == 1) output_si(c, good, s, e, ev.real_start, ev.real_end);
+            else {
+                // IsGoodTD's -N test (sort_output_td), with GoodIndels[0] = the first unique read of the event's box
+                if (S.germline_filter() && ev.real_end - ev.real_start >= (unsigned)(good[ev.box_head].getReadLength() * 2)) {
+                    std::set<std::string> tags;
+                    for (unsigned i = s; i <= e; i++) tags.insert(good[i].Tag);
+                    if (!S.germline->good_td(c.chrom->name, (int64_t)c.chrom->seq.size() - 2 * (int64_t)S.spacer, ev.real_start, ev.real_end, tags))
+                        continue;
+                }
+                output_td(c, good, s, e, ev.real_start, ev.real_end);
+            }
+        }
+    });
+}
+
+// one SV table written: the reporters' output_* for the events flagged PG_EV_REPORT, the inversions' runs harmonised first
+void Caller::write_sv_event_table(Ctx &c, int t, const std::vector<pg_event> &events, const MakeGood &make_good)
+{
+    const int kind = sv_event_kind_of(t);
+    bool any = false;
+    for (const pg_event &ev : events) any = any || (ev.flags & PG_EV_REPORT);
+    if (!any) return;
+    std::vector<SplitRead> good;
+    make_good(good);
+    for_boxes(1, [&](unsigned) {
+        for (const pg_event &ev : events) {
+            if (!(ev.flags & PG_EV_REPORT)) continue;
+            const unsigned s = ev.first, e = ev.first + ev.n_reads - 1;
+            if (kind == PG_SV_DI) {
+                if (ev.flags & PG_EV_SHORT_INV) output_short_inv(c, good, s, e);
+                else output_di(c, good, s, e);
+                continue;
+            }
+            // the run harmonised from the event's IndelSize, as sort_output_inv's harmonise() leaves its members
+            for (unsigned i = s; i <= e; i++) {
+                SplitRead &r = good[i];
+                const unsigned mx = ev.indel_size;
+                const short diff = (short)((mx - r.IndelSize) / 2);
+                r.IndelSize = mx;
+                r.BPLeft = r.BPLeft - diff;
+                r.BPRight = r.BPRight + diff;
+                if (r.MatchedD == '+') {
+                    if (r.BP > diff) r.BP = (short)(r.BP - diff);
+                } else {
+                    if (r.BP + diff < r.getReadLengthMinus()) r.BP = (short)(r.BP + diff);
+                }
+            }
+            // IsGoodINV's -N test (sort_output_inv)
+            if (S.germline_filter() && ev.real_end - ev.real_start >= (unsigned)good[s].getReadLength() * 2 &&
+                !(S.repair(REPAIR_INV_PAIRS) && inv_pairs_good(inv_pairs_, ev.n_reads, ev.real_start, ev.real_end)))
+                continue;
+            output_inv(c, good, s, e, ev.real_start, ev.real_end);
+        }
+    });
+}
+
+// What the pipeline and process_window take from the points of every read, from its summary instead
+void Caller::apply_summaries(std::vector<SplitRead> &reads, const pg_report_summary *summaries, bool read_length_follows)
+{
+    for (size_t k = 0; k < reads.size(); k++) {
+        SplitRead &r = reads[k];
+        const pg_report_summary &s = summaries[k];
+        for (uint8_t f = 0; f < s.rc_flag && f < 2; f++) {          // setUnmatchedSeq(ReverseComplement()), once or twice
+            r.UnmatchedSeq = reverse_complement(r.UnmatchedSeq);
+            while (!r.UnmatchedSeq.empty() && !std::isalnum((unsigned char)r.UnmatchedSeq.back())) r.UnmatchedSeq.pop_back();
+        }
+        if (read_length_follows) r.ReadLength = (short)r.UnmatchedSeq.size();
+        if (s.flags & PG_RS_CLOSE) {
+            // note_close_mapped, from the summary's UP_Close.back()
+            if (g_reportLength < r.getReadLength()) g_reportLength = r.getReadLength();
+            r.Used = false;
+            r.UniqueRead = true;
+            if (r.MatchedD == '+') r.LeftMostPos = (int)(s.close_abs + 1 - s.close_len);
+            else r.LeftMostPos = (int)(s.close_abs + s.close_len - r.getReadLength());
+            r.SampleName2Number.insert(std::make_pair(r.Tag, 1u));
+            g_sampleNames.insert(r.Tag);
+        }
+        if (s.flags & PG_RS_FAR) {
+            // UpdateFarFragName, from the summary's UP_Far[0]
+            const int fc = s.far_chr;
+            r.FarFragName = (genome && fc >= 0 && fc < (int)genome->size()) ? (*genome)[fc].name : r.FragName;
+            r.MatchedFarD = (s.flags & PG_RS_FAR_ANTISENSE) ? '-' : '+';
+            r.CloseVsFar = (s.flags & PG_RS_CLOSE_LEFT) ? -1 : (s.flags & PG_RS_CLOSE_RIGHT) ? 1 : 0;
+        }
+    }
+}
+
+void Caller::process_window_from_tables(const Chromosome &chrom, std::vector<SplitRead> &reads, unsigned win_start, unsigned win_end,
+                                        unsigned region_start, unsigned region_end, const pg_event_read *recs, const pg_event_sizes &sizes,
+                                        const pg_event *events, const pg_sv_event_sizes &sv_sizes, const pg_event *sv_events,
+                                        const pg_report_read *records, const pg_report_summary *summaries, bool summaries_applied)
+{
+    Ctx c;                                                    // (process_window's frame)
+    c.chrom = &chrom;
+    c.reads = &reads;
+    BoxSize = (unsigned)(chrom.seq.size() / 30000);
+    if (BoxSize == 0) BoxSize = 1;
+    c.NumBoxes = (unsigned)(chrom.seq.size() * 2 / BoxSize) + 1;
+    c.win_start = win_start;
+    c.win_end = win_end;
+    c.region_start = region_start;
+    c.region_end = region_end;
+    g_RegionStart = win_start;
+    g_RegionEnd = win_end;
+    if (mask_chr_ != &chrom) {
+        chr_marks_.clear();
+        mask_chr_ = &chrom;
+    }
+    uint64_t n_members[PG_EVENT_TABLES + PG_SV_EVENT_TABLES];
+    std::vector<pg_event> ev[PG_EVENT_TABLES], sv[PG_SV_EVENT_TABLES];
+    size_t e0 = 0;
+    for (int t = 0; t < PG_EVENT_TABLES; t++) {
+        n_members[t] = sizes.members[t];
+        ev[t].assign(events + e0, events + e0 + sizes.events[t]);
+        e0 += (size_t)sizes.events[t];
+    }
+    e0 = 0;
+    for (int t = 0; t < PG_SV_EVENT_TABLES; t++) {
+        n_members[PG_EVENT_TABLES + t] = sv_sizes.members[t];
+        sv[t].assign(sv_events + e0, sv_events + e0 + sv_sizes.events[t]);
+        e0 += (size_t)sv_sizes.events[t];
+    }
+    process_window_tables(c, recs, n_members, ev, sv, records, summaries, summaries_applied);
+    flush_reports();
+}
+
+// The tables path.  Nothing here reads a point, a list or a pair field of the window's reads: they have none.
+void Caller::process_window_tables(Ctx &c, const pg_event_read *recs, const uint64_t *n_members, const std::vector<pg_event> *events,
+                                   const std::vector<pg_event> *sv_events, const pg_report_read *records, const pg_report_summary *summaries,
+                                   bool summaries_applied)
+{
+    std::vector<SplitRead> &reads = *c.reads;
+    const size_t n = reads.size();
+    if (!summaries_applied) apply_summaries(reads, summaries, false);
+    for (size_t k = 0; k < n; k++)
+        if (recs[k].flags & (PG_EVR_BOXED | PG_EVR_USED)) reads[k].Used = true;
+    size_t first[PG_EVENT_TABLES + PG_SV_EVENT_TABLES + 1];
+    first[0] = 0;
+    for (int t = 0; t < PG_EVENT_TABLES + PG_SV_EVENT_TABLES; t++) first[t + 1] = first[t] + (size_t)n_members[t];
+    // `good` of a table: the member's read with the record applied
+    auto good_of = [&](int table, std::vector<SplitRead> &good) {
+        const int kind = table < PG_EVENT_TABLES ? event_kind_of(table) : sv_event_kind_of(table - PG_EVENT_TABLES);
+        // the reporters clear UniqueRead on the duplicates of an inversion box that reaches -M: the box from the pair's own BPLeft
+        std::vector<unsigned> box_size;
+        if (table > PG_EVENT_TABLES) {
+            box_size.assign(c.NumBoxes, 0);
+            for (size_t m = first[table]; m < first[table + 1]; m++) {
+                const unsigned box = (unsigned)((int)records[m].cand.bp_left / (int)BoxSize);
+                if (box < c.NumBoxes) box_size[box]++;
+            }
+        }
+        good.clear();
+        good.reserve(first[table + 1] - first[table]);
+        VariantPair p;
+        for (size_t m = first[table]; m < first[table + 1]; m++) {
+            const pg_report_read &rec = records[m];
+            good.push_back(reads[rec.read]);
+            SplitRead &g = good.back();
+            p.c = rec.cand;
+            if (kind < 2) {
+                p.nt = kind == 1 ? variant_nt_str(g, rec.bp0, rec.cand.indel_size, rec.cand.nt_rot) : std::string();
+                apply_variant_pair(g, p);
+            } else {
+                if (kind == PG_SV_TD) {
+                    // searchTandemDuplications leaves NT_str alone: it is DI's where DI listed a pair, and empty otherwise
+                    g.NT_str.clear();
+                    if (rec.flags & PG_RR_DI) g.NT_str = sv_nt_str(g, PG_SV_DI, rec.di_bp, rec.di_nt_rot, 0);
+                }
+                p.nt = sv_nt_str(g, kind, rec.cand.bp, rec.cand.nt_rot, rec.cand.flags);
+                apply_sv_pair(g, kind, p);
+            }
+            g.NT_size = rec.nt_size;
+            g.Used = true;
+            if (rec.flags & PG_RR_DUP) {
+                const unsigned box = (unsigned)((int)rec.cand.bp_left / (int)BoxSize);
+                if (box < c.NumBoxes && box_size[box] >= S.NumRead2ReportCutOff) g.UniqueRead = false;
+            }
+        }
+    };
+    auto write_table = [&](int t) { write_event_table(c, t, events[t], [&](std::vector<SplitRead> &good) { good_of(t, good); }); };
+    auto write_sv_table = [&](int t) {
+        write_sv_event_table(c, t, sv_events[t], [&](std::vector<SplitRead> &good) { good_of(PG_EVENT_TABLES + t, good); });
+    };
+    write_table(0);
+    write_sv_table(0);
+    if (S.Analyze_TD) {
+        write_table(2);
+        write_table(3);
+    }
+    if (S.Analyze_INV) {
+        write_sv_table(1);
+        write_sv_table(2);
+    }
+    write_table(1);
+    event_path_stats().report_windows++;
+    event_path_stats().report_records += first[PG_EVENT_TABLES + PG_SV_EVENT_TABLES];
 }
 
 bool Caller::process_window_events(Ctx &c)
@@ -198,34 +412,7 @@ bool Caller::process_window_events(Ctx &c)
             g.Used = true;
         }
     };
-    // one table written in table order: the order of the boxes, and of the events within each
-    auto write_table = [&](int t) {
-        const int kind = event_kind_of(t);
-        if (tabs.events[t].empty()) return;
-        bool any = false;
-        for (const pg_event &ev : tabs.events[t]) any = any || (ev.flags & PG_EV_REPORT);
-        if (!any) return;
-        std::vector<SplitRead> good;
-        good_of(t, good);
-        for_boxes(1, [&](unsigned) {
-            for (const pg_event &ev : tabs.events[t]) {
-                if (!(ev.flags & PG_EV_REPORT)) continue;
-                const unsigned s = ev.first, e = ev.first + ev.n_reads - 1;
-                if (kind == 0) output_deletion(c, good, s, e, ev.real_start, ev.real_end);
-                else if (kind == 1) output_si(c, good, s, e, ev.real_start, ev.real_end);
-                else {
-                    // IsGoodTD's -N test (sort_output_td), with GoodIndels[0] = the first unique read of the event's box
-                    if (S.germline_filter() && ev.real_end - ev.real_start >= (unsigned)(good[ev.box_head].getReadLength() * 2)) {
-                        std::set<std::string> tags;
-                        for (unsigned i = s; i <= e; i++) tags.insert(good[i].Tag);
-                        if (!S.germline->good_td(c.chrom->name, (int64_t)c.chrom->seq.size() - 2 * (int64_t)S.spacer, ev.real_start, ev.real_end, tags))
-                            continue;
-                    }
-                    output_td(c, good, s, e, ev.real_start, ev.real_end);
-                }
-            }
-        });
-    };
+    auto write_table = [&](int t) { write_event_table(c, t, tabs.events[t], [&](std::vector<SplitRead> &good) { good_of(t, good); }); };
     // the boxes of a kind that keeps its own reporter, from the per-read records: ascending read index, as the classifier pushes
     auto boxes_of = [&](int kind, std::vector<std::vector<unsigned>> &boxes) {
         boxes.assign(c.NumBoxes, std::vector<unsigned>());
@@ -269,6 +456,49 @@ bool Caller::process_window_events(Ctx &c)
         event_path_stats().sv_table_windows++;
         if (sv_supplied) event_path_stats().sv_supplied_windows++;
     }
+    // ---- the tables path: the records and summaries of the window from its tables, lists and points (the host
+    // statement of pg_report.hip); then the reads lose their points, lists and pair fields, and the reports are written from tables,
+    // records and summaries alone.  If these are the bytes of the paths above, the writers consult nothing the device does not deliver.
+    if (S.use_report_reads && S.use_sv_events) {
+        std::vector<ReportReadIn> in(n);
+        for (size_t k = 0; k < n; k++) {
+            const SplitRead &r = reads[k];
+            ReportReadIn &e = in[k];
+            e.plus = r.MatchedD == '+';
+            e.rc_flag = 0;                                    // (UnmatchedSeq is the post-state already: nothing left to apply)
+            e.close = r.UP_Close.data();
+            e.n_close = r.UP_Close.size();
+            e.far = r.UP_Far.data();
+            e.n_far = r.UP_Far.size();
+            e.var = r.VarCands;
+            e.sv = r.SvCands;
+            e.sv_counts = r.SvCounts;
+        }
+        std::vector<pg_report_read> records;
+        std::vector<pg_report_summary> summaries;
+        report_reads_from_lists(in, tabs.reads.data(), tabs.members, svt.members, records, summaries);
+        for (SplitRead &r : reads) {
+            SplitRead bare;
+            bare.Name.swap(r.Name);
+            bare.UnmatchedSeq.swap(r.UnmatchedSeq);
+            bare.FragName.swap(r.FragName);
+            bare.Tag.swap(r.Tag);
+            bare.MatchedD = r.MatchedD;
+            bare.MatchedRelPos = r.MatchedRelPos;
+            bare.MS = r.MS;
+            bare.InsertSize = r.InsertSize;
+            bare.ReadLength = r.ReadLength;
+            bare.MAX_SNP_ERROR = r.MAX_SNP_ERROR;
+            bare.chr_id = r.chr_id;
+            bare.VarIndex = r.VarIndex;
+            r = std::move(bare);
+        }
+        uint64_t n_members[PG_EVENT_TABLES + PG_SV_EVENT_TABLES];
+        for (int t = 0; t < PG_EVENT_TABLES; t++) n_members[t] = tabs.members[t].size();
+        for (int t = 0; t < PG_SV_EVENT_TABLES; t++) n_members[PG_EVENT_TABLES + t] = svt.members[t].size();
+        process_window_tables(c, tabs.reads.data(), n_members, tabs.events, svt.events, records.data(), summaries.data());
+        return true;
+    }
     // one SV table written: what sort_output_di / sort_output_inv leave of the kind -- the pairs applied to the window's reads, the
     // duplicates of the boxes that reach -M marked -- and the reporters' output_* for the events flagged PG_EV_REPORT
     auto write_sv_table = [&](int t) {
@@ -286,43 +516,11 @@ bool Caller::process_window_events(Ctx &c)
             if (!box.empty() && box.size() >= S.NumRead2ReportCutOff)
                 for (unsigned k : box)
                     if (dup[k]) reads[k].UniqueRead = false;
-        bool any = false;
-        for (const pg_event &ev : svt.events[t]) any = any || (ev.flags & PG_EV_REPORT);
-        if (!any) return;
-        std::vector<SplitRead> good;
-        good.reserve(svt.members[t].size());
-        for (uint32_t m : svt.members[t]) {
-            good.push_back(reads[m & ~PG_SVEV_MEMBER_DUP]);              // (the pair is applied, NT_size is the carried one)
-            good.back().NT_size = tabs.reads[m & ~PG_SVEV_MEMBER_DUP].nt_size;
-        }
-        for_boxes(1, [&](unsigned) {
-            for (const pg_event &ev : svt.events[t]) {
-                if (!(ev.flags & PG_EV_REPORT)) continue;
-                const unsigned s = ev.first, e = ev.first + ev.n_reads - 1;
-                if (kind == PG_SV_DI) {
-                    if (ev.flags & PG_EV_SHORT_INV) output_short_inv(c, good, s, e);
-                    else output_di(c, good, s, e);
-                    continue;
-                }
-                // the run harmonised from the event's IndelSize, as sort_output_inv's harmonise() leaves its members
-                for (unsigned i = s; i <= e; i++) {
-                    SplitRead &r = good[i];
-                    const unsigned mx = ev.indel_size;
-                    const short diff = (short)((mx - r.IndelSize) / 2);
-                    r.IndelSize = mx;
-                    r.BPLeft = r.BPLeft - diff;
-                    r.BPRight = r.BPRight + diff;
-                    if (r.MatchedD == '+') {
-                        if (r.BP > diff) r.BP = (short)(r.BP - diff);
-                    } else {
-                        if (r.BP + diff < r.getReadLengthMinus()) r.BP = (short)(r.BP + diff);
-                    }
-                }
-                // IsGoodINV's -N test (sort_output_inv)
-                if (S.germline_filter() && ev.real_end - ev.real_start >= (unsigned)good[s].getReadLength() * 2 &&
-                    !(S.repair(REPAIR_INV_PAIRS) && inv_pairs_good(inv_pairs_, ev.n_reads, ev.real_start, ev.real_end)))
-                    continue;
-                output_inv(c, good, s, e, ev.real_start, ev.real_end);
+        write_sv_event_table(c, t, svt.events[t], [&](std::vector<SplitRead> &good) {
+            good.reserve(svt.members[t].size());
+            for (uint32_t m : svt.members[t]) {
+                good.push_back(reads[m & ~PG_SVEV_MEMBER_DUP]);              // (the pair is applied, NT_size is the carried one)
+                good.back().NT_size = tabs.reads[m & ~PG_SVEV_MEMBER_DUP].nt_size;
             }
         });
     };

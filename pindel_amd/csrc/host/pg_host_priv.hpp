@@ -196,6 +196,31 @@ inline bool variant_pair(const SplitRead &r, int kind, int ci, int fi, const std
     return true;
 }
 
+// UP_Close[0] against UP_Far[0], as OutputInversions orients a read.  A read that has its points is judged by them and never
+// consults CloseVsFar; only a read of the tables path, which has neither list, is judged by what its summary said of
+// them.  A writer that reads a point in any other way faults on such a read: that is how the gold tests of that path catch it.
+inline bool close_left_of_far(const SplitRead &r)
+{
+    return r.UP_Close.empty() || r.UP_Far.empty() ? r.CloseVsFar < 0 : r.UP_Close[0].AbsLoc < r.UP_Far[0].AbsLoc;
+}
+inline bool close_right_of_far(const SplitRead &r)
+{
+    return r.UP_Close.empty() || r.UP_Far.empty() ? r.CloseVsFar > 0 : r.UP_Close[0].AbsLoc > r.UP_Far[0].AbsLoc;
+}
+
+// NT_str of a kind 1 pair: the read's substring behind bp0 (LengthStr - 1 of the pair's close point for a '+' anchor, of its far
+// point otherwise; pg_report_read::bp0), rotated left by nt_rot
+inline std::string variant_nt_str(const SplitRead &r, short bp0, unsigned indel_size, int32_t nt_rot)
+{
+    std::string nt = r.MatchedD == '+' ? sub(reverse_complement(r.UnmatchedSeq), bp0 + 1, indel_size) : sub(r.UnmatchedSeq, bp0 + 1, indel_size);
+    const long len = (long)nt.size();
+    if (len > 1) {
+        const long rot = (((long)nt_rot % len) + len) % len;
+        std::rotate(nt.begin(), nt.begin() + rot, nt.end());
+    }
+    return nt;
+}
+
 // A listed candidate back to what variant_pair yields: NT_str is rebuilt from the read (cut as the loop cuts it, then rotated).
 // false: the record does not fit the read (indices outside its point lists).
 inline bool variant_pair_from_cand(const SplitRead &r, int kind, const pg_variant_cand &c, VariantPair &out)
@@ -206,12 +231,7 @@ inline bool variant_pair_from_cand(const SplitRead &r, int kind, const pg_varian
     if (kind == 1) {
         const bool plus = r.MatchedD == '+';
         const short bp0 = (short)((plus ? r.UP_Close[c.close_idx].LengthStr : r.UP_Far[c.far_idx].LengthStr) - 1);
-        out.nt = plus ? sub(reverse_complement(r.UnmatchedSeq), bp0 + 1, c.indel_size) : sub(r.UnmatchedSeq, bp0 + 1, c.indel_size);
-        const long len = (long)out.nt.size();
-        if (len > 1) {
-            const long rot = (((long)c.nt_rot % len) + len) % len;
-            std::rotate(out.nt.begin(), out.nt.begin() + rot, out.nt.end());
-        }
+        out.nt = variant_nt_str(r, bp0, c.indel_size, c.nt_rot);
     }
     return true;
 }
@@ -548,17 +568,22 @@ inline bool sv_pair_inv_nt(const SplitRead &r, const pg_sv_params &prm, int whic
     return true;
 }
 
+// NT_str of a pair of kind PG_SV_*: cut from the read behind bp (empty for the two kinds without non-template bases)
+inline std::string sv_nt_str(const SplitRead &r, int kind, short bp, int32_t nt_rot, uint8_t flags)
+{
+    if (kind == PG_SV_TD || kind == PG_SV_INV) return std::string();
+    const int geo = (flags >> PG_SV_GEO_SHIFT) & 3;
+    const bool from_rc = kind == PG_SV_INV_NT ? (geo == 0 || geo == 3) : r.MatchedD == '+';
+    return from_rc ? sub(reverse_complement(r.UnmatchedSeq), bp + 1, (unsigned short)nt_rot) : sub(r.UnmatchedSeq, bp + 1, (unsigned short)nt_rot);
+}
+
 // A listed record of kind PG_SV_* back to what the pair function yields: NT_str is cut from the read again.  false: the record
 // does not fit the read.
 inline bool sv_pair_from_cand(const SplitRead &r, int kind, const pg_variant_cand &c, VariantPair &out)
 {
     if (c.close_idx >= r.UP_Close.size() || c.far_idx >= r.UP_Far.size()) return false;
     out.c = c;
-    out.nt.clear();
-    if (kind == PG_SV_TD || kind == PG_SV_INV) return true;
-    const int geo = (c.flags >> PG_SV_GEO_SHIFT) & 3;
-    const bool from_rc = kind == PG_SV_INV_NT ? (geo == 0 || geo == 3) : r.MatchedD == '+';
-    out.nt = from_rc ? sub(reverse_complement(r.UnmatchedSeq), c.bp + 1, (unsigned short)c.nt_rot) : sub(r.UnmatchedSeq, c.bp + 1, (unsigned short)c.nt_rot);
+    out.nt = sv_nt_str(r, kind, c.bp, c.nt_rot, c.flags);
     return true;
 }
 

@@ -307,7 +307,7 @@ void Caller::output_inv(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsigned 
         if (r.MatchedD != '+') continue;
         short before = (short)(rl - r.BP - 1);
         out << std::string(before > 0 ? before : 0, ' ');
-        if (r.UP_Close[0].AbsLoc < r.UP_Far[0].AbsLoc)
+        if (close_left_of_far(r))
             out << reverse_complement(r.UnmatchedSeq) << std::string(r.BP > 0 ? r.BP : 0, ' ');
         else
             out << r.UnmatchedSeq;
@@ -321,7 +321,7 @@ void Caller::output_inv(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsigned 
         if (r.MatchedD != '-') continue;
         short before = (short)(rl - r.BP - 1);
         out << std::string(before > 0 ? before : 0, ' ');
-        if (r.UP_Close[0].AbsLoc > r.UP_Far[0].AbsLoc)
+        if (close_right_of_far(r))
             out << r.UnmatchedSeq << std::string(r.BP > 0 ? r.BP : 0, ' ');
         else
             out << reverse_complement(r.UnmatchedSeq);

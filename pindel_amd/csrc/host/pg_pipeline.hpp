@@ -134,6 +134,16 @@ inline bool window_pairs(std::vector<BamFile> &files, const std::vector<int> &in
 // pairs_of(chrom, ws, we, pairs) (may be empty): the window's discordant pairs for --repair inv-pairs, asked for every
 // window that is classified; false = a BAM could not be read.
 typedef std::function<bool(const Chromosome &, unsigned, unsigned, std::vector<DiscordantPair> &)> WindowPairs;
+// --device-classifier: one window on the device.  classify(chrom, chr_id, reads, ws, we, bed_start, bed_end, caller,
+// after_close) is given ALL reads of the window as loaded and runs upload, fused search, pg_device_batch_classify and the downloads.
+//   0    the reports are written (Caller::process_window_from_tables); after_close (may be empty) was called once the summaries
+//        were applied to the reads and before anything was written
+//   1    the window fell back: the reads now carry UP_Close, UP_Far and the sequence as GetCloseEnd left it, and go on through the
+//        existing steps, the far-end search excepted
+//   < 0  a pg status
+// Either way it has printed the far-end step's line and counted the window's close and far ends.
+typedef std::function<int(const Chromosome &, int, std::vector<SplitRead> &, unsigned, unsigned, unsigned, unsigned, Caller &,
+                          const std::function<void()> &)> DeviceClassify;
 struct NoFarSearch {
     int operator()(const Chromosome &, int, std::vector<SplitRead> &, unsigned, unsigned) const { return 0; }
 };
@@ -150,7 +160,7 @@ template <class Search, class FarSearch>
 int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<RegionRecord> &plan,
                  const std::vector<SplitRead> &all, const Settings &S, const std::string &prefix,
                  Search search, FarSearch far_search, std::string &err, double *li_seconds = nullptr,
-                 const WindowPairs &pairs_of = WindowPairs())
+                 const WindowPairs &pairs_of = WindowPairs(), const DeviceClassify &device_classify = DeviceClassify())
 {
     Caller caller(S, &genome, prefix, true);
     const unsigned WINDOW = (unsigned)(S.window_mbp * 1000000);
@@ -221,8 +231,23 @@ int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<Region
                 }
             });
             t_copy += now() - t0; t0 = now();
-            int rc = search(chrom, (int)c, reads, bins[w]);
-            if (rc) {
+            int rc = 0;
+            bool far_done = false;
+            if (device_classify) {
+                for (const SplitRead &r : reads) caller.note_insert_size(r.InsertSize);
+                rc = device_classify(chrom, (int)c, reads, ws, we, bed_start, bed_end, caller, std::function<void()>());
+                if (rc < 0) {
+                    err = "device classifier step failed";
+                    return rc;
+                }
+                if (rc == 0) {                                              // written from tables
+                    t_call += now() - t0; t0 = now();
+                    release_reads(reads);
+                    t_free += now() - t0;
+                    continue;
+                }
+                far_done = true;
+            } else if ((rc = search(chrom, (int)c, reads, bins[w]))) {
                 err = "search step failed";
                 return rc;
             }
@@ -239,7 +264,7 @@ int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<Region
                 if (!r.UP_Close.empty()) kept.push_back(std::move(r));      // `reads` is not used after this loop
             if (S.close_mapped_output() && !kept.empty()) caller.report_close_mapped(kept);
             t_keep += now() - t0; t0 = now();
-            if (!S.only_close_mapped && !kept.empty() && (rc = far_search(chrom, (int)c, kept, ws, we))) {
+            if (!S.only_close_mapped && !kept.empty() && !far_done && (rc = far_search(chrom, (int)c, kept, ws, we))) {
                 err = "far-end search step failed";
                 return rc;
             }
@@ -346,7 +371,7 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<Re
                      const std::vector<BamSource> &bams, const BamIngestSettings &ingest, const Settings &S,
                      const std::string &prefix, CloseSoa close_soa, FarSearch far_search, std::string &err, size_t *n_reads_total = nullptr,
                      BDHints *bd = nullptr, bool search_rp = false, size_t *n_rp_events = nullptr,
-                     double *li_seconds = nullptr)
+                     double *li_seconds = nullptr, const DeviceClassify &device_classify = DeviceClassify())
 {
     Caller caller(S, &genome, prefix, true);
     std::ofstream rp_out;
@@ -451,8 +476,53 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<Re
         if (n_reads_total) *n_reads_total += in.size();
         if (in.size() == 0) continue;
         for (size_t i = 0; i < in.size(); i++) caller.note_insert_size(in.batch.isz[i]);
+        auto ref_coverage = [&]() {   // UpdateRefReadCoverage, after the close ends (sample names) and before the classifiers
+            std::vector<Caller::RefReadSpan> spans(in.ref_reads.size());
+            for (size_t i = 0; i < spans.size(); i++) {
+                spans[i].pos = in.ref_reads[i].pos;
+                spans[i].length = in.ref_reads[i].length;
+                spans[i].tag = in.ref_reads[i].tag;
+            }
+            caller.update_ref_coverage(spans, in.ref_tags, win.ws, win.we);
+        };
+        int rc = 0;
+        std::vector<SplitRead> kept;
+        bool far_done = false;
+        if (device_classify) {
+            // every candidate of the window as a SplitRead as ingested: no close end yet, the sequence as it came
+            std::vector<SplitRead> reads(in.size());
+            pg_adapter::parallel_ranges(reads.size(), [&](size_t lo, size_t hi) {
+                for (size_t i = lo; i < hi; i++) {
+                    SplitRead &r = reads[i];
+                    r.Name = in.names[i];
+                    r.UnmatchedSeq.assign((const char *)in.batch.seq.data() + in.batch.off[i], (size_t)(in.batch.off[i + 1] - in.batch.off[i]));
+                    r.ReadLength = (short)r.UnmatchedSeq.size();
+                    r.MatchedD = (char)in.batch.strand[i];
+                    r.MatchedRelPos = (unsigned)in.batch.pos[i];
+                    r.MS = in.ms[i];
+                    r.InsertSize = in.batch.isz[i];
+                    r.Tag = in.tags[i];
+                    r.FragName = chrom.name;
+                    r.chr_id = (int)c;
+                }
+            });
+            rc = device_classify(chrom, (int)c, reads, win.ws, win.we, bed_start, bed_end, caller, ref_coverage);
+            if (rc < 0) {
+                err = "device classifier step failed";
+                status = rc;
+                break;
+            }
+            t_call += now() - t0; t0 = now();
+            if (rc == 0) continue;                            // written from tables
+            for (SplitRead &r : reads)
+                if (!r.UP_Close.empty()) {
+                    r.MAX_SNP_ERROR = (short)S.max_mismatch[std::min<int>(r.ReadLength, 499)];
+                    kept.push_back(std::move(r));
+                }
+            far_done = true;
+        } else {
         CloseView view;
-        int rc = close_soa(chrom, (int)c, in.batch, view);
+        rc = close_soa(chrom, (int)c, in.batch, view);
         if (rc) {
             err = "search step failed";
             status = rc;
@@ -468,7 +538,7 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<Re
                     kept_idx.push_back((uint32_t)(p.first + i));
                     kept_part.push_back(&p);
                 }
-        std::vector<SplitRead> kept(kept_idx.size());
+        kept.resize(kept_idx.size());
         pg_adapter::parallel_ranges(kept.size(), [&](size_t lo, size_t hi) {
             for (size_t k = lo; k < hi; k++) {
                 const size_t i = kept_idx[k];
@@ -492,24 +562,17 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<Re
             }
         });
         if (view.release) view.release();
+        }
         caller.note_close_mapped_all(kept);
         if (S.close_mapped_output() && !kept.empty()) caller.report_close_mapped(kept);
         t_keep += now() - t0; t0 = now();
-        if (!S.only_close_mapped && !kept.empty() && (rc = far_search(chrom, (int)c, kept, win.ws, win.we))) {
+        if (!S.only_close_mapped && !kept.empty() && !far_done && (rc = far_search(chrom, (int)c, kept, win.ws, win.we))) {
             err = "far-end search step failed";
             status = rc;
             break;
         }
         t_far += now() - t0; t0 = now();
-        if (!S.only_close_mapped) {   // UpdateRefReadCoverage, after the close ends (sample names) and before the classifiers
-            std::vector<Caller::RefReadSpan> spans(in.ref_reads.size());
-            for (size_t i = 0; i < spans.size(); i++) {
-                spans[i].pos = in.ref_reads[i].pos;
-                spans[i].length = in.ref_reads[i].length;
-                spans[i].tag = in.ref_reads[i].tag;
-            }
-            caller.update_ref_coverage(spans, in.ref_tags, win.ws, win.we);
-        }
+        if (!S.only_close_mapped) ref_coverage();
         t_cov += now() - t0; t0 = now();
         caller.set_window_pairs(std::move(d->pairs));
         if (!S.only_close_mapped && !kept.empty()) caller.process_window(chrom, kept, win.ws, win.we, bed_start, bed_end);

@@ -29,6 +29,7 @@
 #include <iterator>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "pg_adapter.hpp"
@@ -358,6 +359,142 @@ struct FarSearch {
     }
 };
 
+// --device-classifier: one window as one device batch -- upload, fused search, name ids by first occurrence,
+// pg_device_batch_classify with the window process_window would use, the tables, records and summaries downloaded, and
+// Caller::process_window_from_tables.  The points stay on the device unless the window has an unresolved read or its tables do not
+// fit: then pg_device_batch_download fetches them and the window goes on through the existing steps.
+struct DeviceClassifierStats {
+    size_t windows = 0, from_tables = 0, fallbacks = 0, unresolved = 0, records = 0, runs_kept = 0;
+};
+struct DeviceClassifier {
+    const Seams &s;
+    DeviceClassifierStats &st;
+    bool bam;                                    // BAM input: ReadLength follows the sequence GetCloseEnd left
+    int operator()(const Chromosome &chrom, int chr_id, std::vector<SplitRead> &reads, unsigned ws, unsigned we, unsigned bed_start,
+                   unsigned bed_end, Caller &caller, const std::function<void()> &after_close) const
+    {
+        const double t0 = now_s();
+        pg_ctx *ctx = s.ctxs[0];
+        const size_t n = reads.size();
+        const pg_adapter::Batch batch = pg_adapter::make_batch(reads, chr_of);
+        pg_read_batch v = batch.view();
+        pg_device_batch *b = nullptr;
+        int rc = pg_device_batch_upload(ctx, &v, &b);
+        if (rc) return rc;
+        struct Free {
+            pg_ctx *c;
+            pg_device_batch *b;
+            ~Free() { pg_device_batch_free(c, b); }
+        } free_batch = { ctx, b };
+        if ((rc = pg_device_batch_pack_search(ctx, b))) return rc;
+        std::vector<uint32_t> name_id(n);
+        {
+            std::unordered_map<std::string, uint32_t> seen;
+            seen.reserve(n * 2);
+            for (size_t i = 0; i < n; i++) name_id[i] = seen.emplace(reads[i].Name, (uint32_t)seen.size()).first->second;
+        }
+        pg_classify_params p;
+        p.window.chr_id = chr_id;
+        p.window.win_end = we;
+        p.window.region_start = bed_start;
+        p.window.region_end = bed_end;
+        p.window.min_support = s.o.S.NumRead2ReportCutOff;
+        p.window.balance_cutoff = s.o.S.BalanceCutoff;
+        p.window.analyze_td = s.o.S.Analyze_TD;
+        p.window.analyze_inv = s.o.S.Analyze_INV;
+        p.sv.seq_error_rate = s.o.S.Seq_Error_Rate;
+        p.sv.min_num_matched_bases = s.o.S.Min_Num_Matched_Bases;
+        p.sv.min_inversion_size = s.o.S.MIN_IndelSize_Inversion;
+        p.max_listed = s.o.device_classifier_listed < 0 ? PG_VARIANT_CANDS : s.o.device_classifier_listed;
+        p.reserved = 0;
+        if ((rc = pg_device_batch_classify(ctx, b, &p, name_id.data()))) return rc;
+        pg_event_sizes es;
+        pg_sv_event_sizes ss;
+        pg_report_sizes rs;
+        if ((rc = pg_device_batch_event_sizes(ctx, b, &es)) || (rc = pg_device_batch_sv_event_sizes(ctx, b, &ss)) ||
+            (rc = pg_device_batch_report_sizes(ctx, b, &rs)))
+            return rc;
+        size_t nm = 0, ne = 0, snm = 0, sne = 0;
+        for (int t = 0; t < PG_EVENT_TABLES; t++) nm += es.members[t], ne += es.events[t];
+        for (int t = 0; t < PG_SV_EVENT_TABLES; t++) snm += ss.members[t], sne += ss.events[t];
+        std::vector<pg_event_read> recs(n);
+        std::vector<pg_event> events(ne), sv_events(sne);
+        std::vector<pg_report_read> records(rs.records);
+        std::vector<pg_report_summary> summaries(n);
+        // (the member lists stay on the device: every member has its record)
+        if ((rc = pg_device_batch_events_download(ctx, b, recs.data(), nullptr, events.data())) ||
+            (rc = pg_device_batch_sv_events_download(ctx, b, nullptr, sv_events.data())) ||
+            (rc = pg_device_batch_report_download(ctx, b, records.data(), summaries.data())))
+            return rc;
+        // ReportCloseAndFarEndCounts (src/pindel.cpp:1094-1113), over the reads that kept a close end, from the summaries
+        size_t n_close = 0, n_far = 0;
+        for (const pg_report_summary &x : summaries) {
+            n_close += (x.flags & PG_RS_CLOSE) != 0;
+            n_far += (x.flags & PG_RS_CLOSE) && (x.flags & PG_RS_FAR);
+        }
+        s.counts.n_close += n_close;
+        s.counts.n_far += n_far;
+        printf("Total: %zu;\tClose_end_found %zu;\tFar_end_found %zu;\tUsed\t0.\n\nFor LI and BP: %zu\n\n", n_close, n_close, n_far,
+               n_close - n_far);
+        st.windows++;
+        // do the tables fit ?  every member has a record of a read of this window, every event lies in its member list
+        bool fits = rs.records == nm + snm && rs.reads == n;
+        for (const pg_report_read &r : records) fits = fits && r.read < n && r.table < PG_EVENT_TABLES + PG_SV_EVENT_TABLES;
+        {
+            size_t e0 = 0;
+            for (int t = 0; t < PG_EVENT_TABLES && fits; t++) {
+                for (size_t k = 0; k < es.events[t]; k++) {
+                    const pg_event &ev = events[e0 + k];
+                    fits = fits && ev.n_reads > 0 && (uint64_t)ev.first + ev.n_reads <= es.members[t] && ev.box_head <= ev.first;
+                }
+                e0 += (size_t)es.events[t];
+            }
+            e0 = 0;
+            for (int t = 0; t < PG_SV_EVENT_TABLES && fits; t++) {
+                for (size_t k = 0; k < ss.events[t]; k++) {
+                    const pg_event &ev = sv_events[e0 + k];
+                    fits = fits && ev.n_reads > 0 && (uint64_t)ev.first + ev.n_reads <= ss.members[t];
+                }
+                e0 += (size_t)ss.events[t];
+            }
+        }
+        if (es.unresolved == 0 && fits) {
+            s.counts.t_search += now_s() - t0;
+            if (n_close) {                       // (a window without a close end has nothing to classify, as in the existing steps)
+                caller.apply_summaries(reads, summaries.data(), bam);
+                if (after_close) after_close();
+                caller.process_window_from_tables(chrom, reads, ws, we, bed_start, bed_end, recs.data(), es, events.data(), ss, sv_events.data(),
+                                                  records.data(), summaries.data(), true);
+            } else if (after_close) after_close();
+            uint64_t close_runs = 0, far_runs = 0;
+            (void)pg_device_batch_result_sizes(ctx, b, &close_runs, &far_runs);
+            st.runs_kept += (size_t)(close_runs + far_runs);
+            st.from_tables++;
+            st.records += records.size();
+            return 0;
+        }
+        // the fallback: the window's points after all, and the existing steps
+        st.fallbacks++;
+        st.unresolved += (size_t)es.unresolved;
+        pg_result *res = nullptr;
+        if ((rc = pg_device_batch_download(ctx, b, &res))) return rc;
+        pg_result_view rv;
+        pg_result_view_get(res, &rv);
+        const bool length_follows = bam;
+        pg_adapter::parallel_ranges(n, [&](size_t lo, size_t hi) {
+            for (size_t i = lo; i < hi; i++) {
+                pg_adapter::apply_rc_flag(reads[i], rv.rc_flag[i]);
+                if (length_follows) reads[i].ReadLength = (short)reads[i].UnmatchedSeq.size();
+                pg_adapter::fill_points(reads[i].UP_Close, rv.close_runs, rv.close_off[i], rv.close_off[i + 1], make_point);
+                pg_adapter::fill_points(reads[i].UP_Far, rv.far_runs, rv.far_off[i], rv.far_off[i + 1], make_point);
+            }
+        });
+        pg_result_free(res);
+        s.counts.t_search += now_s() - t0;
+        return 1;
+    }
+};
+
 // -q: searchMEImain (src/search_MEI.cpp:963-1024) over the same plan and windows, after the split-read search.  The reference
 // runs it INSTEAD of that search and exits (`exit(searchMEImain(...))`, src/pindel.cpp:1745-1746, its other reports left
 // empty); here both run, and _DD does not depend on the order (difference 3).
@@ -463,13 +600,17 @@ int main(int argc, char **argv)
     const Seams seams = { o, dev.ctxs, bd, bams.empty() ? o.use_bd : o.search_rp, chromosome_names(genome), counts };
     size_t n_reads = all.size(), n_rp_events = 0;
     double li_seconds = 0.0;
+    DeviceClassifierStats dc_stats;
+    DeviceClassify device_classify;
+    if (o.device_classifier) device_classify = DeviceClassifier{ seams, dc_stats, !bams.empty() };
     if (!bams.empty()) {
         n_reads = 0;
         rc = run_bam_pipeline(genome, plan, bams, ing, o.S, o.prefix, CloseSoa{ seams }, FarSearch{ seams }, err, &n_reads, &bd, o.search_rp,
-                              &n_rp_events, &li_seconds);
+                              &n_rp_events, &li_seconds, device_classify);
         if (o.search_rp) printf("pindel_pg: read-pair events added as window hints: %zu\n", n_rp_events);
     } else
-        rc = run_pipeline(genome, plan, all, o.S, o.prefix, CloseSearch{ seams }, FarSearch{ seams }, err, &li_seconds);
+        rc = run_pipeline(genome, plan, all, o.S, o.prefix, CloseSearch{ seams }, FarSearch{ seams }, err, &li_seconds, WindowPairs(),
+                          device_classify);
     if (!rc && o.detect_dd) rc = detect_dd(o, ctx, genome, sizes, plan, bams, ing, err);
     if (rc) {
         fprintf(stderr, "pindel_pg: %s (%s)\n", err.c_str(), pg_last_error(ctx));
@@ -479,6 +620,10 @@ int main(int argc, char **argv)
         printf("pindel_pg: %zu reads, close end %zu (-S: close-end-mapped reads only, no far-end search)\n", n_reads, counts.n_close);
     else
         printf("pindel_pg: %zu reads, close end %zu, far end %zu\n", n_reads, counts.n_close, counts.n_far);
+    if (o.device_classifier)
+        printf("pindel_pg: device classifier: %zu windows, %zu from tables, %zu fell back, %zu unresolved reads, %zu report records, "
+               "%zu runs not downloaded\n", dc_stats.windows, dc_stats.from_tables, dc_stats.fallbacks, dc_stats.unresolved, dc_stats.records,
+               dc_stats.runs_kept);
     // the phases the reference's Timer reports (pindel.cpp:1990-1996), wall-clock seconds
     printf("pindel_pg: loading %.2f s, split-read search (GPU, incl. adapters) %.2f s, classification + reports %.2f s\n",
            t_loaded - t_start, counts.t_search, now_s() - t_loaded - counts.t_search);

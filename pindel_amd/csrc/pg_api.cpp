@@ -312,6 +312,14 @@ struct pg_device_batch {
     uint32_t *svev_ws = nullptr;           // n: the order kernel's ranks of boxes beyond its LDS
     pg_sv_event_sizes svev_sizes{};
     bool svev_built = false;
+    // the report records of the last pg_device_batch_report_reads; an events or sv events build discards them
+    pg_report_read *rr_records = nullptr;      // n: a read is a member of at most one table
+    pg_report_summary *rr_summaries = nullptr; // n
+    uint64_t rr_n_records = 0;
+    bool rr_built = false;
+    // the candidate lists of the last pg_device_batch_classify: they never leave the device
+    pg_variant_cand *cl_cands = nullptr, *cl_sv_cands = nullptr;   // n x 2 x PG_VARIANT_CANDS; n x PG_SV_SLOTS
+    uint8_t *cl_counts = nullptr, *cl_sv_counts = nullptr;         // n x 2; n x PG_SV_KINDS
 };
 
 struct pg_result {
@@ -466,6 +474,13 @@ void free_batch_buffers(pg_device_batch *b)
 {
     for (void *p : { (void *)b->ev_reads, (void *)b->ev_members, (void *)b->ev_events, (void *)b->svev_members, (void *)b->svev_events, (void *)b->svev_ws })
         if (p) (void)hipFree(p);
+    for (void *p : { (void *)b->rr_records, (void *)b->rr_summaries, (void *)b->cl_cands, (void *)b->cl_sv_cands, (void *)b->cl_counts, (void *)b->cl_sv_counts })
+        if (p) (void)hipFree(p);
+    b->rr_records = nullptr;
+    b->rr_summaries = nullptr;
+    b->rr_built = false;
+    b->cl_cands = b->cl_sv_cands = nullptr;
+    b->cl_counts = b->cl_sv_counts = nullptr;
     b->svev_members = nullptr;
     b->svev_events = nullptr;
     b->svev_ws = nullptr;
@@ -2464,6 +2479,7 @@ int build_events(pg_ctx *ctx, pg_device_batch *b, const pg_event_window *w, cons
 {
     b->ev_built = false;
     b->svev_built = false;                                    // (the SV tables belong to the records of the build they were made from)
+    b->rr_built = false;                                      // (... and so do the report records)
     b->ev_sizes = pg_event_sizes{};
     b->ev_window = *w;
     const size_t n = b->n;
@@ -2667,6 +2683,7 @@ int sv_events_refusal(pg_ctx *ctx, pg_device_batch *b, const void *sv_cands, con
 int build_sv_events(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *d_sv_cands)
 {
     b->svev_built = false;
+    b->rr_built = false;
     b->svev_sizes = pg_sv_event_sizes{};
     const size_t n = b->n;
     if (!n) {                                                 // nothing is launched for an empty batch
@@ -2829,6 +2846,203 @@ int pg_device_batch_sv_events_download_device(pg_ctx *ctx, pg_device_batch *b, u
         return rc;
     if (d_members && nm) HIP_TRY(ctx, hipMemcpy(d_members, b->svev_members, nm * sizeof(uint32_t), hipMemcpyDeviceToDevice));
     if (d_events && ne) HIP_TRY(ctx, hipMemcpy(d_events, b->svev_events, ne * sizeof(pg_event), hipMemcpyDeviceToDevice));
+    return PG_OK;
+}
+
+// ---- ... its fifth part (pg_report.hip): the report records per table member and per read
+namespace {
+int report_refusal(pg_ctx *ctx, pg_device_batch *b, const void *cands, const void *counts, const void *sv_cands, const void *sv_counts)
+{
+    if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
+    if (int rc = stale_batch(ctx, b)) return rc;
+    ctx->last_ms = 0.0;
+    if (b->n && !b->searched) return fail(ctx, PG_E_INVALID, "the batch has not been searched: no close and far ends to classify");
+    if (!b->ev_built) return fail(ctx, PG_E_INVALID, "report reads: pg_device_batch_events has not been run on this batch");
+    if (!b->svev_built) return fail(ctx, PG_E_INVALID, "report reads: pg_device_batch_sv_events has not been run on this batch since its events build");
+    if (b->n && (!cands || !counts || !sv_cands || !sv_counts)) return fail(ctx, PG_E_INVALID, "report reads: null candidate arrays");
+    return PG_OK;
+}
+
+// every list pointer is device memory
+int build_report(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *d_cands, const uint8_t *d_counts, const pg_variant_cand *d_sv_cands,
+                 const uint8_t *d_sv_counts)
+{
+    b->rr_built = false;
+    b->rr_n_records = 0;
+    const size_t n = b->n;
+    if (!n) {                                                 // nothing is launched for an empty batch
+        b->rr_built = true;
+        return PG_OK;
+    }
+    int rc;
+    // (each buffer on its own: an allocation that failed in an earlier call is tried again, never launched with)
+    if ((!b->rr_records && (rc = dev_alloc(ctx, &b->rr_records, n))) || (!b->rr_summaries && (rc = dev_alloc(ctx, &b->rr_summaries, n)))) return rc;
+    PgReportArgs a{};
+    uint64_t total = 0;
+    for (int t = 0; t < PG_REPORT_TABLES; t++) {
+        a.start[t] = (uint32_t)total;
+        total += t < PG_EVENT_TABLES ? b->ev_sizes.members[t] : b->svev_sizes.members[t - PG_EVENT_TABLES];
+    }
+    // (a read is boxed at most once: the seven lists together hold at most n members, the size of the record buffer)
+    if (total > n) return fail(ctx, PG_E_DEVICE, "report reads: the tables hold more members than the batch has reads");
+    a.start[PG_REPORT_TABLES] = (uint32_t)total;
+    a.out = b->out_rec;
+    a.pool = b->pool;
+    a.pool_runs = (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS;
+    a.strand = b->strand;
+    a.n = b->n;
+    a.cands = d_cands;
+    a.counts = d_counts;
+    a.sv_cands = d_sv_cands;
+    a.sv_counts = d_sv_counts;
+    a.reads = b->ev_reads;
+    a.ev_members = b->ev_members;
+    a.sv_members = b->svev_members;
+    a.records = b->rr_records;
+    a.summaries = b->rr_summaries;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if (pg_report_launch(&a, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the report record kernels failed");
+    PgLaunchRec rec{};
+    rec.kernel = PG_KERNEL_REPORT;
+    rec.blocks = (int32_t)PG_EV_BLOCK;
+    log_launch(ctx, rec);
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->last_ms = ms;
+    b->rr_n_records = total;
+    b->rr_built = true;
+    return PG_OK;
+}
+const char *const NO_REPORT = "no report records: pg_device_batch_report_reads has not been run on this batch since its table builds";
+}  // namespace
+
+int pg_device_batch_report_reads_device(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *d_cands, const uint8_t *d_counts,
+                                        const pg_variant_cand *d_sv_cands, const uint8_t *d_sv_counts)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (int rc = report_refusal(ctx, b, d_cands, d_counts, d_sv_cands, d_sv_counts)) return rc;
+    const size_t n = b->n;
+    int rc;
+    if (n && ((rc = check_device_ptr(ctx, d_cands, n * 2 * PG_VARIANT_CANDS * sizeof(pg_variant_cand), 4, "report reads: cands")) ||
+              (rc = check_device_ptr(ctx, d_counts, n * 2, 1, "report reads: counts")) ||
+              (rc = check_device_ptr(ctx, d_sv_cands, n * PG_SV_SLOTS * sizeof(pg_variant_cand), 4, "report reads: sv_cands")) ||
+              (rc = check_device_ptr(ctx, d_sv_counts, n * PG_SV_KINDS, 1, "report reads: sv_counts"))))
+        return rc;
+    return build_report(ctx, b, d_cands, d_counts, d_sv_cands, d_sv_counts);
+}
+
+int pg_device_batch_report_reads(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *cands, const uint8_t *counts,
+                                 const pg_variant_cand *sv_cands, const uint8_t *sv_counts)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (int rc = report_refusal(ctx, b, cands, counts, sv_cands, sv_counts)) return rc;
+    const size_t n = b->n;
+    EventTemps tmp;
+    pg_variant_cand *d_cands = nullptr, *d_sv = nullptr;
+    uint8_t *d_counts = nullptr, *d_svn = nullptr;
+    if (n) {
+        int rc;
+        if ((rc = EV_TAKE(tmp, ctx, d_cands, n * 2 * PG_VARIANT_CANDS)) || (rc = EV_TAKE(tmp, ctx, d_counts, n * 2)) ||
+            (rc = EV_TAKE(tmp, ctx, d_sv, n * PG_SV_SLOTS)) || (rc = EV_TAKE(tmp, ctx, d_svn, n * PG_SV_KINDS)))
+            return rc;
+        HIP_TRY(ctx, hipMemcpy(d_cands, cands, n * 2 * PG_VARIANT_CANDS * sizeof(pg_variant_cand), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_counts, counts, n * 2, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_sv, sv_cands, n * PG_SV_SLOTS * sizeof(pg_variant_cand), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_svn, sv_counts, n * PG_SV_KINDS, hipMemcpyHostToDevice));
+    }
+    return build_report(ctx, b, d_cands, d_counts, d_sv, d_svn);
+}
+
+int pg_device_batch_report_sizes(pg_ctx *ctx, pg_device_batch *b, pg_report_sizes *sizes)
+{
+    use_device(ctx);
+    if (!ctx || !b || !sizes) return PG_E_INVALID;
+    if (!b->rr_built) return fail(ctx, PG_E_INVALID, NO_REPORT);
+    sizes->records = b->rr_n_records;
+    sizes->reads = b->n;
+    return PG_OK;
+}
+
+static int report_download(pg_ctx *ctx, pg_device_batch *b, pg_report_read *records, pg_report_summary *summaries, hipMemcpyKind kind)
+{
+    if (records && b->rr_n_records) HIP_TRY(ctx, hipMemcpy(records, b->rr_records, (size_t)b->rr_n_records * sizeof(pg_report_read), kind));
+    if (summaries && b->n) HIP_TRY(ctx, hipMemcpy(summaries, b->rr_summaries, (size_t)b->n * sizeof(pg_report_summary), kind));
+    return PG_OK;
+}
+
+int pg_device_batch_report_download(pg_ctx *ctx, pg_device_batch *b, pg_report_read *records, pg_report_summary *summaries)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (!b->rr_built) return fail(ctx, PG_E_INVALID, NO_REPORT);
+    return report_download(ctx, b, records, summaries, hipMemcpyDeviceToHost);
+}
+
+int pg_device_batch_report_download_device(pg_ctx *ctx, pg_device_batch *b, pg_report_read *d_records, pg_report_summary *d_summaries)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (!b->rr_built) return fail(ctx, PG_E_INVALID, NO_REPORT);
+    int rc;
+    if ((d_records && (rc = check_device_ptr(ctx, d_records, (size_t)b->rr_n_records * sizeof(pg_report_read), 4, "report download: records"))) ||
+        (d_summaries && (rc = check_device_ptr(ctx, d_summaries, (size_t)b->n * sizeof(pg_report_summary), 4, "report download: summaries"))))
+        return rc;
+    return report_download(ctx, b, d_records, d_summaries, hipMemcpyDeviceToDevice);
+}
+
+// ---- one call per window: the two candidate kernels, both table builds and the report records, the lists staying with the batch
+int pg_device_batch_classify(pg_ctx *ctx, pg_device_batch *b, const pg_classify_params *p, const uint32_t *name_id)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (!p) return fail(ctx, PG_E_INVALID, "classify: null pg_classify_params");
+    // every stage's refusal before the first launch
+    if (int rc = events_refusal(ctx, b, &p->window, false)) return rc;
+    if (int rc = sv_params_ok(ctx, &p->sv)) return rc;
+    if (p->max_listed < 0 || p->max_listed > PG_VARIANT_CANDS) return fail(ctx, PG_E_INVALID, "classify: max_listed must lie in [0, PG_VARIANT_CANDS]");
+    if (b->n >= 0x80000000u) return fail(ctx, PG_E_INVALID, "classify: 2^31 reads or more (bit 31 of a member word is PG_SVEV_MEMBER_DUP)");
+    const size_t n = b->n;
+    int rc;
+    // (each buffer on its own: an allocation that failed in an earlier call is tried again, never launched with)
+    if (n && ((!b->cl_cands && (rc = dev_alloc(ctx, &b->cl_cands, n * 2 * PG_VARIANT_CANDS))) || (!b->cl_counts && (rc = dev_alloc(ctx, &b->cl_counts, n * 2))) ||
+              (!b->cl_sv_cands && (rc = dev_alloc(ctx, &b->cl_sv_cands, n * PG_SV_SLOTS))) ||
+              (!b->cl_sv_counts && (rc = dev_alloc(ctx, &b->cl_sv_counts, n * PG_SV_KINDS)))))
+        return rc;
+    EventTemps tmp;
+    uint32_t *d_name = nullptr;
+    if (n && name_id) {
+        if ((rc = EV_TAKE(tmp, ctx, d_name, n))) return rc;
+        HIP_TRY(ctx, hipMemcpy(d_name, name_id, n * 4, hipMemcpyHostToDevice));
+    }
+    double ms = 0.0;
+    if ((rc = variant_candidates(ctx, b, b->cl_cands, b->cl_counts))) return rc;
+    ms += ctx->last_ms;
+    if ((rc = sv_candidates(ctx, b, &p->sv, b->cl_sv_cands, b->cl_sv_counts))) return rc;
+    ms += ctx->last_ms;
+    if (n && p->max_listed < PG_VARIANT_CANDS) {
+        HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        if (pg_report_cut_launch(b->cl_counts, b->cl_sv_counts, b->n, (uint32_t)p->max_listed, ctx->stream))
+            return fail(ctx, PG_E_DEVICE, "launching the list cut kernel failed");
+        PgLaunchRec rec{};
+        rec.kernel = PG_KERNEL_REPORT;
+        rec.blocks = 0;                                       // (0: the cut; PG_EV_BLOCK: the records)
+        log_launch(ctx, rec);
+        HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        float cut_ms = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&cut_ms, ctx->ev0, ctx->ev1));
+        ms += cut_ms;
+    }
+    if ((rc = build_events(ctx, b, &p->window, b->cl_cands, b->cl_counts, b->cl_sv_cands, b->cl_sv_counts, d_name))) return rc;
+    ms += ctx->last_ms;
+    if ((rc = build_sv_events(ctx, b, b->cl_sv_cands))) return rc;
+    ms += ctx->last_ms;
+    if ((rc = build_report(ctx, b, b->cl_cands, b->cl_counts, b->cl_sv_cands, b->cl_sv_counts))) return rc;
+    ctx->last_ms += ms;
     return PG_OK;
 }
 

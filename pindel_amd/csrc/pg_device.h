@@ -307,6 +307,7 @@ int pg_debug_kargs_check(const PgDevRef *ref, const PgDevParams *prm, const PgDe
 // template arguments.  The launch functions below fill these when given somewhere to put them (null: nothing is recorded).
 enum PgKernelKind { PG_KERNEL_SEARCH = 1, PG_KERNEL_EXACT = 2, PG_KERNEL_PACK = 3, PG_KERNEL_VARIANT = 4, PG_KERNEL_SV = 5,
                     PG_KERNEL_EVENT_CASCADE = 6, PG_KERNEL_EVENT_SORT = 7, PG_KERNEL_EVENT_TABLES = 8, PG_KERNEL_SV_EVENTS = 9 };
+enum { PG_KERNEL_REPORT = 10 };    // ... continued: the report kernels of pg_report.hip (blocks 0: the list cut of pg_device_batch_classify)
 struct PgLaunchRec {
     int32_t kernel;                // PgKernelKind
     int32_t blocks;                // NB of pg_search_kernel, PB of pg_pack_kernel (0: pg_search_exact_kernel)
@@ -501,6 +502,30 @@ int pg_sv_events_sort_pass_launch(const struct PgSvEventArgs *a, const uint32_t 
 // ranks, segments, the record-shift passes per box (perm is permuted in place), duplicates, members, runs and events
 int pg_sv_events_tables_launch(const PgDevRef *ref, const struct PgSvEventArgs *a, uint32_t *perm, const uint32_t *kperm, uint32_t n_boxed,
                                void *stream);
+// Report records (pg_report.hip): one pg_report_read per member of the seven member lists and one pg_report_summary
+// per read, from the two table builds, the lists they were given and the run pool.
+#define PG_REPORT_TABLES (PG_EVENT_TABLES + PG_SV_EVENT_TABLES)
+struct PgReportArgs {
+    const PgOutRec *out;
+    const pg_run *pool;
+    unsigned long long pool_runs;
+    const uint8_t *strand;
+    uint32_t n;
+    uint32_t start[PG_REPORT_TABLES + 1];   // member i lies in table t with start[t] <= i < start[t + 1]; start[PG_EVENT_TABLES] = the events build's total
+    const pg_variant_cand *cands;     // n x 2 x PG_VARIANT_CANDS
+    const uint8_t *counts;
+    const pg_variant_cand *sv_cands;  // n x PG_SV_SLOTS
+    const uint8_t *sv_counts;
+    const pg_event_read *reads;       // n: the events build's records
+    const uint32_t *ev_members;       // the four member lists back to back
+    const uint32_t *sv_members;       // the three member lists back to back
+    pg_report_read *records;          // start[PG_REPORT_TABLES]
+    pg_report_summary *summaries;     // n
+};
+// the summaries of the n reads and the records of the members; n = 0 and "no members" launch nothing that indexes an empty array
+int pg_report_launch(const struct PgReportArgs *a, void *stream);
+// the count bytes of n reads cut to max_listed pairs (pg_device_batch_classify); n = 0 launches nothing
+int pg_report_cut_launch(uint8_t *counts, uint8_t *sv_counts, uint32_t n, uint32_t max_listed, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -90,8 +90,10 @@ def lib():
         L.pgh_variant_candidates.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32] + [C.c_void_p] * 12
         L.pgh_call_from_points_events.argtypes = L.pgh_call_from_points.argtypes + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]
         L.pgh_call_from_points_sv_events.argtypes = L.pgh_call_from_points_events.argtypes + [C.c_int32, C.c_void_p]
+        L.pgh_call_from_points_report_reads.argtypes = L.pgh_call_from_points.argtypes + [C.c_void_p] * 4
         for f in ("pgh_last_event_fallback_windows", "pgh_last_event_table_windows", "pgh_last_event_supplied_windows",
-                  "pgh_last_sv_event_table_windows", "pgh_last_sv_event_supplied_windows"):
+                  "pgh_last_sv_event_table_windows", "pgh_last_sv_event_supplied_windows", "pgh_last_report_windows",
+                  "pgh_last_report_records"):
             getattr(L, f).restype = C.c_uint64
             getattr(L, f).argtypes = []
         L.pgh_last_event_windows.restype = C.c_uint64
@@ -485,6 +487,73 @@ def sv_events_from_lists(chroms, seq, seq_off, anchor_strand, rc_flag, close_off
     return sv_event_tables(members, events, sizes)
 
 
+# report records (include/pindel_pg.h): pg_report_read per table member, pg_report_summary per read
+RR_DUP, RR_DI = 1, 2
+RS_CLOSE, RS_FAR, RS_FAR_ANTISENSE, RS_CLOSE_LEFT, RS_CLOSE_RIGHT = 1, 2, 4, 8, 16
+REPORT_READ_DTYPE = np.dtype([("read", "<u4"), ("cand", VARIANT_CAND_DTYPE), ("nt_size", "<u2"), ("table", "u1"), ("flags", "u1"),
+                              ("bp0", "<i2"), ("di_bp", "<i2"), ("di_nt_rot", "<i4")], align=True)
+REPORT_SUMMARY_DTYPE = np.dtype([("close_abs", "<u4"), ("close_len", "<i2"), ("far_chr", "<i2"), ("flags", "u1"), ("rc_flag", "u1"),
+                                 ("reserved", "<u2")], align=True)
+assert REPORT_READ_DTYPE.itemsize == 48 and REPORT_SUMMARY_DTYPE.itemsize == 12
+
+
+class ReportSizes(C.Structure):
+    """pg_report_sizes"""
+    _fields_ = [("records", C.c_uint64), ("reads", C.c_uint64)]
+
+
+def report_reads_from_lists(anchor_strand, rc_flag, close_off, close_pts, far_off, far_pts, events, sv_events, variant, sv):
+    """Report records on the host (pgh_report_reads_from_lists): the reference Engine.report_reads is compared with,
+    byte for byte.  Strands, rc flags and points as events_from_lists takes them; events / sv_events: the dicts of the two table
+    builds (reads, members_flat, n_members); variant / sv: the (cands, counts) pairs they were given.  Returns (records, summaries):
+    REPORT_READ_DTYPE per member of the seven member lists in order, REPORT_SUMMARY_DTYPE per read."""
+    L = lib()
+    strand = np.ascontiguousarray(anchor_strand, dtype=np.uint8)
+    n = len(strand)
+    rc_flag = np.ascontiguousarray(rc_flag, dtype=np.uint8)
+    close_off = np.ascontiguousarray(close_off, dtype=np.uint64)
+    far_off = np.ascontiguousarray(far_off, dtype=np.uint64)
+    close_pts = np.ascontiguousarray(close_pts)
+    far_pts = np.ascontiguousarray(far_pts)
+    assert close_pts.dtype.itemsize == 12 and far_pts.dtype.itemsize == 12
+    recs = np.ascontiguousarray(events["reads"], dtype=EVENT_READ_DTYPE)
+    evm = np.ascontiguousarray(events["members_flat"], dtype=np.uint32)
+    svm = np.ascontiguousarray(sv_events["members_flat"], dtype=np.uint32)
+    ev_sizes = EventSizes()
+    sv_sizes = SvEventSizes()
+    for t in range(EVENT_TABLES):
+        ev_sizes.members[t] = int(events["n_members"][t])
+    for t in range(SV_EVENT_TABLES):
+        sv_sizes.members[t] = int(sv_events["n_members"][t])
+    vc = np.ascontiguousarray(variant[0], dtype=VARIANT_CAND_DTYPE)
+    sc = np.ascontiguousarray(sv[0], dtype=VARIANT_CAND_DTYPE)
+    sn = np.ascontiguousarray(sv[1], dtype=np.uint8)
+    assert len(rc_flag) == n and len(close_off) == n + 1 and len(far_off) == n + 1 and len(recs) == n
+    assert vc.size == n * 2 * VARIANT_CANDS and sc.size == n * SV_SLOTS and sn.size == n * len(SV_KINDS)
+    assert evm.size == sum(ev_sizes.members) and svm.size == sum(sv_sizes.members)
+    records = np.zeros(max(evm.size + svm.size, 1), dtype=REPORT_READ_DTYPE)
+    summaries = np.zeros(max(n, 1), dtype=REPORT_SUMMARY_DTYPE)
+    sizes = ReportSizes()
+    L.pgh_report_reads_from_lists.argtypes = [C.c_uint32] + [C.c_void_p] * 17
+    rc = L.pgh_report_reads_from_lists(n, strand.ctypes.data, rc_flag.ctypes.data, close_off.ctypes.data, close_pts.ctypes.data,
+                                       far_off.ctypes.data, far_pts.ctypes.data, recs.ctypes.data, evm.ctypes.data, C.addressof(ev_sizes),
+                                       svm.ctypes.data, C.addressof(sv_sizes), vc.ctypes.data, sc.ctypes.data, sn.ctypes.data,
+                                       records.ctypes.data, summaries.ctypes.data, C.addressof(sizes))
+    if rc:
+        raise ValueError("pgh_report_reads_from_lists: " + (L.pgh_last_error() or b"").decode())
+    return records[:int(sizes.records)], summaries[:n]
+
+
+def last_report_windows():
+    """Windows of the last call_from_points(report_reads=True) that Caller::process_window_tables wrote from records and summaries."""
+    return int(lib().pgh_last_report_windows())
+
+
+def last_report_records():
+    """... and the report records those windows took."""
+    return int(lib().pgh_last_report_records())
+
+
 def last_variant_fallbacks():
     """Reads of the last call_from_points(variant_candidates=...) whose list ran out, with VARIANT_MORE set, before one of its
     pairs had made the read Used: they went through the classifier's own pair search."""
@@ -503,7 +572,8 @@ def last_variant_visits():
 
 def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pts, far_off, far_pts,
                      rc_flag, region=None, include_bed=None, exclude_bed=None, reads_config=None, normal_samples=None,
-                     bam_config=None, repairs=None, variant_candidates=None, sv_candidates=None, events=None, sv_events=None):
+                     bam_config=None, repairs=None, variant_candidates=None, sv_candidates=None, events=None, sv_events=None,
+                     report_reads=False):
     """Classify + report (_D, _SI, _TD, _INV) from per-read UP_Close / UP_Far points (CSR over
     all reads of the file, 12-byte pg_point records).  settings.analyze_li / settings.report_close_mapped
     add <out_prefix>_LI / <out_prefix>_CloseEndMapped, settings.report_interchromosomal <out_prefix>_INT and
@@ -529,7 +599,11 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
     events): True -- DI and the inversions are written from their SV tables (sv_events_from_lists' function) instead of through
     the reporters' own quadratic sorts; the reports are the same bytes.  Or a dict {window: tables} of SV tables built elsewhere
     (what Engine.sv_events returns), used for the windows whose event tables are supplied too; tables that do not fit a window
-    are replaced by the host's own (last_sv_event_table_windows)."""
+    are replaced by the host's own (last_sv_event_table_windows).  report_reads (needs both lists, implies the
+    host-built events and sv_events paths): per window the host statements build lists -> tables -> report records -> summaries,
+    the window's reads are replaced by copies without points, lists and pair fields, and the reports are written from tables,
+    records and summaries alone (last_report_windows, last_report_records); a window with an unresolved read takes the existing
+    path (last_event_fallback_windows); the reports are the same bytes."""
     L = lib()
     tmp_cfg = None
     if reads_config is not None and not isinstance(reads_config, (str, bytes, os.PathLike)):
@@ -567,7 +641,13 @@ def call_from_points(fasta, reads_txt, out_prefix, settings, close_off, close_pt
             sv_n = np.ascontiguousarray(sv_candidates[1], dtype=np.uint8)
             if sv_c.size != n * SV_SLOTS or sv_n.size != n * len(SV_KINDS):
                 raise ValueError(f"sv_candidates: {sv_c.size} records and {sv_n.size} counts for {n} reads")
-        if events:
+        if report_reads:
+            if cands is None or sv_c is None:
+                raise ValueError("report_reads: variant_candidates and sv_candidates are both needed")
+            if isinstance(events, dict) or isinstance(sv_events, dict):
+                raise ValueError("report_reads: the tables are built on the host, supplied ones are not taken")
+            rc = L.pgh_call_from_points_report_reads(*args, cands.ctypes.data, counts.ctypes.data, sv_c.ctypes.data, sv_n.ctypes.data)
+        elif events:
             if cands is None or sv_c is None:
                 raise ValueError("events: variant_candidates and sv_candidates are both needed")
             sup, keep_ev = _supplied_events(events, fasta, n)

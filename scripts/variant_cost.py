@@ -131,6 +131,18 @@ def main():
     for _ in range(5):
         svev = eng.sv_events_tensors(db, svt)
         svev_ms.append(eng.last_stats()[0])
+    # the report records over those two builds, then the whole window in one call with the lists kept on the device
+    note("report records and classify on the GPU")
+    rr_ms = []
+    for _ in range(5):
+        eng.report_reads_tensors(db, vt, svt)
+        rr_ms.append(eng.last_stats()[0])
+    cl_ms = []
+    for _ in range(5):
+        eng.classify(db, binding.EventWindow(0, 0xffffffff, 0, 0xffffffff, 1, 100, 1, 1))
+        cl_ms.append(eng.last_stats()[0])
+    n_records = eng.report_sizes(db)[0]
+    cl_ev, cl_sv = eng.event_sizes(db), eng.sv_event_sizes(db)
     ev_reads = binding.events_from_tensors(ev)["reads"]
     del vt, svt
     res = eng.download(db)
@@ -175,6 +187,16 @@ def main():
           f"and tables in device memory) {min(svev_ms):.3f} ms (best of 5; all: {', '.join(f'{x:.3f}' for x in svev_ms)}) = "
           f"{min(svev_ms) * 1e6 / n:.2f} ns per read, beside the events entry's {min(ev_ms):.3f} ms of the same run; members per table "
           f"{svev['n_members']}, events per table {svev['n_events']}, dropped runs {svev['dropped_runs']}, largest box {box} reads\n", flush=True)
+    # what a caller of classify downloads (per-read records, member lists, events, report records, summaries) beside the search result
+    # (offsets, runs, rc flags) it no longer needs
+    table_bytes = n * 8 + (sum(cl_ev[0]) + sum(cl_sv[0])) * 4 + (sum(cl_ev[1]) + sum(cl_sv[1])) * 40 + n_records * 48 + n * 12
+    point_bytes = (n + 1) * 16 + (len(res.close_runs) + len(res.far_runs)) * 12 + n
+    print(f"- report records entry (one thread per member, one per read) {min(rr_ms):.3f} ms (best of 5; all: "
+          f"{', '.join(f'{x:.3f}' for x in rr_ms)}) = {min(rr_ms) * 1e6 / n:.2f} ns per read; {n_records} records\n"
+          f"- pg_device_batch_classify (both candidate kernels, both table builds, the records; sum of the stages' HIP-event times) "
+          f"{min(cl_ms):.3f} ms (best of 5; all: {', '.join(f'{x:.3f}' for x in cl_ms)}) = {min(cl_ms) * 1e6 / n:.2f} ns per read\n"
+          f"- bytes a consumer downloads per read: tables, records and summaries {table_bytes / n:.1f}; the run-length-encoded search "
+          f"result {point_bytes / n:.1f} (expanded on the host to {(len(cp) + len(fp)) * 12 / n:.0f} bytes of points)\n", flush=True)
     if a.device_only:
         return
     modes = ["plain", "lists", "sv"] + (["parent"] if a.parent_lib else [])
