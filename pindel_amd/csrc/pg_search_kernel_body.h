@@ -37,6 +37,10 @@
     S.chr_tab = lds.chr_tab;
     u64 *qplanes = lds.qp;                        // [0]: forward, [1]: reversed consumption order
     if (lane < 8 * NB) qplanes[lane] = 0ull;      // (blocks beyond the batch's plane layout are never written)
+    // The open candidate pass (pg_open_pass) reads its queue slot in every lane: a slot no pass has written yet holds a valid
+    // position from the start (not 0: a kind-B candidate at window position 0 would read below the window), and what a pass leaves
+    // in it is one -- so an idle lane never forms an LDS address from data nobody wrote.
+    if (pg_open_pass<NB, NS, Id, mode, DEF, false, LEN>() && lane < PG_PASS(NB)) lds.queue[lane] = PG_QUEUE_IDLE(NB);
 #ifdef PG_TIMING
     S.t_acc = lds.t_acc;
     S.t_last = &lds.t_last;
