@@ -264,6 +264,24 @@ int  pg_device_batch_repack(pg_ctx *ctx, pg_device_batch *b, double *pack_ms);
  * Wherever the batch's plane layout is that of its search kernels (32-bit candidate ids: always) the search kernel builds the planes
  * and records of its reads itself, claim by claim (the pack is HBM-bound, the search is not: no launch of its own).  Synchronous. */
 int  pg_device_batch_pack_search(pg_ctx *ctx, pg_device_batch *b);
+/* Close end, hint lookup and far end of every read of a resident batch, the results left on the GPU: what pg_search_batch_table
+ * computes, with both run lists resident.  Synchronous.  Afterwards the batch is searched, in the state pg_device_batch_search
+ * would leave had each read's cluster (by the lookup rule of pg_hint_table) been attached with pg_device_batch_set_windows --
+ * close runs, far runs, rc_flag, close_last, close_max -- so pg_device_batch_download, _download_device, _result_sizes, the five
+ * classifier stages and pg_device_batch_classify give bit for bit what they give there.
+ *   - Three steps on the ctx's stream: a close launch (which packs the reads), the lookup of pg_search_batch_table from the
+ *     summary that launch left, and a far launch that appends its runs to the pool behind the close runs.  If the pool
+ *     overflows in either launch it is regrown and all three are done again.
+ *   - A null table or one with n_runs == 0: attached windows are cleared and the call is pg_device_batch_pack_search.
+ *   - A malformed table is PG_E_INVALID before anything is launched (the texts of the _table entries above) and leaves the
+ *     batch as it was: still searched if it was, its results intact.  A missing reference and a batch uploaded before a
+ *     reference reload are refused before any launch as well.
+ *   - The windows the lookup attached stay attached: pg_device_batch_search on the same batch gives the same result again,
+ *     pg_device_batch_set_windows(ctx, b, NULL) detaches them.  Calling this entry again, with any table or none, gives that
+ *     table's result alone.
+ *   - pg_last_search_stats: the two search launches' HIP-event times added up, the pool slots after the far launch;
+ *     pg_debug_last_hint_stats: the lookup. */
+int  pg_device_batch_search_table(pg_ctx *ctx, pg_device_batch *b, const pg_hint_table *table /* nullable */);
 void pg_device_batch_free(pg_ctx *ctx, pg_device_batch *b);
 /* HIP-event duration (ms) of the kernel of the last search on this ctx (events recorded on
  * the ctx's own stream around the launch) and the run-pool slots it took (reserved per read + allocated; the number

@@ -202,7 +202,8 @@ EXPORTS = [
     "pg_device_batch_sv_events", "pg_device_batch_sv_events_device", "pg_device_batch_sv_event_sizes",
     "pg_device_batch_sv_events_download", "pg_device_batch_sv_events_download_device",
     "pg_device_batch_report_reads", "pg_device_batch_report_reads_device", "pg_device_batch_report_sizes",
-    "pg_device_batch_report_download", "pg_device_batch_report_download_device", "pg_device_batch_classify"]
+    "pg_device_batch_report_download", "pg_device_batch_report_download_device", "pg_device_batch_classify",
+    "pg_device_batch_search_table"]
 
 
 def build(force: bool = False) -> str:
@@ -289,6 +290,7 @@ def lib():
     L.pg_device_batch_candidates.argtypes = [vp, vp, C.POINTER(C.c_double)]
     L.pg_device_batch_repack.argtypes = [vp, vp, C.POINTER(C.c_double)]
     L.pg_device_batch_pack_search.argtypes = [vp, vp]
+    L.pg_device_batch_search_table.argtypes = [vp, vp, C.POINTER(PgHintTable)]
     L.pg_debug_last_hint_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u64), C.POINTER(u64)]
     L.pg_load_reference_device.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(u64)]
     L.pg_device_batch_upload_device.argtypes = [vp, C.POINTER(PgReadBatch), C.POINTER(vp)]
@@ -1058,6 +1060,12 @@ class Engine:
     def pack_search_device(self, dbatch):
         """repack + search_device as one step (large batches: one launch, the search kernel packs its own reads)"""
         self._check(self._L.pg_device_batch_pack_search(self._h, dbatch))
+
+    def search_table_device(self, dbatch, hints=None):
+        """hints: a HintTable or None -- close end, lookup on the device and far end of a resident batch, both run lists left on
+        the GPU (pg_device_batch_search_table); None: pack_search_device on the batch without windows"""
+        t = hints.struct() if hints is not None else None
+        self._check(self._L.pg_device_batch_search_table(self._h, dbatch, C.byref(t) if t is not None else None))
 
     def last_step_in_place(self) -> bool:
         """tests: did the last pack_search_device build its records inside the search kernel (one launch)?"""

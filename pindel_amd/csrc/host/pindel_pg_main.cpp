@@ -364,7 +364,7 @@ struct FarSearch {
 // Caller::process_window_from_tables.  The points stay on the device unless the window has an unresolved read or its tables do not
 // fit: then pg_device_batch_download fetches them and the window goes on through the existing steps.
 struct DeviceClassifierStats {
-    size_t windows = 0, from_tables = 0, fallbacks = 0, unresolved = 0, records = 0, runs_kept = 0;
+    size_t windows = 0, from_tables = 0, fallbacks = 0, unresolved = 0, records = 0, runs_kept = 0, hinted = 0;
 };
 struct DeviceClassifier {
     const Seams &s;
@@ -386,7 +386,19 @@ struct DeviceClassifier {
             pg_device_batch *b;
             ~Free() { pg_device_batch_free(c, b); }
         } free_batch = { ctx, b };
-        if ((rc = pg_device_batch_pack_search(ctx, b))) return rc;
+        // a hinted window (--device-classifier-hints): FarSearch's condition without `kept` -- the close ends are
+        // not on the host -- its region and its table, looked up on the device between the close and the far launch
+        const bool hinted = s.use_bd && s.bd.n_events() && n;
+        if (hinted) {
+            std::string berr;
+            if (!s.bd.load_region(s.chr_names, chr_id, ws + s.o.prm.spacer, we + s.o.prm.spacer, berr)) return fail(berr, (int)PG_E_INVALID);
+            HintTableView tab;
+            tab.set(s.bd.table());
+            printf("Window hints: device lookup, table of %u runs / %u clusters / %zu windows\n", tab.t.n_runs, tab.t.n_clusters, tab.win.size());
+            if ((rc = pg_device_batch_search_table(ctx, b, &tab.t))) return rc;
+            st.hinted++;
+        } else if ((rc = pg_device_batch_pack_search(ctx, b)))
+            return rc;
         std::vector<uint32_t> name_id(n);
         {
             std::unordered_map<std::string, uint32_t> seen;
@@ -620,10 +632,13 @@ int main(int argc, char **argv)
         printf("pindel_pg: %zu reads, close end %zu (-S: close-end-mapped reads only, no far-end search)\n", n_reads, counts.n_close);
     else
         printf("pindel_pg: %zu reads, close end %zu, far end %zu\n", n_reads, counts.n_close, counts.n_far);
-    if (o.device_classifier)
+    if (o.device_classifier) {
         printf("pindel_pg: device classifier: %zu windows, %zu from tables, %zu fell back, %zu unresolved reads, %zu report records, "
-               "%zu runs not downloaded\n", dc_stats.windows, dc_stats.from_tables, dc_stats.fallbacks, dc_stats.unresolved, dc_stats.records,
+               "%zu runs not downloaded", dc_stats.windows, dc_stats.from_tables, dc_stats.fallbacks, dc_stats.unresolved, dc_stats.records,
                dc_stats.runs_kept);
+        if (o.device_classifier_hints) printf(", %zu hinted windows", dc_stats.hinted);
+        printf("\n");
+    }
     // the phases the reference's Timer reports (pindel.cpp:1990-1996), wall-clock seconds
     printf("pindel_pg: loading %.2f s, split-read search (GPU, incl. adapters) %.2f s, classification + reports %.2f s\n",
            t_loaded - t_start, counts.t_search, now_s() - t_loaded - counts.t_search);

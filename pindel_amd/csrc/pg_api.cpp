@@ -1114,26 +1114,54 @@ int read_cursors(pg_ctx *ctx, pg_device_batch *b, uint32_t *worst, uint64_t *tot
     return PG_OK;
 }
 
-// Runs the kernel(s) of `mode`; if a pool shard overflowed, the pool is regrown and the launch
-// repeated (still entirely on the GPU).
-int run_search(pg_ctx *ctx, pg_device_batch *b, int mode, bool pack = false)
+// What every search refuses before anything is launched.
+int search_refusals(pg_ctx *ctx, const pg_device_batch *b)
 {
     if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
     // (a batch is validated and its records are packed against the reference loaded at upload time: chromosome offsets and sizes,
     // window bounds; a reference loaded later makes them stale)
-    if (int rc = stale_batch(ctx, b)) return rc;
+    return stale_batch(ctx, b);
+}
+
+// One launch of `mode` over the whole batch, waited for: its runs go behind whatever the pool cursors say is there (the caller
+// zeroes them, or not), and `searched` is the caller's to set.  *ms: the HIP-event time; *worst / *total: the cursors afterwards.
+int search_launch(pg_ctx *ctx, pg_device_batch *b, int mode, bool pack, float *ms, uint32_t *worst, uint64_t *total)
+{
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    int rc = launch_range(ctx, b, mode, 0, b->n, nullptr, 0, false, pack);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
+    return read_cursors(ctx, b, worst, total);
+}
+
+// A larger pool, of `want` slots per shard (at most what 31-bit slot numbers reach).  The runs of the old one are gone.
+int grow_pool(pg_ctx *ctx, pg_device_batch *b, uint64_t want)
+{
+    const uint32_t ncap = (uint32_t)std::min<uint64_t>(want, 0x7fffffffull / PG_POOL_SHARDS);
+    pg_run *npool = nullptr;
+    int rc = dev_alloc(ctx, &npool, (size_t)ncap * PG_POOL_SHARDS);
+    if (rc) return rc;
+    if (!b->in_arena || b->pool_owned) (void)hipFree(b->pool);
+    b->pool = npool;
+    b->pool_owned = true;
+    b->pool_shard_cap = ncap;
+    return PG_OK;
+}
+
+// Runs the kernel(s) of `mode`; if a pool shard overflowed, the pool is regrown and the launch
+// repeated (still entirely on the GPU).
+int run_search(pg_ctx *ctx, pg_device_batch *b, int mode, bool pack = false)
+{
+    if (int rc = search_refusals(ctx, b)) return rc;
     for (int attempt = 0; attempt < 8; attempt++) {
         HIP_TRY(ctx, hipMemsetAsync(b->pool_used, 0, PG_POOL_SHARDS * 16 * sizeof(uint32_t), ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        int rc = launch_range(ctx, b, mode, 0, b->n, nullptr, 0, false, pack);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
         uint32_t worst = 0;
         uint64_t total = 0;
-        if ((rc = read_cursors(ctx, b, &worst, &total))) return rc;
+        int rc = search_launch(ctx, b, mode, pack, &ms, &worst, &total);
+        if (rc) return rc;
         if (worst <= b->pool_shard_cap) {
             ctx->last_ms = ms;
             ctx->last_runs = total;
@@ -1141,14 +1169,7 @@ int run_search(pg_ctx *ctx, pg_device_batch *b, int mode, bool pack = false)
             return PG_OK;
         }
         // overflow: grow the pool and redo the launch
-        uint32_t ncap = (uint32_t)std::min<uint64_t>((uint64_t)worst + worst / 4 + 64, 0x7fffffffull / PG_POOL_SHARDS);
-        pg_run *npool = nullptr;
-        rc = dev_alloc(ctx, &npool, (size_t)ncap * PG_POOL_SHARDS);
-        if (rc) return rc;
-        if (!b->in_arena || b->pool_owned) (void)hipFree(b->pool);
-        b->pool = npool;
-        b->pool_owned = true;
-        b->pool_shard_cap = ncap;
+        if ((rc = grow_pool(ctx, b, (uint64_t)worst + worst / 4 + 64))) return rc;
     }
     return fail(ctx, PG_E_DEVICE, "run pool kept overflowing");
 }
@@ -3555,6 +3576,54 @@ int pg_search_batch_table(pg_ctx *ctx, const pg_read_batch *reads, const pg_hint
     g.r = nullptr;
     g.ok = true;
     return PG_OK;
+}
+
+// The same on a resident batch, with both run lists left in the pool: the far launch does not zero the pool
+// cursors, so its runs go behind the close launch's, and it writes only the far fields of the output records -- the batch ends
+// as a fused search leaves it.  A pool that overflowed in either launch is regrown and everything is done again from the close
+// launch: the regrown pool has lost the close runs.
+int pg_device_batch_search_table(pg_ctx *ctx, pg_device_batch *b, const pg_hint_table *table)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    HintTableDev d;
+    int rc = upload_hint_table(ctx, table, d);
+    if (rc) return rc;
+    if (!d.live() || !b->n) {                   // no hints, or nobody to look up: the fused search of a batch without windows
+        // (attach_table without a lookup: the windows of an earlier call detached, the hint statistics zero)
+        if ((rc = search_refusals(ctx, b)) || (rc = attach_table(ctx, b, d))) return rc;
+        return pg_device_batch_pack_search(ctx, b);
+    }
+    if ((rc = search_refusals(ctx, b))) return rc;
+    b->searched = false;
+    // each launch reserves its PG_RESERVE slots per read, and the batch's pool was sized for one: room for both from the start,
+    // or every batch of more than ~87 000 reads would overflow once and run three times (PG_TEST_TINY_POOL: the regrow path)
+    const uint64_t two_launches = ((2ull * PG_RESERVE + 2ull) * b->n) / PG_POOL_SHARDS + 512ull;
+    if (!env().tiny_pool && b->pool_shard_cap < two_launches && (rc = grow_pool(ctx, b, two_launches))) return rc;
+    const PgSoaOut a = soa_out(b);
+    for (int attempt = 0; attempt < 8; attempt++) {
+        float ms_close = 0.f, ms_far = 0.f;
+        uint32_t worst = 0;
+        uint64_t total = 0;
+        // (the close end reads no windows: those of an earlier call go first, so that they have no say in the launch's kernels)
+        if ((rc = clear_windows(ctx, b))) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(b->pool_used, 0, PG_POOL_SHARDS * 16 * sizeof(uint32_t), ctx->stream));
+        if ((rc = search_launch(ctx, b, PG_MODE_CLOSE, true, &ms_close, &worst, &total))) return rc;
+        if (worst <= b->pool_shard_cap) {
+            if (pg_unpack_close_summary(b->out_rec, &a, b->n, ctx->stream) != 0)
+                return fail(ctx, PG_E_DEVICE, "close-end summary kernel failed");
+            if ((rc = attach_table(ctx, b, d)) || (rc = search_launch(ctx, b, PG_MODE_FAR, true, &ms_far, &worst, &total))) return rc;
+            note_hint_fill(ctx);
+        }
+        if (worst <= b->pool_shard_cap) {
+            ctx->last_ms = (double)ms_close + (double)ms_far;
+            ctx->last_runs = total;
+            b->searched = true;
+            return b->exact_n < 0 ? read_exact_count(ctx, b) : PG_OK;
+        }
+        if ((rc = grow_pool(ctx, b, (uint64_t)worst + worst / 4 + 64))) return rc;
+    }
+    return fail(ctx, PG_E_DEVICE, "run pool kept overflowing");
 }
 
 int pg_debug_last_hint_stats(const pg_ctx *ctx, double *scan_ms, double *fill_ms, uint64_t *table_bytes, uint64_t *n_windows)

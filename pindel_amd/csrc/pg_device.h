@@ -372,6 +372,8 @@ int pg_launch_search_exact(const PgDevRef *ref, const PgDevParams *prm, const Pg
 int pg_pack_reads(const PgSoaIn *soa, PgInRec *in, uint32_t lo, uint32_t cnt, void *stream, struct PgLaunchRec *rec);
 // close-end summary (rc flag, last AbsLoc, max length) of a host result into the output records
 int pg_pack_close_summary(const PgSoaOut *soa, PgOutRec *out, uint32_t n, void *stream);
+// ... and out of the output records a close launch wrote into the batch's summary arrays (the records are left as they are)
+int pg_unpack_close_summary(const struct PgOutRec *out, const PgSoaOut *soa, uint32_t n, void *stream);
 // One chunk (cnt <= PG_DELIVER_CHUNK reads) of a searched batch to read-order CSR behind the earlier chunks: see the
 // delivery kernels in pg_kernels.hip.  local / blk: scratch of cnt and 4096 uint2; run_tot: 2 running totals (zeroed
 // per batch); info: 8 values for the host {close base, far base, close runs, far runs, fullest pool shard, overflow}.

@@ -3083,6 +3083,19 @@ __global__ void pg_pack_close_kernel(PgSoaOut a, PgOutRec *out, uint32_t n)
     out[i] = r;
 }
 
+// ... and the other way: the summary a close launch left in the output records into the batch's arrays, where the hint lookup
+// reads it (what pg_deliver_scan does as a side effect of a delivery).  The records stay as they are.
+__global__ void pg_unpack_close_kernel(const PgOutRec *out, PgSoaOut a, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    // (dwords 4 and 5 of the record: one 8-byte load)
+    const uint2 s = *(const uint2 *)&out[i].close_last;
+    a.close_last[i] = s.x;
+    a.close_max[i] = (uint16_t)(s.y & 0xffffu);
+    a.rc_flag[i] = (uint8_t)((s.y >> 16) & 0xffu);
+}
+
 template <int PB>
 static void launch_pack(const PgSoaIn *soa, PgInRec *in, uint32_t lo, uint32_t cnt, hipStream_t st)
 {
@@ -3110,6 +3123,12 @@ extern "C" int pg_pack_reads(const PgSoaIn *soa, PgInRec *in, uint32_t lo, uint3
 extern "C" int pg_pack_close_summary(const PgSoaOut *soa, PgOutRec *out, uint32_t n, void *stream)
 {
     if (n) pg_pack_close_kernel<<<(n + 255u) / 256u, 256, 0, (hipStream_t)stream>>>(*soa, out, n);
+    return (int)hipGetLastError();
+}
+
+extern "C" int pg_unpack_close_summary(const PgOutRec *out, const PgSoaOut *soa, uint32_t n, void *stream)
+{
+    if (n) pg_unpack_close_kernel<<<(n + 255u) / 256u, 256, 0, (hipStream_t)stream>>>(out, *soa, n);
     return (int)hipGetLastError();
 }
 
