@@ -4,7 +4,9 @@
 // parameters by reference or by value -- the body is optimised once on its own before it is inlined, and six of the existing
 // kernels came out with other register allocations (<NB=3, NS=3, u32, BOTH, defaults>: 127 -> 131 SGPR spill slots, 24 -> 32 bytes
 // of scratch; profiles/r08/README.md).  Included, every existing kernel compiles to what it was.
-    __shared__ Lds<NB, Id> lds;
+    // (a kernel of pg_rev_mismatch keeps the bit-reversed copies of the planes behind the two orientations: Lds::qp)
+    constexpr int QPX = pg_rev_mismatch<NB, NS, Id, mode, DEF, false, LEN>() ? 4 : 2;
+    __shared__ Lds<NB, Id, QPX> lds;
     const int lane = threadIdx.x;
     if (PG_WIN_DYN_BYTES(NB) != 0u) {
         // the window's dynamic tail must begin where the static LDS object ends (see Lds::win)
@@ -36,7 +38,7 @@
     S.mm_tab = lds.mm_tab;
     S.chr_tab = lds.chr_tab;
     u64 *qplanes = lds.qp;                        // [0]: forward, [1]: reversed consumption order
-    if (lane < 8 * NB) qplanes[lane] = 0ull;      // (blocks beyond the batch's plane layout are never written)
+    if (lane < 4 * QPX * NB) qplanes[lane] = 0ull;   // (blocks beyond the batch's plane layout are never written)
     // The open candidate pass (pg_open_pass) reads its queue slot in every lane: a slot no pass has written yet holds a valid
     // position from the start (not 0: a kind-B candidate at window position 0 would read below the window), and what a pass leaves
     // in it is one -- so an idle lane never forms an LDS address from data nobody wrote.

@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/../pindel_amd/csrc" || exit 1
 n=$1; shift
 mkdir -p build
-rest="build/pg_api.o build/pg_dd.o build/pg_hints.o build/pg_devio.o build/pg_variant.o build/pg_sv.o"
+rest="build/pg_api.o build/pg_dd.o build/pg_hints.o build/pg_devio.o build/pg_variant.o build/pg_sv.o build/pg_events.o build/pg_sv_events.o build/pg_report.o"
 for o in $rest; do [ -f $o ] || make $o > /dev/null || exit 1; done
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -pthread --offload-arch=gfx950 -I../../include -I. ${KFLAGS--mllvm -disable-machine-licm -mllvm -phi-elim-split-all-critical-edges} "$@" -c -x hip pg_kernels.hip -o build/pg_kernels_$n.o 2>build/pg_kernels_$n.log || { grep -A6 -E "error" build/pg_kernels_$n.log | head -40; exit 1; }
 /opt/rocm/bin/hipcc -shared -fPIC -pthread --offload-arch=gfx950 build/pg_kernels_$n.o $rest -o ../libpindel_pg_$n.so

@@ -1,7 +1,7 @@
 """Diagnostics: per-read event counts of a -DPG_DIAG build (LDS fills, seed-filter runs, candidate passes, evaluations)
 on the bench workload:  python scripts/diag_counts.py <lib.so> [reads] (PG_X=<n> selects -x n, PG_LEN the read length;
 PG_DIAG_LAYOUT=2 for a -DPG_DIAG=2 build: the census of the evaluations; PG_DIAG_LAYOUT=3 for a -DPG_DIAG=3 build: the census of the
-fold's loops)"""
+fold's loops; PG_DIAG_LAYOUT=4 for a -DPG_DIAG=4 build: block bodies by kind and merged evaluations by qmask)"""
 import ctypes as C
 import os
 import sys
@@ -44,6 +44,14 @@ elif os.environ.get("PG_DIAG_LAYOUT") == "3":
     # its highest value, a bound on the overflows into the next field
     fields = [("tier A full iterations, no rings", 0, 6), ("tier A tail iterations, no rings", 6, 4), ("tier A iterations, rings", 10, 6),
               ("tier B candidate-rounds, round 0", 16, 6), ("tier B candidate-rounds, rounds >= 1", 22, 5), ("AccB stores", 27, 4)]
+    for nm, sh, w in fields:
+        f = (out >> sh) & ((1 << w) - 1)
+        hist = np.bincount(f, minlength=10)
+        print(f"{nm:38s} mean {f.mean():7.3f}  full {(f == (1 << w) - 1).mean():.5f}  histogram 0..9: {(hist[:10] / n).round(3).tolist()}")
+elif os.environ.get("PG_DIAG_LAYOUT") == "4":
+    # a -DPG_DIAG=4 build: the census of the block bodies by kind and of the merged evaluations by qmask (Search::dg, pg_kernels.hip)
+    fields = [("close-end block bodies, kind B", 0, 6), ("close-end block bodies, kind F", 6, 6), ("mixed-pass block bodies", 12, 6),
+              ("evaluations merging two quarters", 18, 5), ("evaluations merging four quarters", 23, 5)]
     for nm, sh, w in fields:
         f = (out >> sh) & ((1 << w) - 1)
         hist = np.bincount(f, minlength=10)
