@@ -575,6 +575,34 @@ typedef struct {
 } pg_classify_params;
 int  pg_device_batch_classify(pg_ctx *ctx, pg_device_batch *b, const pg_classify_params *p, const uint32_t *name_id);
 
+/* ---- device classifier: long-insertion position tables -------------------------------------------------------
+ * What SortOutputLI (src/reporter.cpp:1853-2141) counts per position -- the reads that kept a close end and found no far end, by
+ * anchor strand and by the position of their last close point -- as tables, so that a caller who writes _LI downloads no point.
+ * An LI read is a read of the batch whose chr_id is the events build's window chr_id, that has a close end and no far end, whose
+ * pg_event_read::flags carries neither PG_EVR_BOXED nor PG_EVR_USED (PG_EVR_UNRESOLVED alone does not exclude it) and whose anchor
+ * strand is '+' or '-'.  Its position is UP_Close.back().AbsLoc clamped into the buffered window: min(max(p, lo), hi).  Per strand
+ * (0: '+' anchors, 1: '-' anchors):
+ *   the member list     the LI reads' indices sorted by position, ascending read index within one position
+ *   the position table  one pg_li_pos per distinct position, ascending: members [first, first + n_reads) of the strand's list.
+ *                       n_reads is NOT capped (the reference's counters saturate at Max_short = 128: the consumer's job).  flags:
+ *                       PG_LI_LONGER / PG_LI_SHORTER = some member's close end is longer / shorter than half of its read, the
+ *                       integer form of LengthStr > ReadLength * 0.5 and < with the read's length after GetCloseEnd (rc_flag).
+ * A pure function of the batch (result records, anchor strands, bases), the per-read records of its events build and the window. */
+typedef struct { uint32_t lo, hi; } pg_li_window;       /* the buffered window: a position p counts at min(max(p, lo), hi) */
+#define PG_LI_LONGER  0x1u           /* some member: 2 * close_len > its post-state read length                             */
+#define PG_LI_SHORTER 0x2u           /* some member: 2 * close_len < its post-state read length                             */
+typedef struct { uint32_t pos, first, n_reads, flags; } pg_li_pos;            /* 16 bytes */
+typedef struct { uint64_t members[2], positions[2]; } pg_li_sizes;            /* 0: '+' anchors, 1: '-' anchors */
+/* Builds the tables and keeps them with the batch (a new events build drops them; freed with the batch).  Refused with nothing
+ * launched (PG_E_INVALID): a batch that was not searched, a batch without an events build, a null window, lo > hi.  n_reads == 0
+ * and "no LI read" are valid.  Synchronous; pg_last_search_stats then reports the HIP-event time of the kernels.
+ * pg_device_batch_classify does not run it.  download: members = the two member lists back to back, positions likewise; either may
+ * be NULL; the _device sibling fills device memory under the rules of "device buffers in and out". */
+int  pg_device_batch_li(pg_ctx *ctx, pg_device_batch *b, const pg_li_window *window);
+int  pg_device_batch_li_sizes(pg_ctx *ctx, pg_device_batch *b, pg_li_sizes *sizes);
+int  pg_device_batch_li_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *members, pg_li_pos *positions);
+int  pg_device_batch_li_download_device(pg_ctx *ctx, pg_device_batch *b, uint32_t *d_members, pg_li_pos *d_positions);
+
 /* -q (dispersed duplications): per item i, contains_subseq_any_strand(query_i, window_i, 15) of Pindel's MEI search
  * (src/search_MEI_util.cpp:188-351, bit-exact), where query_i = query[query_off[i] .. query_off[i+1]) (at most
  * PG_MAX_READ_LEN bases) and window_i = the loaded chromosome chr_id[i] at padded (AbsLoc) positions

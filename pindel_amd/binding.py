@@ -147,6 +147,29 @@ class ReportSizes(C.Structure):
     _fields_ = [("records", C.c_uint64), ("reads", C.c_uint64)]
 
 
+# long-insertion position tables (Engine.li): pg_li_window, pg_li_pos, pg_li_sizes; strand 0 = '+' anchors, 1 = '-'
+LI_LONGER, LI_SHORTER = 1, 2
+KERNEL_LI = 11                          # launch-log id of the long-insertion kernels
+LI_POS_DTYPE = np.dtype([("pos", "<u4"), ("first", "<u4"), ("n_reads", "<u4"), ("flags", "<u4")])
+assert LI_POS_DTYPE.itemsize == 16
+
+
+class LiWindow(C.Structure):
+    """pg_li_window"""
+    _fields_ = [("lo", C.c_uint32), ("hi", C.c_uint32)]
+
+
+class LiSizes(C.Structure):
+    """pg_li_sizes"""
+    _fields_ = [("members", C.c_uint64 * 2), ("positions", C.c_uint64 * 2)]
+
+
+def _li_tables(members, positions, nm, npos):
+    mo, po = [0, nm[0], nm[0] + nm[1]], [0, npos[0], npos[0] + npos[1]]
+    return dict(members=[members[mo[s]:mo[s + 1]] for s in range(2)], positions=[positions[po[s]:po[s + 1]] for s in range(2)],
+                members_flat=members, positions_flat=positions, n_members=nm, n_positions=npos)
+
+
 class EventWindow(C.Structure):
     """pg_event_window"""
     _fields_ = [("chr_id", C.c_int32), ("win_end", C.c_uint32), ("region_start", C.c_uint32), ("region_end", C.c_uint32),
@@ -203,7 +226,8 @@ EXPORTS = [
     "pg_device_batch_sv_events_download", "pg_device_batch_sv_events_download_device",
     "pg_device_batch_report_reads", "pg_device_batch_report_reads_device", "pg_device_batch_report_sizes",
     "pg_device_batch_report_download", "pg_device_batch_report_download_device", "pg_device_batch_classify",
-    "pg_device_batch_search_table"]
+    "pg_device_batch_search_table",
+    "pg_device_batch_li", "pg_device_batch_li_sizes", "pg_device_batch_li_download", "pg_device_batch_li_download_device"]
 
 
 def build(force: bool = False) -> str:
@@ -316,6 +340,10 @@ def lib():
     L.pg_device_batch_report_download.argtypes = [vp] * 4
     L.pg_device_batch_report_download_device.argtypes = [vp] * 4
     L.pg_device_batch_classify.argtypes = [vp] * 4
+    L.pg_device_batch_li.argtypes = [vp, vp, vp]
+    L.pg_device_batch_li_sizes.argtypes = [vp, vp, vp]
+    L.pg_device_batch_li_download.argtypes = [vp] * 4
+    L.pg_device_batch_li_download_device.argtypes = [vp] * 4
     _lib = L
     return L
 
@@ -1027,6 +1055,47 @@ class Engine:
             if nid.size != n:
                 raise ValueError(f"classify: name_id: {n} entries are expected, got {nid.size}")
         self._check(self._L.pg_device_batch_classify(self._h, dbatch, C.addressof(prm), nid.ctypes.data if nid is not None and n else None))
+
+    def li_sizes(self, dbatch):
+        """pg_device_batch_li_sizes: (members per strand, positions per strand) of the long-insertion tables built last."""
+        sz = LiSizes()
+        self._check(self._L.pg_device_batch_li_sizes(self._h, dbatch, C.addressof(sz)))
+        return [int(x) for x in sz.members], [int(x) for x in sz.positions]
+
+    def li_download(self, dbatch):
+        """The long-insertion tables the batch holds (pg_device_batch_li_download) as a dict: members and positions, lists of two
+        arrays (uint32 read indices, LI_POS_DTYPE) for the '+' and the '-' anchors; members_flat / positions_flat (back to back)."""
+        nm, npos = self.li_sizes(dbatch)
+        members = np.zeros(sum(nm), dtype=np.uint32)
+        positions = np.zeros(sum(npos), dtype=LI_POS_DTYPE)
+        self._check(self._L.pg_device_batch_li_download(self._h, dbatch, members.ctypes.data if members.size else None,
+                                                        positions.ctypes.data if positions.size else None))
+        return _li_tables(members, positions, nm, npos)
+
+    def _li_build(self, dbatch, lo, hi):
+        if not (0 <= int(lo) < 2 ** 32 and 0 <= int(hi) < 2 ** 32):
+            raise ValueError("li: lo and hi are uint32 positions")
+        w = LiWindow(int(lo), int(hi))
+        self._check(self._L.pg_device_batch_li(self._h, dbatch, C.addressof(w)))
+
+    def li(self, dbatch, lo, hi):
+        """Long-insertion position tables of a batch that holds an events build (pg_device_batch_li): per anchor
+        strand the reads with a close end and no far end that the events build left unused, sorted by the position of their last
+        close point clamped into [lo, hi], and one LI_POS_DTYPE record per distinct position.  Returns li_download(dbatch)."""
+        self._li_build(dbatch, lo, hi)
+        return self.li_download(dbatch)
+
+    def li_tensors(self, dbatch, lo, hi):
+        """li with the tables staying on the GPU (pg_device_batch_li_download_device): a dict of tensors on this engine's device,
+        members int32[total], positions uint8[total, 16], plus n_members / n_positions (lists of two)."""
+        torch, dev = self._torch_ready()
+        self._li_build(dbatch, lo, hi)
+        nm, npos = self.li_sizes(dbatch)
+        out = dict(members=torch.empty(sum(nm), dtype=torch.int32, device=dev), positions=torch.empty((sum(npos), 16), dtype=torch.uint8, device=dev))
+        self._check(self._L.pg_device_batch_li_download_device(self._h, dbatch, out["members"].data_ptr() if sum(nm) else None,
+                                                               out["positions"].data_ptr() if sum(npos) else None))
+        out.update(n_members=nm, n_positions=npos)
+        return out
 
     def events_download(self, dbatch):
         """The event tables the batch holds (pg_device_batch_event_sizes / _events_download) as the dict events() returns."""

@@ -33,6 +33,7 @@ struct CliOptions {
     bool device_classifier = false;        // --device-classifier: windows are classified on the device and written from tables
     int device_classifier_listed = -1;     // --device-classifier-listed 0..4: pg_classify_params::max_listed (-1: not given, no cut)
     bool device_classifier_hints = false;  // --device-classifier-hints: hinted windows are searched on the device-resident path
+    bool device_classifier_li = false;     // --device-classifier-li: -l and -s are written from device tables and summaries
 };
 
 // A flag's word as the parser hands it to the row: as typed, as a number (kinds i and f), as a switch's state (kind u)
@@ -138,20 +139,26 @@ static const CliFlag CLI_DEVICE_FLAGS[] = {
          return true;
      } },
 };
-// ... and the switch that admits window hints there, in a third table that parse_cli walks last
+// ... and the switch that admits window hints there, in a third table that parse_cli walks after it
 static const CliFlag CLI_DEVICE_HINT_FLAGS[] = {
     { "", "--device-classifier-hints", 'u', PG_CLI_SET(o.device_classifier_hints = a.on) },
 };
+// ... and the switch that admits -l and -s there, in a fourth table that parse_cli walks last
+static const CliFlag CLI_DEVICE_LI_FLAGS[] = {
+    { "", "--device-classifier-li", 'u', PG_CLI_SET(o.device_classifier_li = a.on) },
+};
 #undef PG_CLI_SET
 
-// What --device-classifier does not deliver yet (DESIGN.md 7o, 7p): "" or the refusal, looked at after the last flag
+// What --device-classifier does not deliver yet (DESIGN.md 7o, 7p, 7q): "" or the refusal, looked at after the last flag
 inline std::string device_classifier_refusal(const CliOptions &o)
 {
     if (!o.device_classifier)
         return o.device_classifier_listed >= 0  ? "--device-classifier-listed needs --device-classifier"
                : o.device_classifier_hints      ? "--device-classifier-hints needs --device-classifier"
+               : o.device_classifier_li         ? "--device-classifier-li needs --device-classifier"
                                                 : "";
-    const char *with = o.S.Analyze_LI ? "-l" : o.S.report_close_mapped ? "-s" : o.S.only_close_mapped ? "-S" : o.S.report_interchromosomal ? "-I"
+    const bool li = o.device_classifier_li;                // -l and -s are admitted with the switch alone
+    const char *with = o.S.Analyze_LI && !li ? "-l" : o.S.report_close_mapped && !li ? "-s" : o.S.only_close_mapped ? "-S" : o.S.report_interchromosomal ? "-I"
                      : o.detect_dd ? "-q" : o.S.NormalSamples ? "-N" : nullptr;
     if (with) return std::string("--device-classifier cannot be combined with ") + with + ": its report needs points or pairs this path does not deliver";
     if (o.use_bd && !o.device_classifier_hints) return "--device-classifier cannot be combined with --bd-hints on: window hints are not searched on this path";
@@ -189,6 +196,9 @@ inline int parse_cli(int argc, char **argv, CliOptions &o, std::string &err)
                 if (f == x.lg) fl = &x;
         if (!fl)
             for (const CliFlag &x : CLI_DEVICE_HINT_FLAGS)
+                if (f == x.lg) fl = &x;
+        if (!fl)
+            for (const CliFlag &x : CLI_DEVICE_LI_FLAGS)
                 if (f == x.lg) fl = &x;
         if (!fl) {
             err = "unknown argument: " + f;

@@ -1035,6 +1035,7 @@ void Caller::process_window(const Chromosome &chrom, std::vector<SplitRead> &rea
             return;
         }
         es.fallback_windows++;
+        if (S.close_mapped_by_window()) report_close_mapped(reads);      // (the window's one write: the tables route did not make it)
     }
     search_variant(c, 0);
     lap("deletions");

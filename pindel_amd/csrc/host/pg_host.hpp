@@ -214,6 +214,9 @@ struct Settings {                 // the flags the downstream steps read (src/fn
     // copies without points, lists and pair fields, and writes the reports from tables, records and summaries alone
     // (Caller::process_window_tables).
     bool use_report_reads = false;
+    // ... on that route -s is written per window by process_window -- from the summaries, or from the points of a
+    // window that falls back -- and not by the pipeline before the far end
+    bool close_mapped_by_window() const { return use_events && use_sv_events && use_report_reads && report_close_mapped && !only_close_mapped; }
 };
 
 // What the events path of the last run did.  windows: six values per window process_window saw with use_events set -- chromosome
@@ -229,6 +232,26 @@ struct EventPathStats {
     std::vector<uint32_t> windows;
 };
 EventPathStats &event_path_stats();
+
+// The long-insertion position tables (include/pindel_pg.h "device classifier: long-insertion position tables") on
+// the host.  LiReadIn: what the contract reads of one read of the batch; LiTables: per strand (0 '+', 1 '-') the member list and
+// the position table.  li_tables_from_reads states the contract in plain loops: the reference pg_device_batch_li is compared with,
+// byte for byte, and what the existing _LI path builds its counters from.  recs (nullable): the events build's per-read records;
+// a read is used if its `used` is set or its record carries PG_EVR_BOXED or PG_EVR_USED.
+struct LiReadIn {
+    bool in_window = true;               // chr_id == the events build's window chr_id
+    bool has_close = false, has_far = false;
+    bool used = false;
+    char strand = 0;                     // the anchor strand
+    uint32_t close_abs = 0;              // UP_Close.back().AbsLoc
+    int32_t close_len = 0;               // UP_Close.back().LengthStr
+    int32_t read_length = 0;             // the post-state read length
+};
+struct LiTables {
+    std::vector<uint32_t> members[2];
+    std::vector<pg_li_pos> positions[2];
+};
+void li_tables_from_reads(const std::vector<LiReadIn> &in, const pg_event_read *recs, uint32_t lo, uint32_t hi, LiTables &out);
 
 int load_fasta(const std::string &path, std::vector<Chromosome> &out, unsigned spacer, std::string &err);
 
@@ -321,6 +344,25 @@ public:
                                     unsigned region_start, unsigned region_end, const pg_event_read *recs, const pg_event_sizes &sizes,
                                     const pg_event *events, const pg_sv_event_sizes &sv_sizes, const pg_event *sv_events,
                                     const pg_report_read *records, const pg_report_summary *summaries, bool summaries_applied);
+    // -l and -s on the tables path, for reads without points:
+    //   li_window                        the buffered window of SortOutputLI for [win_start, win_end): four times g_maxInsertSize on
+    //                                    either side (every read that entered a search so far must have been noted: note_insert_size)
+    //   write_li_from_tables             _LI of the window from its position tables (over `reads`, the window's reads in batch order) and
+    //                                    the summaries' close lengths; call it after process_window_from_tables, where process_window
+    //                                    runs SortOutputLI
+    //   report_close_mapped_summaries    report_close_mapped for reads whose summaries have been applied: PG_RS_CLOSE stands for
+    //                                    a non-empty UP_Close
+    void li_window(const Chromosome &chrom, unsigned win_start, unsigned win_end, unsigned &lo, unsigned &hi) const;
+    void write_li_from_tables(const Chromosome &chrom, std::vector<SplitRead> &reads, unsigned win_start, unsigned win_end,
+                              const LiTables &tables, const pg_report_summary *summaries);
+    void report_close_mapped_summaries(const std::vector<SplitRead> &reads, const pg_report_summary *summaries);
+    // tests: CurrentChrMask of `chrom` as earlier reports would have left it (padded positions)
+    void set_marks_for_test(const Chromosome &chrom, const uint32_t *marks, uint32_t n)
+    {
+        mask_chr_ = &chrom;
+        chr_marks_.clear();
+        if (n) chr_marks_.insert(marks, marks + n);
+    }
     ~Caller();
 
 private:
@@ -388,7 +430,12 @@ private:
     void output_td(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsigned e, unsigned rs, unsigned re);
     void output_inv(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsigned e, unsigned rs, unsigned re);
     void output_short_inv(Ctx &c, std::vector<SplitRead> &g, unsigned s, unsigned e);
+    // SortOutputLI in two parts: the position tables of the window's reads (li_tables_from_reads over their points -- or, on the
+    // tables route of the events path, the ones process_window_events left in Ctx before the reads lost their points), then
+    // sort_output_li_tables: the walk over the buffered window, the pairing, the event membership and the text, from the tables,
+    // chr_marks_, close_len (UP_Close.back().LengthStr per read) and fields a read without points has
     void sort_output_li(Ctx &c, unsigned win_start, unsigned win_end);
+    void sort_output_li_tables(Ctx &c, unsigned lo, unsigned hi, const LiTables &tables, const int16_t *close_len);
     // -I (pg_host_int.cpp): the window's reads whose far end lies on another chromosome, copied before the classifiers
     // touch them (InterChromosome_SR, pindel.cpp:1905-1917), and their calls, appended to <prefix>_INT after the window's
     // other reports (pindel.cpp:1940-1942)

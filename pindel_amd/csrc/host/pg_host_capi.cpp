@@ -312,6 +312,9 @@ int pgh_call_from_points_sv_events(const char *fasta_path, const char *reads_pat
  * tables -> report records -> summaries, the window's reads are replaced by copies without points, lists and pair fields, and
  * Caller::process_window_tables writes the reports from tables, records and summaries alone.  A window with an unresolved read, or
  * whose tables do not fit, takes the existing path and is counted, as before.  The reports are the bytes pgh_call_from_points writes.
+ * With analyze_li / report_close_mapped _LI and _CloseEndMapped take the same route: the host statement builds the
+ * window's long-insertion tables while its reads still have points, _CloseEndMapped is written from the summaries, and the shared
+ * consumer writes _LI from the tables after the reads were stripped; a window that falls back writes both the existing way.
  */
 int pgh_call_from_points_report_reads(const char *fasta_path, const char *reads_path, const char *out_prefix, const pgh_settings *st,
                                       uint32_t n_reads, const uint64_t *close_off, const pg_point *close_pts, const uint64_t *far_off,
@@ -719,6 +722,132 @@ int pgh_report_reads_from_lists(uint32_t n_reads, const uint8_t *strand, const u
     if (n_reads) memcpy(out_summaries, summaries.data(), (size_t)n_reads * sizeof(pg_report_summary));
     sizes->records = records.size();
     sizes->reads = n_reads;
+    return 0;
+}
+
+/*
+ * The long-insertion position tables (pindel_pg.h "long-insertion position tables"), on the host: the plain-loop
+ * statement (li_tables_from_reads) the device entry pg_device_batch_li is compared with, byte for byte.  The reads as they were
+ * handed to the search (seq, seq_off, strand, chr_id) with the rc flags; the post-state read length is taken from the read as rc_flag
+ * applications of setUnmatchedSeq(ReverseComplement()) leave it.  close_off / close_pts: the expanded close points (the last one
+ * counts); far_off: only whether the read has a far end.  recs: the events build's per-read records, win_chr its window's chr_id.
+ * out_members, out_positions: room for n_reads entries each, both strands back to back; sizes: what was filled.  -1: a null array
+ * or lo > hi.
+ */
+int pgh_li_tables_from_lists(uint32_t n_reads, const uint8_t *seq, const uint64_t *seq_off, const uint8_t *strand, const int32_t *chr_id,
+                             const uint8_t *rc_flag, const uint64_t *close_off, const pg_point *close_pts, const uint64_t *far_off,
+                             const pg_event_read *recs, int32_t win_chr, uint32_t lo, uint32_t hi, uint32_t *out_members,
+                             pg_li_pos *out_positions, pg_li_sizes *sizes)
+{
+    if (!sizes || (n_reads && (!seq_off || !strand || !chr_id || !rc_flag || !close_off || !far_off || !recs || !out_members || !out_positions))) {
+        g_err = "pgh_li_tables_from_lists: null array";
+        return -1;
+    }
+    if (lo > hi) {
+        g_err = "pgh_li_tables_from_lists: lo > hi";
+        return -1;
+    }
+    std::vector<LiReadIn> in(n_reads);
+    for (uint32_t i = 0; i < n_reads; i++) {
+        LiReadIn &e = in[i];
+        e.in_window = chr_id[i] == win_chr;
+        e.has_close = close_off[i + 1] > close_off[i];
+        e.has_far = far_off[i + 1] > far_off[i];
+        e.strand = (char)strand[i];
+        SplitRead r;
+        r.UnmatchedSeq.assign((const char *)seq + seq_off[i], (size_t)(seq_off[i + 1] - seq_off[i]));
+        pg_adapter::apply_rc_flag(r, rc_flag[i]);
+        e.read_length = (int32_t)(short)r.UnmatchedSeq.size();
+        if (e.has_close) {
+            const UniquePoint last = to_unique_point(close_pts[close_off[i + 1] - 1]);
+            e.close_abs = last.AbsLoc;
+            e.close_len = last.LengthStr;
+        }
+    }
+    LiTables t;
+    li_tables_from_reads(in, recs, lo, hi, t);
+    size_t m = 0, p = 0;
+    for (int s = 0; s < 2; s++) {
+        if (!t.members[s].empty()) memcpy(out_members + m, t.members[s].data(), t.members[s].size() * sizeof(uint32_t));
+        if (!t.positions[s].empty()) memcpy(out_positions + p, t.positions[s].data(), t.positions[s].size() * sizeof(pg_li_pos));
+        m += t.members[s].size();
+        p += t.positions[s].size();
+        sizes->members[s] = t.members[s].size();
+        sizes->positions[s] = t.positions[s].size();
+    }
+    return 0;
+}
+
+/*
+ * Test hook: the single consumer of the long-insertion tables (Caller::sort_output_li_tables) on tables made by hand.  One
+ * chromosome chr_name / chr_seq (padded), a window [win_start, win_end) whose buffered window follows from max_insert_size as in
+ * SortOutputLI, n_reads reads -- sequence, anchor strand and close length each; read i is named "r<i>", tagged "S", mapped at i --
+ * and the tables over them (members / positions of both strands back to back, sizes).  marks: n_marks padded positions an earlier
+ * report has marked.  Appends to <out_prefix>_LI.  -1: a table that points outside its arrays.
+ */
+int pgh_li_write_from_tables(const char *chr_name, const char *chr_seq, uint64_t chr_len, uint32_t spacer, uint32_t min_support,
+                             uint32_t win_start, uint32_t win_end, int32_t max_insert_size, uint32_t n_reads, const uint8_t *seq,
+                             const uint64_t *seq_off, const uint8_t *strand, const int16_t *close_len, const uint32_t *members,
+                             const pg_li_pos *positions, const pg_li_sizes *sizes, const uint32_t *marks, uint32_t n_marks,
+                             const char *out_prefix)
+{
+    if (!chr_name || !chr_seq || !sizes || !out_prefix || (n_reads && (!seq || !seq_off || !strand || !close_len))) {
+        g_err = "pgh_li_write_from_tables: null array";
+        return -1;
+    }
+    LiTables t;
+    size_t m = 0, p = 0;
+    for (int s = 0; s < 2; s++) {
+        for (uint64_t k = 0; k < sizes->members[s]; k++) {
+            if (members[m + k] >= n_reads) {
+                g_err = "pgh_li_write_from_tables: a member outside the reads";
+                return -1;
+            }
+            t.members[s].push_back(members[m + k]);
+        }
+        for (uint64_t k = 0; k < sizes->positions[s]; k++) {
+            const pg_li_pos &q = positions[p + k];
+            if ((uint64_t)q.first + q.n_reads > sizes->members[s]) {
+                g_err = "pgh_li_write_from_tables: a position outside its member list";
+                return -1;
+            }
+            t.positions[s].push_back(q);
+        }
+        m += sizes->members[s];
+        p += sizes->positions[s];
+    }
+    std::vector<Chromosome> genome(1);
+    genome[0].name = chr_name;
+    genome[0].seq.assign(chr_seq, (size_t)chr_len);
+    Settings S;
+    S.spacer = spacer;
+    S.NumRead2ReportCutOff = min_support;
+    S.Analyze_LI = true;
+    Caller caller(S, &genome, out_prefix, false);
+    caller.note_insert_size(max_insert_size);
+    std::vector<SplitRead> reads(n_reads);
+    std::vector<pg_report_summary> summaries(n_reads);
+    for (uint32_t i = 0; i < n_reads; i++) {
+        SplitRead &r = reads[i];
+        r.Name = "r" + std::to_string(i);
+        r.UnmatchedSeq.assign((const char *)seq + seq_off[i], (size_t)(seq_off[i + 1] - seq_off[i]));
+        r.ReadLength = (short)r.UnmatchedSeq.size();
+        r.MatchedD = (char)strand[i];
+        r.MatchedRelPos = i;
+        r.MS = 60;
+        r.InsertSize = (short)max_insert_size;
+        r.Tag = "S";
+        r.FragName = chr_name;
+        r.chr_id = 0;
+        pg_report_summary &s = summaries[i];
+        memset(&s, 0, sizeof s);
+        s.close_len = close_len[i];
+        s.flags = PG_RS_CLOSE;
+    }
+    caller.apply_summaries(reads, summaries.data(), false);
+    caller.begin_region();
+    caller.set_marks_for_test(genome[0], marks, n_marks);
+    caller.write_li_from_tables(genome[0], reads, win_start, win_end, t, summaries.data());
     return 0;
 }
 

@@ -477,6 +477,29 @@ bool Caller::process_window_events(Ctx &c)
         std::vector<pg_report_read> records;
         std::vector<pg_report_summary> summaries;
         report_reads_from_lists(in, tabs.reads.data(), tabs.members, svt.members, records, summaries);
+        // -s and -l on this route: _CloseEndMapped from the summaries, the long-insertion tables from the host
+        // statement while the reads still have their points; sort_output_li then finds them in the frame
+        if (S.report_close_mapped) report_close_mapped_summaries(reads, summaries.data());
+        if (S.Analyze_LI) {
+            unsigned lo, hi;
+            li_window(*c.chrom, c.win_start, c.win_end, lo, hi);
+            std::vector<LiReadIn> li_in(n);
+            c.li_close_len.assign(n, 0);
+            for (size_t k = 0; k < n; k++) {
+                const SplitRead &r = reads[k];
+                LiReadIn &e = li_in[k];
+                e.has_close = !r.UP_Close.empty();
+                e.has_far = !r.UP_Far.empty();
+                e.strand = r.MatchedD;
+                e.read_length = r.getReadLength();
+                if (e.has_close) {
+                    e.close_abs = r.UP_Close.back().AbsLoc;
+                    e.close_len = c.li_close_len[k] = r.UP_Close.back().LengthStr;
+                }
+            }
+            li_tables_from_reads(li_in, tabs.reads.data(), lo, hi, c.li);
+            c.li_ready = true;
+        }
         for (SplitRead &r : reads) {
             SplitRead bare;
             bare.Name.swap(r.Name);

@@ -24,6 +24,10 @@ struct Caller::Ctx {
     unsigned NumBoxes;
     unsigned win_start, win_end;
     unsigned region_start, region_end;
+    // the tables route: the window's long-insertion tables and close lengths, built before its reads lost their points
+    bool li_ready = false;
+    LiTables li;
+    std::vector<int16_t> li_close_len;
 };
 
 namespace detail {

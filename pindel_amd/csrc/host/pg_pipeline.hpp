@@ -262,7 +262,7 @@ int run_pipeline(const std::vector<Chromosome> &genome, const std::vector<Region
             }
             for (SplitRead &r : reads)
                 if (!r.UP_Close.empty()) kept.push_back(std::move(r));      // `reads` is not used after this loop
-            if (S.close_mapped_output() && !kept.empty()) caller.report_close_mapped(kept);
+            if (S.close_mapped_output() && !S.close_mapped_by_window() && !kept.empty()) caller.report_close_mapped(kept);
             t_keep += now() - t0; t0 = now();
             if (!S.only_close_mapped && !kept.empty() && !far_done && (rc = far_search(chrom, (int)c, kept, ws, we))) {
                 err = "far-end search step failed";
@@ -564,7 +564,7 @@ int run_bam_pipeline(const std::vector<Chromosome> &genome, const std::vector<Re
         if (view.release) view.release();
         }
         caller.note_close_mapped_all(kept);
-        if (S.close_mapped_output() && !kept.empty()) caller.report_close_mapped(kept);
+        if (S.close_mapped_output() && !S.close_mapped_by_window() && !kept.empty()) caller.report_close_mapped(kept);
         t_keep += now() - t0; t0 = now();
         if (!S.only_close_mapped && !kept.empty() && !far_done && (rc = far_search(chrom, (int)c, kept, win.ws, win.we))) {
             err = "far-end search step failed";

@@ -365,6 +365,7 @@ struct FarSearch {
 // fit: then pg_device_batch_download fetches them and the window goes on through the existing steps.
 struct DeviceClassifierStats {
     size_t windows = 0, from_tables = 0, fallbacks = 0, unresolved = 0, records = 0, runs_kept = 0, hinted = 0;
+    size_t li_windows = 0, li_bytes = 0;         // windows with LI tables, and the bytes downloaded for them
 };
 struct DeviceClassifier {
     const Seams &s;
@@ -471,12 +472,41 @@ struct DeviceClassifier {
             }
         }
         if (es.unresolved == 0 && fits) {
+            // -l (--device-classifier-li): the long-insertion position tables of the window, built on the device from
+            // the records the classify left; the pipeline has noted every read's insert size before this call
+            LiTables li;
+            const bool want_li = s.o.S.Analyze_LI && n_close;
+            if (want_li) {
+                pg_li_window lw;
+                caller.li_window(chrom, ws, we, lw.lo, lw.hi);
+                pg_li_sizes ls;
+                if ((rc = pg_device_batch_li(ctx, b, &lw)) || (rc = pg_device_batch_li_sizes(ctx, b, &ls))) return rc;
+                std::vector<uint32_t> members((size_t)(ls.members[0] + ls.members[1]));
+                std::vector<pg_li_pos> positions((size_t)(ls.positions[0] + ls.positions[1]));
+                if ((rc = pg_device_batch_li_download(ctx, b, members.data(), positions.data()))) return rc;
+                size_t m0 = 0, p0 = 0;
+                bool li_fits = true;
+                for (int k = 0; k < 2; k++) {
+                    li.members[k].assign(members.begin() + m0, members.begin() + m0 + (size_t)ls.members[k]);
+                    li.positions[k].assign(positions.begin() + p0, positions.begin() + p0 + (size_t)ls.positions[k]);
+                    for (uint32_t m : li.members[k]) li_fits = li_fits && m < n;
+                    for (const pg_li_pos &q : li.positions[k]) li_fits = li_fits && (uint64_t)q.first + q.n_reads <= ls.members[k];
+                    m0 += (size_t)ls.members[k];
+                    p0 += (size_t)ls.positions[k];
+                }
+                if (!li_fits) return fail("the long-insertion tables of a window do not fit its reads", (int)PG_E_DEVICE);
+                st.li_windows++;
+                st.li_bytes += members.size() * sizeof(uint32_t) + positions.size() * sizeof(pg_li_pos);
+            }
             s.counts.t_search += now_s() - t0;
             if (n_close) {                       // (a window without a close end has nothing to classify, as in the existing steps)
                 caller.apply_summaries(reads, summaries.data(), bam);
                 if (after_close) after_close();
+                // -s: the reads that kept a close end, in input order, the sequence as rc_flag left it
+                if (s.o.S.report_close_mapped) caller.report_close_mapped_summaries(reads, summaries.data());
                 caller.process_window_from_tables(chrom, reads, ws, we, bed_start, bed_end, recs.data(), es, events.data(), ss, sv_events.data(),
                                                   records.data(), summaries.data(), true);
+                if (want_li) caller.write_li_from_tables(chrom, reads, ws, we, li, summaries.data());
             } else if (after_close) after_close();
             uint64_t close_runs = 0, far_runs = 0;
             (void)pg_device_batch_result_sizes(ctx, b, &close_runs, &far_runs);
@@ -637,6 +667,7 @@ int main(int argc, char **argv)
                "%zu runs not downloaded", dc_stats.windows, dc_stats.from_tables, dc_stats.fallbacks, dc_stats.unresolved, dc_stats.records,
                dc_stats.runs_kept);
         if (o.device_classifier_hints) printf(", %zu hinted windows", dc_stats.hinted);
+        if (o.device_classifier_li) printf(", %zu windows with LI tables", dc_stats.li_windows);
         printf("\n");
     }
     // the phases the reference's Timer reports (pindel.cpp:1990-1996), wall-clock seconds
@@ -644,5 +675,7 @@ int main(int argc, char **argv)
            t_loaded - t_start, counts.t_search, now_s() - t_loaded - counts.t_search);
     if (o.S.Analyze_LI && !o.S.only_close_mapped)
         printf("pindel_pg: long insertions (_LI, host, part of classification + reports) %.3f s\n", li_seconds);
+    if (o.device_classifier_li && o.S.Analyze_LI)
+        printf("pindel_pg: long-insertion tables downloaded: %zu bytes for %zu reads\n", dc_stats.li_bytes, n_reads);
     return 0;
 }

@@ -320,6 +320,11 @@ struct pg_device_batch {
     // the candidate lists of the last pg_device_batch_classify: they never leave the device
     pg_variant_cand *cl_cands = nullptr, *cl_sv_cands = nullptr;   // n x 2 x PG_VARIANT_CANDS; n x PG_SV_SLOTS
     uint8_t *cl_counts = nullptr, *cl_sv_counts = nullptr;         // n x 2; n x PG_SV_KINDS
+    // the long-insertion tables of the last pg_device_batch_li; an events build discards them
+    uint32_t *li_members = nullptr;            // n: the two member lists back to back
+    pg_li_pos *li_positions = nullptr;         // n: the two position tables back to back
+    pg_li_sizes li_sizes{};
+    bool li_built = false;
 };
 
 struct pg_result {
@@ -476,6 +481,11 @@ void free_batch_buffers(pg_device_batch *b)
         if (p) (void)hipFree(p);
     for (void *p : { (void *)b->rr_records, (void *)b->rr_summaries, (void *)b->cl_cands, (void *)b->cl_sv_cands, (void *)b->cl_counts, (void *)b->cl_sv_counts })
         if (p) (void)hipFree(p);
+    for (void *p : { (void *)b->li_members, (void *)b->li_positions })
+        if (p) (void)hipFree(p);
+    b->li_members = nullptr;
+    b->li_positions = nullptr;
+    b->li_built = false;
     b->rr_records = nullptr;
     b->rr_summaries = nullptr;
     b->rr_built = false;
@@ -2501,6 +2511,7 @@ int build_events(pg_ctx *ctx, pg_device_batch *b, const pg_event_window *w, cons
     b->ev_built = false;
     b->svev_built = false;                                    // (the SV tables belong to the records of the build they were made from)
     b->rr_built = false;                                      // (... and so do the report records)
+    b->li_built = false;                                      // (... and the long-insertion tables: they read the records' Used state)
     b->ev_sizes = pg_event_sizes{};
     b->ev_window = *w;
     const size_t n = b->n;
@@ -3013,6 +3024,128 @@ int pg_device_batch_report_download_device(pg_ctx *ctx, pg_device_batch *b, pg_r
         (d_summaries && (rc = check_device_ptr(ctx, d_summaries, (size_t)b->n * sizeof(pg_report_summary), 4, "report download: summaries"))))
         return rc;
     return report_download(ctx, b, d_records, d_summaries, hipMemcpyDeviceToDevice);
+}
+
+// ---- ... its sixth part (pg_li.hip): the long-insertion position tables
+int pg_device_batch_li(pg_ctx *ctx, pg_device_batch *b, const pg_li_window *window)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
+    if (int rc = stale_batch(ctx, b)) return rc;
+    ctx->last_ms = 0.0;
+    if (b->n && !b->searched) return fail(ctx, PG_E_INVALID, "the batch has not been searched: no close and far ends to classify");
+    if (!b->ev_built) return fail(ctx, PG_E_INVALID, "li: pg_device_batch_events has not been run on this batch");
+    if (!window) return fail(ctx, PG_E_INVALID, "li: null pg_li_window");
+    if (window->lo > window->hi) return fail(ctx, PG_E_INVALID, "li: lo > hi");
+    b->li_built = false;
+    b->li_sizes = pg_li_sizes{};
+    const size_t n = b->n;
+    if (!n) {                                                 // nothing is launched for an empty batch
+        b->li_built = true;
+        return PG_OK;
+    }
+    int rc;
+    // (each buffer on its own: an allocation that failed in an earlier call is tried again, never launched with)
+    if ((!b->li_members && (rc = dev_alloc(ctx, &b->li_members, n))) || (!b->li_positions && (rc = dev_alloc(ctx, &b->li_positions, n)))) return rc;
+    EventTemps tmp;
+    PgLiArgs a{};
+    const size_t n_blk = n / PG_EV_BLOCK + 2;
+    if ((rc = EV_TAKE(tmp, ctx, a.rec_a, n)) || (rc = EV_TAKE(tmp, ctx, a.rec_b, n)) || (rc = EV_TAKE(tmp, ctx, a.flag, n)) ||
+        (rc = EV_TAKE(tmp, ctx, a.rank, n)) || (rc = EV_TAKE(tmp, ctx, a.blk, n_blk)) || (rc = EV_TAKE(tmp, ctx, a.pfirst, n + 1)) ||
+        (rc = EV_TAKE(tmp, ctx, a.digit_cnt, 256 * n_blk + 1)) || (rc = EV_TAKE(tmp, ctx, a.info, 1)))
+        return rc;
+    a.out = b->out_rec;
+    a.pool_runs = (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS;
+    a.seq = b->seq;
+    a.seq_off = b->seq_off;
+    a.strand = b->strand;
+    a.chr = b->chr;
+    a.reads = b->ev_reads;
+    a.n = b->n;
+    a.chr_id = b->ev_window.chr_id;
+    a.lo = window->lo;
+    a.hi = window->hi;
+    a.members = b->li_members;
+    a.positions = b->li_positions;
+    PgLaunchRec rec{};
+    rec.kernel = PG_KERNEL_LI;
+    rec.blocks = (int32_t)PG_EV_BLOCK;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if (pg_li_gather_launch(&a, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the long-insertion gather kernels failed");
+    log_launch(ctx, rec);
+    PgLiInfo info;
+    HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (info.n_li > n || info.n_plus > info.n_li) return fail(ctx, PG_E_DEVICE, "li: the count of long-insertion reads exceeds the batch");
+    const uint32_t n_li = info.n_li, n_plus = info.n_plus;
+    if (n_li) {                                               // (no LI read: nothing below indexes an empty array)
+        PgLiRec *src = a.rec_b, *dst = a.rec_a;
+        for (int pass = 0; pass < PG_LI_SORT_PASSES; pass++) {
+            const int word = pass >= 4 ? 1 : 0, shift = pass >= 4 ? 0 : pass * 8;
+            if ((((info.key_or[word] ^ info.key_and[word]) >> shift) & 0xffu) == 0u) continue;      // the byte is constant: no pass
+            if (pg_li_sort_pass_launch(&a, src, dst, n_li, pass, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching a long-insertion sort pass failed");
+            log_launch(ctx, rec);
+            std::swap(src, dst);
+        }
+        if (pg_li_tables_launch(&a, src, n_li, n_plus, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the long-insertion table kernels failed");
+        log_launch(ctx, rec);
+        HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->last_ms = ms;
+    if (n_li) {
+        if (info.n_pos > n_li || info.pos_plus > info.n_pos) return fail(ctx, PG_E_DEVICE, "li: inconsistent table sizes");
+        b->li_sizes.members[0] = n_plus;
+        b->li_sizes.members[1] = n_li - n_plus;
+        b->li_sizes.positions[0] = info.pos_plus;
+        b->li_sizes.positions[1] = info.n_pos - info.pos_plus;
+    }
+    b->li_built = true;
+    return PG_OK;
+}
+
+static const char *const NO_LI = "no long-insertion tables: pg_device_batch_li has not been run on this batch since its events build";
+
+int pg_device_batch_li_sizes(pg_ctx *ctx, pg_device_batch *b, pg_li_sizes *sizes)
+{
+    use_device(ctx);
+    if (!ctx || !b || !sizes) return PG_E_INVALID;
+    if (!b->li_built) return fail(ctx, PG_E_INVALID, NO_LI);
+    *sizes = b->li_sizes;
+    return PG_OK;
+}
+
+static int li_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *members, pg_li_pos *positions, hipMemcpyKind kind)
+{
+    const size_t nm = (size_t)(b->li_sizes.members[0] + b->li_sizes.members[1]), np = (size_t)(b->li_sizes.positions[0] + b->li_sizes.positions[1]);
+    if (members && nm) HIP_TRY(ctx, hipMemcpy(members, b->li_members, nm * sizeof(uint32_t), kind));
+    if (positions && np) HIP_TRY(ctx, hipMemcpy(positions, b->li_positions, np * sizeof(pg_li_pos), kind));
+    return PG_OK;
+}
+
+int pg_device_batch_li_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *members, pg_li_pos *positions)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (!b->li_built) return fail(ctx, PG_E_INVALID, NO_LI);
+    return li_download(ctx, b, members, positions, hipMemcpyDeviceToHost);
+}
+
+int pg_device_batch_li_download_device(pg_ctx *ctx, pg_device_batch *b, uint32_t *d_members, pg_li_pos *d_positions)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (!b->li_built) return fail(ctx, PG_E_INVALID, NO_LI);
+    const size_t nm = (size_t)(b->li_sizes.members[0] + b->li_sizes.members[1]), np = (size_t)(b->li_sizes.positions[0] + b->li_sizes.positions[1]);
+    int rc;
+    if ((d_members && (rc = check_device_ptr(ctx, d_members, nm * sizeof(uint32_t), 4, "li download: members"))) ||
+        (d_positions && (rc = check_device_ptr(ctx, d_positions, np * sizeof(pg_li_pos), 4, "li download: positions"))))
+        return rc;
+    return li_download(ctx, b, d_members, d_positions, hipMemcpyDeviceToDevice);
 }
 
 // ---- one call per window: the two candidate kernels, both table builds and the report records, the lists staying with the batch

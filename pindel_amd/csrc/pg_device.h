@@ -528,6 +528,43 @@ struct PgReportArgs {
 int pg_report_launch(const struct PgReportArgs *a, void *stream);
 // the count bytes of n reads cut to max_listed pairs (pg_device_batch_classify); n = 0 launches nothing
 int pg_report_cut_launch(uint8_t *counts, uint8_t *sv_counts, uint32_t n, uint32_t max_listed, void *stream);
+// Long-insertion position tables (pg_li.hip): the reads with a close end and no far end that the events build left
+// unused, compacted in ascending read index, ordered by (strand, clamped position) with stable counting passes, then positions.
+enum { PG_KERNEL_LI = 11 };           // ... continued: the launch-log id of pg_device_batch_li
+#define PG_LI_SORT_PASSES 5           // the four bytes of the position, least significant first, then the strand
+struct PgLiRec { uint32_t w[4]; };    // one LI read: clamped position, read, strand (0 '+', 1 '-'), PG_LI_* of this read
+struct PgLiInfo {                     // what the host reads back
+    uint32_t n_li;                    // LI reads of both strands
+    uint32_t n_plus;                  // ... of them with a '+' anchor
+    uint32_t key_or[2], key_and[2];   // over w[0] and w[2] of the compacted records: a byte equal in both is constant
+    uint32_t n_pos, pos_plus;         // positions of both strands; of the '+' strand
+};
+struct PgLiArgs {
+    const PgOutRec *out;
+    unsigned long long pool_runs;
+    const uint8_t *seq;
+    const uint64_t *seq_off;
+    const uint8_t *strand;
+    const int32_t *chr;
+    const pg_event_read *reads;       // n: the events build's records
+    uint32_t n;
+    int32_t chr_id;                   // the events build's window chr_id
+    uint32_t lo, hi;
+    uint32_t *members;                // n
+    pg_li_pos *positions;             // n
+    struct PgLiRec *rec_a, *rec_b;    // n each
+    uint8_t *flag;                    // n
+    uint32_t *rank, *blk;             // n; n / PG_EV_BLOCK + 2
+    uint32_t *pfirst;                 // n + 1
+    uint32_t *digit_cnt;              // 256 x (n / PG_EV_BLOCK + 2) + 1
+    struct PgLiInfo *info;
+};
+// the LI reads flagged and compacted into rec_b (ascending read index); info->n_li, n_plus and the key masks are then valid
+int pg_li_gather_launch(const struct PgLiArgs *a, void *stream);
+// one stable counting pass over key byte `pass` of src[0 .. n_li) into dst
+int pg_li_sort_pass_launch(const struct PgLiArgs *a, const struct PgLiRec *src, struct PgLiRec *dst, uint32_t n_li, int pass, void *stream);
+// head flags, members, positions over the sorted records; fills the rest of info.  n_li > 0
+int pg_li_tables_launch(const struct PgLiArgs *a, const struct PgLiRec *sorted, uint32_t n_li, uint32_t n_plus, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -544,6 +544,90 @@ def report_reads_from_lists(anchor_strand, rc_flag, close_off, close_pts, far_of
     return records[:int(sizes.records)], summaries[:n]
 
 
+# long-insertion position tables (include/pindel_pg.h): strand 0 = '+' anchors, 1 = '-' anchors
+LI_LONGER, LI_SHORTER = 1, 2
+LI_POS_DTYPE = np.dtype([("pos", "<u4"), ("first", "<u4"), ("n_reads", "<u4"), ("flags", "<u4")])
+assert LI_POS_DTYPE.itemsize == 16
+
+
+class LiSizes(C.Structure):
+    """pg_li_sizes"""
+    _fields_ = [("members", C.c_uint64 * 2), ("positions", C.c_uint64 * 2)]
+
+
+def li_tables(members, positions, sizes):
+    """The flat outputs of a long-insertion entry as a dict: members / positions (lists of the two strands' arrays), the flat arrays
+    (members_flat, positions_flat) and the sizes (n_members, n_positions)."""
+    nm = [int(x) for x in sizes.members]
+    npos = [int(x) for x in sizes.positions]
+    mo, po = [0, nm[0], nm[0] + nm[1]], [0, npos[0], npos[0] + npos[1]]
+    members, positions = members[:mo[2]], positions[:po[2]]
+    return dict(members=[members[mo[s]:mo[s + 1]] for s in range(2)], positions=[positions[po[s]:po[s + 1]] for s in range(2)],
+                members_flat=members, positions_flat=positions, n_members=nm, n_positions=npos)
+
+
+def li_tables_from_lists(seq, seq_off, anchor_strand, chr_id, rc_flag, close_off, close_pts, far_off, reads, win_chr, lo, hi):
+    """The long-insertion position tables on the host (pgh_li_tables_from_lists): the reference Engine.li is compared
+    with, byte for byte.  Reads, rc flags and close points as events_from_lists takes them; far_off: the far ends' CSR offsets (only
+    whether a read has one counts); reads: the events build's per-read records (EVENT_READ_DTYPE[n]); win_chr: that build's window
+    chr_id; [lo, hi]: the buffered window.  Returns li_tables(...)."""
+    L = lib()
+    n = len(seq_off) - 1
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    strand = np.ascontiguousarray(anchor_strand, dtype=np.uint8)
+    chr_id = np.ascontiguousarray(chr_id, dtype=np.int32)
+    rc_flag = np.ascontiguousarray(rc_flag, dtype=np.uint8)
+    close_off = np.ascontiguousarray(close_off, dtype=np.uint64)
+    far_off = np.ascontiguousarray(far_off, dtype=np.uint64)
+    close_pts = np.ascontiguousarray(close_pts)
+    recs = np.ascontiguousarray(reads, dtype=EVENT_READ_DTYPE)
+    assert close_pts.dtype.itemsize == 12
+    assert len(strand) == n and len(chr_id) == n and len(rc_flag) == n and len(close_off) == n + 1 and len(far_off) == n + 1 and len(recs) == n
+    members = np.zeros(max(n, 1), dtype=np.uint32)
+    positions = np.zeros(max(n, 1), dtype=LI_POS_DTYPE)
+    sizes = LiSizes()
+    L.pgh_li_tables_from_lists.argtypes = [C.c_uint32] + [C.c_void_p] * 9 + [C.c_int32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 3
+    rc = L.pgh_li_tables_from_lists(n, seq.ctypes.data, seq_off.ctypes.data, strand.ctypes.data, chr_id.ctypes.data, rc_flag.ctypes.data,
+                                    close_off.ctypes.data, close_pts.ctypes.data, far_off.ctypes.data, recs.ctypes.data, int(win_chr),
+                                    int(lo), int(hi), members.ctypes.data, positions.ctypes.data, C.addressof(sizes))
+    if rc:
+        raise ValueError("pgh_li_tables_from_lists: " + (L.pgh_last_error() or b"").decode())
+    return li_tables(members, positions, sizes)
+
+
+def li_write_from_tables(chrom, out_prefix, seqs, anchor_strand, close_len, members, positions, n_members, n_positions, win_start,
+                         win_end, max_insert_size, min_support=1, marks=(), spacer=100000):
+    """Test hook (pgh_li_write_from_tables): the single consumer of the long-insertion tables on tables made by hand.  chrom: (name,
+    padded sequence); seqs: the reads' sequences (bytes each); members / positions: both strands back to back, n_members /
+    n_positions their sizes per strand; marks: padded positions an earlier report marked.  Appends to <out_prefix>_LI."""
+    L = lib()
+    n = len(seqs)
+    seq = np.frombuffer(b"".join(seqs), dtype=np.uint8) if n else np.zeros(0, dtype=np.uint8)
+    seq_off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.uint64)
+    strand = np.ascontiguousarray(anchor_strand, dtype=np.uint8)
+    close_len = np.ascontiguousarray(close_len, dtype=np.int16)
+    members = np.ascontiguousarray(members, dtype=np.uint32)
+    positions = np.ascontiguousarray(positions, dtype=LI_POS_DTYPE)
+    marks = np.ascontiguousarray(marks, dtype=np.uint32)
+    sizes = LiSizes()
+    for s in range(2):
+        sizes.members[s] = int(n_members[s])
+        sizes.positions[s] = int(n_positions[s])
+    assert len(strand) == n and len(close_len) == n and members.size == sum(n_members) and positions.size == sum(n_positions)
+    name, padded = chrom
+    padded = bytes(padded)
+    L.pgh_li_write_from_tables.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64] + [C.c_uint32] * 4 + [C.c_int32, C.c_uint32] + \
+        [C.c_void_p] * 8 + [C.c_uint32, C.c_char_p]
+    rc = L.pgh_li_write_from_tables(name.encode(), padded, len(padded), int(spacer), int(min_support), int(win_start), int(win_end),
+                                    int(max_insert_size), n, seq.ctypes.data if n else None, seq_off.ctypes.data, strand.ctypes.data if n else None,
+                                    close_len.ctypes.data if n else None, members.ctypes.data if members.size else None,
+                                    positions.ctypes.data if positions.size else None, C.addressof(sizes),
+                                    marks.ctypes.data if marks.size else None, int(marks.size), str(out_prefix).encode())
+    if rc:
+        raise ValueError("pgh_li_write_from_tables: " + (L.pgh_last_error() or b"").decode())
+
+
 def last_report_windows():
     """Windows of the last call_from_points(report_reads=True) that Caller::process_window_tables wrote from records and summaries."""
     return int(lib().pgh_last_report_windows())
