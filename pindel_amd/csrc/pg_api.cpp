@@ -3,6 +3,7 @@
 // to HBM, launches the search kernel (pg_kernels.hip) and turns its pooled runs
 // back into per-read CSR results.  There is NO CPU implementation of the search
 // here: without a working HIP device every entry point fails with PG_E_DEVICE.
+// The device classifier's entries are pg_api_classify.cpp; what the two files share is pg_api_priv.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +18,7 @@
 #include <thread>
 #include <vector>
 
+#include "pg_api_priv.h"
 #include "pg_device.h"
 #include "pg_host_plan.h"
 #include "pg_window_plan.h"
@@ -182,20 +184,6 @@ struct HostBuf {
     }
 };
 
-// Grow-only device arena of a ctx: the buffers of a host-path batch (pg_search_batch & co) are carved out of
-// it instead of ~25 hipMalloc / hipFree per call.
-struct DevArena {
-    char *base = nullptr;
-    size_t cap = 0, used = 0;
-    void *take(size_t bytes)
-    {
-        const size_t at = pg_arena_align(used);
-        if (at + bytes > cap) return nullptr;
-        used = at + bytes;
-        return base + at;
-    }
-};
-
 }  // namespace
 
 // The kernel keeps window bounds, anchor positions and candidate positions in signed 32-bit integers
@@ -203,129 +191,12 @@ struct DevArena {
 // guard/overhang arithmetic around a window end.
 static const uint64_t PG_MAX_CHR_PADDED = 0x7fffffffull - 65536ull;
 
-struct pg_ctx {
-    pg_params prm{};
-    uint32_t mm[512]{};
-    uint16_t thr[512]{};
-    uint16_t *d_thr = nullptr;
-    uint32_t *d_mm = nullptr;
-    int32_t *d_sv_budget = nullptr;    // [PG_SV_BUDGET_N] the NT kinds' mismatch budget by length sum (pg_sv.hip), for sv_budget_rate
-    double sv_budget_rate = 0.0;
-    PgLenRec *d_len_tab = nullptr;     // [512] pg_len_rec of every read length under this context's parameters (the pack's per-length fields)
-    hipStream_t stream = nullptr, copy_stream = nullptr;   // kernels / host-to-device input copies
-    hipStream_t dl_stream = nullptr;                       // device-to-host result copies of the chunked host path
-    hipStream_t stream2 = nullptr;                         // second kernel stream of the chunked host path (odd chunks)
-    std::vector<hipEvent_t> events;                        // reused by the chunked host path (no timing)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // hint tables (pg_hints.hip): events around the fill kernel (created on first use), and the last lookup's figures
-    // (pg_debug_last_hint_stats): HIP-event ms of count + scan and of the fill, bytes of the table uploaded, windows written
-    hipEvent_t evh0 = nullptr, evh1 = nullptr;
-    bool hint_fill_timed = false;
-    double hint_scan_ms = 0.0, hint_fill_ms = 0.0;
-    uint64_t hint_table_bytes = 0, hint_windows = 0;
-    // reference
-    std::vector<std::string> names;
-    std::vector<uint64_t> comp_size;
-    std::vector<uint64_t> word_off;   // index of the word holding AbsLoc 0
-    // host mirror of the planes: only pg_reference_fetch and pg_reference_save_packed read it.  A host load fills it on its way
-    // to the device; after pg_load_reference_device it is empty (mirror_ok false) until one of the two asks (host_mirror)
-    mutable std::vector<uint32_t> h_lo, h_hi, h_nn;
-    mutable bool mirror_ok = false;
-    uint64_t plane_words = 0;          // words of each plane in HBM
-    uint32_t *d_lo = nullptr, *d_hi = nullptr, *d_nn = nullptr;
-    uint64_t *d_word_off = nullptr;
-    uint32_t *d_chr_size = nullptr;
-    DevArena arena;                    // device memory of the host-path batches, reused across calls
-    // stats of the last search
-    double last_ms = 0.0;
-    uint64_t last_runs = 0;
-    std::string err;
-    bool counted = false;              // in g_live_ctx (the pinned-memory cache is trimmed with the last context)
-    uint32_t ref_epoch = 0;            // counts reference (re)loads: a device batch's records hold chromosome offsets and sizes
-    bool kargs_checked = false;        // the kernels' view of the kernarg segment was checked on this device (pg_debug_kargs_check)
-    bool last_in_place = false;        // the last launch asked to pack did so inside the search kernel (pg_debug_last_pack_in_place)
-    // the fixed-length kernels (PgFixedLen, pg_device.h): this context's length tables reproduce every baked row (compared once, at
-    // pg_create: only then may a launch run one); the LEN of the last search launch's kernel, 0 if it was any other (pg_debug_last_fixed_len)
-    bool fixed_ok = false;
-    std::atomic<uint32_t> last_fixed_len{0};
-    // The launch log (pg_debug_launch_log): every kernel launch on the search path in launch order, the first PG_LAUNCH_LOG_CAP
-    // since the last pg_debug_clear_launch_log; launch_n counts them all.  A slot is claimed atomically (launches of one context
-    // may come from more than one host thread) and costs a few host stores, no device work.
-    static constexpr uint32_t PG_LAUNCH_LOG_CAP = 256;
-    PgLaunchRec launch_log[PG_LAUNCH_LOG_CAP]{};
-    std::atomic<uint32_t> launch_n{0};
-};
-
 void log_launch(pg_ctx *ctx, const PgLaunchRec &r)
 {
     if (!r.kernel) return;
     const uint32_t i = ctx->launch_n.fetch_add(1u, std::memory_order_relaxed);
     if (i < pg_ctx::PG_LAUNCH_LOG_CAP) ctx->launch_log[i] = r;
 }
-
-struct pg_device_batch {
-    uint32_t n = 0;
-    uint32_t max_len = 0, levels = 0;
-    uint32_t uniform_len = 0;          // the length of every read of the batch when they all have one (0: mixed lengths, no reads)
-    int32_t max_isz = 0;
-    int64_t max_bd_window = 0;         // largest BreakDancer window attached (positions)
-    uint64_t max_bd_cluster = 0;       // most windows attached to one read
-    uint8_t *seq = nullptr;
-    uint64_t *seq_off = nullptr;
-    uint8_t *strand = nullptr;
-    int32_t *pos = nullptr;
-    int16_t *isz = nullptr;
-    int32_t *chr = nullptr;
-    uint8_t *rc_flag = nullptr;
-    uint32_t *close_last = nullptr;
-    uint16_t *close_max = nullptr;
-    uint64_t *bd_off = nullptr;
-    pg_window *bd = nullptr;
-    PgInRec *in_rec = nullptr;         // packed per-read records the kernel reads / writes (pg_device.h)
-    uint32_t ref_epoch = 0;            // pg_ctx::ref_epoch when the records were packed (a reload of the reference: pack again)
-    uint64_t *planes = nullptr;        // the reads as bit planes (PgDevBatch::planes)
-    PgOutRec *out_rec = nullptr;
-    bool in_arena = false;             // buffers belong to the ctx arena (not freed one by one)
-    bool pool_owned = false;           // ... except a run pool that had to be regrown
-    pg_run *pool = nullptr;
-    uint32_t pool_shard_cap = 0;       // runs per shard (PG_POOL_SHARDS shards)
-    uint32_t *pool_used = nullptr;     // [PG_POOL_SHARDS * 16]
-    unsigned long long *run_tot = nullptr;   // running totals of the chunked delivery (zeroed with the outputs)
-    // reads with a character outside ACGTN, listed by the pack kernel for the exact kernel (pg_search_exact_kernel)
-    uint32_t *exact_list = nullptr;    // [n]
-    uint32_t *exact_count = nullptr;   // device counter (zeroed with the outputs / before a pack of the whole batch)
-    PgSoaIn *d_soa = nullptr;          // the pack's view of the inputs, in device memory, for launches that pack in place (PgDevBatch::soa)
-    PgSoaIn h_soa;                     // ... and what was copied there last (the source of an asynchronous copy)
-    bool soa_uploaded = false;
-    long long exact_n = -1;            // host copy of the counter; -1: not read back (the exact kernel is launched regardless)
-    bool searched = false;             // close end + far end have run on the batch: its output records and run pool hold a result
-    // the event tables of the last pg_device_batch_events (always allocations of their own; null: none built)
-    pg_event_read *ev_reads = nullptr;     // n
-    uint32_t *ev_members = nullptr;        // n: the four member lists back to back
-    pg_event *ev_events = nullptr;         // n: the four event lists back to back
-    pg_event_sizes ev_sizes{};
-    bool ev_built = false;
-    pg_event_window ev_window{};           // ... and the window they were built for
-    // the SV tables of the last pg_device_batch_sv_events; an events build discards them
-    uint32_t *svev_members = nullptr;      // n: the three member lists back to back
-    pg_event *svev_events = nullptr;       // n: the three event lists back to back
-    uint32_t *svev_ws = nullptr;           // n: the order kernel's ranks of boxes beyond its LDS
-    pg_sv_event_sizes svev_sizes{};
-    bool svev_built = false;
-    // the report records of the last pg_device_batch_report_reads; an events or sv events build discards them
-    pg_report_read *rr_records = nullptr;      // n: a read is a member of at most one table
-    pg_report_summary *rr_summaries = nullptr; // n
-    uint64_t rr_n_records = 0;
-    bool rr_built = false;
-    // the candidate lists of the last pg_device_batch_classify: they never leave the device
-    pg_variant_cand *cl_cands = nullptr, *cl_sv_cands = nullptr;   // n x 2 x PG_VARIANT_CANDS; n x PG_SV_SLOTS
-    uint8_t *cl_counts = nullptr, *cl_sv_counts = nullptr;         // n x 2; n x PG_SV_KINDS
-    // the long-insertion tables of the last pg_device_batch_li; an events build discards them
-    uint32_t *li_members = nullptr;            // n: the two member lists back to back
-    pg_li_pos *li_positions = nullptr;         // n: the two position tables back to back
-    pg_li_sizes li_sizes{};
-    bool li_built = false;
-};
 
 struct pg_result {
     uint32_t n = 0;
@@ -341,44 +212,6 @@ struct pg_result {
 };
 
 namespace {
-
-// One ctx drives one device; a process may hold several (one host thread each): every entry point selects
-// its ctx's device for the calling thread first.
-void use_device(const pg_ctx *ctx);
-
-int fail(pg_ctx *ctx, int code, const std::string &msg)
-{
-    if (ctx) ctx->err = msg;
-    return code;
-}
-
-// (the device-buffer entries: a caller's pointer, checked before anything is launched -- defined with them, below)
-int check_device_ptr(pg_ctx *ctx, const void *p, size_t bytes, size_t align, const char *what);
-
-#define HIP_TRY(ctx, call)                                                                  \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail(ctx, e_ == hipErrorOutOfMemory ? PG_E_NOMEM : PG_E_DEVICE,           \
-                        std::string(#call) + ": " + hipGetErrorString(e_));                  \
-    } while (0)
-
-template <typename T>
-int dev_alloc(pg_ctx *ctx, T **p, size_t n)
-{
-    *p = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
-    return PG_OK;
-}
-
-template <typename T>
-int dev_upload(pg_ctx *ctx, T **p, const T *src, size_t n)
-{
-    int rc = dev_alloc(ctx, p, n);
-    if (rc) return rc;
-    if (n) HIP_TRY(ctx, hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return PG_OK;
-}
 
 // probOfReadWithTheseErrors / createProbTable, src/pindel.cpp:781-819
 double prob_of_read_with_these_errors(unsigned length, unsigned n_err, double rate)
@@ -438,23 +271,6 @@ void free_reference(pg_ctx *ctx)
     ctx->plane_words = 0;
 }
 
-void use_device(const pg_ctx *ctx)
-{
-    if (ctx) (void)hipSetDevice(ctx->prm.device);
-}
-
-PgDevRef dev_ref(const pg_ctx *ctx)
-{
-    PgDevRef r;
-    r.lo = ctx->d_lo;
-    r.hi = ctx->d_hi;
-    r.nn = ctx->d_nn;
-    r.chr_word_off = ctx->d_word_off;
-    r.chr_size = ctx->d_chr_size;
-    r.n_chr = (int32_t)ctx->names.size();
-    return r;
-}
-
 PgDevParams dev_params(const pg_ctx *ctx)
 {
     PgDevParams p;
@@ -477,28 +293,7 @@ PgDevParams dev_params(const pg_ctx *ctx)
 
 void free_batch_buffers(pg_device_batch *b)
 {
-    for (void *p : { (void *)b->ev_reads, (void *)b->ev_members, (void *)b->ev_events, (void *)b->svev_members, (void *)b->svev_events, (void *)b->svev_ws })
-        if (p) (void)hipFree(p);
-    for (void *p : { (void *)b->rr_records, (void *)b->rr_summaries, (void *)b->cl_cands, (void *)b->cl_sv_cands, (void *)b->cl_counts, (void *)b->cl_sv_counts })
-        if (p) (void)hipFree(p);
-    for (void *p : { (void *)b->li_members, (void *)b->li_positions })
-        if (p) (void)hipFree(p);
-    b->li_members = nullptr;
-    b->li_positions = nullptr;
-    b->li_built = false;
-    b->rr_records = nullptr;
-    b->rr_summaries = nullptr;
-    b->rr_built = false;
-    b->cl_cands = b->cl_sv_cands = nullptr;
-    b->cl_counts = b->cl_sv_counts = nullptr;
-    b->svev_members = nullptr;
-    b->svev_events = nullptr;
-    b->svev_ws = nullptr;
-    b->svev_built = false;
-    b->ev_reads = nullptr;
-    b->ev_members = nullptr;
-    b->ev_events = nullptr;
-    b->ev_built = false;
+    b->cls.release();
     if (b->in_arena) {
         if (b->pool_owned && b->pool) (void)hipFree(b->pool);
         if (b->bd_off) (void)hipFree(b->bd_off);          // window clusters are always allocated on their own
@@ -958,15 +753,6 @@ PgSoaOut soa_out(const pg_device_batch *b)
     return a;
 }
 
-// A device batch whose reference has been replaced since it was validated: its chromosome ids, anchor windows and (once packed)
-// word offsets belong to the old reference.
-int stale_batch(pg_ctx *ctx, const pg_device_batch *b)
-{
-    if (b->ref_epoch != ctx->ref_epoch && b->n)
-        return fail(ctx, PG_E_INVALID, "the reference was (re)loaded after this batch was uploaded: upload the batch again");
-    return PG_OK;
-}
-
 // The length of the exact kernel's list, once the batch's pack has finished (synchronous entries only: a device-resident batch is
 // searched many times, and every search would otherwise carry a launch that finds nothing to do).
 int read_exact_count(pg_ctx *ctx, pg_device_batch *b)
@@ -1183,30 +969,6 @@ int run_search(pg_ctx *ctx, pg_device_batch *b, int mode, bool pack = false)
     }
     return fail(ctx, PG_E_DEVICE, "run pool kept overflowing");
 }
-
-// Device temporaries of one call: from the ctx arena where the batch lives there and the arena has room, hipMalloc'd otherwise;
-// all given back when the call ends.
-struct DevTemps {
-    pg_ctx *ctx;
-    const bool in_arena;
-    const size_t arena_mark;
-    std::vector<void *> owned;                            // hipMalloc'd (none while the arena has room)
-    DevTemps(pg_ctx *c, const pg_device_batch *b) : ctx(c), in_arena(b->in_arena), arena_mark(c->arena.used) {}
-    DevTemps(const DevTemps &) = delete;
-    ~DevTemps()
-    {
-        for (void *p : owned) (void)hipFree(p);
-        if (in_arena) ctx->arena.used = arena_mark;
-    }
-    void *take(size_t bytes)
-    {
-        void *p = in_arena ? ctx->arena.take(bytes) : nullptr;
-        if (p) return p;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
-        owned.push_back(p);
-        return p;
-    }
-};
 
 // The two passes of a whole-batch delivery (n > 0), shared by the download to the host and the one into the caller's device
 // buffers: the delivery kernels of the host path (pg_deliver_chunk) over the whole batch.  Pass 1 scans every chunk -- per-read
@@ -1671,6 +1433,8 @@ int host_mirror(const pg_ctx *ctx)
     return PG_OK;
 }
 
+}  // namespace
+
 // A pointer a device entry was handed: device memory of the context's own GPU, aligned for its element type, with the `bytes`
 // the library will read or write inside its allocation.  Checked before anything is launched: a host pointer must end in a
 // status code, never in a fault.  bytes = 0: nothing will be touched, nothing is checked.
@@ -1698,6 +1462,8 @@ int check_device_ptr(pg_ctx *ctx, const void *p, size_t bytes, size_t align, con
         return fail(ctx, PG_E_INVALID, std::string(what) + ": reaches past the end of its device allocation");
     return PG_OK;
 }
+
+namespace {
 
 // pg_device_batch_upload_device: the batch's arrays are in device memory.  The measurement kernel (pg_devio.hip) is the
 // device twin of validate_and_measure; only its 40-byte record comes to the host, which reports, sizes and allocates as the
@@ -2325,879 +2091,6 @@ int pg_device_batch_download_device(pg_ctx *ctx, pg_device_batch *b, const pg_de
         (dst->close_max && (rc = check_device_ptr(ctx, dst->close_max, n * 2, 2, "pg_device_result.close_max"))))
         return rc;
     return download_device(ctx, b, dst);
-}
-
-// ---- the device classifier (pg_variant.hip): deletion and short-insertion candidates of a searched batch
-// d_cands / d_counts: device memory (checked by the caller where it is the user's).  The launch is recorded in the launch log and
-// timed with HIP events like a search's.
-static int variant_candidates(pg_ctx *ctx, pg_device_batch *b, pg_variant_cand *d_cands, uint8_t *d_counts)
-{
-    if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
-    if (int rc = stale_batch(ctx, b)) return rc;
-    ctx->last_ms = 0.0;
-    if (!b->n) return PG_OK;                                  // nothing is launched for an empty batch
-    if (!b->searched) return fail(ctx, PG_E_INVALID, "the batch has not been searched: no close and far ends to classify");
-    const PgDevRef ref = dev_ref(ctx);
-    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    if (pg_variant_launch(&ref, b->out_rec, b->pool, (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS, b->seq, b->seq_off, b->strand,
-                          b->chr, ctx->d_mm, ctx->prm.spacer, b->n, d_cands, d_counts, ctx->stream))
-        return fail(ctx, PG_E_DEVICE, "launching the variant-candidate kernel failed");
-    PgLaunchRec rec{};
-    rec.kernel = PG_KERNEL_VARIANT;
-    rec.blocks = 4;                                           // reads (waves) per workgroup
-    log_launch(ctx, rec);
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->last_ms = ms;
-    return PG_OK;
-}
-
-int pg_device_batch_variant_candidates_device(pg_ctx *ctx, pg_device_batch *b, pg_variant_cand *d_cands, uint8_t *d_counts)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    const size_t n = b->n;
-    int rc;
-    if ((rc = check_device_ptr(ctx, d_cands, n * 2 * PG_VARIANT_CANDS * sizeof(pg_variant_cand), 4, "variant candidates: cands")) ||
-        (rc = check_device_ptr(ctx, d_counts, n * 2, 1, "variant candidates: counts")))
-        return rc;
-    return variant_candidates(ctx, b, d_cands, d_counts);
-}
-
-int pg_device_batch_variant_candidates(pg_ctx *ctx, pg_device_batch *b, pg_variant_cand *cands, uint8_t *counts)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    const size_t n = b->n;
-    if (n && (!cands || !counts)) return fail(ctx, PG_E_INVALID, "variant candidates: null output array");
-    if (!n || !b->searched) return variant_candidates(ctx, b, nullptr, nullptr);      // (nothing to do, or the refusal)
-    DevTemps tmp(ctx, b);
-    const size_t cand_bytes = n * 2 * PG_VARIANT_CANDS * sizeof(pg_variant_cand);
-    pg_variant_cand *d_cands = (pg_variant_cand *)tmp.take(cand_bytes);
-    uint8_t *d_counts = (uint8_t *)tmp.take(n * 2);
-    if (!d_cands || !d_counts) return fail(ctx, PG_E_NOMEM, "device memory for the variant candidates");
-    if (int rc = variant_candidates(ctx, b, d_cands, d_counts)) return rc;
-    HIP_TRY(ctx, hipMemcpy(cands, d_cands, cand_bytes, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(counts, d_counts, n * 2, hipMemcpyDeviceToHost));
-    return PG_OK;
-}
-
-// ---- ... of the five other kinds (pg_sv.hip): DI, tandem-duplication and inversion candidates
-// (short)(1 + Seq_Error_Rate * length sum) for every length sum, as the host classifiers compute it: the product is stored before
-// the add, so that no compiler fuses the two
-static int sv_budget_table(pg_ctx *ctx, double rate)
-{
-    if (ctx->d_sv_budget && std::memcmp(&ctx->sv_budget_rate, &rate, sizeof rate) == 0) return PG_OK;
-    std::vector<int32_t> t(PG_SV_BUDGET_N);
-    for (int len = 0; len < PG_SV_BUDGET_N; len++) {
-        volatile double prod = rate * len;
-        const double v = 1 + prod;
-        t[(size_t)len] = v >= -32768.0 && v < 32768.0 ? (int32_t)(short)v : 32767;      // (NaN or out of a short's range: undefined on the host)
-    }
-    if (ctx->d_sv_budget) {
-        HIP_TRY(ctx, hipMemcpy(ctx->d_sv_budget, t.data(), t.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    } else if (int rc = dev_upload(ctx, &ctx->d_sv_budget, t.data(), t.size())) {
-        return rc;
-    }
-    ctx->sv_budget_rate = rate;
-    return PG_OK;
-}
-
-static int sv_params_ok(pg_ctx *ctx, const pg_sv_params *p)
-{
-    if (!p) return fail(ctx, PG_E_INVALID, "sv candidates: null pg_sv_params");
-    if (p->min_inversion_size < 0 || p->min_inversion_size > PG_SV_MAX_INVERSION_SIZE)
-        return fail(ctx, PG_E_INVALID, "sv candidates: the minimum inversion size (-v) must lie in [0, 2^30]");
-    return PG_OK;
-}
-
-static int sv_candidates(pg_ctx *ctx, pg_device_batch *b, const pg_sv_params *p, pg_variant_cand *d_cands, uint8_t *d_counts)
-{
-    if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
-    if (int rc = stale_batch(ctx, b)) return rc;
-    ctx->last_ms = 0.0;
-    if (int rc = sv_params_ok(ctx, p)) return rc;
-    if (!b->n) return PG_OK;                                  // nothing is launched for an empty batch
-    if (!b->searched) return fail(ctx, PG_E_INVALID, "the batch has not been searched: no close and far ends to classify");
-    if (int rc = sv_budget_table(ctx, p->seq_error_rate)) return rc;
-    const PgDevRef ref = dev_ref(ctx);
-    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    if (pg_sv_launch(&ref, b->out_rec, b->pool, (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS, b->seq, b->seq_off, b->strand, b->chr,
-                     ctx->d_mm, ctx->d_sv_budget, p->min_num_matched_bases, (uint32_t)p->min_inversion_size, ctx->prm.spacer, b->n, d_cands,
-                     d_counts, ctx->stream))
-        return fail(ctx, PG_E_DEVICE, "launching the sv-candidate kernel failed");
-    PgLaunchRec rec{};
-    rec.kernel = PG_KERNEL_SV;
-    rec.blocks = 4;                                           // reads (waves) per workgroup
-    log_launch(ctx, rec);
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->last_ms = ms;
-    return PG_OK;
-}
-
-int pg_device_batch_sv_candidates_device(pg_ctx *ctx, pg_device_batch *b, const pg_sv_params *p, pg_variant_cand *d_cands, uint8_t *d_counts)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    const size_t n = b->n;
-    int rc;
-    if ((rc = check_device_ptr(ctx, d_cands, n * PG_SV_SLOTS * sizeof(pg_variant_cand), 4, "sv candidates: cands")) ||
-        (rc = check_device_ptr(ctx, d_counts, n * PG_SV_KINDS, 1, "sv candidates: counts")))
-        return rc;
-    return sv_candidates(ctx, b, p, d_cands, d_counts);
-}
-
-int pg_device_batch_sv_candidates(pg_ctx *ctx, pg_device_batch *b, const pg_sv_params *p, pg_variant_cand *cands, uint8_t *counts)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    const size_t n = b->n;
-    if (n && (!cands || !counts)) return fail(ctx, PG_E_INVALID, "sv candidates: null output array");
-    if (!n || !b->searched || sv_params_ok(ctx, p)) return sv_candidates(ctx, b, p, nullptr, nullptr);      // (nothing to do, or the refusal)
-    DevTemps tmp(ctx, b);
-    const size_t cand_bytes = n * PG_SV_SLOTS * sizeof(pg_variant_cand);
-    pg_variant_cand *d_cands = (pg_variant_cand *)tmp.take(cand_bytes);
-    uint8_t *d_counts = (uint8_t *)tmp.take(n * PG_SV_KINDS);
-    if (!d_cands || !d_counts) return fail(ctx, PG_E_NOMEM, "device memory for the sv candidates");
-    if (int rc = sv_candidates(ctx, b, p, d_cands, d_counts)) return rc;
-    HIP_TRY(ctx, hipMemcpy(cands, d_cands, cand_bytes, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(counts, d_counts, n * PG_SV_KINDS, hipMemcpyDeviceToHost));
-    return PG_OK;
-}
-
-// ---- ... its third part (pg_events.hip): window tail, boxes and event tables
-namespace {
-struct EventTemps {                                           // device scratch of one build, released when it ends
-    std::vector<void *> owned;
-    ~EventTemps()
-    {
-        for (void *p : owned) (void)hipFree(p);
-    }
-    // n elements of elem bytes into *p (as dev_alloc: at least one)
-    int take(pg_ctx *ctx, void *p, size_t n, size_t elem)
-    {
-        uint8_t *q = nullptr;
-        if (int rc = dev_alloc(ctx, &q, std::max<size_t>(n, 1) * elem)) return rc;
-        owned.push_back(q);
-        *(void **)p = q;
-        return PG_OK;
-    }
-};
-#define EV_TAKE(tmp, ctx, p, n) (tmp).take(ctx, &(p), n, sizeof *(p))
-
-// the refusals of both build entries, before anything is launched or copied
-int events_refusal(pg_ctx *ctx, pg_device_batch *b, const pg_event_window *w, bool lists_null_mismatch)
-{
-    if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
-    if (int rc = stale_batch(ctx, b)) return rc;
-    ctx->last_ms = 0.0;
-    if (!w) return fail(ctx, PG_E_INVALID, "events: null pg_event_window");
-    if (lists_null_mismatch) return fail(ctx, PG_E_INVALID, "events: candidate arrays come in pairs (records and count bytes)");
-    if (w->chr_id < 0 || w->chr_id >= (int32_t)ctx->names.size()) return fail(ctx, PG_E_INVALID, "events: the window's chr_id lies outside the reference");
-    if (w->region_start > w->region_end) return fail(ctx, PG_E_INVALID, "events: region_start > region_end");
-    if (b->n && !b->searched) return fail(ctx, PG_E_INVALID, "the batch has not been searched: no close and far ends to classify");
-    return PG_OK;
-}
-
-// every list pointer is device memory (or null)
-int build_events(pg_ctx *ctx, pg_device_batch *b, const pg_event_window *w, const pg_variant_cand *d_cands, const uint8_t *d_counts,
-                 const pg_variant_cand *d_sv_cands, const uint8_t *d_sv_counts, const uint32_t *d_name_id)
-{
-    b->ev_built = false;
-    b->svev_built = false;                                    // (the SV tables belong to the records of the build they were made from)
-    b->rr_built = false;                                      // (... and so do the report records)
-    b->li_built = false;                                      // (... and the long-insertion tables: they read the records' Used state)
-    b->ev_sizes = pg_event_sizes{};
-    b->ev_window = *w;
-    const size_t n = b->n;
-    if (!n) {                                                 // nothing is launched for an empty batch
-        b->ev_built = true;
-        return PG_OK;
-    }
-    int rc;
-    if (!b->ev_reads && ((rc = dev_alloc(ctx, &b->ev_reads, n)) || (rc = dev_alloc(ctx, &b->ev_members, n)) || (rc = dev_alloc(ctx, &b->ev_events, n))))
-        return rc;
-    EventTemps tmp;
-    PgEventArgs a{};
-    const size_t n_blk = n / PG_EV_BLOCK + 2;
-    if ((rc = EV_TAKE(tmp, ctx, a.rec_a, n)) || (rc = EV_TAKE(tmp, ctx, a.rec_b, n)) || (rc = EV_TAKE(tmp, ctx, a.flag, n)) ||
-        (rc = EV_TAKE(tmp, ctx, a.rank, n)) || (rc = EV_TAKE(tmp, ctx, a.blk, n_blk)) || (rc = EV_TAKE(tmp, ctx, a.midx, n)) ||
-        (rc = EV_TAKE(tmp, ctx, a.efirst, n + 1)) || (rc = EV_TAKE(tmp, ctx, a.digit_cnt, 256 * n_blk + 1)) || (rc = EV_TAKE(tmp, ctx, a.info, 1)))
-        return rc;
-    a.out = b->out_rec;
-    a.pool = b->pool;
-    a.pool_runs = (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS;
-    a.seq = b->seq;
-    a.seq_off = b->seq_off;
-    a.strand = b->strand;
-    a.chr = b->chr;
-    a.isz = b->isz;
-    a.spacer = ctx->prm.spacer;
-    a.n = b->n;
-    a.win = *w;
-    // BoxSize / NumBoxes from the padded chromosome length, as Caller::process_window computes them (pindel.cpp:1806-1810)
-    const uint64_t chr_len = ctx->comp_size[(size_t)w->chr_id];
-    a.box_size = (uint32_t)(chr_len / 30000);
-    if (a.box_size == 0) a.box_size = 1;
-    a.n_boxes = (uint32_t)(chr_len * 2 / a.box_size) + 1;
-    a.cands = d_cands;
-    a.counts = d_counts;
-    a.sv_cands = d_sv_cands;
-    a.sv_counts = d_sv_counts;
-    a.name_id = d_name_id;
-    a.reads = b->ev_reads;
-    a.members = b->ev_members;
-    a.events = b->ev_events;
-    const PgDevRef ref = dev_ref(ctx);
-    PgLaunchRec rec{};
-    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    if (pg_events_cascade_launch(&a, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the event cascade kernels failed");
-    rec.kernel = PG_KERNEL_EVENT_CASCADE;
-    rec.blocks = (int32_t)PG_EV_BLOCK;
-    log_launch(ctx, rec);
-    PgEventInfo info;
-    HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (info.n_boxed > n) return fail(ctx, PG_E_DEVICE, "events: the boxed count exceeds the batch");
-    const PgEventRec *sorted = a.rec_b;
-    if (info.n_boxed) {                                       // (nothing boxed: nothing below indexes an empty array)
-        PgEventRec *src = a.rec_b, *dst = a.rec_a;
-        for (int pass = 0; pass < PG_EV_SORT_PASSES; pass++) {
-            const int word = pass >= 16 ? 4 : 3 - (pass >> 2), shift = pass >= 16 ? 0 : (pass & 3) * 8;
-            if ((((info.key_or[word] ^ info.key_and[word]) >> shift) & 0xffu) == 0u) continue;      // the byte is constant: no pass
-            if (pg_events_sort_pass_launch(&a, src, dst, info.n_boxed, pass, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching an event sort pass failed");
-            rec.kernel = PG_KERNEL_EVENT_SORT;
-            rec.blocks = pass;
-            log_launch(ctx, rec);
-            std::swap(src, dst);
-        }
-        sorted = src;
-        if (pg_events_tables_launch(&ref, &a, sorted, info.n_boxed, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the event table kernels failed");
-        rec.kernel = PG_KERNEL_EVENT_TABLES;
-        rec.blocks = (int32_t)PG_EV_BLOCK;
-        log_launch(ctx, rec);
-        HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->last_ms = ms;
-    if (info.n_boxed) {
-        if (info.n_members > info.n_boxed || info.n_events > info.n_members) return fail(ctx, PG_E_DEVICE, "events: inconsistent table sizes");
-        for (int t = 0; t < PG_EVENT_TABLES; t++) {
-            b->ev_sizes.members[t] = info.member_start[t + 1] - info.member_start[t];
-            b->ev_sizes.events[t] = info.event_start[t + 1] - info.event_start[t];
-        }
-    }
-    b->ev_sizes.unresolved = info.n_unresolved;
-    b->ev_built = true;
-    return PG_OK;
-}
-}  // namespace
-
-int pg_device_batch_events_device(pg_ctx *ctx, pg_device_batch *b, const pg_event_window *window, const pg_variant_cand *d_cands,
-                                  const uint8_t *d_counts, const pg_variant_cand *d_sv_cands, const uint8_t *d_sv_counts, const uint32_t *d_name_id)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (int rc = events_refusal(ctx, b, window, (d_cands == nullptr) != (d_counts == nullptr) || (d_sv_cands == nullptr) != (d_sv_counts == nullptr)))
-        return rc;
-    const size_t n = b->n;
-    int rc;
-    if ((d_cands && ((rc = check_device_ptr(ctx, d_cands, n * 2 * PG_VARIANT_CANDS * sizeof(pg_variant_cand), 4, "events: cands")) ||
-                     (rc = check_device_ptr(ctx, d_counts, n * 2, 1, "events: counts")))) ||
-        (d_sv_cands && ((rc = check_device_ptr(ctx, d_sv_cands, n * PG_SV_SLOTS * sizeof(pg_variant_cand), 4, "events: sv_cands")) ||
-                        (rc = check_device_ptr(ctx, d_sv_counts, n * PG_SV_KINDS, 1, "events: sv_counts")))) ||
-        (d_name_id && (rc = check_device_ptr(ctx, d_name_id, n * 4, 4, "events: name_id"))))
-        return rc;
-    return build_events(ctx, b, window, d_cands, d_counts, d_sv_cands, d_sv_counts, d_name_id);
-}
-
-int pg_device_batch_events(pg_ctx *ctx, pg_device_batch *b, const pg_event_window *window, const pg_variant_cand *cands, const uint8_t *counts,
-                           const pg_variant_cand *sv_cands, const uint8_t *sv_counts, const uint32_t *name_id)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (int rc = events_refusal(ctx, b, window, (cands == nullptr) != (counts == nullptr) || (sv_cands == nullptr) != (sv_counts == nullptr)))
-        return rc;
-    const size_t n = b->n;
-    EventTemps tmp;
-    pg_variant_cand *d_cands = nullptr, *d_sv = nullptr;
-    uint8_t *d_counts = nullptr, *d_svn = nullptr;
-    uint32_t *d_name = nullptr;
-    int rc;
-    if (n && cands) {
-        if ((rc = EV_TAKE(tmp, ctx, d_cands, n * 2 * PG_VARIANT_CANDS)) || (rc = EV_TAKE(tmp, ctx, d_counts, n * 2))) return rc;
-        HIP_TRY(ctx, hipMemcpy(d_cands, cands, n * 2 * PG_VARIANT_CANDS * sizeof(pg_variant_cand), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(d_counts, counts, n * 2, hipMemcpyHostToDevice));
-    }
-    if (n && sv_cands) {
-        if ((rc = EV_TAKE(tmp, ctx, d_sv, n * PG_SV_SLOTS)) || (rc = EV_TAKE(tmp, ctx, d_svn, n * PG_SV_KINDS))) return rc;
-        HIP_TRY(ctx, hipMemcpy(d_sv, sv_cands, n * PG_SV_SLOTS * sizeof(pg_variant_cand), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(d_svn, sv_counts, n * PG_SV_KINDS, hipMemcpyHostToDevice));
-    }
-    if (n && name_id) {
-        if ((rc = EV_TAKE(tmp, ctx, d_name, n))) return rc;
-        HIP_TRY(ctx, hipMemcpy(d_name, name_id, n * 4, hipMemcpyHostToDevice));
-    }
-    return build_events(ctx, b, window, d_cands, d_counts, d_sv, d_svn, d_name);
-}
-
-int pg_device_batch_event_sizes(pg_ctx *ctx, pg_device_batch *b, pg_event_sizes *sizes)
-{
-    use_device(ctx);
-    if (!ctx || !b || !sizes) return PG_E_INVALID;
-    if (!b->ev_built) return fail(ctx, PG_E_INVALID, "no event tables: pg_device_batch_events has not been run on this batch");
-    *sizes = b->ev_sizes;
-    return PG_OK;
-}
-
-static int events_download(pg_ctx *ctx, pg_device_batch *b, pg_event_read *reads, uint32_t *members, pg_event *events, hipMemcpyKind kind)
-{
-    if (!b->ev_built) return fail(ctx, PG_E_INVALID, "no event tables: pg_device_batch_events has not been run on this batch");
-    size_t nm = 0, ne = 0;
-    for (int t = 0; t < PG_EVENT_TABLES; t++) {
-        nm += b->ev_sizes.members[t];
-        ne += b->ev_sizes.events[t];
-    }
-    if (reads && b->n) HIP_TRY(ctx, hipMemcpy(reads, b->ev_reads, (size_t)b->n * sizeof(pg_event_read), kind));
-    if (members && nm) HIP_TRY(ctx, hipMemcpy(members, b->ev_members, nm * sizeof(uint32_t), kind));
-    if (events && ne) HIP_TRY(ctx, hipMemcpy(events, b->ev_events, ne * sizeof(pg_event), kind));
-    return PG_OK;
-}
-
-int pg_device_batch_events_download(pg_ctx *ctx, pg_device_batch *b, pg_event_read *reads, uint32_t *members, pg_event *events)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    return events_download(ctx, b, reads, members, events, hipMemcpyDeviceToHost);
-}
-
-int pg_device_batch_events_download_device(pg_ctx *ctx, pg_device_batch *b, pg_event_read *d_reads, uint32_t *d_members, pg_event *d_events)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (!b->ev_built) return fail(ctx, PG_E_INVALID, "no event tables: pg_device_batch_events has not been run on this batch");
-    size_t nm = 0, ne = 0;
-    for (int t = 0; t < PG_EVENT_TABLES; t++) {
-        nm += b->ev_sizes.members[t];
-        ne += b->ev_sizes.events[t];
-    }
-    int rc;
-    if ((d_reads && (rc = check_device_ptr(ctx, d_reads, (size_t)b->n * sizeof(pg_event_read), 2, "events download: reads"))) ||
-        (d_members && (rc = check_device_ptr(ctx, d_members, nm * sizeof(uint32_t), 4, "events download: members"))) ||
-        (d_events && (rc = check_device_ptr(ctx, d_events, ne * sizeof(pg_event), 4, "events download: events"))))
-        return rc;
-    return events_download(ctx, b, d_reads, d_members, d_events, hipMemcpyDeviceToDevice);
-}
-
-// ---- ... its fourth part (pg_sv_events.hip): the event tables of DI, INV and INV_NT
-namespace {
-int sv_events_refusal(pg_ctx *ctx, pg_device_batch *b, const void *sv_cands, const void *sv_counts)
-{
-    if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
-    if (int rc = stale_batch(ctx, b)) return rc;
-    ctx->last_ms = 0.0;
-    if (b->n && !b->searched) return fail(ctx, PG_E_INVALID, "the batch has not been searched: no close and far ends to classify");
-    if (!b->ev_built) return fail(ctx, PG_E_INVALID, "sv events: pg_device_batch_events has not been run on this batch");
-    if (b->n && (!sv_cands || !sv_counts)) return fail(ctx, PG_E_INVALID, "sv events: null sv candidate arrays");
-    if (b->n >= 0x80000000u) return fail(ctx, PG_E_INVALID, "sv events: 2^31 reads or more (bit 31 of a member word is PG_SVEV_MEMBER_DUP)");
-    return PG_OK;
-}
-
-// d_sv_cands is device memory
-int build_sv_events(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *d_sv_cands)
-{
-    b->svev_built = false;
-    b->rr_built = false;
-    b->svev_sizes = pg_sv_event_sizes{};
-    const size_t n = b->n;
-    if (!n) {                                                 // nothing is launched for an empty batch
-        b->svev_built = true;
-        return PG_OK;
-    }
-    int rc;
-    if (!b->svev_members && ((rc = dev_alloc(ctx, &b->svev_members, n)) || (rc = dev_alloc(ctx, &b->svev_events, n)) || (rc = dev_alloc(ctx, &b->svev_ws, n))))
-        return rc;
-    EventTemps tmp;
-    PgSvEventArgs a{};
-    const size_t n_blk = n / PG_EV_BLOCK + 2;
-    if ((rc = EV_TAKE(tmp, ctx, a.rec_a, n)) || (rc = EV_TAKE(tmp, ctx, a.rec, n)) || (rc = EV_TAKE(tmp, ctx, a.flag, n)) ||
-        (rc = EV_TAKE(tmp, ctx, a.dupf, n)) || (rc = EV_TAKE(tmp, ctx, a.rank, n)) || (rc = EV_TAKE(tmp, ctx, a.blk, n_blk)) ||
-        (rc = EV_TAKE(tmp, ctx, a.perm_a, n)) || (rc = EV_TAKE(tmp, ctx, a.perm_b, n)) || (rc = EV_TAKE(tmp, ctx, a.kperm_a, n)) ||
-        (rc = EV_TAKE(tmp, ctx, a.kperm_b, n)) || (rc = EV_TAKE(tmp, ctx, a.krank, n)) || (rc = EV_TAKE(tmp, ctx, a.seg_first, n + 1)) ||
-        (rc = EV_TAKE(tmp, ctx, a.midx, n)) || (rc = EV_TAKE(tmp, ctx, a.rfirst, n + 1)) || (rc = EV_TAKE(tmp, ctx, a.rmx, n)) ||
-        (rc = EV_TAKE(tmp, ctx, a.rfail, n)) || (rc = EV_TAKE(tmp, ctx, a.digit_cnt, 256 * n_blk + 1)) || (rc = EV_TAKE(tmp, ctx, a.info, 1)))
-        return rc;
-    a.out = b->out_rec;
-    a.seq = b->seq;
-    a.seq_off = b->seq_off;
-    a.strand = b->strand;
-    a.spacer = ctx->prm.spacer;
-    a.n = b->n;
-    a.win = b->ev_window;
-    const uint64_t chr_len = ctx->comp_size[(size_t)a.win.chr_id];
-    a.box_size = (uint32_t)(chr_len / 30000);
-    if (a.box_size == 0) a.box_size = 1;
-    a.sv_cands = d_sv_cands;
-    a.reads = b->ev_reads;
-    a.members = b->svev_members;
-    a.events = b->svev_events;
-    a.ws_rank = b->svev_ws;
-    const PgDevRef ref = dev_ref(ctx);
-    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    if (pg_sv_events_gather_launch(&a, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the sv event gather kernels failed");
-    PgLaunchRec rec{};
-    rec.kernel = PG_KERNEL_SV_EVENTS;
-    rec.blocks = (int32_t)PG_EV_BLOCK;
-    log_launch(ctx, rec);
-    PgSvEventInfo info;
-    HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (info.n_boxed > n) return fail(ctx, PG_E_DEVICE, "sv events: the boxed count exceeds the batch");
-    if (info.n_boxed) {                                       // (nothing boxed: nothing below indexes an empty array)
-        // a pass over a byte that is constant over the boxed records changes nothing: skipped
-        auto sort = [&](uint32_t *&src, uint32_t *&dst, int pass, uint32_t vary) -> int {
-            if (!vary) return 0;
-            if (pg_sv_events_sort_pass_launch(&a, src, dst, info.n_boxed, pass, ctx->stream)) return -1;
-            std::swap(src, dst);
-            return 0;
-        };
-        uint32_t *perm = a.perm_a, *perm_t = a.perm_b, *kperm = a.kperm_a, *kperm_t = a.kperm_b;
-        const uint32_t seg_vary = info.seg_or ^ info.seg_and;
-        for (int k = 0; k < 4; k++)
-            if (sort(perm, perm_t, PG_SVEV_PASS_BOX + k, (seg_vary >> (8 * k)) & 0xffu)) return fail(ctx, PG_E_DEVICE, "launching an sv event sort pass failed");
-        for (int pass = 0; pass < PG_SVEV_PASS_TABLE; pass++) {
-            const int word = PG_SVEV_KEY_WORDS - 1 - (pass >> 2);
-            if (sort(kperm, kperm_t, pass, ((info.key_or[word] ^ info.key_and[word]) >> ((pass & 3) * 8)) & 0xffu))
-                return fail(ctx, PG_E_DEVICE, "launching an sv event sort pass failed");
-        }
-        if (sort(kperm, kperm_t, PG_SVEV_PASS_TABLE, seg_vary >> 24)) return fail(ctx, PG_E_DEVICE, "launching an sv event sort pass failed");
-        if (pg_sv_events_tables_launch(&ref, &a, perm, kperm, info.n_boxed, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the sv event table kernels failed");
-        HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->last_ms = ms;
-    if (info.n_boxed) {
-        uint64_t nm = 0, ne = 0;
-        for (int t = 0; t < PG_SV_EVENT_TABLES; t++) {
-            b->svev_sizes.members[t] = info.n_mem[t];
-            b->svev_sizes.events[t] = info.n_ev[t];
-            b->svev_sizes.dropped_runs[t] = info.dropped[t];
-            nm += info.n_mem[t];
-            ne += info.n_ev[t];
-        }
-        if (nm != info.n_members || nm > info.n_boxed || ne > info.n_runs || info.n_runs > nm) {
-            b->svev_sizes = pg_sv_event_sizes{};
-            return fail(ctx, PG_E_DEVICE, "sv events: inconsistent table sizes");
-        }
-    }
-    b->svev_built = true;
-    return PG_OK;
-}
-
-void sv_event_totals(const pg_device_batch *b, size_t *nm, size_t *ne)
-{
-    *nm = *ne = 0;
-    for (int t = 0; t < PG_SV_EVENT_TABLES; t++) {
-        *nm += b->svev_sizes.members[t];
-        *ne += b->svev_sizes.events[t];
-    }
-}
-const char *const NO_SV_TABLES = "no sv event tables: pg_device_batch_sv_events has not been run on this batch since its events build";
-}  // namespace
-
-int pg_device_batch_sv_events_device(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *d_sv_cands, const uint8_t *d_sv_counts)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (int rc = sv_events_refusal(ctx, b, d_sv_cands, d_sv_counts)) return rc;
-    const size_t n = b->n;
-    int rc;
-    if (n && ((rc = check_device_ptr(ctx, d_sv_cands, n * PG_SV_SLOTS * sizeof(pg_variant_cand), 4, "sv events: sv_cands")) ||
-              (rc = check_device_ptr(ctx, d_sv_counts, n * PG_SV_KINDS, 1, "sv events: sv_counts"))))
-        return rc;
-    return build_sv_events(ctx, b, d_sv_cands);
-}
-
-int pg_device_batch_sv_events(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *sv_cands, const uint8_t *sv_counts)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (int rc = sv_events_refusal(ctx, b, sv_cands, sv_counts)) return rc;
-    const size_t n = b->n;
-    EventTemps tmp;
-    pg_variant_cand *d_sv = nullptr;
-    if (n) {
-        if (int rc = EV_TAKE(tmp, ctx, d_sv, n * PG_SV_SLOTS)) return rc;
-        HIP_TRY(ctx, hipMemcpy(d_sv, sv_cands, n * PG_SV_SLOTS * sizeof(pg_variant_cand), hipMemcpyHostToDevice));
-    }
-    return build_sv_events(ctx, b, d_sv);
-}
-
-int pg_device_batch_sv_event_sizes(pg_ctx *ctx, pg_device_batch *b, pg_sv_event_sizes *sizes)
-{
-    use_device(ctx);
-    if (!ctx || !b || !sizes) return PG_E_INVALID;
-    if (!b->svev_built) return fail(ctx, PG_E_INVALID, NO_SV_TABLES);
-    *sizes = b->svev_sizes;
-    return PG_OK;
-}
-
-int pg_device_batch_sv_events_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *members, pg_event *events)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (!b->svev_built) return fail(ctx, PG_E_INVALID, NO_SV_TABLES);
-    size_t nm, ne;
-    sv_event_totals(b, &nm, &ne);
-    if (members && nm) HIP_TRY(ctx, hipMemcpy(members, b->svev_members, nm * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (events && ne) HIP_TRY(ctx, hipMemcpy(events, b->svev_events, ne * sizeof(pg_event), hipMemcpyDeviceToHost));
-    return PG_OK;
-}
-
-int pg_device_batch_sv_events_download_device(pg_ctx *ctx, pg_device_batch *b, uint32_t *d_members, pg_event *d_events)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (!b->svev_built) return fail(ctx, PG_E_INVALID, NO_SV_TABLES);
-    size_t nm, ne;
-    sv_event_totals(b, &nm, &ne);
-    int rc;
-    if ((d_members && (rc = check_device_ptr(ctx, d_members, nm * sizeof(uint32_t), 4, "sv events download: members"))) ||
-        (d_events && (rc = check_device_ptr(ctx, d_events, ne * sizeof(pg_event), 4, "sv events download: events"))))
-        return rc;
-    if (d_members && nm) HIP_TRY(ctx, hipMemcpy(d_members, b->svev_members, nm * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-    if (d_events && ne) HIP_TRY(ctx, hipMemcpy(d_events, b->svev_events, ne * sizeof(pg_event), hipMemcpyDeviceToDevice));
-    return PG_OK;
-}
-
-// ---- ... its fifth part (pg_report.hip): the report records per table member and per read
-namespace {
-int report_refusal(pg_ctx *ctx, pg_device_batch *b, const void *cands, const void *counts, const void *sv_cands, const void *sv_counts)
-{
-    if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
-    if (int rc = stale_batch(ctx, b)) return rc;
-    ctx->last_ms = 0.0;
-    if (b->n && !b->searched) return fail(ctx, PG_E_INVALID, "the batch has not been searched: no close and far ends to classify");
-    if (!b->ev_built) return fail(ctx, PG_E_INVALID, "report reads: pg_device_batch_events has not been run on this batch");
-    if (!b->svev_built) return fail(ctx, PG_E_INVALID, "report reads: pg_device_batch_sv_events has not been run on this batch since its events build");
-    if (b->n && (!cands || !counts || !sv_cands || !sv_counts)) return fail(ctx, PG_E_INVALID, "report reads: null candidate arrays");
-    return PG_OK;
-}
-
-// every list pointer is device memory
-int build_report(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *d_cands, const uint8_t *d_counts, const pg_variant_cand *d_sv_cands,
-                 const uint8_t *d_sv_counts)
-{
-    b->rr_built = false;
-    b->rr_n_records = 0;
-    const size_t n = b->n;
-    if (!n) {                                                 // nothing is launched for an empty batch
-        b->rr_built = true;
-        return PG_OK;
-    }
-    int rc;
-    // (each buffer on its own: an allocation that failed in an earlier call is tried again, never launched with)
-    if ((!b->rr_records && (rc = dev_alloc(ctx, &b->rr_records, n))) || (!b->rr_summaries && (rc = dev_alloc(ctx, &b->rr_summaries, n)))) return rc;
-    PgReportArgs a{};
-    uint64_t total = 0;
-    for (int t = 0; t < PG_REPORT_TABLES; t++) {
-        a.start[t] = (uint32_t)total;
-        total += t < PG_EVENT_TABLES ? b->ev_sizes.members[t] : b->svev_sizes.members[t - PG_EVENT_TABLES];
-    }
-    // (a read is boxed at most once: the seven lists together hold at most n members, the size of the record buffer)
-    if (total > n) return fail(ctx, PG_E_DEVICE, "report reads: the tables hold more members than the batch has reads");
-    a.start[PG_REPORT_TABLES] = (uint32_t)total;
-    a.out = b->out_rec;
-    a.pool = b->pool;
-    a.pool_runs = (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS;
-    a.strand = b->strand;
-    a.n = b->n;
-    a.cands = d_cands;
-    a.counts = d_counts;
-    a.sv_cands = d_sv_cands;
-    a.sv_counts = d_sv_counts;
-    a.reads = b->ev_reads;
-    a.ev_members = b->ev_members;
-    a.sv_members = b->svev_members;
-    a.records = b->rr_records;
-    a.summaries = b->rr_summaries;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    if (pg_report_launch(&a, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the report record kernels failed");
-    PgLaunchRec rec{};
-    rec.kernel = PG_KERNEL_REPORT;
-    rec.blocks = (int32_t)PG_EV_BLOCK;
-    log_launch(ctx, rec);
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->last_ms = ms;
-    b->rr_n_records = total;
-    b->rr_built = true;
-    return PG_OK;
-}
-const char *const NO_REPORT = "no report records: pg_device_batch_report_reads has not been run on this batch since its table builds";
-}  // namespace
-
-int pg_device_batch_report_reads_device(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *d_cands, const uint8_t *d_counts,
-                                        const pg_variant_cand *d_sv_cands, const uint8_t *d_sv_counts)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (int rc = report_refusal(ctx, b, d_cands, d_counts, d_sv_cands, d_sv_counts)) return rc;
-    const size_t n = b->n;
-    int rc;
-    if (n && ((rc = check_device_ptr(ctx, d_cands, n * 2 * PG_VARIANT_CANDS * sizeof(pg_variant_cand), 4, "report reads: cands")) ||
-              (rc = check_device_ptr(ctx, d_counts, n * 2, 1, "report reads: counts")) ||
-              (rc = check_device_ptr(ctx, d_sv_cands, n * PG_SV_SLOTS * sizeof(pg_variant_cand), 4, "report reads: sv_cands")) ||
-              (rc = check_device_ptr(ctx, d_sv_counts, n * PG_SV_KINDS, 1, "report reads: sv_counts"))))
-        return rc;
-    return build_report(ctx, b, d_cands, d_counts, d_sv_cands, d_sv_counts);
-}
-
-int pg_device_batch_report_reads(pg_ctx *ctx, pg_device_batch *b, const pg_variant_cand *cands, const uint8_t *counts,
-                                 const pg_variant_cand *sv_cands, const uint8_t *sv_counts)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (int rc = report_refusal(ctx, b, cands, counts, sv_cands, sv_counts)) return rc;
-    const size_t n = b->n;
-    EventTemps tmp;
-    pg_variant_cand *d_cands = nullptr, *d_sv = nullptr;
-    uint8_t *d_counts = nullptr, *d_svn = nullptr;
-    if (n) {
-        int rc;
-        if ((rc = EV_TAKE(tmp, ctx, d_cands, n * 2 * PG_VARIANT_CANDS)) || (rc = EV_TAKE(tmp, ctx, d_counts, n * 2)) ||
-            (rc = EV_TAKE(tmp, ctx, d_sv, n * PG_SV_SLOTS)) || (rc = EV_TAKE(tmp, ctx, d_svn, n * PG_SV_KINDS)))
-            return rc;
-        HIP_TRY(ctx, hipMemcpy(d_cands, cands, n * 2 * PG_VARIANT_CANDS * sizeof(pg_variant_cand), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(d_counts, counts, n * 2, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(d_sv, sv_cands, n * PG_SV_SLOTS * sizeof(pg_variant_cand), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(d_svn, sv_counts, n * PG_SV_KINDS, hipMemcpyHostToDevice));
-    }
-    return build_report(ctx, b, d_cands, d_counts, d_sv, d_svn);
-}
-
-int pg_device_batch_report_sizes(pg_ctx *ctx, pg_device_batch *b, pg_report_sizes *sizes)
-{
-    use_device(ctx);
-    if (!ctx || !b || !sizes) return PG_E_INVALID;
-    if (!b->rr_built) return fail(ctx, PG_E_INVALID, NO_REPORT);
-    sizes->records = b->rr_n_records;
-    sizes->reads = b->n;
-    return PG_OK;
-}
-
-static int report_download(pg_ctx *ctx, pg_device_batch *b, pg_report_read *records, pg_report_summary *summaries, hipMemcpyKind kind)
-{
-    if (records && b->rr_n_records) HIP_TRY(ctx, hipMemcpy(records, b->rr_records, (size_t)b->rr_n_records * sizeof(pg_report_read), kind));
-    if (summaries && b->n) HIP_TRY(ctx, hipMemcpy(summaries, b->rr_summaries, (size_t)b->n * sizeof(pg_report_summary), kind));
-    return PG_OK;
-}
-
-int pg_device_batch_report_download(pg_ctx *ctx, pg_device_batch *b, pg_report_read *records, pg_report_summary *summaries)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (!b->rr_built) return fail(ctx, PG_E_INVALID, NO_REPORT);
-    return report_download(ctx, b, records, summaries, hipMemcpyDeviceToHost);
-}
-
-int pg_device_batch_report_download_device(pg_ctx *ctx, pg_device_batch *b, pg_report_read *d_records, pg_report_summary *d_summaries)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (!b->rr_built) return fail(ctx, PG_E_INVALID, NO_REPORT);
-    int rc;
-    if ((d_records && (rc = check_device_ptr(ctx, d_records, (size_t)b->rr_n_records * sizeof(pg_report_read), 4, "report download: records"))) ||
-        (d_summaries && (rc = check_device_ptr(ctx, d_summaries, (size_t)b->n * sizeof(pg_report_summary), 4, "report download: summaries"))))
-        return rc;
-    return report_download(ctx, b, d_records, d_summaries, hipMemcpyDeviceToDevice);
-}
-
-// ---- ... its sixth part (pg_li.hip): the long-insertion position tables
-int pg_device_batch_li(pg_ctx *ctx, pg_device_batch *b, const pg_li_window *window)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (ctx->names.empty()) return fail(ctx, PG_E_NO_REFERENCE, "no reference loaded");
-    if (int rc = stale_batch(ctx, b)) return rc;
-    ctx->last_ms = 0.0;
-    if (b->n && !b->searched) return fail(ctx, PG_E_INVALID, "the batch has not been searched: no close and far ends to classify");
-    if (!b->ev_built) return fail(ctx, PG_E_INVALID, "li: pg_device_batch_events has not been run on this batch");
-    if (!window) return fail(ctx, PG_E_INVALID, "li: null pg_li_window");
-    if (window->lo > window->hi) return fail(ctx, PG_E_INVALID, "li: lo > hi");
-    b->li_built = false;
-    b->li_sizes = pg_li_sizes{};
-    const size_t n = b->n;
-    if (!n) {                                                 // nothing is launched for an empty batch
-        b->li_built = true;
-        return PG_OK;
-    }
-    int rc;
-    // (each buffer on its own: an allocation that failed in an earlier call is tried again, never launched with)
-    if ((!b->li_members && (rc = dev_alloc(ctx, &b->li_members, n))) || (!b->li_positions && (rc = dev_alloc(ctx, &b->li_positions, n)))) return rc;
-    EventTemps tmp;
-    PgLiArgs a{};
-    const size_t n_blk = n / PG_EV_BLOCK + 2;
-    if ((rc = EV_TAKE(tmp, ctx, a.rec_a, n)) || (rc = EV_TAKE(tmp, ctx, a.rec_b, n)) || (rc = EV_TAKE(tmp, ctx, a.flag, n)) ||
-        (rc = EV_TAKE(tmp, ctx, a.rank, n)) || (rc = EV_TAKE(tmp, ctx, a.blk, n_blk)) || (rc = EV_TAKE(tmp, ctx, a.pfirst, n + 1)) ||
-        (rc = EV_TAKE(tmp, ctx, a.digit_cnt, 256 * n_blk + 1)) || (rc = EV_TAKE(tmp, ctx, a.info, 1)))
-        return rc;
-    a.out = b->out_rec;
-    a.pool_runs = (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS;
-    a.seq = b->seq;
-    a.seq_off = b->seq_off;
-    a.strand = b->strand;
-    a.chr = b->chr;
-    a.reads = b->ev_reads;
-    a.n = b->n;
-    a.chr_id = b->ev_window.chr_id;
-    a.lo = window->lo;
-    a.hi = window->hi;
-    a.members = b->li_members;
-    a.positions = b->li_positions;
-    PgLaunchRec rec{};
-    rec.kernel = PG_KERNEL_LI;
-    rec.blocks = (int32_t)PG_EV_BLOCK;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    if (pg_li_gather_launch(&a, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the long-insertion gather kernels failed");
-    log_launch(ctx, rec);
-    PgLiInfo info;
-    HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (info.n_li > n || info.n_plus > info.n_li) return fail(ctx, PG_E_DEVICE, "li: the count of long-insertion reads exceeds the batch");
-    const uint32_t n_li = info.n_li, n_plus = info.n_plus;
-    if (n_li) {                                               // (no LI read: nothing below indexes an empty array)
-        PgLiRec *src = a.rec_b, *dst = a.rec_a;
-        for (int pass = 0; pass < PG_LI_SORT_PASSES; pass++) {
-            const int word = pass >= 4 ? 1 : 0, shift = pass >= 4 ? 0 : pass * 8;
-            if ((((info.key_or[word] ^ info.key_and[word]) >> shift) & 0xffu) == 0u) continue;      // the byte is constant: no pass
-            if (pg_li_sort_pass_launch(&a, src, dst, n_li, pass, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching a long-insertion sort pass failed");
-            log_launch(ctx, rec);
-            std::swap(src, dst);
-        }
-        if (pg_li_tables_launch(&a, src, n_li, n_plus, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the long-insertion table kernels failed");
-        log_launch(ctx, rec);
-        HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->last_ms = ms;
-    if (n_li) {
-        if (info.n_pos > n_li || info.pos_plus > info.n_pos) return fail(ctx, PG_E_DEVICE, "li: inconsistent table sizes");
-        b->li_sizes.members[0] = n_plus;
-        b->li_sizes.members[1] = n_li - n_plus;
-        b->li_sizes.positions[0] = info.pos_plus;
-        b->li_sizes.positions[1] = info.n_pos - info.pos_plus;
-    }
-    b->li_built = true;
-    return PG_OK;
-}
-
-static const char *const NO_LI = "no long-insertion tables: pg_device_batch_li has not been run on this batch since its events build";
-
-int pg_device_batch_li_sizes(pg_ctx *ctx, pg_device_batch *b, pg_li_sizes *sizes)
-{
-    use_device(ctx);
-    if (!ctx || !b || !sizes) return PG_E_INVALID;
-    if (!b->li_built) return fail(ctx, PG_E_INVALID, NO_LI);
-    *sizes = b->li_sizes;
-    return PG_OK;
-}
-
-static int li_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *members, pg_li_pos *positions, hipMemcpyKind kind)
-{
-    const size_t nm = (size_t)(b->li_sizes.members[0] + b->li_sizes.members[1]), np = (size_t)(b->li_sizes.positions[0] + b->li_sizes.positions[1]);
-    if (members && nm) HIP_TRY(ctx, hipMemcpy(members, b->li_members, nm * sizeof(uint32_t), kind));
-    if (positions && np) HIP_TRY(ctx, hipMemcpy(positions, b->li_positions, np * sizeof(pg_li_pos), kind));
-    return PG_OK;
-}
-
-int pg_device_batch_li_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *members, pg_li_pos *positions)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (!b->li_built) return fail(ctx, PG_E_INVALID, NO_LI);
-    return li_download(ctx, b, members, positions, hipMemcpyDeviceToHost);
-}
-
-int pg_device_batch_li_download_device(pg_ctx *ctx, pg_device_batch *b, uint32_t *d_members, pg_li_pos *d_positions)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (!b->li_built) return fail(ctx, PG_E_INVALID, NO_LI);
-    const size_t nm = (size_t)(b->li_sizes.members[0] + b->li_sizes.members[1]), np = (size_t)(b->li_sizes.positions[0] + b->li_sizes.positions[1]);
-    int rc;
-    if ((d_members && (rc = check_device_ptr(ctx, d_members, nm * sizeof(uint32_t), 4, "li download: members"))) ||
-        (d_positions && (rc = check_device_ptr(ctx, d_positions, np * sizeof(pg_li_pos), 4, "li download: positions"))))
-        return rc;
-    return li_download(ctx, b, d_members, d_positions, hipMemcpyDeviceToDevice);
-}
-
-// ---- one call per window: the two candidate kernels, both table builds and the report records, the lists staying with the batch
-int pg_device_batch_classify(pg_ctx *ctx, pg_device_batch *b, const pg_classify_params *p, const uint32_t *name_id)
-{
-    use_device(ctx);
-    if (!ctx || !b) return PG_E_INVALID;
-    if (!p) return fail(ctx, PG_E_INVALID, "classify: null pg_classify_params");
-    // every stage's refusal before the first launch
-    if (int rc = events_refusal(ctx, b, &p->window, false)) return rc;
-    if (int rc = sv_params_ok(ctx, &p->sv)) return rc;
-    if (p->max_listed < 0 || p->max_listed > PG_VARIANT_CANDS) return fail(ctx, PG_E_INVALID, "classify: max_listed must lie in [0, PG_VARIANT_CANDS]");
-    if (b->n >= 0x80000000u) return fail(ctx, PG_E_INVALID, "classify: 2^31 reads or more (bit 31 of a member word is PG_SVEV_MEMBER_DUP)");
-    const size_t n = b->n;
-    int rc;
-    // (each buffer on its own: an allocation that failed in an earlier call is tried again, never launched with)
-    if (n && ((!b->cl_cands && (rc = dev_alloc(ctx, &b->cl_cands, n * 2 * PG_VARIANT_CANDS))) || (!b->cl_counts && (rc = dev_alloc(ctx, &b->cl_counts, n * 2))) ||
-              (!b->cl_sv_cands && (rc = dev_alloc(ctx, &b->cl_sv_cands, n * PG_SV_SLOTS))) ||
-              (!b->cl_sv_counts && (rc = dev_alloc(ctx, &b->cl_sv_counts, n * PG_SV_KINDS)))))
-        return rc;
-    EventTemps tmp;
-    uint32_t *d_name = nullptr;
-    if (n && name_id) {
-        if ((rc = EV_TAKE(tmp, ctx, d_name, n))) return rc;
-        HIP_TRY(ctx, hipMemcpy(d_name, name_id, n * 4, hipMemcpyHostToDevice));
-    }
-    double ms = 0.0;
-    if ((rc = variant_candidates(ctx, b, b->cl_cands, b->cl_counts))) return rc;
-    ms += ctx->last_ms;
-    if ((rc = sv_candidates(ctx, b, &p->sv, b->cl_sv_cands, b->cl_sv_counts))) return rc;
-    ms += ctx->last_ms;
-    if (n && p->max_listed < PG_VARIANT_CANDS) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        if (pg_report_cut_launch(b->cl_counts, b->cl_sv_counts, b->n, (uint32_t)p->max_listed, ctx->stream))
-            return fail(ctx, PG_E_DEVICE, "launching the list cut kernel failed");
-        PgLaunchRec rec{};
-        rec.kernel = PG_KERNEL_REPORT;
-        rec.blocks = 0;                                       // (0: the cut; PG_EV_BLOCK: the records)
-        log_launch(ctx, rec);
-        HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        float cut_ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&cut_ms, ctx->ev0, ctx->ev1));
-        ms += cut_ms;
-    }
-    if ((rc = build_events(ctx, b, &p->window, b->cl_cands, b->cl_counts, b->cl_sv_cands, b->cl_sv_counts, d_name))) return rc;
-    ms += ctx->last_ms;
-    if ((rc = build_sv_events(ctx, b, b->cl_sv_cands))) return rc;
-    ms += ctx->last_ms;
-    if ((rc = build_report(ctx, b, b->cl_cands, b->cl_counts, b->cl_sv_cands, b->cl_sv_counts))) return rc;
-    ctx->last_ms += ms;
-    return PG_OK;
 }
 
 void pg_device_batch_free(pg_ctx *ctx, pg_device_batch *b)

@@ -413,6 +413,11 @@ int pg_devio_store_totals(const unsigned long long *info, unsigned long long *cl
 // Event tables (pg_events.hip): the window tail and cascade per read, the order of the boxed reads of the four
 // sorted kinds, duplicates and events.  Every pointer is device memory of the library's own or one the host has checked.
 #define PG_EV_BLOCK 256u              // the scan / sort block: reads (records) per workgroup of the count, rank and scatter kernels
+// The scan stages every table build shares (pg_table_prims.hip; they launch and return, errors surface at the caller's hipGetLastError):
+// rank[i] = flagged elements of flag[0 .. m) before i in its block, then blk[0 .. blocks) to its exclusive scan, blk[blocks] = the total
+void pg_table_rank_scan_launch(const uint8_t *flag, uint32_t m, uint32_t *rank, uint32_t *blk, void *stream);
+// a[0 .. m) to its exclusive scan in place, a[m] = the total (one workgroup; the array has m + 1 entries)
+void pg_table_scan_launch(uint32_t *a, uint32_t m, void *stream);
 #define PG_EV_SORT_PASSES 17          // one per key byte, least significant first: BP (2), NT_size (2), IndelSize, BPRight, BPLeft (4 each), table
 struct PgEventRec { uint32_t w[8]; }; // one boxed read: BPLeft, BPRight, IndelSize, NT_size << 16 | (BP ^ 0x8000), Left, Right, read, table | plus << 8 | ReadLength << 16
 struct PgEventInfo {                  // what the host reads back, 96 bytes

@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "pg_device.h"
+#include "pg_table_prims.h"
 #include "pg_variant_align.h"
 #include "pg_variant_dev.h"
 
@@ -38,56 +39,6 @@ __device__ __forceinline__ u32 rec_nt(const PgEventRec &r) { return r.w[3] >> 16
 __device__ __forceinline__ int32_t rec_bp(const PgEventRec &r) { return (int32_t)(int16_t)((r.w[3] & 0xffffu) ^ 0x8000u); }
 // (boxed reads have 0 <= (int)BPLeft: the division is the host's)
 __device__ __forceinline__ u32 rec_box(const PgEventRec &r, u32 box_size) { return (u32)((int32_t)r.w[0] / (int32_t)box_size); }
-
-// the post-state's length (pg_variant.hip): rc_flag applications of setUnmatchedSeq(ReverseComplement()) strip the bytes outside
-// ACGTN the read began with (first application) and ended with (second); *lead = its first base among the bytes as uploaded
-__device__ int32_t post_state_len(const uint8_t *s, int32_t L, uint32_t rc_flag, int32_t *lead)
-{
-    *lead = 0;
-    if (!rc_flag) return L;
-    int32_t first_ok = 0;
-    while (first_ok < L && base_code(s[first_ok]) == (uint32_t)PG_VA_NONE) first_ok++;
-    int32_t last_ok = L - 1;
-    if (rc_flag >= 2)
-        while (last_ok >= first_ok && base_code(s[last_ok]) == (uint32_t)PG_VA_NONE) last_ok--;
-    *lead = first_ok;
-    return last_ok + 1 - first_ok;
-}
-
-// exclusive scan of one value per thread over a workgroup of NW waves; *total = the workgroup's sum
-template <u32 NW>
-__device__ __forceinline__ u32 block_excl_scan(u32 v, u32 *total)
-{
-    __shared__ u32 wave_sum[NW];
-    const u32 lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    u32 inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const u32 o = (u32)__shfl_up((int)inc, d, 64);
-        if (lane >= (u32)d) inc += o;
-    }
-    if (lane == 63u) wave_sum[w] = inc;
-    __syncthreads();
-    u32 base = 0, tot = 0;
-    for (u32 k = 0; k < NW; k++) {
-        const u32 s = wave_sum[k];
-        if (k < w) base += s;
-        tot += s;
-    }
-    __syncthreads();                                      // (the next call writes wave_sum again)
-    *total = tot;
-    return base + inc - v;
-}
-
-__device__ __forceinline__ u32 wave_or(u32 v)
-{
-    for (int m = 32; m >= 1; m >>= 1) v |= (u32)__shfl_xor((int)v, m, 64);
-    return v;
-}
-__device__ __forceinline__ u32 wave_and(u32 v)
-{
-    for (int m = 32; m >= 1; m >>= 1) v &= (u32)__shfl_xor((int)v, m, 64);
-    return v;
-}
 
 }  // namespace
 
@@ -178,36 +129,6 @@ extern "C" __global__ void __launch_bounds__(PG_EV_BLOCK) pg_events_cascade_kern
     a.flag[i] = boxed_flag;
 }
 
-// ---- rank, scan, fill: rank[i] = flagged elements before i in its block, blk[b] = the block's count
-extern "C" __global__ void __launch_bounds__(PG_EV_BLOCK) pg_events_rank_kernel(const uint8_t *flag, u32 m, u32 *rank, u32 *blk)
-{
-    const u32 i = blockIdx.x * PG_EV_BLOCK + threadIdx.x;
-    const u32 v = i < m ? (u32)(flag[i] != 0) : 0u;
-    u32 tot;
-    const u32 ex = block_excl_scan<PG_EV_BLOCK / 64u>(v, &tot);
-    if (i < m) rank[i] = ex;
-    if (threadIdx.x == 0u) blk[blockIdx.x] = tot;
-}
-
-// one workgroup: a[0 .. m) to its exclusive scan, in place; a[m] = the total (the array has m + 1 entries)
-#define PG_EV_SCAN_THREADS 1024u
-extern "C" __global__ void __launch_bounds__(PG_EV_SCAN_THREADS) pg_events_scan_kernel(u32 *a, u32 m)
-{
-    const u32 chunk = (m + PG_EV_SCAN_THREADS - 1u) / PG_EV_SCAN_THREADS;
-    const u32 lo = threadIdx.x * chunk < m ? threadIdx.x * chunk : m;
-    const u32 hi = lo + chunk < m ? lo + chunk : m;
-    u32 s = 0;
-    for (u32 k = lo; k < hi; k++) s += a[k];
-    u32 tot;
-    u32 run = block_excl_scan<PG_EV_SCAN_THREADS / 64u>(s, &tot);
-    for (u32 k = lo; k < hi; k++) {
-        const u32 v = a[k];
-        a[k] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0u) a[m] = tot;
-}
-
 // the boxed reads to rec_b in descending read index; the masks of their key bytes
 extern "C" __global__ void __launch_bounds__(PG_EV_BLOCK) pg_events_compact_kernel(PgEventArgs a)
 {
@@ -240,36 +161,14 @@ __device__ __forceinline__ u32 key_digit(const PgEventRec &r, int pass)
 }
 }  // namespace
 
-// cnt[d * n_blk + b] = records of block b with digit d
 extern "C" __global__ void __launch_bounds__(PG_EV_BLOCK) pg_events_digit_count_kernel(const PgEventRec *src, u32 m, int pass, u32 n_blk, u32 *cnt)
 {
-    __shared__ u32 hist[256];
-    hist[threadIdx.x] = 0u;
-    __syncthreads();
-    const u32 i = blockIdx.x * PG_EV_BLOCK + threadIdx.x;
-    if (i < m) atomicAdd(&hist[key_digit(src[i], pass)], 1u);
-    __syncthreads();
-    cnt[threadIdx.x * n_blk + blockIdx.x] = hist[threadIdx.x];
+    tab_digit_count(src, m, n_blk, cnt, [pass](const PgEventRec &r) { return key_digit(r, pass); });
 }
-
-// cnt scanned: the place of a record = cnt[its digit][its block] + the records of its block before it with the same digit
 extern "C" __global__ void __launch_bounds__(PG_EV_BLOCK) pg_events_scatter_kernel(const PgEventRec *src, PgEventRec *dst, u32 m, int pass, u32 n_blk,
                                                                                     const u32 *cnt)
 {
-    __shared__ uint8_t dig[PG_EV_BLOCK];
-    const u32 i = blockIdx.x * PG_EV_BLOCK + threadIdx.x;
-    PgEventRec r;
-    u32 d = 0;
-    if (i < m) {
-        r = src[i];
-        d = key_digit(r, pass);
-    }
-    dig[threadIdx.x] = (uint8_t)d;
-    __syncthreads();
-    if (i >= m) return;
-    u32 before = 0;
-    for (u32 t = 0; t < threadIdx.x; t++) before += (u32)(dig[t] == (uint8_t)d);
-    dst[cnt[d * n_blk + blockIdx.x] + before] = r;
+    tab_scatter(src, dst, m, n_blk, cnt, [pass](const PgEventRec &r) { return key_digit(r, pass); });
 }
 
 // ---- stage C: flag[i] = the read is unique.  The walk back over the box is the literal one: quadratic in the size of a box
@@ -462,7 +361,7 @@ extern "C" __global__ void __launch_bounds__(PG_EV_BLOCK) pg_events_event_kernel
     }
 }
 
-// ---- host side of the launches (pg_api.cpp checks the arguments and owns the buffers)
+// ---- host side of the launches (pg_api_classify.cpp checks the arguments and owns the buffers)
 static inline u32 ev_blocks(u32 m) { return (m + PG_EV_BLOCK - 1u) / PG_EV_BLOCK; }
 
 int pg_events_cascade_launch(const PgEventArgs *a, void *stream)
@@ -476,8 +375,7 @@ int pg_events_cascade_launch(const PgEventArgs *a, void *stream)
     if (!a->n) return 0;
     const u32 nb = ev_blocks(a->n);
     hipLaunchKernelGGL(pg_events_cascade_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, *a);
-    hipLaunchKernelGGL(pg_events_rank_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, (const uint8_t *)a->flag, a->n, a->rank, a->blk);
-    hipLaunchKernelGGL(pg_events_scan_kernel, dim3(1), dim3(PG_EV_SCAN_THREADS), 0, st, a->blk, nb);
+    pg_table_rank_scan_launch(a->flag, a->n, a->rank, a->blk, st);
     hipLaunchKernelGGL(pg_events_compact_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, *a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -488,7 +386,7 @@ int pg_events_sort_pass_launch(const PgEventArgs *a, const PgEventRec *src, PgEv
     if (!n_boxed) return 0;
     const u32 nb = ev_blocks(n_boxed);
     hipLaunchKernelGGL(pg_events_digit_count_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, src, n_boxed, pass, nb, a->digit_cnt);
-    hipLaunchKernelGGL(pg_events_scan_kernel, dim3(1), dim3(PG_EV_SCAN_THREADS), 0, st, a->digit_cnt, 256u * nb);
+    pg_table_scan_launch(a->digit_cnt, 256u * nb, st);
     hipLaunchKernelGGL(pg_events_scatter_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, src, dst, n_boxed, pass, nb, (const u32 *)a->digit_cnt);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -499,12 +397,10 @@ int pg_events_tables_launch(const PgDevRef *ref, const PgEventArgs *a, const PgE
     if (!n_boxed) return 0;
     const u32 nb = ev_blocks(n_boxed);
     hipLaunchKernelGGL(pg_events_unique_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, *a, sorted, n_boxed);
-    hipLaunchKernelGGL(pg_events_rank_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, (const uint8_t *)a->flag, n_boxed, a->rank, a->blk);
-    hipLaunchKernelGGL(pg_events_scan_kernel, dim3(1), dim3(PG_EV_SCAN_THREADS), 0, st, a->blk, nb);
+    pg_table_rank_scan_launch(a->flag, n_boxed, a->rank, a->blk, st);
     hipLaunchKernelGGL(pg_events_member_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, *a, sorted, n_boxed);
     hipLaunchKernelGGL(pg_events_head_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, *a, sorted, n_boxed);
-    hipLaunchKernelGGL(pg_events_rank_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, (const uint8_t *)a->flag, n_boxed, a->rank, a->blk);
-    hipLaunchKernelGGL(pg_events_scan_kernel, dim3(1), dim3(PG_EV_SCAN_THREADS), 0, st, a->blk, nb);
+    pg_table_rank_scan_launch(a->flag, n_boxed, a->rank, a->blk, st);
     hipLaunchKernelGGL(pg_events_first_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, *a, sorted, n_boxed);
     // (at most n_boxed events: a grid over that many waves, the surplus ones leave at once)
     hipLaunchKernelGGL(pg_events_event_kernel, dim3((n_boxed + PG_EV_BLOCK / 64u - 1u) / (PG_EV_BLOCK / 64u)), dim3(PG_EV_BLOCK), 0, st, *ref, *a,

@@ -130,7 +130,7 @@ extern "C" __global__ void __launch_bounds__(PG_EV_BLOCK) pg_report_cut_kernel(u
     }
 }
 
-// ---- host side of the launches (pg_api.cpp checks the arguments and owns the buffers)
+// ---- host side of the launches (pg_api_classify.cpp checks the arguments and owns the buffers)
 int pg_report_launch(const PgReportArgs *a, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;

@@ -333,7 +333,7 @@ extern "C" __global__ void __launch_bounds__(256) pg_sv_kernel(PgDevRef ref, PgS
         a.counts[(size_t)read * PG_SV_KINDS + lane] = (uint8_t)(lane == 0u ? n_di : lane == 1u ? n_td : lane == 2u ? n_tdnt : lane == 3u ? n_inv : n_invnt);
 }
 
-// Host side of the launch (pg_api.cpp checks the batch and the parameters and owns the buffers): four reads per workgroup.
+// Host side of the launch (pg_api_classify.cpp checks the batch and the parameters and owns the buffers): four reads per workgroup.
 int pg_sv_launch(const PgDevRef *ref, const PgOutRec *out, const pg_run *pool, unsigned long long pool_runs, const uint8_t *seq,
                  const uint64_t *seq_off, const uint8_t *strand, const int32_t *chr, const uint32_t *d_mm, const int32_t *d_budget,
                  int32_t min_matched, uint32_t min_inv, uint32_t spacer, uint32_t n, pg_variant_cand *d_cands, uint8_t *d_counts, void *stream)

@@ -18,6 +18,7 @@
 
 #include "pg_device.h"
 #include "pg_sv_order.h"
+#include "pg_table_prims.h"
 #include "pg_variant_align.h"
 #include "pg_variant_dev.h"
 
@@ -56,64 +57,6 @@ __device__ __forceinline__ u32 sort_digit(const PgSvEventRec &r, int pass)
     if (pass < PG_SVEV_PASS_TABLE) return (key_word(r, PG_SVEV_KEY_WORDS - 1 - (pass >> 2)) >> ((pass & 3) * 8)) & 0xffu;
     if (pass == PG_SVEV_PASS_TABLE) return rec_table(r);
     return (r.w[7] >> ((pass - PG_SVEV_PASS_BOX) * 8)) & 0xffu;
-}
-
-// the post-state's length (pg_variant.hip): rc_flag applications of setUnmatchedSeq(ReverseComplement()) strip the bytes outside
-// ACGTN the read began with (first application) and ended with (second); *lead = its first base among the bytes as uploaded
-__device__ int32_t post_state_len(const uint8_t *s, int32_t L, uint32_t rc_flag, int32_t *lead)
-{
-    *lead = 0;
-    if (!rc_flag) return L;
-    int32_t first_ok = 0;
-    while (first_ok < L && base_code(s[first_ok]) == (uint32_t)PG_VA_NONE) first_ok++;
-    int32_t last_ok = L - 1;
-    if (rc_flag >= 2)
-        while (last_ok >= first_ok && base_code(s[last_ok]) == (uint32_t)PG_VA_NONE) last_ok--;
-    *lead = first_ok;
-    return last_ok + 1 - first_ok;
-}
-
-// exclusive scan of one value per thread over a workgroup of NW waves; *total = the workgroup's sum
-template <u32 NW>
-__device__ __forceinline__ u32 block_excl_scan(u32 v, u32 *total)
-{
-    __shared__ u32 wave_sum[NW];
-    const u32 lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    u32 inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const u32 o = (u32)__shfl_up((int)inc, d, 64);
-        if (lane >= (u32)d) inc += o;
-    }
-    if (lane == 63u) wave_sum[w] = inc;
-    __syncthreads();
-    u32 base = 0, tot = 0;
-    for (u32 k = 0; k < NW; k++) {
-        const u32 s = wave_sum[k];
-        if (k < w) base += s;
-        tot += s;
-    }
-    __syncthreads();                                      // (the next call writes wave_sum again)
-    *total = tot;
-    return base + inc - v;
-}
-
-__device__ __forceinline__ u32 wave_or(u32 v)
-{
-    for (int m = 32; m >= 1; m >>= 1) v |= (u32)__shfl_xor((int)v, m, 64);
-    return v;
-}
-__device__ __forceinline__ u32 wave_and(u32 v)
-{
-    for (int m = 32; m >= 1; m >>= 1) v &= (u32)__shfl_xor((int)v, m, 64);
-    return v;
-}
-__device__ __forceinline__ u32 wave_max(u32 v)
-{
-    for (int m = 32; m >= 1; m >>= 1) {
-        const u32 o = (u32)__shfl_xor((int)v, m, 64);
-        v = o > v ? o : v;
-    }
-    return v;
 }
 
 // One member against its run's largest IndelSize (pg_host_sv.cpp:410): the quotient is a float, 0.95 a double
@@ -167,36 +110,6 @@ extern "C" __global__ void __launch_bounds__(PG_EV_BLOCK) pg_sv_events_gather_ke
     a.flag[i] = boxed;
 }
 
-// ---- rank, scan, fill: rank[i] = flagged elements before i in its block, blk[b] = the block's count
-extern "C" __global__ void __launch_bounds__(PG_EV_BLOCK) pg_sv_events_rank_kernel(const uint8_t *flag, u32 m, u32 *rank, u32 *blk)
-{
-    const u32 i = blockIdx.x * PG_EV_BLOCK + threadIdx.x;
-    const u32 v = i < m ? (u32)(flag[i] != 0) : 0u;
-    u32 tot;
-    const u32 ex = block_excl_scan<PG_EV_BLOCK / 64u>(v, &tot);
-    if (i < m) rank[i] = ex;
-    if (threadIdx.x == 0u) blk[blockIdx.x] = tot;
-}
-
-// one workgroup: a[0 .. m) to its exclusive scan, in place; a[m] = the total (the array has m + 1 entries)
-#define PG_SVEV_SCAN_THREADS 1024u
-extern "C" __global__ void __launch_bounds__(PG_SVEV_SCAN_THREADS) pg_sv_events_scan_kernel(u32 *a, u32 m)
-{
-    const u32 chunk = (m + PG_SVEV_SCAN_THREADS - 1u) / PG_SVEV_SCAN_THREADS;
-    const u32 lo = threadIdx.x * chunk < m ? threadIdx.x * chunk : m;
-    const u32 hi = lo + chunk < m ? lo + chunk : m;
-    u32 s = 0;
-    for (u32 k = lo; k < hi; k++) s += a[k];
-    u32 tot;
-    u32 run = block_excl_scan<PG_SVEV_SCAN_THREADS / 64u>(s, &tot);
-    for (u32 k = lo; k < hi; k++) {
-        const u32 v = a[k];
-        a[k] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0u) a[m] = tot;
-}
-
 // the boxed reads to rec in ascending read index; the identity permutations; the masks of the segment and key bytes
 extern "C" __global__ void __launch_bounds__(PG_EV_BLOCK) pg_sv_events_compact_kernel(PgSvEventArgs a)
 {
@@ -233,32 +146,13 @@ extern "C" __global__ void __launch_bounds__(PG_EV_BLOCK) pg_sv_events_compact_k
 extern "C" __global__ void __launch_bounds__(PG_EV_BLOCK) pg_sv_events_digit_count_kernel(const PgSvEventRec *rec, const u32 *src, u32 m, int pass,
                                                                                            u32 n_blk, u32 *cnt)
 {
-    __shared__ u32 hist[256];
-    hist[threadIdx.x] = 0u;
-    __syncthreads();
-    const u32 i = blockIdx.x * PG_EV_BLOCK + threadIdx.x;
-    if (i < m) atomicAdd(&hist[sort_digit(rec[src[i]], pass)], 1u);
-    __syncthreads();
-    cnt[threadIdx.x * n_blk + blockIdx.x] = hist[threadIdx.x];
+    tab_digit_count(src, m, n_blk, cnt, [rec, pass](const u32 &p) { return sort_digit(rec[p], pass); });
 }
-
 // cnt scanned: the slot of a place = cnt[its digit][its block] + the places of its block before it with the same digit
 extern "C" __global__ void __launch_bounds__(PG_EV_BLOCK) pg_sv_events_scatter_kernel(const PgSvEventRec *rec, const u32 *src, u32 *dst, u32 m, int pass,
                                                                                        u32 n_blk, const u32 *cnt)
 {
-    __shared__ uint8_t dig[PG_EV_BLOCK];
-    const u32 i = blockIdx.x * PG_EV_BLOCK + threadIdx.x;
-    u32 p = 0, d = 0;
-    if (i < m) {
-        p = src[i];
-        d = sort_digit(rec[p], pass);
-    }
-    dig[threadIdx.x] = (uint8_t)d;
-    __syncthreads();
-    if (i >= m) return;
-    u32 before = 0;
-    for (u32 t = 0; t < threadIdx.x; t++) before += (u32)(dig[t] == (uint8_t)d);
-    dst[cnt[d * n_blk + blockIdx.x] + before] = p;
+    tab_scatter(src, dst, m, n_blk, cnt, [rec, pass](const u32 &p) { return sort_digit(rec[p], pass); });
 }
 
 // ---- ranks: flag[i] = the place kperm[i] opens a class of equal (table, key)
@@ -626,7 +520,7 @@ extern "C" __global__ void __launch_bounds__(PG_EV_BLOCK) pg_sv_events_event_ker
     }
 }
 
-// ---- host side of the launches (pg_api.cpp checks the arguments and owns the buffers)
+// ---- host side of the launches (pg_api_classify.cpp checks the arguments and owns the buffers)
 static inline u32 ev_blocks(u32 m) { return (m + PG_EV_BLOCK - 1u) / PG_EV_BLOCK; }
 
 int pg_sv_events_gather_launch(const PgSvEventArgs *a, void *stream)
@@ -641,8 +535,7 @@ int pg_sv_events_gather_launch(const PgSvEventArgs *a, void *stream)
     if (!a->n) return 0;
     const u32 nb = ev_blocks(a->n);
     hipLaunchKernelGGL(pg_sv_events_gather_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, *a);
-    hipLaunchKernelGGL(pg_sv_events_rank_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, (const uint8_t *)a->flag, a->n, a->rank, a->blk);
-    hipLaunchKernelGGL(pg_sv_events_scan_kernel, dim3(1), dim3(PG_SVEV_SCAN_THREADS), 0, st, a->blk, nb);
+    pg_table_rank_scan_launch(a->flag, a->n, a->rank, a->blk, st);
     hipLaunchKernelGGL(pg_sv_events_compact_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, *a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -654,7 +547,7 @@ int pg_sv_events_sort_pass_launch(const PgSvEventArgs *a, const uint32_t *src, u
     const u32 nb = ev_blocks(n_boxed);
     hipLaunchKernelGGL(pg_sv_events_digit_count_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, (const PgSvEventRec *)a->rec, src, n_boxed, pass, nb,
                        a->digit_cnt);
-    hipLaunchKernelGGL(pg_sv_events_scan_kernel, dim3(1), dim3(PG_SVEV_SCAN_THREADS), 0, st, a->digit_cnt, 256u * nb);
+    pg_table_scan_launch(a->digit_cnt, 256u * nb, st);
     hipLaunchKernelGGL(pg_sv_events_scatter_kernel, dim3(nb), dim3(PG_EV_BLOCK), 0, st, (const PgSvEventRec *)a->rec, src, dst, n_boxed, pass, nb,
                        (const u32 *)a->digit_cnt);
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -665,30 +558,24 @@ int pg_sv_events_tables_launch(const PgDevRef *ref, const PgSvEventArgs *a, uint
     hipStream_t st = (hipStream_t)stream;
     if (!n_boxed) return 0;
     const u32 nb = ev_blocks(n_boxed);
-    const dim3 grid(nb), block(PG_EV_BLOCK), one(1), scan(PG_SVEV_SCAN_THREADS);
+    const dim3 grid(nb), block(PG_EV_BLOCK);
     const dim3 waves((n_boxed + PG_EV_BLOCK / 64u - 1u) / (PG_EV_BLOCK / 64u));   // (at most n_boxed runs: the surplus waves leave at once)
-    const uint8_t *flag = a->flag;
     hipLaunchKernelGGL(pg_sv_events_key_head_kernel, grid, block, 0, st, *a, kperm, n_boxed);
-    hipLaunchKernelGGL(pg_sv_events_rank_kernel, grid, block, 0, st, flag, n_boxed, a->rank, a->blk);
-    hipLaunchKernelGGL(pg_sv_events_scan_kernel, one, scan, 0, st, a->blk, nb);
+    pg_table_rank_scan_launch(a->flag, n_boxed, a->rank, a->blk, st);
     hipLaunchKernelGGL(pg_sv_events_key_rank_kernel, grid, block, 0, st, *a, kperm, n_boxed);
     hipLaunchKernelGGL(pg_sv_events_seg_head_kernel, grid, block, 0, st, *a, (const u32 *)perm, n_boxed);
-    hipLaunchKernelGGL(pg_sv_events_rank_kernel, grid, block, 0, st, flag, n_boxed, a->rank, a->blk);
-    hipLaunchKernelGGL(pg_sv_events_scan_kernel, one, scan, 0, st, a->blk, nb);
+    pg_table_rank_scan_launch(a->flag, n_boxed, a->rank, a->blk, st);
     hipLaunchKernelGGL(pg_sv_events_seg_first_kernel, grid, block, 0, st, *a, n_boxed);
     hipLaunchKernelGGL(pg_sv_events_order_kernel, dim3(n_boxed), dim3(64), 0, st, *a, perm);
     hipLaunchKernelGGL(pg_sv_events_unique_kernel, grid, block, 0, st, *a, (const u32 *)perm, n_boxed);
-    hipLaunchKernelGGL(pg_sv_events_rank_kernel, grid, block, 0, st, flag, n_boxed, a->rank, a->blk);
-    hipLaunchKernelGGL(pg_sv_events_scan_kernel, one, scan, 0, st, a->blk, nb);
+    pg_table_rank_scan_launch(a->flag, n_boxed, a->rank, a->blk, st);
     hipLaunchKernelGGL(pg_sv_events_member_kernel, grid, block, 0, st, *a, (const u32 *)perm, n_boxed);
     hipLaunchKernelGGL(pg_sv_events_run_head_kernel, grid, block, 0, st, *a, n_boxed);
-    hipLaunchKernelGGL(pg_sv_events_rank_kernel, grid, block, 0, st, flag, n_boxed, a->rank, a->blk);
-    hipLaunchKernelGGL(pg_sv_events_scan_kernel, one, scan, 0, st, a->blk, nb);
+    pg_table_rank_scan_launch(a->flag, n_boxed, a->rank, a->blk, st);
     hipLaunchKernelGGL(pg_sv_events_run_first_kernel, grid, block, 0, st, *a, n_boxed);
     hipLaunchKernelGGL(pg_sv_events_run_kernel, waves, block, 0, st, *a);
     hipLaunchKernelGGL(pg_sv_events_alive_kernel, grid, block, 0, st, *a, n_boxed);
-    hipLaunchKernelGGL(pg_sv_events_rank_kernel, grid, block, 0, st, flag, n_boxed, a->rank, a->blk);
-    hipLaunchKernelGGL(pg_sv_events_scan_kernel, one, scan, 0, st, a->blk, nb);
+    pg_table_rank_scan_launch(a->flag, n_boxed, a->rank, a->blk, st);
     hipLaunchKernelGGL(pg_sv_events_event_kernel, waves, block, 0, st, *ref, *a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -197,7 +197,7 @@ extern "C" __global__ void __launch_bounds__(256) pg_variant_kernel(PgDevRef ref
     if (lane < 2u) a.counts[(size_t)read * 2u + lane] = (uint8_t)(lane ? count[1] : count[0]);
 }
 
-// Host side of the launch (pg_api.cpp checks the batch and owns the buffers): four reads per workgroup.
+// Host side of the launch (pg_api_classify.cpp checks the batch and owns the buffers): four reads per workgroup.
 int pg_variant_launch(const PgDevRef *ref, const PgOutRec *out, const pg_run *pool, unsigned long long pool_runs, const uint8_t *seq,
                       const uint64_t *seq_off, const uint8_t *strand, const int32_t *chr, const uint32_t *d_mm, uint32_t spacer,
                       uint32_t n, pg_variant_cand *d_cands, uint8_t *d_counts, void *stream)

@@ -18,7 +18,7 @@ static int g_fail = 0;
         }                                                                                    \
     } while (0)
 
-// DevArena::take of pg_api.cpp, on offsets
+// DevArena::take of pg_api_priv.h, on offsets
 struct Arena {
     size_t cap, used;
     bool take(size_t bytes, size_t *at)

@@ -58,14 +58,14 @@ class Case:
 
 @pytest.fixture(scope="module")
 def pool(eng):
-    """300 junction reads, 6 without a close end, 6 deletion reads, searched once: which of them are LI reads"""
-    recs = lc.records(50, 6, 6, seed=21)
+    """1080 junction reads, 6 without a close end, 6 deletion reads, searched once: which of them are LI reads"""
+    recs = lc.records(180, 6, 6, seed=21)
     c = Case(eng, recs, classify=False)
     try:
         li_idx = c.li_reads()
     finally:
         c.close()
-    assert len(li_idx) >= 257
+    assert len(li_idx) >= 1025
     return recs, li_idx
 
 
@@ -89,9 +89,10 @@ def test_batch_sizes(eng, pool, n):
         c.close()
 
 
-@pytest.mark.parametrize("k", [0, 1, 255, 256, 257])
+@pytest.mark.parametrize("k", [0, 1, 255, 256, 257, 1024, 1025])
 def test_li_read_totals(eng, pool, k):
-    """k LI reads beside the reads that are none: the compaction and the sort at one block, at its edge and beyond it"""
+    """k LI reads beside the reads that are none: the compaction and the sort at one block, at its edge and beyond it; at 1024 the
+    shared scan kernel has one digit count per thread (4 blocks x 256 digits), at 1025 two with a ragged tail (1280 counts)"""
     recs, li_idx = pool
     others = sorted(set(range(len(recs))) - set(li_idx.tolist()))
     pick = sorted(li_idx[:k].tolist() + others)

@@ -31,7 +31,8 @@ def test_abi_entries_are_declared_exported_and_bound():
         assert callable(getattr(binding.Engine, name)), name
     with open(binding.LIB_PATH, "rb") as f:
         blob = f.read()
-    for kernel in (b"pg_li_flag_kernel", b"pg_li_compact_kernel", b"pg_li_scatter_kernel", b"pg_li_head_kernel", b"pg_li_pos_kernel"):
+    for kernel in (b"pg_li_flag_kernel", b"pg_li_compact_kernel", b"pg_li_scatter_kernel", b"pg_li_head_kernel", b"pg_li_pos_kernel",
+                   b"pg_table_rank_kernel", b"pg_table_scan_kernel"):
         assert kernel in blob, kernel
 
 
