@@ -603,6 +603,50 @@ int  pg_device_batch_li_sizes(pg_ctx *ctx, pg_device_batch *b, pg_li_sizes *size
 int  pg_device_batch_li_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *members, pg_li_pos *positions);
 int  pg_device_batch_li_download_device(pg_ctx *ctx, pg_device_batch *b, uint32_t *d_members, pg_li_pos *d_positions);
 
+/* ---- device classifier: interchromosomal junction tables ----------------------------------------------------------
+ * What SortAndReportInterChromosomalEvents (src/reporter.cpp:2395-2665) takes from the points of the reads whose far end lies on
+ * another chromosome -- per read the pair of points that carries its call -- as tables, so that a caller who writes _INT downloads
+ * no point.  chr_rank (host memory, n_chr entries): per chromosome of the loaded reference the rank of its name in std::string
+ * order, equal names getting equal ranks (the reference walks a std::set<std::string> of names; only the order matters here).
+ * A junction read is a read of the batch with 0 <= chr_id < n_chr, an anchor strand '+' or '-', a close end and a far end whose
+ * first point (UP_Far[0]) lies on a chromosome fc in [0, n_chr) with chr_rank[chr_id] != chr_rank[fc]: FragName != FarFragName.  No window, no -c / -j filter and no
+ * Used state take part (the reference copies these reads before its classifiers run): the build needs a searched batch, no events
+ * build.  The call of a junction read, with len its read length after GetCloseEnd (rc_flag):
+ *   scan direction   close_ascending = chr_rank[chr_id] < chr_rank[fc] ? the anchor strand is '+' : UP_Far[0] has Strand ANTISENSE
+ *   template call    the close points in scan order (index ascending, or descending otherwise); the first one for which some far
+ *                    point has LengthStr == len - its LengthStr wins, with the first such far point in the OPPOSITE scan order
+ *   fallback call    when no pair fits: c = UP_Close.back(), f = UP_Far.back(), eff = c.LengthStr + f.LengthStr; a call only if
+ *                    eff >= 30 and both lengths >= 10.  Its inserted bases are [nt_off, nt_off + nt_len) of the read as rc_flag left
+ *                    it: nt_off = f.LengthStr, nt_len = eff > len ? len - nt_off : len - eff (0 where that is negative)
+ * A junction read without a call is in no table.  A run list that does not lie in the batch's pool counts as empty.
+ *   the member list   the reads that have a call, sorted by key, ascending read index within one key
+ *   the call table    one pg_int_call per distinct key: members [first, first + n_reads) of the member list
+ * The key is every field of pg_int_call but first / n_reads; the order of both tables is ascending
+ * (chr, far_chr, flags, close_abs, far_abs, nt_off, nt_len).  n_reads counts members: it is neither reduced by read names nor split by
+ * the inserted bases themselves (two fallback reads with equal offsets and different bases share a call); both are the consumer's job. */
+typedef struct { const int32_t *chr_rank; uint32_t n_chr; } pg_int_window;
+#define PG_INT_ANCHOR_MINUS 0x1u     /* the anchor strand is not '+'                                                          */
+#define PG_INT_FAR_MINUS    0x2u     /* UP_Far[0] has Strand ANTISENSE (the reference's MatchedFarD is '-')                   */
+#define PG_INT_FALLBACK     0x4u     /* a fallback call: close_abs / far_abs are the last points', nt_off / nt_len are set    */
+typedef struct {
+    int16_t  chr, far_chr;           /* the read's chromosome; UP_Far[0]'s                                                    */
+    uint32_t close_abs, far_abs;     /* AbsLoc of the chosen close and far point (not reduced by the spacer)                  */
+    uint32_t first, n_reads;         /* the members                                                                           */
+    uint16_t nt_off, nt_len;         /* the inserted bases within the read as rc_flag left it; 0, 0 for a template call       */
+    uint32_t flags;                  /* PG_INT_*                                                                              */
+    uint32_t reserved;               /* 0                                                                                     */
+} pg_int_call;                       /* 32 bytes, no padding                                                                  */
+typedef struct { uint64_t members, calls; } pg_int_sizes;
+/* Builds the tables and keeps them with the batch (a new search or upload drops them; freed with the batch).  Refused with nothing
+ * launched (PG_E_INVALID): a batch that was not searched, a null window or a null chr_rank, n_chr other than the loaded reference's
+ * number of chromosomes.  n_reads == 0 and "no junction read" are valid.  Synchronous; pg_last_search_stats then reports the
+ * HIP-event time of the kernels.  pg_device_batch_classify does not run it.  download: either array may be NULL; the _device sibling
+ * fills device memory under the rules of "device buffers in and out". */
+int  pg_device_batch_int(pg_ctx *ctx, pg_device_batch *b, const pg_int_window *window);
+int  pg_device_batch_int_sizes(pg_ctx *ctx, pg_device_batch *b, pg_int_sizes *sizes);
+int  pg_device_batch_int_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *members, pg_int_call *calls);
+int  pg_device_batch_int_download_device(pg_ctx *ctx, pg_device_batch *b, uint32_t *d_members, pg_int_call *d_calls);
+
 /* -q (dispersed duplications): per item i, contains_subseq_any_strand(query_i, window_i, 15) of Pindel's MEI search
  * (src/search_MEI_util.cpp:188-351, bit-exact), where query_i = query[query_off[i] .. query_off[i+1]) (at most
  * PG_MAX_READ_LEN bases) and window_i = the loaded chromosome chr_id[i] at padded (AbsLoc) positions

@@ -170,6 +170,24 @@ def _li_tables(members, positions, nm, npos):
                 members_flat=members, positions_flat=positions, n_members=nm, n_positions=npos)
 
 
+# interchromosomal junction tables (Engine.int_calls): pg_int_window, pg_int_call, pg_int_sizes
+INT_ANCHOR_MINUS, INT_FAR_MINUS, INT_FALLBACK = 1, 2, 4
+KERNEL_INT = 12                         # launch-log id of the junction kernels
+INT_CALL_DTYPE = np.dtype([("chr", "<i2"), ("far_chr", "<i2"), ("close_abs", "<u4"), ("far_abs", "<u4"), ("first", "<u4"), ("n_reads", "<u4"),
+                           ("nt_off", "<u2"), ("nt_len", "<u2"), ("flags", "<u4"), ("reserved", "<u4")])
+assert INT_CALL_DTYPE.itemsize == 32
+
+
+class IntWindow(C.Structure):
+    """pg_int_window"""
+    _fields_ = [("chr_rank", C.c_void_p), ("n_chr", C.c_uint32)]
+
+
+class IntSizes(C.Structure):
+    """pg_int_sizes"""
+    _fields_ = [("members", C.c_uint64), ("calls", C.c_uint64)]
+
+
 class EventWindow(C.Structure):
     """pg_event_window"""
     _fields_ = [("chr_id", C.c_int32), ("win_end", C.c_uint32), ("region_start", C.c_uint32), ("region_end", C.c_uint32),
@@ -227,7 +245,8 @@ EXPORTS = [
     "pg_device_batch_report_reads", "pg_device_batch_report_reads_device", "pg_device_batch_report_sizes",
     "pg_device_batch_report_download", "pg_device_batch_report_download_device", "pg_device_batch_classify",
     "pg_device_batch_search_table",
-    "pg_device_batch_li", "pg_device_batch_li_sizes", "pg_device_batch_li_download", "pg_device_batch_li_download_device"]
+    "pg_device_batch_li", "pg_device_batch_li_sizes", "pg_device_batch_li_download", "pg_device_batch_li_download_device",
+    "pg_device_batch_int", "pg_device_batch_int_sizes", "pg_device_batch_int_download", "pg_device_batch_int_download_device"]
 
 
 def build(force: bool = False) -> str:
@@ -344,6 +363,10 @@ def lib():
     L.pg_device_batch_li_sizes.argtypes = [vp, vp, vp]
     L.pg_device_batch_li_download.argtypes = [vp] * 4
     L.pg_device_batch_li_download_device.argtypes = [vp] * 4
+    L.pg_device_batch_int.argtypes = [vp, vp, vp]
+    L.pg_device_batch_int_sizes.argtypes = [vp, vp, vp]
+    L.pg_device_batch_int_download.argtypes = [vp] * 4
+    L.pg_device_batch_int_download_device.argtypes = [vp] * 4
     _lib = L
     return L
 
@@ -1095,6 +1118,51 @@ class Engine:
         self._check(self._L.pg_device_batch_li_download_device(self._h, dbatch, out["members"].data_ptr() if sum(nm) else None,
                                                                out["positions"].data_ptr() if sum(npos) else None))
         out.update(n_members=nm, n_positions=npos)
+        return out
+
+    def int_sizes(self, dbatch):
+        """pg_device_batch_int_sizes: (members, calls) of the junction tables built last."""
+        sz = IntSizes()
+        self._check(self._L.pg_device_batch_int_sizes(self._h, dbatch, C.addressof(sz)))
+        return int(sz.members), int(sz.calls)
+
+    def int_download(self, dbatch):
+        """The junction tables the batch holds (pg_device_batch_int_download) as a dict: members (uint32 read indices sorted by their
+        call's key) and calls (INT_CALL_DTYPE, one per distinct key)."""
+        nm, nc = self.int_sizes(dbatch)
+        members = np.zeros(nm, dtype=np.uint32)
+        calls = np.zeros(nc, dtype=INT_CALL_DTYPE)
+        self._check(self._L.pg_device_batch_int_download(self._h, dbatch, members.ctypes.data if nm else None, calls.ctypes.data if nc else None))
+        return dict(members=members, calls=calls)
+
+    def chr_ranks(self):
+        """The chr_rank of pg_int_window for the loaded reference: per chromosome the rank of its name in string order."""
+        names = [self._L.pg_reference_name(self._h, c) for c in range(self._L.pg_reference_n_chr(self._h))]
+        order = sorted(set(names))
+        return np.array([order.index(n) for n in names], dtype=np.int32)
+
+    def _int_build(self, dbatch, chr_rank):
+        rank = np.ascontiguousarray(self.chr_ranks() if chr_rank is None else chr_rank, dtype=np.int32)
+        w = IntWindow(rank.ctypes.data if rank.size else None, int(rank.size))
+        self._check(self._L.pg_device_batch_int(self._h, dbatch, C.addressof(w)))
+
+    def int_calls(self, dbatch, chr_rank=None):
+        """Interchromosomal junction tables of a searched batch (pg_device_batch_int): the reads whose far end lies on
+        another chromosome and whose points carry a call, sorted by the call's key, and one INT_CALL_DTYPE record per distinct key.
+        chr_rank: int32 per chromosome of the reference (None: chr_ranks()).  Returns int_download(dbatch)."""
+        self._int_build(dbatch, chr_rank)
+        return self.int_download(dbatch)
+
+    def int_tensors(self, dbatch, chr_rank=None):
+        """int_calls with the tables staying on the GPU (pg_device_batch_int_download_device): a dict of tensors on this engine's
+        device, members int32[n_members], calls uint8[n_calls, 32], plus n_members / n_calls."""
+        torch, dev = self._torch_ready()
+        self._int_build(dbatch, chr_rank)
+        nm, nc = self.int_sizes(dbatch)
+        out = dict(members=torch.empty(nm, dtype=torch.int32, device=dev), calls=torch.empty((nc, 32), dtype=torch.uint8, device=dev))
+        self._check(self._L.pg_device_batch_int_download_device(self._h, dbatch, out["members"].data_ptr() if nm else None,
+                                                                out["calls"].data_ptr() if nc else None))
+        out.update(n_members=nm, n_calls=nc)
         return out
 
     def events_download(self, dbatch):

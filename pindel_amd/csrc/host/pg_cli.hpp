@@ -34,6 +34,7 @@ struct CliOptions {
     int device_classifier_listed = -1;     // --device-classifier-listed 0..4: pg_classify_params::max_listed (-1: not given, no cut)
     bool device_classifier_hints = false;  // --device-classifier-hints: hinted windows are searched on the device-resident path
     bool device_classifier_li = false;     // --device-classifier-li: -l and -s are written from device tables and summaries
+    bool device_classifier_int = false;    // --device-classifier-int: -I is written from device junction tables and summaries
 };
 
 // A flag's word as the parser hands it to the row: as typed, as a number (kinds i and f), as a switch's state (kind u)
@@ -143,22 +144,30 @@ static const CliFlag CLI_DEVICE_FLAGS[] = {
 static const CliFlag CLI_DEVICE_HINT_FLAGS[] = {
     { "", "--device-classifier-hints", 'u', PG_CLI_SET(o.device_classifier_hints = a.on) },
 };
-// ... and the switch that admits -l and -s there, in a fourth table that parse_cli walks last
+// ... and the switch that admits -l and -s there, in a fourth table that parse_cli walks after it
 static const CliFlag CLI_DEVICE_LI_FLAGS[] = {
     { "", "--device-classifier-li", 'u', PG_CLI_SET(o.device_classifier_li = a.on) },
 };
+// ... and the switch that admits -I there, in a fifth table that parse_cli walks last
+static const CliFlag CLI_DEVICE_INT_FLAGS[] = {
+    { "", "--device-classifier-int", 'u', PG_CLI_SET(o.device_classifier_int = a.on) },
+};
 #undef PG_CLI_SET
 
-// What --device-classifier does not deliver yet: "" or the refusal, looked at after the last flag
+// What --device-classifier does not deliver yet: "" or the refusal, looked at after the last flag.  -l / -s
+// and -I are admitted by a switch of their own each; -S, -q, -N and several devices stay refused.
 inline std::string device_classifier_refusal(const CliOptions &o)
 {
     if (!o.device_classifier)
         return o.device_classifier_listed >= 0  ? "--device-classifier-listed needs --device-classifier"
                : o.device_classifier_hints      ? "--device-classifier-hints needs --device-classifier"
                : o.device_classifier_li         ? "--device-classifier-li needs --device-classifier"
+               : o.device_classifier_int        ? "--device-classifier-int needs --device-classifier"
                                                 : "";
     const bool li = o.device_classifier_li;                // -l and -s are admitted with the switch alone
-    const char *with = o.S.Analyze_LI && !li ? "-l" : o.S.report_close_mapped && !li ? "-s" : o.S.only_close_mapped ? "-S" : o.S.report_interchromosomal ? "-I"
+    const bool junctions = o.device_classifier_int;        // ... and -I with its own
+    const char *with = o.S.Analyze_LI && !li ? "-l" : o.S.report_close_mapped && !li ? "-s" : o.S.only_close_mapped ? "-S"
+                     : o.S.report_interchromosomal && !junctions ? "-I"
                      : o.detect_dd ? "-q" : o.S.NormalSamples ? "-N" : nullptr;
     if (with) return std::string("--device-classifier cannot be combined with ") + with + ": its report needs points or pairs this path does not deliver";
     if (o.use_bd && !o.device_classifier_hints) return "--device-classifier cannot be combined with --bd-hints on: window hints are not searched on this path";
@@ -199,6 +208,9 @@ inline int parse_cli(int argc, char **argv, CliOptions &o, std::string &err)
                 if (f == x.lg) fl = &x;
         if (!fl)
             for (const CliFlag &x : CLI_DEVICE_LI_FLAGS)
+                if (f == x.lg) fl = &x;
+        if (!fl)
+            for (const CliFlag &x : CLI_DEVICE_INT_FLAGS)
                 if (f == x.lg) fl = &x;
         if (!fl) {
             err = "unknown argument: " + f;

@@ -1003,7 +1003,10 @@ void Caller::process_window(const Chromosome &chrom, std::vector<SplitRead> &rea
             r.MatchedFarD = r.UP_Far[0].Strand;
         }
     }
-    if (S.report_interchromosomal) collect_interchr(reads);
+    // (the tables route of the events path builds its junction tables itself, from the reads before they lose their points: the
+    // copy is made only where that route is not taken -- below, for a window that falls back, whose reads are still untouched)
+    const bool int_from_tables = S.report_interchromosomal && S.use_events && S.use_sv_events && S.use_report_reads;
+    if (S.report_interchromosomal && !int_from_tables) collect_interchr(reads);
     // PGH_TIMING=1: wall-clock seconds per classifier on stderr (diagnostics)
     static const bool timing = getenv("PGH_TIMING") != nullptr;
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -1031,10 +1034,18 @@ void Caller::process_window(const Chromosome &chrom, std::vector<SplitRead> &rea
                 sort_output_li(c, win_start, win_end);
                 li_seconds += now() - t_li;
             }
-            if (S.report_interchromosomal) report_interchr();
+            if (S.report_interchromosomal) {
+                if (c.int_ready) {           // (the tables route: the reads have no points any more)
+                    write_int_from_tables(reads, c.int_summaries.data(), c.int_tables);
+                    es.int_table_windows++;
+                } else {
+                    report_interchr();
+                }
+            }
             return;
         }
         es.fallback_windows++;
+        if (int_from_tables) collect_interchr(reads);        // (process_window_events returns false before it changes a read)
         if (S.close_mapped_by_window()) report_close_mapped(reads);      // (the window's one write: the tables route did not make it)
     }
     search_variant(c, 0);

@@ -229,6 +229,7 @@ struct EventPathStats {
     uint64_t sv_supplied_windows = 0;    // ... of them, from supplied SV tables
     uint64_t report_windows = 0;         // windows written by process_window_tables, from records and summaries
     uint64_t report_records = 0;         // ... and the records they took
+    uint64_t int_table_windows = 0;      // windows whose _INT was written from junction tables built before the reads lost their points
     std::vector<uint32_t> windows;
 };
 EventPathStats &event_path_stats();
@@ -252,6 +253,26 @@ struct LiTables {
     std::vector<pg_li_pos> positions[2];
 };
 void li_tables_from_reads(const std::vector<LiReadIn> &in, const pg_event_read *recs, uint32_t lo, uint32_t hi, LiTables &out);
+
+// The interchromosomal junction tables (include/pindel_pg.h "interchromosomal junction tables") on the host.
+// IntReadIn: what the contract reads of one read; IntTables: the member list and the call table.  int_tables_from_reads states the
+// contract in plain loops over the points: the reference pg_device_batch_int is compared with, byte for byte, and what
+// Caller::report_interchr builds its calls from.
+struct IntReadIn {
+    int chr = -1, far_chr = -1;          // the read's chromosome; UP_Far[0]'s
+    char strand = 0;                     // the anchor strand
+    bool far_minus = false;              // UP_Far[0] has Strand ANTISENSE
+    int32_t read_length = 0;             // the post-state read length
+    const UniquePoint *close = nullptr, *far = nullptr;
+    size_t n_close = 0, n_far = 0;
+};
+struct IntTables {
+    std::vector<uint32_t> members;
+    std::vector<pg_int_call> calls;
+};
+void int_tables_from_reads(const std::vector<IntReadIn> &in, const int32_t *chr_rank, uint32_t n_chr, IntTables &out);
+// Ranks of names in std::string order, equal names getting equal ranks: the chr_rank of pg_int_window
+std::vector<int32_t> int_chr_ranks(const std::vector<std::string> &names);
 
 int load_fasta(const std::string &path, std::vector<Chromosome> &out, unsigned spacer, std::string &err);
 
@@ -440,6 +461,8 @@ private:
     // touch them (InterChromosome_SR, pindel.cpp:1905-1917), and their calls, appended to <prefix>_INT after the window's
     // other reports (pindel.cpp:1940-1942)
     std::vector<SplitRead> interchr_;
+    std::vector<int32_t> int_chr_rank_;  // the ranks of the genome's chromosome names (int_chr_ranks), computed at the first use
+    bool int_chr_rank_ready_ = false;
     std::vector<DiscordantPair> inv_pairs_;
     // the events path (pg_host_events.cpp): false = the window has to go through the existing path
     bool process_window_events(Ctx &c);
@@ -456,7 +479,17 @@ private:
                                const std::vector<pg_event> *sv_events, const pg_report_read *records, const pg_report_summary *summaries,
                                bool summaries_applied = false);
     void collect_interchr(const std::vector<SplitRead> &reads);
+    // report_interchr in two parts: the junction tables of the copied reads (int_tables_from_reads over their points),
+    // then report_interchr_tables, the one consumer of such tables wherever they were built
     void report_interchr();
+
+public:
+    // _INT of one window from its junction tables.  reads: the window's reads in the order the tables index them; they need no points,
+    // only Name, FragName, FarFragName and UnmatchedSeq as rc_flag left it.  junction: the indices of the junction reads, with or
+    // without a call, ascending (the reference enters every one of them into its name set).  Call it where process_window reports _INT.
+    void report_interchr_tables(const std::vector<SplitRead> &reads, const std::vector<uint32_t> &junction, const IntTables &tables);
+    // ... with the junction reads taken from the summaries of reads they were applied to (apply_summaries)
+    void write_int_from_tables(const std::vector<SplitRead> &reads, const pg_report_summary *summaries, const IntTables &tables);
 };
 
 }  // namespace pgh

@@ -331,6 +331,8 @@ int pgh_call_from_points_report_reads(const char *fasta_path, const char *reads_
 /* windows of the last run written by process_window_tables, and the report records they took */
 uint64_t pgh_last_report_windows(void) { return event_path_stats().report_windows; }
 uint64_t pgh_last_report_records(void) { return event_path_stats().report_records; }
+/* ... and those whose _INT was written by the consumer from the window's junction tables */
+uint64_t pgh_last_int_table_windows(void) { return event_path_stats().int_table_windows; }
 /* windows of the last run whose DI and inversion reports came from SV tables / ... from supplied SV tables */
 uint64_t pgh_last_sv_event_table_windows(void) { return event_path_stats().sv_table_windows; }
 uint64_t pgh_last_sv_event_supplied_windows(void) { return event_path_stats().sv_supplied_windows; }
@@ -848,6 +850,108 @@ int pgh_li_write_from_tables(const char *chr_name, const char *chr_seq, uint64_t
     caller.begin_region();
     caller.set_marks_for_test(genome[0], marks, n_marks);
     caller.write_li_from_tables(genome[0], reads, win_start, win_end, t, summaries.data());
+    return 0;
+}
+
+/*
+ * The interchromosomal junction tables (pindel_pg.h "interchromosomal junction tables"), on the host: the plain-loop
+ * statement (int_tables_from_reads) the device entry pg_device_batch_int is compared with, byte for byte.  The reads as they were
+ * handed to the search (seq, seq_off, strand, chr_id) with the rc flags; the post-state read length is taken from the read as rc_flag
+ * applications of setUnmatchedSeq(ReverseComplement()) leave it.  The expanded points of both ends (CSR); chr_rank: n_chr ranks.
+ * out_members, out_calls: room for n_reads entries each; sizes: what was filled.  -1: a null array.
+ */
+int pgh_int_tables_from_lists(uint32_t n_reads, const uint8_t *seq, const uint64_t *seq_off, const uint8_t *strand, const int32_t *chr_id,
+                              const uint8_t *rc_flag, const uint64_t *close_off, const pg_point *close_pts, const uint64_t *far_off,
+                              const pg_point *far_pts, const int32_t *chr_rank, uint32_t n_chr, uint32_t *out_members, pg_int_call *out_calls,
+                              pg_int_sizes *sizes)
+{
+    if (!sizes || (n_chr && !chr_rank) ||
+        (n_reads && (!seq_off || !strand || !chr_id || !rc_flag || !close_off || !far_off || !out_members || !out_calls))) {
+        g_err = "pgh_int_tables_from_lists: null array";
+        return -1;
+    }
+    std::vector<UniquePoint> close(n_reads ? (size_t)close_off[n_reads] : 0), far(n_reads ? (size_t)far_off[n_reads] : 0);
+    for (size_t q = 0; q < close.size(); q++) close[q] = to_unique_point(close_pts[q]);
+    for (size_t q = 0; q < far.size(); q++) far[q] = to_unique_point(far_pts[q]);
+    std::vector<IntReadIn> in(n_reads);
+    for (uint32_t i = 0; i < n_reads; i++) {
+        IntReadIn &e = in[i];
+        e.chr = chr_id[i];
+        e.strand = (char)strand[i];
+        SplitRead r;
+        r.UnmatchedSeq.assign((const char *)seq + seq_off[i], (size_t)(seq_off[i + 1] - seq_off[i]));
+        pg_adapter::apply_rc_flag(r, rc_flag[i]);
+        e.read_length = (int32_t)(short)r.UnmatchedSeq.size();
+        e.close = close.data() + close_off[i];
+        e.n_close = (size_t)(close_off[i + 1] - close_off[i]);
+        e.far = far.data() + far_off[i];
+        e.n_far = (size_t)(far_off[i + 1] - far_off[i]);
+        if (e.n_far) {
+            e.far_chr = e.far[0].chr;
+            e.far_minus = e.far[0].Strand == '-';
+        }
+    }
+    IntTables t;
+    int_tables_from_reads(in, chr_rank, n_chr, t);
+    if (!t.members.empty()) memcpy(out_members, t.members.data(), t.members.size() * sizeof(uint32_t));
+    if (!t.calls.empty()) memcpy(out_calls, t.calls.data(), t.calls.size() * sizeof(pg_int_call));
+    sizes->members = t.members.size();
+    sizes->calls = t.calls.size();
+    return 0;
+}
+
+/*
+ * Test hook: the single consumer of the junction tables (Caller::report_interchr_tables) on tables made by hand.  n_reads reads --
+ * name, chromosome name, far chromosome name (NUL-terminated strings each) and sequence as rc_flag left it -- the ascending indices
+ * of the junction reads among them, and the tables over them.  repairs: REPAIR_* bits (int-pairs).  Appends to <out_prefix>_INT.
+ * -1: a table or a junction index that points outside its arrays.
+ */
+int pgh_int_write_from_tables(uint32_t spacer, uint32_t repairs, uint32_t n_reads, const char *const *names, const char *const *chr_names,
+                              const char *const *far_names, const uint8_t *seq, const uint64_t *seq_off, const uint32_t *junction,
+                              uint32_t n_junction, const uint32_t *members, const pg_int_call *calls, const pg_int_sizes *sizes,
+                              const char *out_prefix)
+{
+    if (!sizes || !out_prefix || (n_reads && (!names || !chr_names || !far_names || !seq_off)) || (n_junction && !junction) ||
+        (sizes->members && !members) || (sizes->calls && !calls)) {
+        g_err = "pgh_int_write_from_tables: null array";
+        return -1;
+    }
+    IntTables t;
+    for (uint64_t k = 0; k < sizes->members; k++) {
+        if (members[k] >= n_reads) {
+            g_err = "pgh_int_write_from_tables: a member outside the reads";
+            return -1;
+        }
+        t.members.push_back(members[k]);
+    }
+    for (uint64_t k = 0; k < sizes->calls; k++) {
+        if ((uint64_t)calls[k].first + calls[k].n_reads > sizes->members) {
+            g_err = "pgh_int_write_from_tables: a call outside the member list";
+            return -1;
+        }
+        t.calls.push_back(calls[k]);
+    }
+    std::vector<uint32_t> junc(junction, junction + n_junction);
+    for (size_t k = 0; k < junc.size(); k++)
+        if (junc[k] >= n_reads || (k && junc[k] <= junc[k - 1])) {
+            g_err = "pgh_int_write_from_tables: the junction reads are ascending indices of the reads";
+            return -1;
+        }
+    Settings S;
+    S.spacer = spacer;
+    S.report_interchromosomal = true;
+    S.repairs = repairs;
+    Caller caller(S, nullptr, out_prefix, false);
+    std::vector<SplitRead> reads(n_reads);
+    for (uint32_t i = 0; i < n_reads; i++) {
+        SplitRead &r = reads[i];
+        r.Name = names[i];
+        r.FragName = chr_names[i];
+        r.FarFragName = far_names[i];
+        r.UnmatchedSeq.assign((const char *)seq + seq_off[i], (size_t)(seq_off[i + 1] - seq_off[i]));
+        r.ReadLength = (short)r.UnmatchedSeq.size();
+    }
+    caller.report_interchr_tables(reads, junc, t);
     return 0;
 }
 

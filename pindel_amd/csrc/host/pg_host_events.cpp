@@ -500,6 +500,37 @@ bool Caller::process_window_events(Ctx &c)
             li_tables_from_reads(li_in, tabs.reads.data(), lo, hi, c.li);
             c.li_ready = true;
         }
+        // -I on this route: the junction tables from the host statement while the reads still have their points;
+        // process_window then writes _INT from them and the summaries, where it reports _INT
+        if (S.report_interchromosomal) {
+            if (!int_chr_rank_ready_) {                       // (the ranks depend on the reference alone: once per run)
+                std::vector<std::string> chr_names;
+                if (genome)
+                    for (const Chromosome &g : *genome) chr_names.push_back(g.name);
+                int_chr_rank_ = int_chr_ranks(chr_names);
+                int_chr_rank_ready_ = true;
+            }
+            const std::vector<int32_t> &rank = int_chr_rank_;
+            std::vector<IntReadIn> int_in(n);
+            for (size_t k = 0; k < n; k++) {
+                const SplitRead &r = reads[k];
+                IntReadIn &e = int_in[k];
+                e.chr = r.chr_id;
+                e.strand = r.MatchedD;
+                e.read_length = r.getReadLength();
+                e.close = r.UP_Close.data();
+                e.n_close = r.UP_Close.size();
+                e.far = r.UP_Far.data();
+                e.n_far = r.UP_Far.size();
+                if (e.n_far) {
+                    e.far_chr = r.UP_Far[0].chr;
+                    e.far_minus = r.UP_Far[0].Strand == '-';
+                }
+            }
+            int_tables_from_reads(int_in, rank.data(), (uint32_t)rank.size(), c.int_tables);
+            c.int_summaries = summaries;
+            c.int_ready = true;
+        }
         for (SplitRead &r : reads) {
             SplitRead bare;
             bare.Name.swap(r.Name);

@@ -28,6 +28,10 @@ struct Caller::Ctx {
     bool li_ready = false;
     LiTables li;
     std::vector<int16_t> li_close_len;
+    // ... and its interchromosomal junction tables, with the summaries that name the junction reads
+    bool int_ready = false;
+    IntTables int_tables;
+    std::vector<pg_report_summary> int_summaries;
 };
 
 namespace detail {

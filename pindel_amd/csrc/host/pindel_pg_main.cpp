@@ -9,7 +9,8 @@
 // -l adds <prefix>_LI (long insertions), -s <prefix>_CloseEndMapped (the reads with a close end),
 // -S writes <prefix>_CloseEndMapped only (no far end, no SV search); -q adds <prefix>_DD (dispersed duplications, BAM input,
 // pg_dd.hpp); -I adds <prefix>_INT and <prefix>_INT_final (interchromosomal events, pg_host_int.cpp: far ends on other chromosomes
-// need window hints, i.e. BAM input with -R or `-b file --bd-hints on`).  -P lists Pindel-text files, one per line (read before a
+// need window hints, i.e. BAM input with -R or `-b file --bd-hints on`; on the --device-classifier path -I needs
+// --device-classifier-int, which writes _INT from junction tables built on the device).  -P lists Pindel-text files, one per line (read before a
 // -p file when both are given); a text file whose name ends in .gz is read through zlib.  -N (--NormalSamples) turns on the
 // germline filter of _TD and _INV for BAM input (pg_depth.hpp); for text input it changes nothing.
 // --repair LIST (off by default) turns on fixes of reference defects that are otherwise reproduced byte for byte:
@@ -366,11 +367,13 @@ struct FarSearch {
 struct DeviceClassifierStats {
     size_t windows = 0, from_tables = 0, fallbacks = 0, unresolved = 0, records = 0, runs_kept = 0, hinted = 0;
     size_t li_windows = 0, li_bytes = 0;         // windows with LI tables, and the bytes downloaded for them
+    size_t int_windows = 0, int_bytes = 0;       // windows with junction tables, and the bytes downloaded for them
 };
 struct DeviceClassifier {
     const Seams &s;
     DeviceClassifierStats &st;
     bool bam;                                    // BAM input: ReadLength follows the sequence GetCloseEnd left
+    std::vector<int32_t> chr_rank;               // -I: the ranks of the reference's chromosome names (pg_int_window), once per run
     int operator()(const Chromosome &chrom, int chr_id, std::vector<SplitRead> &reads, unsigned ws, unsigned we, unsigned bed_start,
                    unsigned bed_end, Caller &caller, const std::function<void()> &after_close) const
     {
@@ -498,6 +501,24 @@ struct DeviceClassifier {
                 st.li_windows++;
                 st.li_bytes += members.size() * sizeof(uint32_t) + positions.size() * sizeof(pg_li_pos);
             }
+            // -I (--device-classifier-int): the junction tables of the window, built on the device from the search
+            // result alone
+            IntTables junctions;
+            const bool want_int = s.o.S.report_interchromosomal && n_close;
+            if (want_int) {
+                const pg_int_window iw = { chr_rank.data(), (uint32_t)chr_rank.size() };
+                pg_int_sizes is;
+                if ((rc = pg_device_batch_int(ctx, b, &iw)) || (rc = pg_device_batch_int_sizes(ctx, b, &is))) return rc;
+                junctions.members.resize((size_t)is.members);
+                junctions.calls.resize((size_t)is.calls);
+                if ((rc = pg_device_batch_int_download(ctx, b, junctions.members.data(), junctions.calls.data()))) return rc;
+                bool int_fits = true;
+                for (uint32_t m : junctions.members) int_fits = int_fits && m < n;
+                for (const pg_int_call &q : junctions.calls) int_fits = int_fits && (uint64_t)q.first + q.n_reads <= is.members;
+                if (!int_fits) return fail("the junction tables of a window do not fit its reads", (int)PG_E_DEVICE);
+                st.int_windows++;
+                st.int_bytes += junctions.members.size() * sizeof(uint32_t) + junctions.calls.size() * sizeof(pg_int_call);
+            }
             s.counts.t_search += now_s() - t0;
             if (n_close) {                       // (a window without a close end has nothing to classify, as in the existing steps)
                 caller.apply_summaries(reads, summaries.data(), bam);
@@ -507,6 +528,7 @@ struct DeviceClassifier {
                 caller.process_window_from_tables(chrom, reads, ws, we, bed_start, bed_end, recs.data(), es, events.data(), ss, sv_events.data(),
                                                   records.data(), summaries.data(), true);
                 if (want_li) caller.write_li_from_tables(chrom, reads, ws, we, li, summaries.data());
+                if (want_int) caller.write_int_from_tables(reads, summaries.data(), junctions);
             } else if (after_close) after_close();
             uint64_t close_runs = 0, far_runs = 0;
             (void)pg_device_batch_result_sizes(ctx, b, &close_runs, &far_runs);
@@ -644,7 +666,7 @@ int main(int argc, char **argv)
     double li_seconds = 0.0;
     DeviceClassifierStats dc_stats;
     DeviceClassify device_classify;
-    if (o.device_classifier) device_classify = DeviceClassifier{ seams, dc_stats, !bams.empty() };
+    if (o.device_classifier) device_classify = DeviceClassifier{ seams, dc_stats, !bams.empty(), int_chr_ranks(seams.chr_names) };
     if (!bams.empty()) {
         n_reads = 0;
         rc = run_bam_pipeline(genome, plan, bams, ing, o.S, o.prefix, CloseSoa{ seams }, FarSearch{ seams }, err, &n_reads, &bd, o.search_rp,
@@ -668,6 +690,7 @@ int main(int argc, char **argv)
                dc_stats.runs_kept);
         if (o.device_classifier_hints) printf(", %zu hinted windows", dc_stats.hinted);
         if (o.device_classifier_li) printf(", %zu windows with LI tables", dc_stats.li_windows);
+        if (o.device_classifier_int) printf(", %zu windows with junction tables", dc_stats.int_windows);
         printf("\n");
     }
     // the phases the reference's Timer reports (pindel.cpp:1990-1996), wall-clock seconds
@@ -677,5 +700,7 @@ int main(int argc, char **argv)
         printf("pindel_pg: long insertions (_LI, host, part of classification + reports) %.3f s\n", li_seconds);
     if (o.device_classifier_li && o.S.Analyze_LI)
         printf("pindel_pg: long-insertion tables downloaded: %zu bytes for %zu reads\n", dc_stats.li_bytes, n_reads);
+    if (o.device_classifier_int && o.S.report_interchromosomal)
+        printf("pindel_pg: junction tables downloaded: %zu bytes for %zu reads\n", dc_stats.int_bytes, n_reads);
     return 0;
 }

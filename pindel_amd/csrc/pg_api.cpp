@@ -951,6 +951,7 @@ int grow_pool(pg_ctx *ctx, pg_device_batch *b, uint64_t want)
 int run_search(pg_ctx *ctx, pg_device_batch *b, int mode, bool pack = false)
 {
     if (int rc = search_refusals(ctx, b)) return rc;
+    b->cls.drop_search_tables();
     for (int attempt = 0; attempt < 8; attempt++) {
         HIP_TRY(ctx, hipMemsetAsync(b->pool_used, 0, PG_POOL_SHARDS * 16 * sizeof(uint32_t), ctx->stream));
         float ms = 0.f;
@@ -2622,6 +2623,7 @@ int pg_device_batch_search_table(pg_ctx *ctx, pg_device_batch *b, const pg_hint_
     }
     if ((rc = search_refusals(ctx, b))) return rc;
     b->searched = false;
+    b->cls.drop_search_tables();
     // each launch reserves its PG_RESERVE slots per read, and the batch's pool was sized for one: room for both from the start,
     // or every batch of more than ~87 000 reads would overflow once and run three times (PG_TEST_TINY_POOL: the regrow path)
     const uint64_t two_launches = ((2ull * PG_RESERVE + 2ull) * b->n) / PG_POOL_SHARDS + 512ull;

@@ -1,7 +1,8 @@
-// pg_api_classify.cpp -- the device classifier's entries of the C ABI (include/pindel_pg.h; DESIGN.md 7k - 7q): candidates per
-// read, event tables, SV event tables, report records, long-insertion tables, and the one call per window that chains them.
+// pg_api_classify.cpp -- the device classifier's entries of the C ABI (include/pindel_pg.h; DESIGN.md 7k - 7r): candidates per
+// read, event tables, SV event tables, report records, long-insertion tables, junction tables, and the one call per window that chains
+// the first five.
 // Every entry checks its arguments and owns its buffers here; the kernels and their launchers are pg_variant.hip, pg_sv.hip,
-// pg_events.hip, pg_sv_events.hip, pg_report.hip and pg_li.hip.  What this file shares with pg_api.cpp is pg_api_priv.h.
+// pg_events.hip, pg_sv_events.hip, pg_report.hip, pg_li.hip and pg_int.hip.  What this file shares with pg_api.cpp is pg_api_priv.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -790,6 +791,113 @@ int pg_device_batch_li_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *membe
 int pg_device_batch_li_download_device(pg_ctx *ctx, pg_device_batch *b, uint32_t *d_members, pg_li_pos *d_positions)
 {
     return li_download(ctx, b, d_members, d_positions, true);
+}
+
+// ---- ... its seventh part (pg_int.hip): the interchromosomal junction tables, from the search result alone
+int pg_device_batch_int(pg_ctx *ctx, pg_device_batch *b, const pg_int_window *window)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (int rc = entry_refusal(ctx, b, true)) return rc;
+    if (!window) return fail(ctx, PG_E_INVALID, "int: null pg_int_window");
+    if (!window->chr_rank) return fail(ctx, PG_E_INVALID, "int: null chr_rank");
+    if (window->n_chr != ctx->names.size()) return fail(ctx, PG_E_INVALID, "int: n_chr is not the number of chromosomes of the loaded reference");
+    ClassifierState &c = b->cls;
+    c.int_built = false;
+    c.int_sizes = pg_int_sizes{};
+    const size_t n = b->n;
+    if (!n) {                                                 // nothing is launched for an empty batch
+        c.int_built = true;
+        return PG_OK;
+    }
+    int rc;
+    // (each buffer on its own: an allocation that failed in an earlier call is tried again, never launched with)
+    if ((!c.int_members && (rc = dev_alloc(ctx, &c.int_members, n))) || (!c.int_calls && (rc = dev_alloc(ctx, &c.int_calls, n)))) return rc;
+    DevTemps tmp(ctx, b);
+    PgIntArgs a{};
+    const size_t n_blk = n / PG_EV_BLOCK + 2;
+    int32_t *d_rank = nullptr;
+    if ((rc = tmp.take(&a.rec_a, n)) || (rc = tmp.take(&a.rec_b, n)) || (rc = tmp.take(&a.flag, n)) || (rc = tmp.take(&a.rank, n)) ||
+        (rc = tmp.take(&a.blk, n_blk)) || (rc = tmp.take(&a.cfirst, n + 1)) || (rc = tmp.take(&a.digit_cnt, 256 * n_blk + 1)) ||
+        (rc = tmp.take(&a.info, 1)) || (rc = tmp.take(&d_rank, window->n_chr)))
+        return rc;
+    HIP_TRY(ctx, hipMemcpy(d_rank, window->chr_rank, window->n_chr * sizeof(int32_t), hipMemcpyHostToDevice));
+    a.out = b->out_rec;
+    a.pool = b->pool;
+    a.pool_runs = pool_runs(b);
+    a.seq = b->seq;
+    a.seq_off = b->seq_off;
+    a.strand = b->strand;
+    a.chr = b->chr;
+    a.chr_rank = d_rank;
+    a.n = b->n;
+    a.n_chr = window->n_chr;
+    a.members = c.int_members;
+    a.calls = c.int_calls;
+    PgIntInfo info;
+    uint32_t n_mem = 0;
+    rc = timed(ctx, [&]() -> int {
+        if (pg_int_gather_launch(&a, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the junction gather kernels failed");
+        log_kernel(ctx, PG_KERNEL_INT, (int32_t)PG_EV_BLOCK);
+        HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (info.n_mem > n) return fail(ctx, PG_E_DEVICE, "int: the count of reads with a call exceeds the batch");
+        n_mem = info.n_mem;
+        if (!n_mem) return PG_OK;                             // (no read with a call: nothing below indexes an empty array)
+        PgIntRec *src = a.rec_b, *dst = a.rec_a;
+        for (int pass = 0; pass < PG_INT_SORT_PASSES; pass++) {
+            const int word = pass < 12 ? pass >> 2 : pass == 12 ? 3 : 4, shift = (pass < 12 ? pass & 3 : pass == 12 ? 0 : pass - 13) * 8;
+            if ((((info.key_or[word] ^ info.key_and[word]) >> shift) & 0xffu) == 0u) continue;      // the byte is constant: no pass
+            if (pg_int_sort_pass_launch(&a, src, dst, n_mem, pass, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching a junction sort pass failed");
+            log_kernel(ctx, PG_KERNEL_INT, (int32_t)PG_EV_BLOCK);
+            std::swap(src, dst);
+        }
+        if (pg_int_tables_launch(&a, src, n_mem, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the junction table kernels failed");
+        log_kernel(ctx, PG_KERNEL_INT, (int32_t)PG_EV_BLOCK);
+        HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
+        return PG_OK;
+    });
+    if (rc) return rc;
+    if (n_mem) {
+        if (!info.n_calls || info.n_calls > n_mem) return fail(ctx, PG_E_DEVICE, "int: inconsistent table sizes");
+        c.int_sizes.members = n_mem;
+        c.int_sizes.calls = info.n_calls;
+    }
+    c.int_built = true;
+    return PG_OK;
+}
+
+static const char *const NO_INT = "no junction tables: pg_device_batch_int has not been run on this batch since its search";
+
+int pg_device_batch_int_sizes(pg_ctx *ctx, pg_device_batch *b, pg_int_sizes *sizes)
+{
+    use_device(ctx);
+    if (!ctx || !b || !sizes) return PG_E_INVALID;
+    if (!b->cls.int_built) return fail(ctx, PG_E_INVALID, NO_INT);
+    *sizes = b->cls.int_sizes;
+    return PG_OK;
+}
+
+static int int_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *members, pg_int_call *calls, bool to_device)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    const ClassifierState &c = b->cls;
+    if (!c.int_built) return fail(ctx, PG_E_INVALID, NO_INT);
+    return copy_tables(ctx,
+                       { { members, c.int_members, (size_t)c.int_sizes.members, sizeof(uint32_t), 4, "int download: members" },
+                         { calls, c.int_calls, (size_t)c.int_sizes.calls, sizeof(pg_int_call), 4, "int download: calls" } },
+                       to_device);
+}
+
+int pg_device_batch_int_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *members, pg_int_call *calls)
+{
+    return int_download(ctx, b, members, calls, false);
+}
+
+int pg_device_batch_int_download_device(pg_ctx *ctx, pg_device_batch *b, uint32_t *d_members, pg_int_call *d_calls)
+{
+    return int_download(ctx, b, d_members, d_calls, true);
 }
 
 // ---- one call per window: the two candidate kernels, both table builds and the report records, the lists staying with the batch

@@ -111,6 +111,13 @@ struct ClassifierState {
     pg_li_pos *li_positions = nullptr;         // n: the two position tables back to back
     pg_li_sizes li_sizes{};
     bool li_built = false;
+    // the interchromosomal junction tables of the last pg_device_batch_int: made from the search result alone, so a
+    // new search discards them (drop_search_tables) and no table build does
+    uint32_t *int_members = nullptr;           // n
+    pg_int_call *int_calls = nullptr;          // n
+    pg_int_sizes int_sizes{};
+    bool int_built = false;
+    void drop_search_tables() { int_built = false; }
 
     enum Build { EVENTS, SV_EVENTS, REPORT, LI };
     // A build discards its own tables and whatever was made from them: the SV tables belong to the records of the events build they
@@ -127,7 +134,7 @@ struct ClassifierState {
     {
         for (void *p : { (void *)ev_reads, (void *)ev_members, (void *)ev_events, (void *)svev_members, (void *)svev_events, (void *)svev_ws,
                          (void *)rr_records, (void *)rr_summaries, (void *)cl_cands, (void *)cl_sv_cands, (void *)cl_counts, (void *)cl_sv_counts,
-                         (void *)li_members, (void *)li_positions })
+                         (void *)li_members, (void *)li_positions, (void *)int_members, (void *)int_calls })
             if (p) (void)hipFree(p);
         *this = ClassifierState();
     }

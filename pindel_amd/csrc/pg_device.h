@@ -570,6 +570,43 @@ int pg_li_gather_launch(const struct PgLiArgs *a, void *stream);
 int pg_li_sort_pass_launch(const struct PgLiArgs *a, const struct PgLiRec *src, struct PgLiRec *dst, uint32_t n_li, int pass, void *stream);
 // head flags, members, positions over the sorted records; fills the rest of info.  n_li > 0
 int pg_li_tables_launch(const struct PgLiArgs *a, const struct PgLiRec *sorted, uint32_t n_li, uint32_t n_plus, void *stream);
+// Interchromosomal junction tables (pg_int.hip): the reads whose far end lies on another chromosome and whose points
+// carry a call, compacted in ascending read index, ordered by the call's key with stable counting passes, then one record per call.
+enum { PG_KERNEL_INT = 12 };          // ... continued: the launch-log id of pg_device_batch_int
+#define PG_INT_KEY_WORDS 5            // w[0 .. 4] of a record, least significant first
+#define PG_INT_SORT_PASSES 17         // one per key byte: nt (4), far_abs (4), close_abs (4), flags (1), the chromosomes (4)
+// one read with a call: nt_off << 16 | nt_len, far_abs, close_abs, flags, chr << 16 | far_chr, read, 0, 0
+struct PgIntRec { uint32_t w[8]; };
+struct PgIntInfo {                    // what the host reads back
+    uint32_t n_mem;                   // reads with a call
+    uint32_t n_calls;
+    uint32_t key_or[PG_INT_KEY_WORDS], key_and[PG_INT_KEY_WORDS];   // over the compacted records' key words: a byte equal in both is constant
+};
+struct PgIntArgs {
+    const PgOutRec *out;
+    const pg_run *pool;
+    unsigned long long pool_runs;
+    const uint8_t *seq;
+    const uint64_t *seq_off;
+    const uint8_t *strand;
+    const int32_t *chr;
+    const int32_t *chr_rank;          // n_chr, device memory
+    uint32_t n, n_chr;
+    uint32_t *members;                // n
+    pg_int_call *calls;               // n
+    struct PgIntRec *rec_a, *rec_b;   // n each
+    uint8_t *flag;                    // n
+    uint32_t *rank, *blk;             // n; n / PG_EV_BLOCK + 2
+    uint32_t *cfirst;                 // n + 1
+    uint32_t *digit_cnt;              // 256 x (n / PG_EV_BLOCK + 2) + 1
+    struct PgIntInfo *info;
+};
+// the reads with a call flagged and compacted into rec_b (ascending read index); info->n_mem and the key masks are then valid.  n > 0
+int pg_int_gather_launch(const struct PgIntArgs *a, void *stream);
+// one stable counting pass over key byte `pass` of src[0 .. n_mem) into dst
+int pg_int_sort_pass_launch(const struct PgIntArgs *a, const struct PgIntRec *src, struct PgIntRec *dst, uint32_t n_mem, int pass, void *stream);
+// head flags, members, calls over the sorted records; fills info->n_calls.  n_mem > 0
+int pg_int_tables_launch(const struct PgIntArgs *a, const struct PgIntRec *sorted, uint32_t n_mem, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-// pg_table_prims.h -- what the table builds of the device classifier share (pg_events.hip, pg_sv_events.hip, pg_li.hip): the
+// pg_table_prims.h -- what the table builds of the device classifier share (pg_events.hip, pg_sv_events.hip, pg_li.hip, pg_int.hip): the
 // workgroup scan, the wave reductions, the post-state's length and the two bodies of one LSD counting pass.  Device-only inline
 // code; the rank and scan kernels themselves live once in pg_table_prims.hip (launchers in pg_device.h).
 #pragma once

@@ -93,7 +93,7 @@ def lib():
         L.pgh_call_from_points_report_reads.argtypes = L.pgh_call_from_points.argtypes + [C.c_void_p] * 4
         for f in ("pgh_last_event_fallback_windows", "pgh_last_event_table_windows", "pgh_last_event_supplied_windows",
                   "pgh_last_sv_event_table_windows", "pgh_last_sv_event_supplied_windows", "pgh_last_report_windows",
-                  "pgh_last_report_records"):
+                  "pgh_last_report_records", "pgh_last_int_table_windows"):
             getattr(L, f).restype = C.c_uint64
             getattr(L, f).argtypes = []
         L.pgh_last_event_windows.restype = C.c_uint64
@@ -628,6 +628,81 @@ def li_write_from_tables(chrom, out_prefix, seqs, anchor_strand, close_len, memb
         raise ValueError("pgh_li_write_from_tables: " + (L.pgh_last_error() or b"").decode())
 
 
+# interchromosomal junction tables (include/pindel_pg.h): pg_int_call, pg_int_sizes
+INT_ANCHOR_MINUS, INT_FAR_MINUS, INT_FALLBACK = 1, 2, 4
+INT_CALL_DTYPE = np.dtype([("chr", "<i2"), ("far_chr", "<i2"), ("close_abs", "<u4"), ("far_abs", "<u4"), ("first", "<u4"), ("n_reads", "<u4"),
+                           ("nt_off", "<u2"), ("nt_len", "<u2"), ("flags", "<u4"), ("reserved", "<u4")])
+assert INT_CALL_DTYPE.itemsize == 32
+
+
+class IntSizes(C.Structure):
+    """pg_int_sizes"""
+    _fields_ = [("members", C.c_uint64), ("calls", C.c_uint64)]
+
+
+def chr_ranks(names):
+    """The chr_rank of pg_int_window: per name its rank in string order (bytewise, as std::string compares), equal names sharing one."""
+    order = sorted({n.encode() if isinstance(n, str) else bytes(n) for n in names})
+    return np.array([order.index(n.encode() if isinstance(n, str) else bytes(n)) for n in names], dtype=np.int32)
+
+
+def int_tables_from_lists(seq, seq_off, anchor_strand, chr_id, rc_flag, close_off, close_pts, far_off, far_pts, chr_rank):
+    """The interchromosomal junction tables on the host (pgh_int_tables_from_lists): the reference Engine.int_calls is
+    compared with, byte for byte.  Reads, rc flags and the expanded points of both ends as events_from_lists takes them; chr_rank:
+    see chr_ranks().  Returns a dict: members (uint32 read indices), calls (INT_CALL_DTYPE)."""
+    L = lib()
+    n = len(seq_off) - 1
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    strand = np.ascontiguousarray(anchor_strand, dtype=np.uint8)
+    chr_id = np.ascontiguousarray(chr_id, dtype=np.int32)
+    rc_flag = np.ascontiguousarray(rc_flag, dtype=np.uint8)
+    close_off = np.ascontiguousarray(close_off, dtype=np.uint64)
+    far_off = np.ascontiguousarray(far_off, dtype=np.uint64)
+    close_pts = np.ascontiguousarray(close_pts)
+    far_pts = np.ascontiguousarray(far_pts)
+    chr_rank = np.ascontiguousarray(chr_rank, dtype=np.int32)
+    assert close_pts.dtype.itemsize == 12 and far_pts.dtype.itemsize == 12
+    assert len(strand) == n and len(chr_id) == n and len(rc_flag) == n and len(close_off) == n + 1 and len(far_off) == n + 1
+    members = np.zeros(max(n, 1), dtype=np.uint32)
+    calls = np.zeros(max(n, 1), dtype=INT_CALL_DTYPE)
+    sizes = IntSizes()
+    L.pgh_int_tables_from_lists.argtypes = [C.c_uint32] + [C.c_void_p] * 10 + [C.c_uint32] + [C.c_void_p] * 3
+    rc = L.pgh_int_tables_from_lists(n, seq.ctypes.data, seq_off.ctypes.data, strand.ctypes.data, chr_id.ctypes.data, rc_flag.ctypes.data,
+                                     close_off.ctypes.data, close_pts.ctypes.data, far_off.ctypes.data, far_pts.ctypes.data,
+                                     chr_rank.ctypes.data if chr_rank.size else None, int(chr_rank.size), members.ctypes.data,
+                                     calls.ctypes.data, C.addressof(sizes))
+    if rc:
+        raise ValueError("pgh_int_tables_from_lists: " + (L.pgh_last_error() or b"").decode())
+    return dict(members=members[:int(sizes.members)], calls=calls[:int(sizes.calls)])
+
+
+def int_write_from_tables(out_prefix, names, chr_names, far_names, seqs, junction, members, calls, repairs=0, spacer=100000):
+    """Test hook (pgh_int_write_from_tables): the single consumer of the junction tables on tables made by hand.  Per read its name,
+    chromosome name, far chromosome name and sequence (bytes) as rc_flag left it; junction: the ascending indices of the junction
+    reads; members / calls: the tables; repairs: REPAIR_* bits.  Appends to <out_prefix>_INT."""
+    L = lib()
+    n = len(seqs)
+    assert len(names) == n and len(chr_names) == n and len(far_names) == n
+    seq = np.frombuffer(b"".join(seqs), dtype=np.uint8) if n else np.zeros(0, dtype=np.uint8)
+    seq_off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.uint64)
+    junction = np.ascontiguousarray(junction, dtype=np.uint32)
+    members = np.ascontiguousarray(members, dtype=np.uint32)
+    calls = np.ascontiguousarray(calls, dtype=INT_CALL_DTYPE)
+    sizes = IntSizes(int(members.size), int(calls.size))
+
+    def strings(v):
+        return (C.c_char_p * max(n, 1))(*[s.encode() if isinstance(s, str) else bytes(s) for s in v])
+    L.pgh_int_write_from_tables.argtypes = [C.c_uint32] * 3 + [C.c_void_p] * 6 + [C.c_uint32] + [C.c_void_p] * 3 + [C.c_char_p]
+    a, b, c = strings(names), strings(chr_names), strings(far_names)
+    rc = L.pgh_int_write_from_tables(int(spacer), int(repairs), n, C.cast(a, C.c_void_p), C.cast(b, C.c_void_p), C.cast(c, C.c_void_p),
+                                     seq.ctypes.data if seq.size else None, seq_off.ctypes.data, junction.ctypes.data if junction.size else None,
+                                     int(junction.size), members.ctypes.data if members.size else None,
+                                     calls.ctypes.data if calls.size else None, C.addressof(sizes), str(out_prefix).encode())
+    if rc:
+        raise ValueError("pgh_int_write_from_tables: " + (L.pgh_last_error() or b"").decode())
+
+
 def last_report_windows():
     """Windows of the last call_from_points(report_reads=True) that Caller::process_window_tables wrote from records and summaries."""
     return int(lib().pgh_last_report_windows())
@@ -636,6 +711,12 @@ def last_report_windows():
 def last_report_records():
     """... and the report records those windows took."""
     return int(lib().pgh_last_report_records())
+
+
+def last_int_table_windows():
+    """Windows of the last call_from_points(report_reads=True) with -I whose _INT lines were written by the consumer from junction
+    tables built while the window's reads still had points, not from copies of the reads."""
+    return int(lib().pgh_last_int_table_windows())
 
 
 def last_variant_fallbacks():
