@@ -282,6 +282,16 @@ int  pg_device_batch_pack_search(pg_ctx *ctx, pg_device_batch *b);
  *   - pg_last_search_stats: the two search launches' HIP-event times added up, the pool slots after the far launch;
  *     pg_debug_last_hint_stats: the lookup. */
 int  pg_device_batch_search_table(pg_ctx *ctx, pg_device_batch *b, const pg_hint_table *table /* nullable */);
+/* The close half of pg_device_batch_search_table on its own: attached windows are cleared, one close launch (which packs the reads)
+ * runs with the pool cursors zeroed, and the per-read summary (rc_flag, close_last, close_max) is left in the batch's arrays; a pool
+ * that overflowed is regrown and the launch repeated.  Synchronous.  Afterwards the batch is CLOSE-searched, not searched: its
+ * output records hold the close end and its pool the close runs, which is what pg_device_batch_dd needs; the classifier stages and
+ * pg_device_batch_li / _int / _classify, which need a full search, keep refusing it as a batch that has not been searched.
+ * The far fields of the records are cleared: pg_device_batch_download then delivers the close runs and empty far lists, also on a
+ * batch that had a full search before.  A full search makes a batch close-searched too.
+ * Refusals as for every search (no reference, a batch uploaded before a reference reload).  pg_last_search_stats: the launch's
+ * HIP-event time and the pool slots taken. */
+int  pg_device_batch_close_search(pg_ctx *ctx, pg_device_batch *b);
 void pg_device_batch_free(pg_ctx *ctx, pg_device_batch *b);
 /* HIP-event duration (ms) of the kernel of the last search on this ctx (events recorded on
  * the ctx's own stream around the launch) and the run-pool slots it took (reserved per read + allocated; the number
@@ -646,6 +656,58 @@ int  pg_device_batch_int(pg_ctx *ctx, pg_device_batch *b, const pg_int_window *w
 int  pg_device_batch_int_sizes(pg_ctx *ctx, pg_device_batch *b, pg_int_sizes *sizes);
 int  pg_device_batch_int_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *members, pg_int_call *calls);
 int  pg_device_batch_int_download_device(pg_ctx *ctx, pg_device_batch *b, uint32_t *d_members, pg_int_call *d_calls);
+
+/* ---- device classifier: dispersed-duplication breakpoint tables and consensus ---------------------------------------
+ * What searchMEIBreakpoints (src/search_MEI.cpp:367-424) makes of the split reads around its discordant clusters -- per candidate
+ * breakpoint the supporting reads, their consensus (get_consensus_unmapped, :156-218) and the containment verdict
+ * (contains_subseq_any_strand) -- as tables, so that a caller who writes _DD downloads no point and uploads no consensus.  The build
+ * needs a close-searched batch only (pg_device_batch_close_search, or any full search): it reads close_last / close_max / rc_flag of
+ * the output records, the anchor strands and the read bytes.
+ * Segment s is the reads [seg_first[s], seg_first[s + 1]) of the batch: the split reads ingested for one big-enough cluster (the same
+ * BAM record may sit in several segments as separate reads).  A DD read of segment s is a read of it with a close end
+ * (close_max != 0) whose anchor strand equals seg_strand[s].  Its key is (s, pos = close_last) -- UP_Close.back() -- and its
+ * close_len = close_max.  A candidate is a key with at least min_bp_support DD reads (1 or less admits every key; the reference counts
+ * "this read and the later ones with the same position" at a position's first occurrence and never succeeds later: the total count).
+ *   the member list     the DD reads of candidates, by (seg, pos) ascending with pos UNSIGNED, ascending read index within a key
+ *   the candidate table one pg_dd_cand per candidate in the same order: members [first, first + n_reads)
+ *   the consensus pool  the consensus bytes of the candidates back to back: [cons_off, cons_off + cons_len)
+ * The signed order of (int)(pos - spacer) that the reference's std::map<int, ...> imposes and the std::sort by unmapped length of a
+ * candidate's reads stay with the consumer.
+ * Consensus.  Per member, S = the read as rc_flag left it, len its length, u = len - close_len (0 where that is negative).  Column i of
+ * a member with u > i is S[u - 1 - i] for a '-' segment and rc4n(S[u - 1 - i]) for a '+' segment (rc4n: A<->T, C<->G, N->N, anything
+ * else -> byte 0): the unmapped bases walking away from the breakpoint.  Per column i = 0 .. max u - 1: n = members with u > i; the
+ * winner is the byte with the largest count, the smallest byte compared as signed char on a tie (the iteration order of
+ * std::map<char,int> with a strict >); the column is accepted iff 5 * max >= 4 * n, and the first rejected column ends the consensus.
+ * (The reference tests max_count >= 0.8f * read_count in float: the two agree for every n up to 200 000 at the threshold and one
+ * either side of it.)  Fewer than 15 columns: cons_len = 0, no bytes in the pool, not tested.  Otherwise a '+' segment stores the
+ * bytes in column order and a '-' segment reversed.
+ * Containment, per tested candidate: win_start = max(0, (int)pos - min_map_distance), win_len = min(padded length of chr_id -
+ * win_start, 2 * min_map_distance) (0 where win_start is not below that length; the unsigned expressions of the reference otherwise),
+ * and PG_DD_CONTAINED = pg_dd_contains_batch of the consensus in that window. */
+typedef struct {
+    const uint32_t *seg_first;   /* host, n_seg + 1 read indices, non-decreasing, seg_first[n_seg] <= n_reads   */
+    const uint8_t  *seg_strand;  /* host, n_seg bytes '+' / '-': the strand of the segment's discordant cluster  */
+    uint32_t n_seg;
+    int32_t  chr_id;             /* the window's chromosome (containment window, all reads' chr_id)              */
+    int32_t  min_bp_support;     /* --MIN_DD_BREAKPOINT_SUPPORT                                                  */
+    int32_t  min_map_distance;   /* --MIN_DD_MAP_DISTANCE, >= 1                                                  */
+} pg_dd_window;
+typedef struct { uint32_t read; uint16_t close_len; uint8_t rc_flag, reserved; } pg_dd_member;        /*  8 bytes */
+typedef struct { uint32_t seg, pos, first, n_reads, cons_off, cons_len, flags, win_len; uint64_t win_start; } pg_dd_cand; /* 40 bytes, no padding */
+#define PG_DD_TESTED    0x1u   /* cons_len >= 15: the containment test ran */
+#define PG_DD_CONTAINED 0x2u   /* ... and found the consensus in the window */
+typedef struct { uint64_t members, cands, cons_bytes; } pg_dd_sizes;
+/* Builds the tables and keeps them with the batch (a new search or upload drops them; freed with the batch).  Refused with nothing
+ * launched (PG_E_INVALID): a batch that is not close-searched, a null window, n_seg > 0 with a null array, seg_first decreasing or
+ * beyond n_reads, a strand byte other than '+' / '-', chr_id outside the reference, min_map_distance < 1.  n_reads == 0, n_seg == 0
+ * and "no candidate" are valid (a batch of no reads has nothing to search: it is accepted whether it was close-searched or not, as
+ * the entries that need a full search accept it).  Synchronous; pg_last_search_stats then reports the summed HIP-event time of the kernels.
+ * pg_device_batch_classify does not run it.  download: any pointer may be NULL; the _device sibling fills device memory under the
+ * rules of "device buffers in and out". */
+int  pg_device_batch_dd(pg_ctx *ctx, pg_device_batch *b, const pg_dd_window *window);
+int  pg_device_batch_dd_sizes(pg_ctx *ctx, pg_device_batch *b, pg_dd_sizes *sizes);
+int  pg_device_batch_dd_download(pg_ctx *ctx, pg_device_batch *b, pg_dd_member *members, pg_dd_cand *cands, uint8_t *cons);
+int  pg_device_batch_dd_download_device(pg_ctx *ctx, pg_device_batch *b, pg_dd_member *d_members, pg_dd_cand *d_cands, uint8_t *d_cons);
 
 /* -q (dispersed duplications): per item i, contains_subseq_any_strand(query_i, window_i, 15) of Pindel's MEI search
  * (src/search_MEI_util.cpp:188-351, bit-exact), where query_i = query[query_off[i] .. query_off[i+1]) (at most

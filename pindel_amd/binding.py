@@ -188,6 +188,26 @@ class IntSizes(C.Structure):
     _fields_ = [("members", C.c_uint64), ("calls", C.c_uint64)]
 
 
+# dispersed-duplication breakpoint tables (Engine.dd_tables): pg_dd_window, pg_dd_member, pg_dd_cand, pg_dd_sizes
+DD_TESTED, DD_CONTAINED = 1, 2
+KERNEL_DD_TABLES = 13                   # launch-log id of the DD table kernels
+DD_MEMBER_DTYPE = np.dtype([("read", "<u4"), ("close_len", "<u2"), ("rc_flag", "u1"), ("reserved", "u1")])
+DD_CAND_DTYPE = np.dtype([("seg", "<u4"), ("pos", "<u4"), ("first", "<u4"), ("n_reads", "<u4"), ("cons_off", "<u4"), ("cons_len", "<u4"),
+                          ("flags", "<u4"), ("win_len", "<u4"), ("win_start", "<u8")])
+assert DD_MEMBER_DTYPE.itemsize == 8 and DD_CAND_DTYPE.itemsize == 40
+
+
+class DdWindow(C.Structure):
+    """pg_dd_window"""
+    _fields_ = [("seg_first", C.c_void_p), ("seg_strand", C.c_void_p), ("n_seg", C.c_uint32), ("chr_id", C.c_int32),
+                ("min_bp_support", C.c_int32), ("min_map_distance", C.c_int32)]
+
+
+class DdSizes(C.Structure):
+    """pg_dd_sizes"""
+    _fields_ = [("members", C.c_uint64), ("cands", C.c_uint64), ("cons_bytes", C.c_uint64)]
+
+
 class EventWindow(C.Structure):
     """pg_event_window"""
     _fields_ = [("chr_id", C.c_int32), ("win_end", C.c_uint32), ("region_start", C.c_uint32), ("region_end", C.c_uint32),
@@ -246,7 +266,9 @@ EXPORTS = [
     "pg_device_batch_report_download", "pg_device_batch_report_download_device", "pg_device_batch_classify",
     "pg_device_batch_search_table",
     "pg_device_batch_li", "pg_device_batch_li_sizes", "pg_device_batch_li_download", "pg_device_batch_li_download_device",
-    "pg_device_batch_int", "pg_device_batch_int_sizes", "pg_device_batch_int_download", "pg_device_batch_int_download_device"]
+    "pg_device_batch_int", "pg_device_batch_int_sizes", "pg_device_batch_int_download", "pg_device_batch_int_download_device",
+    "pg_device_batch_close_search",
+    "pg_device_batch_dd", "pg_device_batch_dd_sizes", "pg_device_batch_dd_download", "pg_device_batch_dd_download_device"]
 
 
 def build(force: bool = False) -> str:
@@ -367,6 +389,11 @@ def lib():
     L.pg_device_batch_int_sizes.argtypes = [vp, vp, vp]
     L.pg_device_batch_int_download.argtypes = [vp] * 4
     L.pg_device_batch_int_download_device.argtypes = [vp] * 4
+    L.pg_device_batch_close_search.argtypes = [vp, vp]
+    L.pg_device_batch_dd.argtypes = [vp, vp, vp]
+    L.pg_device_batch_dd_sizes.argtypes = [vp, vp, vp]
+    L.pg_device_batch_dd_download.argtypes = [vp] * 5
+    L.pg_device_batch_dd_download_device.argtypes = [vp] * 5
     _lib = L
     return L
 
@@ -1165,6 +1192,51 @@ class Engine:
         out.update(n_members=nm, n_calls=nc)
         return out
 
+    def dd_sizes(self, dbatch):
+        """pg_device_batch_dd_sizes: (members, cands, cons_bytes) of the DD tables built last."""
+        sz = DdSizes()
+        self._check(self._L.pg_device_batch_dd_sizes(self._h, dbatch, C.addressof(sz)))
+        return int(sz.members), int(sz.cands), int(sz.cons_bytes)
+
+    def dd_download(self, dbatch):
+        """The DD tables the batch holds (pg_device_batch_dd_download) as a dict: members (DD_MEMBER_DTYPE, by (seg, pos), ascending read
+        index within a key), cands (DD_CAND_DTYPE, one per candidate) and cons (the consensus pool, bytes)."""
+        nm, nc, nb = self.dd_sizes(dbatch)
+        members = np.zeros(nm, dtype=DD_MEMBER_DTYPE)
+        cands = np.zeros(nc, dtype=DD_CAND_DTYPE)
+        cons = np.zeros(nb, dtype=np.uint8)
+        self._check(self._L.pg_device_batch_dd_download(self._h, dbatch, members.ctypes.data if nm else None, cands.ctypes.data if nc else None,
+                                                        cons.ctypes.data if nb else None))
+        return dict(members=members, cands=cands, cons=cons.tobytes())
+
+    def _dd_build(self, dbatch, seg_first, seg_strand, chr_id, min_bp_support, min_map_distance):
+        first = np.ascontiguousarray(seg_first, dtype=np.uint32)
+        strand = np.frombuffer(seg_strand.encode() if isinstance(seg_strand, str) else bytes(seg_strand), dtype=np.uint8)
+        n_seg = int(strand.size)
+        assert first.size == (n_seg + 1 if n_seg else first.size), "seg_first has n_seg + 1 entries"
+        w = DdWindow(first.ctypes.data if first.size else None, strand.ctypes.data if n_seg else None, n_seg, int(chr_id),
+                     int(min_bp_support), int(min_map_distance))
+        self._check(self._L.pg_device_batch_dd(self._h, dbatch, C.addressof(w)))
+
+    def dd_tables(self, dbatch, seg_first, seg_strand, chr_id, min_bp_support=3, min_map_distance=8000):
+        """Dispersed-duplication breakpoint tables of a close-searched batch (pg_device_batch_dd).  seg_first: n_seg + 1
+        read indices; seg_strand: n_seg bytes '+' / '-' (str or bytes); chr_id: the window's chromosome.  Returns dd_download(dbatch)."""
+        self._dd_build(dbatch, seg_first, seg_strand, chr_id, min_bp_support, min_map_distance)
+        return self.dd_download(dbatch)
+
+    def dd_tensors(self, dbatch, seg_first, seg_strand, chr_id, min_bp_support=3, min_map_distance=8000):
+        """dd_tables with the tables staying on the GPU (pg_device_batch_dd_download_device): a dict of uint8 tensors on this engine's
+        device, members [n_members, 8], cands [n_cands, 40], cons [cons_bytes], plus n_members / n_cands / cons_bytes."""
+        torch, dev = self._torch_ready()
+        self._dd_build(dbatch, seg_first, seg_strand, chr_id, min_bp_support, min_map_distance)
+        nm, nc, nb = self.dd_sizes(dbatch)
+        out = dict(members=torch.empty((nm, 8), dtype=torch.uint8, device=dev), cands=torch.empty((nc, 40), dtype=torch.uint8, device=dev),
+                   cons=torch.empty(nb, dtype=torch.uint8, device=dev))
+        self._check(self._L.pg_device_batch_dd_download_device(self._h, dbatch, out["members"].data_ptr() if nm else None,
+                                                               out["cands"].data_ptr() if nc else None, out["cons"].data_ptr() if nb else None))
+        out.update(n_members=nm, n_cands=nc, cons_bytes=nb)
+        return out
+
     def events_download(self, dbatch):
         """The event tables the batch holds (pg_device_batch_event_sizes / _events_download) as the dict events() returns."""
         n = self._batch_n[dbatch.value]
@@ -1203,6 +1275,11 @@ class Engine:
         the GPU (pg_device_batch_search_table); None: pack_search_device on the batch without windows"""
         t = hints.struct() if hints is not None else None
         self._check(self._L.pg_device_batch_search_table(self._h, dbatch, C.byref(t) if t is not None else None))
+
+    def close_search(self, dbatch):
+        """The close end alone of a resident batch (pg_device_batch_close_search): the batch ends close-searched -- what dd_tables
+        needs -- and not searched: everything that needs both ends refuses it."""
+        self._check(self._L.pg_device_batch_close_search(self._h, dbatch))
 
     def last_step_in_place(self) -> bool:
         """tests: did the last pack_search_device build its records inside the search kernel (one launch)?"""

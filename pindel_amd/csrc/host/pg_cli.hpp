@@ -35,6 +35,7 @@ struct CliOptions {
     bool device_classifier_hints = false;  // --device-classifier-hints: hinted windows are searched on the device-resident path
     bool device_classifier_li = false;     // --device-classifier-li: -l and -s are written from device tables and summaries
     bool device_classifier_int = false;    // --device-classifier-int: -I is written from device junction tables and summaries
+    bool device_classifier_dd = false;     // --device-classifier-dd: -q takes its breakpoint tables and consensus from the device
 };
 
 // A flag's word as the parser hands it to the row: as typed, as a number (kinds i and f), as a switch's state (kind u)
@@ -148,14 +149,18 @@ static const CliFlag CLI_DEVICE_HINT_FLAGS[] = {
 static const CliFlag CLI_DEVICE_LI_FLAGS[] = {
     { "", "--device-classifier-li", 'u', PG_CLI_SET(o.device_classifier_li = a.on) },
 };
-// ... and the switch that admits -I there, in a fifth table that parse_cli walks last
+// ... and the switch that admits -I there, in a fifth table that parse_cli walks after it
 static const CliFlag CLI_DEVICE_INT_FLAGS[] = {
     { "", "--device-classifier-int", 'u', PG_CLI_SET(o.device_classifier_int = a.on) },
 };
+// ... and the switch that admits -q there, in a sixth table that parse_cli walks last
+static const CliFlag CLI_DEVICE_DD_FLAGS[] = {
+    { "", "--device-classifier-dd", 'u', PG_CLI_SET(o.device_classifier_dd = a.on) },
+};
 #undef PG_CLI_SET
 
-// What --device-classifier does not deliver yet: "" or the refusal, looked at after the last flag.  -l / -s
-// and -I are admitted by a switch of their own each; -S, -q, -N and several devices stay refused.
+// What --device-classifier does not deliver yet: "" or the refusal, looked at after the last flag.  -l / -s,
+// -I and -q are admitted by a switch of their own each; -S, -N and several devices stay refused.
 inline std::string device_classifier_refusal(const CliOptions &o)
 {
     if (!o.device_classifier)
@@ -163,12 +168,14 @@ inline std::string device_classifier_refusal(const CliOptions &o)
                : o.device_classifier_hints      ? "--device-classifier-hints needs --device-classifier"
                : o.device_classifier_li         ? "--device-classifier-li needs --device-classifier"
                : o.device_classifier_int        ? "--device-classifier-int needs --device-classifier"
+               : o.device_classifier_dd         ? "--device-classifier-dd needs --device-classifier"
                                                 : "";
     const bool li = o.device_classifier_li;                // -l and -s are admitted with the switch alone
     const bool junctions = o.device_classifier_int;        // ... and -I with its own
+    const bool dd = o.device_classifier_dd;                // ... and -q with its own
     const char *with = o.S.Analyze_LI && !li ? "-l" : o.S.report_close_mapped && !li ? "-s" : o.S.only_close_mapped ? "-S"
                      : o.S.report_interchromosomal && !junctions ? "-I"
-                     : o.detect_dd ? "-q" : o.S.NormalSamples ? "-N" : nullptr;
+                     : o.detect_dd && !dd ? "-q" : o.S.NormalSamples ? "-N" : nullptr;
     if (with) return std::string("--device-classifier cannot be combined with ") + with + ": its report needs points or pairs this path does not deliver";
     if (o.use_bd && !o.device_classifier_hints) return "--device-classifier cannot be combined with --bd-hints on: window hints are not searched on this path";
     if (!o.bam_config.empty() && o.search_rp && !o.device_classifier_hints)
@@ -211,6 +218,9 @@ inline int parse_cli(int argc, char **argv, CliOptions &o, std::string &err)
                 if (f == x.lg) fl = &x;
         if (!fl)
             for (const CliFlag &x : CLI_DEVICE_INT_FLAGS)
+                if (f == x.lg) fl = &x;
+        if (!fl)
+            for (const CliFlag &x : CLI_DEVICE_DD_FLAGS)
                 if (f == x.lg) fl = &x;
         if (!fl) {
             err = "unknown argument: " + f;

@@ -80,6 +80,128 @@ bool dd_contains_any_strand(const std::string &query, const char *db, size_t db_
     return dd_contains_subseq(query, db, db_len, 15, max_mismatch) || dd_contains_subseq(reverse_complement(query), db, db_len, 15, max_mismatch);
 }
 
+// ------------------------------------------------------------------------------------------ the breakpoint tables
+// The contract of pindel_pg.h "dispersed-duplication breakpoint tables" in plain loops: what get_breakpoints and
+// get_consensus_unmapped (src/search_MEI.cpp:120-218, 367-424) make of the close ends, as the device entry pg_device_batch_dd
+// builds it.  The two must agree byte for byte.
+int dd_tables_from_close(const pg_adapter::Batch &batch, const std::vector<DDClose> &close, const std::vector<uint32_t> &seg_first,
+                         const std::vector<uint8_t> &seg_strand, const DDWindow &w, const DDContainsFn &contains_fn, DDTables &out)
+{
+    out = DDTables();
+    const size_t n = batch.strand.size(), n_seg = seg_strand.size();
+    // the DD reads: segment by segment in ascending read index, then by (seg, pos) with pos unsigned -- a stable sort, so that equal
+    // keys keep the ascending read index
+    struct DDRead {
+        uint32_t seg, pos, read;
+    };
+    std::vector<DDRead> dd;
+    for (size_t s = 0; s < n_seg; s++)
+        for (size_t i = seg_first[s]; i < seg_first[s + 1] && i < n; i++)
+            if (close[i].has && batch.strand[i] == seg_strand[s]) dd.push_back({ (uint32_t)s, close[i].last_abs, (uint32_t)i });
+    std::stable_sort(dd.begin(), dd.end(), [](const DDRead &a, const DDRead &b) { return a.seg != b.seg ? a.seg < b.seg : a.pos < b.pos; });
+    for (size_t g0 = 0; g0 < dd.size();) {
+        size_t g1 = g0;
+        while (g1 < dd.size() && dd[g1].seg == dd[g0].seg && dd[g1].pos == dd[g0].pos) g1++;
+        const size_t first = g0, end = g1;
+        g0 = g1;
+        // (the reference counts "this read and the later ones" at a position's first occurrence only: the total)
+        if (w.min_bp_support > 1 && end - first < (size_t)w.min_bp_support) continue;
+        const bool plus = seg_strand[dd[first].seg] == '+';
+        pg_dd_cand c;
+        c.seg = dd[first].seg;
+        c.pos = dd[first].pos;
+        c.first = (uint32_t)out.members.size();
+        c.n_reads = (uint32_t)(end - first);
+        c.cons_off = (uint32_t)out.cons.size();
+        c.cons_len = c.flags = c.win_len = 0;
+        c.win_start = 0;
+        // per member the unmapped bases walking away from the breakpoint
+        std::vector<std::string> walk;
+        size_t max_u = 0;
+        for (size_t k = first; k < end; k++) {
+            const uint32_t i = dd[k].read;
+            out.members.push_back({ i, close[i].last_len, close[i].rc_flag, 0 });
+            SplitRead r;
+            r.UnmatchedSeq.assign((const char *)batch.seq.data() + batch.off[i], (size_t)(batch.off[i + 1] - batch.off[i]));
+            pg_adapter::apply_rc_flag(r, close[i].rc_flag);
+            const std::string &S = r.UnmatchedSeq;
+            const size_t u = S.size() > close[i].last_len ? S.size() - close[i].last_len : 0;
+            std::string wk(u, '\0');
+            for (size_t col = 0; col < u; col++) wk[col] = plus ? detail::rc4n(S[u - 1 - col]) : S[u - 1 - col];
+            max_u = std::max(max_u, u);
+            walk.push_back(wk);
+        }
+        std::string cons;
+        for (size_t col = 0; col < max_u; col++) {
+            int counts[256] = { 0 }, n_col = 0;
+            for (const std::string &wk : walk)
+                if (wk.size() > col) {
+                    n_col++;
+                    counts[(uint8_t)wk[col]]++;
+                }
+            // the largest count, the smallest signed char on a tie: std::map<char,int> in order with a strict >
+            char best = '?';
+            int max_count = 0;
+            for (int v = -128; v < 128; v++)
+                if (counts[(uint8_t)(signed char)v] > max_count) {
+                    max_count = counts[(uint8_t)(signed char)v];
+                    best = (char)v;
+                }
+            // max_count >= 0.8f * read_count in integers: the two agree for every n up to 200 000 at the threshold and one either
+            // side of it
+            if (5ll * max_count < 4ll * n_col) break;
+            cons += best;
+        }
+        if (cons.size() >= 15u) {
+            // (sr_strand is the opposite of the cluster strand, and the reference reverses for sr_strand == PLUS)
+            if (!plus) std::reverse(cons.begin(), cons.end());
+            c.cons_len = (uint32_t)cons.size();
+            c.flags = PG_DD_TESTED;
+            // the unsigned expressions of searchMEIBreakpoints; a start at or beyond the chromosome's end has a window of no bases
+            const int64_t st = (int64_t)(int32_t)c.pos - (int64_t)w.min_map_distance;
+            c.win_start = st > 0 ? (uint64_t)st : 0;
+            if (c.win_start < w.chr_len) c.win_len = std::min((unsigned)w.chr_len - (unsigned)c.win_start, 2 * (unsigned)w.min_map_distance);
+            out.cons.insert(out.cons.end(), cons.begin(), cons.end());
+        }
+        out.cands.push_back(c);
+    }
+    // the containment tests of all tested candidates as ONE call
+    std::vector<std::string> queries;
+    std::vector<int32_t> q_chr;
+    std::vector<uint64_t> q_start;
+    std::vector<uint32_t> q_len;
+    for (const pg_dd_cand &c : out.cands)
+        if (c.flags & PG_DD_TESTED) {
+            queries.push_back(std::string((const char *)out.cons.data() + c.cons_off, c.cons_len));
+            q_chr.push_back(w.chr_id);
+            q_start.push_back(c.win_start);
+            q_len.push_back(c.win_len);
+        }
+    if (queries.empty()) return 0;
+    std::vector<uint8_t> found(queries.size(), 0);
+    if (const int rc = contains_fn(queries, q_chr, q_start, q_len, found)) return rc;
+    size_t item = 0;
+    for (pg_dd_cand &c : out.cands)
+        if (c.flags & PG_DD_TESTED)
+            if (found[item++]) c.flags |= PG_DD_CONTAINED;
+    return 0;
+}
+
+int dd_tables_from_close(const pg_adapter::Batch &batch, const std::vector<DDClose> &close, const std::vector<uint32_t> &seg_first,
+                         const std::vector<uint8_t> &seg_strand, const DDWindow &w, const std::string &chrom_seq, const uint32_t *max_mismatch,
+                         DDTables &out)
+{
+    return dd_tables_from_close(
+        batch, close, seg_first, seg_strand, w,
+        [&](const std::vector<std::string> &q, const std::vector<int32_t> &, const std::vector<uint64_t> &st, const std::vector<uint32_t> &len,
+            std::vector<uint8_t> &found) {
+            found.assign(q.size(), 0);
+            for (size_t i = 0; i < q.size(); i++) found[i] = dd_contains_any_strand(q[i], chrom_seq.data() + st[i], len[i], max_mismatch) ? 1 : 0;
+            return 0;
+        },
+        out);
+}
+
 namespace {
 
 const char PLUS = '+', MINUS = '-';
@@ -239,38 +361,6 @@ void cluster_reads(std::vector<SimpleRead *> &reads, int insert_size, const DDSe
     if (!current.empty()) clusters.push_back(current);
 }
 
-// get_consensus_unmapped (search_MEI.cpp:156-218); sorts `reads` in place, as the reference does
-std::string consensus_unmapped(std::vector<SimpleRead> &reads, char strand)
-{
-    if (reads.empty()) return "";
-    std::sort(reads.begin(), reads.end(), comp_unmapped_seqsize);
-    const int max_len = (int)reads[0].unmapped_sequence.length();
-    const float MIN_FRACTION_CONSENSUS = 0.8;
-    std::string cons;
-    for (int i = 0; i < max_len; i++) {
-        std::map<char, int> counts;
-        int read_count = 0;
-        for (const SimpleRead &r : reads) {
-            const int index = strand == MINUS ? i : (int)r.unmapped_sequence.length() - 1 - i;
-            if (index < 0 || index >= (int)r.unmapped_sequence.length()) continue;
-            read_count++;
-            counts[r.unmapped_sequence.at((size_t)index)]++;
-        }
-        char c = '?';
-        int max_count = 0;
-        for (const auto &kv : counts)
-            if (kv.second > max_count) {
-                max_count = kv.second;
-                c = kv.first;
-            }
-        if (max_count >= MIN_FRACTION_CONSENSUS * read_count) cons += c;
-        else break;
-    }
-    if (cons.length() < 15u) return "";
-    if (strand == PLUS) std::reverse(cons.begin(), cons.end());
-    return cons;
-}
-
 // get_breakpoint_estimation (search_MEI.cpp:335-362)
 void breakpoint_estimation(const std::vector<SimpleRead *> &cluster, int tid, char strand, std::vector<Breakpoint> &bps)
 {
@@ -290,19 +380,74 @@ void breakpoint_estimation(const std::vector<SimpleRead *> &cluster, int tid, ch
     bps.push_back(bp);
 }
 
-// One split read of get_breakpoints as the loop there sees it (SPLIT_READ after ReadBuffer::flush)
-struct DDSplit {
-    std::string name, seq, read_group;
-    char matched_d = 0;
-    uint32_t last_abs = 0;
-    uint16_t close_len = 0;
+// One candidate breakpoint of a cluster as searchMEIBreakpoints holds it
+struct Cand {
+    size_t cluster;
+    int bio_bp;
+    std::vector<SimpleRead> split_reads;
+    std::string consensus;
+    bool tested = false, contained = false;
 };
+
+// The one consumer of the breakpoint tables: per segment the candidates in the order of the reference's
+// std::map<int, ...> over (int)(pos - spacer) -- the tables order pos unsigned -- each with its reads as get_breakpoints makes
+// them (name, sample, sequence, mapped / unmapped part; table order = the order the reference appends them in) after the std::sort
+// by unmapped length that get_consensus_unmapped leaves behind, and its consensus.  false: a table that does not fit the reads.
+bool cands_from_tables(const DDState &st, const DDTables &t, const IngestedReads &in, const std::vector<size_t> &big, unsigned spacer,
+                       std::vector<std::vector<Cand>> &cands)
+{
+    cands.assign(big.size(), std::vector<Cand>());
+    std::vector<std::map<int, size_t>> order(big.size());
+    for (size_t e = 0; e < t.cands.size(); e++) {
+        const pg_dd_cand &c = t.cands[e];
+        if (c.seg >= big.size() || !c.n_reads || (uint64_t)c.first + c.n_reads > t.members.size() ||
+            (uint64_t)c.cons_off + c.cons_len > t.cons.size() || ((c.flags & PG_DD_TESTED) != 0) != (c.cons_len != 0))
+            return false;
+        if (!order[c.seg].insert(std::make_pair((int)(c.pos - spacer), e)).second) return false;
+    }
+    for (size_t b = 0; b < big.size(); b++)
+        for (const auto &kv : order[b]) {
+            const pg_dd_cand &tc = t.cands[kv.second];
+            Cand c;
+            c.cluster = big[b];
+            c.bio_bp = kv.first;
+            for (uint32_t k = tc.first; k < tc.first + tc.n_reads; k++) {
+                const pg_dd_member &m = t.members[k];
+                if (m.read >= in.size()) return false;
+                SplitRead r;
+                r.UnmatchedSeq.assign((const char *)in.batch.seq.data() + in.batch.off[m.read], (size_t)(in.batch.off[m.read + 1] - in.batch.off[m.read]));
+                pg_adapter::apply_rc_flag(r, m.rc_flag);
+                if (m.close_len > r.UnmatchedSeq.size()) return false;
+                SimpleRead s;
+                s.is_split = true;
+                s.name = in.names[m.read];
+                if ((char)in.batch.strand[m.read] == PLUS) {
+                    s.sequence = reverse_complement(r.UnmatchedSeq);
+                    s.mapped_sequence = s.sequence.substr(0, m.close_len);
+                    s.unmapped_sequence = s.sequence.substr(m.close_len, s.sequence.length());
+                } else {
+                    s.sequence = r.UnmatchedSeq;
+                    s.mapped_sequence = s.sequence.substr(s.sequence.length() - m.close_len, s.sequence.length());
+                    s.unmapped_sequence = s.sequence.substr(0, s.sequence.length() - m.close_len);
+                }
+                sample_name_of(st, in.read_groups[m.read], s.sample_name);
+                c.split_reads.push_back(s);
+            }
+            std::sort(c.split_reads.begin(), c.split_reads.end(), comp_unmapped_seqsize);
+            c.consensus.assign((const char *)t.cons.data() + tc.cons_off, tc.cons_len);
+            c.tested = (tc.flags & PG_DD_TESTED) != 0;
+            c.contained = (tc.flags & PG_DD_CONTAINED) != 0;
+            cands[b].push_back(c);
+        }
+    return true;
+}
 
 // searchMEIBreakpoints (search_MEI.cpp:367-424) for the discordant reads of one window; get_breakpoints' split-read fetch
 // (get_split_reads_for_cluster, :120-150) runs for all clusters first, with ONE close-end call, and the containment tests of
-// all their candidates then run as ONE call.
+// all their candidates then run as ONE call: statement (dd_tables_from_close), then consumer (cands_from_tables).  With a
+// tables_fn the tables come from it instead of close_fn, the statement and contains_fn.
 int window_breakpoints(DDState &st, const DDSettings &dd, int chr_id, std::vector<SimpleRead> &disc, const BamIngestSettings &ingest,
-                       const DDCloseFn &close_fn, const DDContainsFn &contains_fn, std::string &err)
+                       const DDCloseFn &close_fn, const DDContainsFn &contains_fn, const DDTablesFn &tables_fn, std::string &err)
 {
     const Chromosome &chrom = (*st.genome)[(size_t)chr_id];
     std::vector<SimpleRead *> ptrs;
@@ -319,10 +464,12 @@ int window_breakpoints(DDState &st, const DDSettings &dd, int chr_id, std::vecto
     ing.read_groups = true;                        // SPLIT_READ::read_group: the RG of the anchor, for get_sample_name
     IngestedReads in;
     in.clear();
-    std::vector<size_t> first_read(big.size() + 1, 0);
+    std::vector<uint32_t> seg_first(big.size() + 1, 0);
+    std::vector<uint8_t> seg_strand(big.size(), 0);
     for (size_t b = 0; b < big.size(); b++) {
         const std::vector<SimpleRead *> &cl = clusters[big[b]];
         const char strand = cl[0]->strand;
+        seg_strand[b] = (uint8_t)strand;
         const int outer = strand == MINUS ? cl.back()->pos : cl[0]->pos;
         for (size_t k = 0; k < st.bams->size(); k++) {
             const int isz = (*st.bams)[k].insert_size;
@@ -335,115 +482,61 @@ int window_breakpoints(DDState &st, const DDSettings &dd, int chr_id, std::vecto
                 return -1;
             }
         }
-        first_read[b + 1] = in.size();
+        seg_first[b + 1] = (uint32_t)in.size();
     }
-    std::vector<DDClose> close;
-    if (in.size()) {
-        const int rc = close_fn(chr_id, in.batch, close);
+    DDWindow w;
+    w.chr_id = chr_id;
+    w.chr_len = chrom.seq.size();
+    w.min_bp_support = dd.min_bp_support;
+    w.min_map_distance = dd.min_map_distance;
+    DDTables tables;
+    if (in.size() && tables_fn) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const int rc = tables_fn(in.batch, seg_first, seg_strand, w, tables);
+        st.stats->contains_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (rc) {
+            err = "building the DD breakpoint tables failed";
+            return rc;
+        }
+        st.stats->table_windows++;
+        st.stats->table_bytes += tables.members.size() * sizeof(pg_dd_member) + tables.cands.size() * sizeof(pg_dd_cand) + tables.cons.size();
+    } else if (in.size()) {
+        std::vector<DDClose> close;
+        int rc = close_fn(chr_id, in.batch, close);
         if (rc) {
             err = "close-end search of the DD split reads failed";
             return rc;
         }
-    }
-    // per cluster: candidate breakpoints and their consensus; the containment items of all of them
-    struct Cand {
-        size_t cluster;
-        int bio_bp;
-        std::vector<SimpleRead> split_reads;
-        std::string consensus;
-        int item = -1;
-    };
-    std::vector<std::vector<Cand>> cands(big.size());
-    std::vector<std::string> queries;
-    std::vector<int32_t> q_chr;
-    std::vector<uint64_t> q_start;
-    std::vector<uint32_t> q_len;
-    for (size_t b = 0; b < big.size(); b++) {
-        const std::vector<SimpleRead *> &cl = clusters[big[b]];
-        const char cluster_strand = cl[0]->strand;
-        std::vector<DDSplit> split;
-        for (size_t i = first_read[b]; i < first_read[b + 1]; i++) {
-            if (!close[i].has) continue;
-            SplitRead r;
-            r.UnmatchedSeq.assign((const char *)in.batch.seq.data() + in.batch.off[i], (size_t)(in.batch.off[i + 1] - in.batch.off[i]));
-            pg_adapter::apply_rc_flag(r, close[i].rc_flag);
-            DDSplit s;
-            s.name = in.names[i];
-            s.seq = r.UnmatchedSeq;
-            s.read_group = in.read_groups[i];
-            s.matched_d = (char)in.batch.strand[i];
-            s.last_abs = close[i].last_abs;
-            s.close_len = close[i].last_len;
-            split.push_back(s);
-        }
-        std::map<int, std::vector<SimpleRead>> bio_cands;
-        for (size_t i = 0; i < split.size(); i++) {
-            const DDSplit &read = split[i];
-            if (read.matched_d != cluster_strand) continue;
-            const unsigned comp_bp = read.last_abs;
-            const unsigned bio_bp = comp_bp - spacer;
-            if (bio_cands.find((int)bio_bp) == bio_cands.end()) {
-                int support = 1;
-                for (size_t j = i + 1; j < split.size(); j++)
-                    if (split[j].last_abs == comp_bp && split[j].matched_d == cluster_strand) support++;
-                if (support < dd.min_bp_support) continue;
-                bio_cands.insert(std::make_pair((int)bio_bp, std::vector<SimpleRead>()));
-            }
-            SimpleRead s;
-            s.is_split = true;
-            s.name = read.name;
-            if (read.matched_d == PLUS) {
-                s.sequence = reverse_complement(read.seq);
-                s.mapped_sequence = s.sequence.substr(0, read.close_len);
-                s.unmapped_sequence = s.sequence.substr(read.close_len, s.sequence.length());
-            } else {
-                s.sequence = read.seq;
-                s.mapped_sequence = s.sequence.substr(s.sequence.length() - read.close_len, s.sequence.length());
-                s.unmapped_sequence = s.sequence.substr(0, s.sequence.length() - read.close_len);
-            }
-            sample_name_of(st, read.read_group, s.sample_name);
-            bio_cands.find((int)bio_bp)->second.push_back(s);
-        }
-        const char sr_strand = cluster_strand == PLUS ? MINUS : PLUS;
-        for (auto &kv : bio_cands) {
-            Cand c;
-            c.cluster = big[b];
-            c.bio_bp = kv.first;
-            c.consensus = consensus_unmapped(kv.second, sr_strand);
-            c.split_reads = kv.second;
-            if (!c.consensus.empty()) {
-                const size_t fe_start = (size_t)std::max(0, (int)(c.bio_bp + spacer) - dd.min_map_distance);
-                const size_t fe_size = std::min((unsigned)chrom.seq.size() - (unsigned)fe_start, 2 * (unsigned)dd.min_map_distance);
-                c.item = (int)queries.size();
-                queries.push_back(c.consensus);
-                q_chr.push_back(chr_id);
-                q_start.push_back(fe_start);
-                q_len.push_back((uint32_t)fe_size);
-            }
-            cands[b].push_back(c);
-        }
-    }
-    std::vector<uint8_t> found(queries.size(), 0);
-    if (!queries.empty()) {
-        const auto t0 = std::chrono::steady_clock::now();
-        const int rc = contains_fn(queries, q_chr, q_start, q_len, found);
-        st.stats->contains_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        rc = dd_tables_from_close(in.batch, close, seg_first, seg_strand, w,
+                                  [&](const std::vector<std::string> &q, const std::vector<int32_t> &chr, const std::vector<uint64_t> &start,
+                                      const std::vector<uint32_t> &len, std::vector<uint8_t> &found) {
+                                      const auto t0 = std::chrono::steady_clock::now();
+                                      const int r = contains_fn(q, chr, start, len, found);
+                                      st.stats->contains_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+                                      return r;
+                                  },
+                                  tables);
         if (rc) {
             err = "containment test of the DD consensus sequences failed";
             return rc;
         }
-        st.stats->candidates += queries.size();
     }
+    std::vector<std::vector<Cand>> cands;
+    if (!cands_from_tables(st, tables, in, big, spacer, cands)) {
+        err = "the DD breakpoint tables of a window do not fit its split reads";
+        return -1;
+    }
+    for (const pg_dd_cand &c : tables.cands) st.stats->candidates += (c.flags & PG_DD_TESTED) != 0;
     for (size_t b = 0; b < big.size(); b++) {
         const std::vector<SimpleRead *> &cl = clusters[big[b]];
         const char strand = cl[0]->strand;
         const int tid = cl[0]->tid;
         std::vector<Breakpoint> bps;
         for (Cand &c : cands[b]) {
-            if (c.item >= 0)
+            if (c.tested)
                 st.stats->tested += std::to_string(tid) + "\t" + std::to_string(c.bio_bp) + "\t" + strand + "\t" + std::to_string(c.split_reads.size()) +
-                                    "\t" + c.consensus + "\t" + (found[(size_t)c.item] ? "1" : "0") + "\n";
-            if (c.item < 0 || found[(size_t)c.item]) continue;
+                                    "\t" + c.consensus + "\t" + (c.contained ? "1" : "0") + "\n";
+            if (!c.tested || c.contained) continue;
             st.stats->kept_by_containment++;
             Breakpoint bp;
             bp.tid = tid;
@@ -580,9 +673,44 @@ void report_event(const std::vector<Chromosome> &genome, const std::map<int, std
 
 }  // namespace
 
+bool dd_cands_text(unsigned spacer, const std::vector<std::string> &names, const std::string &sample, const uint8_t *seq, const uint64_t *seq_off,
+                   const uint8_t *strand, uint32_t n_reads, uint32_t n_seg, const DDTables &tables, std::string &out)
+{
+    DDStats stats;
+    DDState st;
+    st.genome = nullptr;
+    st.bams = nullptr;
+    st.files = nullptr;
+    st.stats = &stats;
+    st.sample_tags.insert(sample);
+    IngestedReads in;
+    in.clear();
+    if (n_reads) {
+        in.batch.off.assign(seq_off, seq_off + n_reads + 1);
+        in.batch.seq.assign(seq, seq + seq_off[n_reads]);
+        in.batch.strand.assign(strand, strand + n_reads);
+    }
+    in.names = names;
+    in.read_groups.assign(n_reads, std::string());
+    std::vector<size_t> big(n_seg);
+    for (uint32_t b = 0; b < n_seg; b++) big[b] = b;
+    std::vector<std::vector<Cand>> cands;
+    if (!cands_from_tables(st, tables, in, big, spacer, cands)) return false;
+    out.clear();
+    for (uint32_t b = 0; b < n_seg; b++)
+        for (const Cand &c : cands[b]) {
+            out += "C\t" + std::to_string(b) + "\t" + std::to_string(c.bio_bp) + "\t" + (c.tested ? "1" : "0") + "\t" + (c.contained ? "1" : "0") + "\t" +
+                   c.consensus + "\n";
+            for (const SimpleRead &r : c.split_reads)
+                out += "R\t" + r.name + "\t" + r.sample_name + "\t" + r.sequence + "\t" + r.mapped_sequence + "\t" + r.unmapped_sequence + "\n";
+        }
+    return true;
+}
+
 int run_dd(const std::vector<Chromosome> &genome, const std::vector<unsigned> &sizes, const std::vector<RegionRecord> &plan,
            const std::vector<BamSource> &bams, const BamIngestSettings &ingest, double window_mbp, const DDSettings &dd,
-           const std::string &prefix, const DDCloseFn &close_fn, const DDContainsFn &contains_fn, std::string &err, DDStats *stats)
+           const std::string &prefix, const DDCloseFn &close_fn, const DDContainsFn &contains_fn, std::string &err, DDStats *stats,
+           const DDTablesFn &tables_fn)
 {
     const unsigned spacer = ingest.spacer;
     DDStats local;
@@ -610,7 +738,7 @@ int run_dd(const std::vector<Chromosome> &genome, const std::vector<unsigned> &s
             std::vector<SimpleRead> disc;
             if (!load_discordant(st, dd, chrom.name, w.first, w.second, disc, err)) return -1;
             stats->discordant += disc.size();
-            const int rc = window_breakpoints(st, dd, rec.chr, disc, ingest, close_fn, contains_fn, err);
+            const int rc = window_breakpoints(st, dd, rec.chr, disc, ingest, close_fn, contains_fn, tables_fn, err);
             if (rc) return rc;
         }
     }

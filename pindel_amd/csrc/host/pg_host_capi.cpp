@@ -1477,6 +1477,105 @@ int pgh_dd_contains_cpu(uint32_t n, const uint8_t *q, const uint64_t *q_off, con
     return 0;
 }
 
+/*
+ * The dispersed-duplication breakpoint tables (pindel_pg.h "dispersed-duplication breakpoint tables"), on the host: the
+ * plain-loop statement (dd_tables_from_close) the device entry pg_device_batch_dd is compared with, byte for byte.  The reads as they
+ * were handed to the search (seq, seq_off, strand) with their close end (has, rc_flag, last_abs = close_last, last_len = close_max);
+ * the segments and window parameters of pg_dd_window; chrom = the chrom_len padded bases of chr_id, mm500 = g_maxMismatch: the
+ * containment test runs on the host.  out_members: room for n_reads entries, out_cands likewise, out_cons: cons_cap bytes; sizes:
+ * what was filled.  -1: a null array, an argument pg_device_batch_dd refuses, or a consensus pool beyond cons_cap.
+ */
+int pgh_dd_tables_from_close(uint32_t n_reads, const uint8_t *seq, const uint64_t *seq_off, const uint8_t *strand, const uint8_t *has,
+                             const uint8_t *rc_flag, const uint32_t *last_abs, const uint16_t *last_len, const uint32_t *seg_first,
+                             const uint8_t *seg_strand, uint32_t n_seg, int32_t chr_id, int32_t min_bp_support, int32_t min_map_distance,
+                             const uint8_t *chrom, uint64_t chrom_len, const uint32_t *mm500, pg_dd_member *out_members, pg_dd_cand *out_cands,
+                             uint8_t *out_cons, uint64_t cons_cap, pg_dd_sizes *sizes)
+{
+    if (!sizes || !mm500 || (chrom_len && !chrom) || (n_seg && (!seg_first || !seg_strand)) ||
+        (n_reads && (!seq_off || !strand || !has || !rc_flag || !last_abs || !last_len || !out_members || !out_cands))) {
+        g_err = "pgh_dd_tables_from_close: null array";
+        return -1;
+    }
+    for (uint32_t s = 0; s < n_seg; s++)
+        if (seg_first[s] > seg_first[s + 1] || seg_first[s + 1] > n_reads || (seg_strand[s] != '+' && seg_strand[s] != '-')) {
+            g_err = "pgh_dd_tables_from_close: malformed segments";
+            return -1;
+        }
+    if (min_map_distance < 1) {
+        g_err = "pgh_dd_tables_from_close: min_map_distance < 1";
+        return -1;
+    }
+    pg_adapter::Batch batch;
+    batch.off.assign(1, 0);
+    if (n_reads) {
+        batch.off.assign(seq_off, seq_off + n_reads + 1);
+        batch.seq.assign(seq, seq + seq_off[n_reads]);
+        batch.strand.assign(strand, strand + n_reads);
+    }
+    std::vector<DDClose> close(n_reads);
+    for (uint32_t i = 0; i < n_reads; i++) {
+        close[i].has = has[i];
+        close[i].rc_flag = rc_flag[i];
+        close[i].last_abs = last_abs[i];
+        close[i].last_len = last_len[i];
+    }
+    DDWindow w;
+    w.chr_id = chr_id;
+    w.chr_len = chrom_len;
+    w.min_bp_support = min_bp_support;
+    w.min_map_distance = min_map_distance;
+    const std::string chrom_seq = chrom_len ? std::string((const char *)chrom, (size_t)chrom_len) : std::string();
+    DDTables t;
+    dd_tables_from_close(batch, close, std::vector<uint32_t>(seg_first, seg_first + (n_seg ? n_seg + 1 : 0)),
+                         std::vector<uint8_t>(seg_strand, seg_strand + n_seg), w, chrom_seq, mm500, t);
+    if (t.cons.size() > cons_cap) {
+        g_err = "pgh_dd_tables_from_close: the consensus pool exceeds cons_cap";
+        return -1;
+    }
+    if (!t.members.empty()) memcpy(out_members, t.members.data(), t.members.size() * sizeof(pg_dd_member));
+    if (!t.cands.empty()) memcpy(out_cands, t.cands.data(), t.cands.size() * sizeof(pg_dd_cand));
+    if (!t.cons.empty()) memcpy(out_cons, t.cons.data(), t.cons.size());
+    sizes->members = t.members.size();
+    sizes->cands = t.cands.size();
+    sizes->cons_bytes = t.cons.size();
+    return 0;
+}
+
+/*
+ * Test hook: the single consumer of the breakpoint tables (dd_cands_text) on tables made by hand.  The n_reads split reads as ingested
+ * (name as a NUL-terminated string, bytes, anchor strand; every read gets `sample`), the tables and the number of segments.  text
+ * (text_cap bytes): per segment and candidate, in the consumer's order, a line "C seg bio_bp tested contained consensus" followed by
+ * one line "R name sample sequence mapped unmapped" per read (tab-separated).  -1: tables that do not fit the reads, or a text
+ * beyond text_cap.
+ */
+int pgh_dd_cands_from_tables(uint32_t spacer, uint32_t n_reads, const char *const *names, const char *sample, const uint8_t *seq,
+                             const uint64_t *seq_off, const uint8_t *strand, uint32_t n_seg, const pg_dd_member *members, const pg_dd_cand *cands,
+                             const uint8_t *cons, const pg_dd_sizes *sizes, char *text, uint64_t text_cap)
+{
+    if (!sizes || !text || !text_cap || !sample || (n_reads && (!names || !seq_off || !strand)) || (sizes->members && !members) ||
+        (sizes->cands && !cands) || (sizes->cons_bytes && !cons)) {
+        g_err = "pgh_dd_cands_from_tables: null array";
+        return -1;
+    }
+    DDTables t;
+    t.members.assign(members, members + sizes->members);
+    t.cands.assign(cands, cands + sizes->cands);
+    t.cons.assign(cons, cons + sizes->cons_bytes);
+    std::vector<std::string> nm(n_reads);
+    for (uint32_t i = 0; i < n_reads; i++) nm[i] = names[i];
+    std::string out;
+    if (!dd_cands_text(spacer, nm, sample, seq, seq_off, strand, n_reads, n_seg, t, out)) {
+        g_err = "pgh_dd_cands_from_tables: the tables do not fit the reads";
+        return -1;
+    }
+    if (out.size() + 1 > text_cap) {
+        g_err = "pgh_dd_cands_from_tables: the text exceeds text_cap";
+        return -1;
+    }
+    memcpy(text, out.c_str(), out.size() + 1);
+    return 0;
+}
+
 // The close end of one batch for pgh_dd_run, supplied by the caller: per read has / rc_flag / UP_Close.back() AbsLoc, LengthStr.
 typedef int (*pgh_dd_close_cb)(uint32_t n, const uint8_t *seq, const uint64_t *off, const uint8_t *strand, const int32_t *pos,
                                const int16_t *isz, const int32_t *chr, uint8_t *has, uint8_t *rc_flag, uint32_t *last_abs,

@@ -3,14 +3,17 @@
 //                                              [-x 2 -a 1 -m 3 -u 0.02 -e 0.01 -E 0.95 -H 8
 //                                               -M 1 -B 100 -d 30 -v 50 -w 5 -G device -l -s -S -I
 //                                               -c ALL|chr[:start[-end]] -j include.bed -J exclude.bed -N
-//                                               --repair int-pairs,inv-pairs,depth-mapq,bed0|all]
+//                                               --repair int-pairs,inv-pairs,depth-mapq,bed0|all
+//                                               --device-classifier [-listed 0..4 -hints -li -int -dd]]
 // FASTA + Pindel-text reads -> close/far-end search on the MI355X (C ABI, libpindel_pg.so)
 // -> SV classification and <prefix>_D/_SI/_TD/_INV reports (host code in this directory);
 // -l adds <prefix>_LI (long insertions), -s <prefix>_CloseEndMapped (the reads with a close end),
 // -S writes <prefix>_CloseEndMapped only (no far end, no SV search); -q adds <prefix>_DD (dispersed duplications, BAM input,
 // pg_dd.hpp); -I adds <prefix>_INT and <prefix>_INT_final (interchromosomal events, pg_host_int.cpp: far ends on other chromosomes
 // need window hints, i.e. BAM input with -R or `-b file --bd-hints on`; on the --device-classifier path -I needs
-// --device-classifier-int, which writes _INT from junction tables built on the device).  -P lists Pindel-text files, one per line (read before a
+// --device-classifier-int, which writes _INT from junction tables built on the device; likewise -q needs
+// --device-classifier-dd there, which takes the breakpoint tables, their consensus and the containment verdicts of _DD from the device,
+// DESIGN.md 7s).  -P lists Pindel-text files, one per line (read before a
 // -p file when both are given); a text file whose name ends in .gz is read through zlib.  -N (--NormalSamples) turns on the
 // germline filter of _TD and _INV for BAM input (pg_depth.hpp); for text input it changes nothing.
 // --repair LIST (off by default) turns on fixes of reference defects that are otherwise reproduced byte for byte:
@@ -597,6 +600,36 @@ static int dd_contains(pg_ctx *ctx, const std::vector<std::string> &q, const std
     return pg_dd_contains_batch(ctx, (uint32_t)q.size(), qs.data(), qo.data(), chr.data(), st.data(), len.data(), found.data());
 }
 
+// --device-classifier-dd: the breakpoint tables of one window's split reads from the device -- a resident upload, the
+// close end alone, pg_device_batch_dd and ONE download of members, candidates and consensus pool.  No point and no consensus crosses
+// the bus before the verdicts.
+static int dd_device_tables(pg_ctx *ctx, const pg_adapter::Batch &batch, const std::vector<uint32_t> &seg_first, const std::vector<uint8_t> &seg_strand,
+                            const DDWindow &w, DDTables &out)
+{
+    pg_read_batch v = batch.view();
+    pg_device_batch *b = nullptr;
+    int rc = pg_device_batch_upload(ctx, &v, &b);
+    if (rc) return rc;
+    struct Free {
+        pg_ctx *c;
+        pg_device_batch *b;
+        ~Free() { pg_device_batch_free(c, b); }
+    } free_batch = { ctx, b };
+    pg_dd_window dw;
+    dw.seg_first = seg_first.data();
+    dw.seg_strand = seg_strand.data();
+    dw.n_seg = (uint32_t)seg_strand.size();
+    dw.chr_id = w.chr_id;
+    dw.min_bp_support = w.min_bp_support;
+    dw.min_map_distance = w.min_map_distance;
+    pg_dd_sizes sz;
+    if ((rc = pg_device_batch_close_search(ctx, b)) || (rc = pg_device_batch_dd(ctx, b, &dw)) || (rc = pg_device_batch_dd_sizes(ctx, b, &sz))) return rc;
+    out.members.resize((size_t)sz.members);
+    out.cands.resize((size_t)sz.cands);
+    out.cons.resize((size_t)sz.cons_bytes);
+    return pg_device_batch_dd_download(ctx, b, out.members.data(), out.cands.data(), out.cons.data());
+}
+
 static int detect_dd(const CliOptions &o, pg_ctx *ctx, const std::vector<Chromosome> &genome, const std::vector<unsigned> &sizes,
                      const std::vector<RegionRecord> &plan, const std::vector<BamSource> &bams, const BamIngestSettings &ing, std::string &err)
 {
@@ -612,11 +645,18 @@ static int detect_dd(const CliOptions &o, pg_ctx *ctx, const std::vector<Chromos
         [ctx](int, const pg_adapter::Batch &batch, std::vector<DDClose> &outc) { return dd_close(ctx, batch, outc); },
         [ctx](const std::vector<std::string> &q, const std::vector<int32_t> &chr, const std::vector<uint64_t> &st, const std::vector<uint32_t> &len,
               std::vector<uint8_t> &found) { return dd_contains(ctx, q, chr, st, len, found); },
-        err, &dst);
+        err, &dst,
+        o.device_classifier_dd ? DDTablesFn([ctx](const pg_adapter::Batch &batch, const std::vector<uint32_t> &seg_first,
+                                                  const std::vector<uint8_t> &seg_strand, const DDWindow &w,
+                                                  DDTables &out) { return dd_device_tables(ctx, batch, seg_first, seg_strand, w, out); })
+                               : DDTablesFn());
     if (rc) return rc;
     printf("pindel_pg: dispersed duplications: %zu discordant reads, %zu clusters, %zu breakpoints, %zu consensus tests "
            "(GPU %.3f s, %zu kept), %zu events\n", dst.discordant, dst.clusters, dst.breakpoints, dst.candidates,
            dst.contains_seconds, dst.kept_by_containment, dst.events);
+    if (o.device_classifier_dd)
+        printf("pindel_pg: dispersed duplications: %zu windows built from device tables, %zu bytes downloaded for them\n", dst.table_windows,
+               dst.table_bytes);
     if (!dst.note.empty()) printf("pindel_pg: %s\n", dst.note.c_str());
     return 0;
 }

@@ -6,6 +6,8 @@
 // The device classifier's entries are pg_api_classify.cpp; what the two files share is pg_api_priv.h.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -962,7 +964,7 @@ int run_search(pg_ctx *ctx, pg_device_batch *b, int mode, bool pack = false)
         if (worst <= b->pool_shard_cap) {
             ctx->last_ms = ms;
             ctx->last_runs = total;
-            if (mode == PG_MODE_BOTH) b->searched = true;
+            if (mode == PG_MODE_BOTH) b->searched = b->close_searched = true;
             return PG_OK;
         }
         // overflow: grow the pool and redo the launch
@@ -2622,7 +2624,7 @@ int pg_device_batch_search_table(pg_ctx *ctx, pg_device_batch *b, const pg_hint_
         return pg_device_batch_pack_search(ctx, b);
     }
     if ((rc = search_refusals(ctx, b))) return rc;
-    b->searched = false;
+    b->searched = b->close_searched = false;
     b->cls.drop_search_tables();
     // each launch reserves its PG_RESERVE slots per read, and the batch's pool was sized for one: room for both from the start,
     // or every batch of more than ~87 000 reads would overflow once and run three times (PG_TEST_TINY_POOL: the regrow path)
@@ -2646,7 +2648,44 @@ int pg_device_batch_search_table(pg_ctx *ctx, pg_device_batch *b, const pg_hint_
         if (worst <= b->pool_shard_cap) {
             ctx->last_ms = (double)ms_close + (double)ms_far;
             ctx->last_runs = total;
-            b->searched = true;
+            b->searched = b->close_searched = true;
+            return b->exact_n < 0 ? read_exact_count(ctx, b) : PG_OK;
+        }
+        if ((rc = grow_pool(ctx, b, (uint64_t)worst + worst / 4 + 64))) return rc;
+    }
+    return fail(ctx, PG_E_DEVICE, "run pool kept overflowing");
+}
+
+// The close half of the above on its own: the batch ends close-searched (its records and pool hold the close end alone), which is
+// what the DD tables read; `searched` goes, so everything that needs both ends refuses the batch.
+int pg_device_batch_close_search(pg_ctx *ctx, pg_device_batch *b)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    int rc;
+    if ((rc = search_refusals(ctx, b))) return rc;
+    b->searched = b->close_searched = false;
+    b->cls.drop_search_tables();
+    const PgSoaOut a = soa_out(b);
+    for (int attempt = 0; attempt < 8; attempt++) {
+        float ms = 0.f;
+        uint32_t worst = 0;
+        uint64_t total = 0;
+        // (the close end reads no windows: those of an earlier call go first, so that they have no say in the launch's kernels)
+        if ((rc = clear_windows(ctx, b))) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(b->pool_used, 0, PG_POOL_SHARDS * 16 * sizeof(uint32_t), ctx->stream));
+        if ((rc = search_launch(ctx, b, PG_MODE_CLOSE, true, &ms, &worst, &total))) return rc;
+        if (worst <= b->pool_shard_cap) {
+            if (b->n && pg_unpack_close_summary(b->out_rec, &a, b->n, ctx->stream) != 0)
+                return fail(ctx, PG_E_DEVICE, "close-end summary kernel failed");
+            // (the far half of the records is not this launch's to write: what an earlier full search left there names pool slots
+            // that the close runs have taken by now.  The two far words of every 32-byte record go to zero: no far end)
+            static_assert(sizeof(PgOutRec) == 32 && offsetof(PgOutRec, far_off) == 8 && offsetof(PgOutRec, far_cnt) == 12, "the far words of a record");
+            if (b->n) HIP_TRY(ctx, hipMemset2DAsync((char *)b->out_rec + offsetof(PgOutRec, far_off), sizeof(PgOutRec), 0, 8, b->n, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            ctx->last_ms = (double)ms;
+            ctx->last_runs = total;
+            b->close_searched = true;
             return b->exact_n < 0 ? read_exact_count(ctx, b) : PG_OK;
         }
         if ((rc = grow_pool(ctx, b, (uint64_t)worst + worst / 4 + 64))) return rc;

@@ -1,8 +1,8 @@
-// pg_api_classify.cpp -- the device classifier's entries of the C ABI (include/pindel_pg.h; DESIGN.md 7k - 7r): candidates per
-// read, event tables, SV event tables, report records, long-insertion tables, junction tables, and the one call per window that chains
-// the first five.
+// pg_api_classify.cpp -- the device classifier's entries of the C ABI (include/pindel_pg.h; DESIGN.md 7k - 7s): candidates per
+// read, event tables, SV event tables, report records, long-insertion tables, junction tables, dispersed-duplication tables, and the
+// one call per window that chains the first five.
 // Every entry checks its arguments and owns its buffers here; the kernels and their launchers are pg_variant.hip, pg_sv.hip,
-// pg_events.hip, pg_sv_events.hip, pg_report.hip, pg_li.hip and pg_int.hip.  What this file shares with pg_api.cpp is pg_api_priv.h.
+// pg_events.hip, pg_sv_events.hip, pg_report.hip, pg_li.hip, pg_int.hip and pg_dd_tables.hip.  What this file shares with pg_api.cpp is pg_api_priv.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -129,6 +129,30 @@ int copy_tables(pg_ctx *ctx, std::initializer_list<TableCopy> tables, bool to_de
         if (t.dst && t.count) HIP_TRY(ctx, hipMemcpy(t.dst, t.src, t.count * t.elem, to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
     return PG_OK;
 }
+
+// Several temporaries of one call as ONE allocation of `tmp`: add() notes an array of n elements (at least one), take() allocates and
+// hands every array its place, each at a 256-byte boundary of the block
+struct TempBlock {
+    struct Part {
+        void **p;
+        size_t at;
+    };
+    std::vector<Part> parts;
+    size_t bytes = 0;
+    template <typename T>
+    void add(T **p, size_t n)
+    {
+        parts.push_back({ (void **)p, bytes });
+        bytes += (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255;
+    }
+    int take(pg_ctx *ctx, DevTemps &tmp)
+    {
+        char *base = (char *)tmp.take(bytes);
+        if (!base) return fail(ctx, PG_E_NOMEM, "device memory for a table build's temporaries");
+        for (const Part &x : parts) *x.p = base + x.at;
+        return PG_OK;
+    }
+};
 
 unsigned long long pool_runs(const pg_device_batch *b) { return (unsigned long long)b->pool_shard_cap * PG_POOL_SHARDS; }
 
@@ -898,6 +922,195 @@ int pg_device_batch_int_download(pg_ctx *ctx, pg_device_batch *b, uint32_t *memb
 int pg_device_batch_int_download_device(pg_ctx *ctx, pg_device_batch *b, uint32_t *d_members, pg_int_call *d_calls)
 {
     return int_download(ctx, b, d_members, d_calls, true);
+}
+
+// ---- ... its eighth part (pg_dd_tables.hip): the dispersed-duplication breakpoint tables, their consensus and the
+// containment verdicts, from the close end alone
+int pg_device_batch_dd(pg_ctx *ctx, pg_device_batch *b, const pg_dd_window *window)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    if (int rc = entry_refusal(ctx, b, false)) return rc;
+    if (b->n && !b->close_searched) return fail(ctx, PG_E_INVALID, "dd: the batch has not been close-searched: no close ends to group");
+    if (!window) return fail(ctx, PG_E_INVALID, "dd: null pg_dd_window");
+    const uint32_t n_seg = window->n_seg;
+    if (n_seg && (!window->seg_first || !window->seg_strand)) return fail(ctx, PG_E_INVALID, "dd: n_seg > 0 with a null segment array");
+    for (uint32_t s = 0; s < n_seg; s++) {
+        if (window->seg_first[s] > window->seg_first[s + 1]) return fail(ctx, PG_E_INVALID, "dd: seg_first decreases");
+        if (window->seg_strand[s] != '+' && window->seg_strand[s] != '-') return fail(ctx, PG_E_INVALID, "dd: a segment strand is neither '+' nor '-'");
+    }
+    if (n_seg && window->seg_first[n_seg] > b->n) return fail(ctx, PG_E_INVALID, "dd: seg_first reaches beyond the batch's reads");
+    if (window->chr_id < 0 || (size_t)window->chr_id >= ctx->names.size()) return fail(ctx, PG_E_INVALID, "dd: chr_id is not a chromosome of the loaded reference");
+    if (window->min_map_distance < 1) return fail(ctx, PG_E_INVALID, "dd: min_map_distance < 1");
+    ClassifierState &c = b->cls;
+    c.dd_built = false;
+    c.dd_sizes = pg_dd_sizes{};
+    // (the tables are sized by what the build finds: its predecessor's go first)
+    for (void *p : { (void *)c.dd_members, (void *)c.dd_cands, (void *)c.dd_cons })
+        if (p) (void)hipFree(p);
+    c.dd_members = nullptr;
+    c.dd_cands = nullptr;
+    c.dd_cons = nullptr;
+    const size_t n = b->n;
+    if (!n || !n_seg) {                                       // nothing is launched for an empty batch or without a segment
+        c.dd_built = true;
+        return PG_OK;
+    }
+    int rc;
+    DevTemps tmp(ctx, b);
+    PgDdArgs a{};
+    const size_t n_blk = n / PG_EV_BLOCK + 2;
+    uint32_t *d_seg_first = nullptr;
+    uint8_t *d_seg_strand = nullptr;
+    // (one sized block for the read-sized temporaries, a second one below for the candidate-sized ones: a resident batch lives
+    // outside the arena, where every array of its own would be a hipMalloc and a hipFree)
+    {
+        TempBlock blk;
+        blk.add(&a.rec_a, n), blk.add(&a.rec_b, n), blk.add(&a.aux, n), blk.add(&a.flag, n), blk.add(&a.keep, n), blk.add(&a.keep_head, n);
+        blk.add(&a.rank, n), blk.add(&a.blk, n_blk), blk.add(&a.rank_m, n), blk.add(&a.blk_m, n_blk), blk.add(&a.rank_c, n), blk.add(&a.blk_c, n_blk);
+        blk.add(&a.cfirst, n + 1), blk.add(&a.digit_cnt, 256 * n_blk + 1), blk.add(&a.info, 1);
+        blk.add(&d_seg_first, (size_t)n_seg + 1), blk.add(&d_seg_strand, n_seg);
+        if ((rc = blk.take(ctx, tmp))) return rc;
+    }
+    HIP_TRY(ctx, hipMemcpy(d_seg_first, window->seg_first, ((size_t)n_seg + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d_seg_strand, window->seg_strand, n_seg, hipMemcpyHostToDevice));
+    a.out = b->out_rec;
+    a.seq = b->seq;
+    a.seq_off = b->seq_off;
+    a.strand = b->strand;
+    a.seg_first = d_seg_first;
+    a.seg_strand = d_seg_strand;
+    a.n = b->n;
+    a.n_seg = n_seg;
+    a.chr_id = window->chr_id;
+    a.min_bp_support = window->min_bp_support;
+    a.min_map_distance = window->min_map_distance;
+    a.chr_size = (uint32_t)ctx->comp_size[(size_t)window->chr_id];
+    a.slot = std::max<uint32_t>(b->max_len, 1u);
+    PgDdInfo info;
+    uint32_t n_dd = 0, n_mem = 0, n_cands = 0, cons_bytes = 0;
+    PgDdRec *sorted = nullptr;
+    double ms = 0.0;
+    // A, B and the first half of C: which keys are candidates
+    rc = timed(ctx, [&]() -> int {
+        if (pg_ddt_gather_launch(&a, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the DD gather kernels failed");
+        log_kernel(ctx, PG_KERNEL_DD_TABLES, (int32_t)PG_EV_BLOCK);
+        HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (info.n_dd > n) return fail(ctx, PG_E_DEVICE, "dd: the count of DD reads exceeds the batch");
+        n_dd = info.n_dd;
+        if (!n_dd) return PG_OK;                              // (no DD read: nothing below indexes an empty array)
+        PgDdRec *src = a.rec_b, *dst = a.rec_a;
+        for (int pass = 0; pass < PG_DD_SORT_PASSES; pass++) {
+            const int word = pass < 4 ? 1 : 0, shift = (pass & 3) * 8;
+            if ((((info.key_or[word] ^ info.key_and[word]) >> shift) & 0xffu) == 0u) continue;      // the byte is constant: no pass
+            if (pg_ddt_sort_pass_launch(&a, src, dst, n_dd, pass, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching a DD sort pass failed");
+            log_kernel(ctx, PG_KERNEL_DD_TABLES, (int32_t)PG_EV_BLOCK);
+            std::swap(src, dst);
+        }
+        sorted = src;
+        if (pg_ddt_keys_launch(&a, sorted, n_dd, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the DD key kernels failed");
+        log_kernel(ctx, PG_KERNEL_DD_TABLES, (int32_t)PG_EV_BLOCK);
+        HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
+        return PG_OK;
+    });
+    if (rc) return rc;
+    ms += ctx->last_ms;
+    if (n_dd) {
+        if (info.n_mem > n_dd || info.n_cands > info.n_mem || (info.n_mem && !info.n_cands)) return fail(ctx, PG_E_DEVICE, "dd: inconsistent table sizes");
+        n_mem = info.n_mem;
+        n_cands = info.n_cands;
+    }
+    if (n_cands) {
+        if ((rc = dev_alloc(ctx, &c.dd_members, n_mem)) || (rc = dev_alloc(ctx, &c.dd_cands, n_cands))) return rc;
+        {
+            TempBlock blk;
+            blk.add(&a.slots, (size_t)n_cands * a.slot), blk.add(&a.cons_off, (size_t)n_cands + 1), blk.add(&a.q_off, (size_t)n_cands + 1);
+            blk.add(&a.q_chr, n_cands), blk.add(&a.q_ws, n_cands), blk.add(&a.q_wl, n_cands), blk.add(&a.q_out, 2 * (size_t)n_cands);
+            if ((rc = blk.take(ctx, tmp))) return rc;
+        }
+        a.members = c.dd_members;
+        a.cands = c.dd_cands;
+        // the second half of C, and D up to the lengths' scan
+        rc = timed(ctx, [&]() -> int {
+            if (pg_ddt_tables_launch(&a, sorted, n_dd, ctx->stream) || pg_ddt_consensus_launch(&a, n_cands, ctx->stream))
+                return fail(ctx, PG_E_DEVICE, "launching the DD table and consensus kernels failed");
+            log_kernel(ctx, PG_KERNEL_DD_TABLES, (int32_t)(PG_DD_WAVES * 64u));
+            HIP_TRY(ctx, hipMemcpyAsync(&cons_bytes, a.cons_off + n_cands, sizeof cons_bytes, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(&info, a.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
+            return PG_OK;
+        });
+        if (rc) return rc;
+        ms += ctx->last_ms;
+        if ((uint64_t)cons_bytes > (uint64_t)n_cands * a.slot || info.max_cons > a.slot || info.n_tested > n_cands)
+            return fail(ctx, PG_E_DEVICE, "dd: inconsistent consensus sizes");
+        if ((rc = dev_alloc(ctx, &c.dd_cons, cons_bytes))) return rc;
+        a.cons = c.dd_cons;
+        // E: the containment kernel as pg_dd_contains_batch launches it -- one wave per (candidate, strand), at most 8192 resident
+        // waves; with a consensus of more than 64 bases each wave keeps one boundary row of its window, capped at 512 MB in all
+        const uint64_t n_tasks = 2ull * n_cands;
+        const uint64_t max_win = std::min<uint64_t>(2ull * (uint64_t)window->min_map_distance, a.chr_size);
+        const uint64_t stride = info.max_cons > 64 ? (max_win + 63) / 64 * 64 : 0;
+        uint64_t waves = std::min<uint64_t>(n_tasks, 8192);
+        if (stride) waves = std::min<uint64_t>(waves, std::max<uint64_t>(4, (512ull << 20) / (stride * 4)));
+        const uint64_t blocks = (waves + 3) / 4;
+        uint32_t *d_scr = nullptr;
+        if (info.n_tested && (rc = tmp.take(&d_scr, (size_t)(stride ? blocks * 4 * stride : 1)))) return rc;
+        const PgDevRef ref = dev_ref(ctx);
+        rc = timed(ctx, [&]() -> int {
+            if (pg_ddt_pool_launch(&a, n_cands, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the DD pool kernel failed");
+            log_kernel(ctx, PG_KERNEL_DD_TABLES, (int32_t)(PG_DD_WAVES * 64u));
+            if (!info.n_tested) return PG_OK;                 // (no consensus of 15 bases: no containment test, no flag to set)
+            if (pg_dd_launch(&ref, ctx->d_mm, a.cons, a.q_off, a.q_chr, a.q_ws, a.q_wl, a.q_out, d_scr, std::max<uint64_t>(stride, 1),
+                             (uint32_t)n_tasks, (uint32_t)blocks, ctx->stream))
+                return fail(ctx, PG_E_DEVICE, "launching the containment kernel failed");
+            if (pg_ddt_verdict_launch(&a, n_cands, ctx->stream)) return fail(ctx, PG_E_DEVICE, "launching the DD verdict kernel failed");
+            log_kernel(ctx, PG_KERNEL_DD_TABLES, (int32_t)PG_EV_BLOCK);
+            return PG_OK;
+        });
+        if (rc) return rc;
+        ms += ctx->last_ms;
+        c.dd_sizes.members = n_mem;
+        c.dd_sizes.cands = n_cands;
+        c.dd_sizes.cons_bytes = cons_bytes;
+    }
+    ctx->last_ms = ms;
+    c.dd_built = true;
+    return PG_OK;
+}
+
+static const char *const NO_DD = "no DD tables: pg_device_batch_dd has not been run on this batch since its search";
+
+int pg_device_batch_dd_sizes(pg_ctx *ctx, pg_device_batch *b, pg_dd_sizes *sizes)
+{
+    use_device(ctx);
+    if (!ctx || !b || !sizes) return PG_E_INVALID;
+    if (!b->cls.dd_built) return fail(ctx, PG_E_INVALID, NO_DD);
+    *sizes = b->cls.dd_sizes;
+    return PG_OK;
+}
+
+static int dd_download(pg_ctx *ctx, pg_device_batch *b, pg_dd_member *members, pg_dd_cand *cands, uint8_t *cons, bool to_device)
+{
+    use_device(ctx);
+    if (!ctx || !b) return PG_E_INVALID;
+    const ClassifierState &c = b->cls;
+    if (!c.dd_built) return fail(ctx, PG_E_INVALID, NO_DD);
+    return copy_tables(ctx,
+                       { { members, c.dd_members, (size_t)c.dd_sizes.members, sizeof(pg_dd_member), 4, "dd download: members" },
+                         { cands, c.dd_cands, (size_t)c.dd_sizes.cands, sizeof(pg_dd_cand), 8, "dd download: cands" },
+                         { cons, c.dd_cons, (size_t)c.dd_sizes.cons_bytes, 1, 1, "dd download: cons" } },
+                       to_device);
+}
+
+int pg_device_batch_dd_download(pg_ctx *ctx, pg_device_batch *b, pg_dd_member *members, pg_dd_cand *cands, uint8_t *cons)
+{
+    return dd_download(ctx, b, members, cands, cons, false);
+}
+
+int pg_device_batch_dd_download_device(pg_ctx *ctx, pg_device_batch *b, pg_dd_member *d_members, pg_dd_cand *d_cands, uint8_t *d_cons)
+{
+    return dd_download(ctx, b, d_members, d_cands, d_cons, true);
 }
 
 // ---- one call per window: the two candidate kernels, both table builds and the report records, the lists staying with the batch

@@ -117,7 +117,14 @@ struct ClassifierState {
     pg_int_call *int_calls = nullptr;          // n
     pg_int_sizes int_sizes{};
     bool int_built = false;
-    void drop_search_tables() { int_built = false; }
+    // the dispersed-duplication tables of the last pg_device_batch_dd: made from the close end alone and sized by
+    // what the build found (each build frees its predecessor's); a new search discards them as well
+    pg_dd_member *dd_members = nullptr;        // dd_sizes.members
+    pg_dd_cand *dd_cands = nullptr;            // dd_sizes.cands
+    uint8_t *dd_cons = nullptr;                // dd_sizes.cons_bytes
+    pg_dd_sizes dd_sizes{};
+    bool dd_built = false;
+    void drop_search_tables() { int_built = dd_built = false; }
 
     enum Build { EVENTS, SV_EVENTS, REPORT, LI };
     // A build discards its own tables and whatever was made from them: the SV tables belong to the records of the events build they
@@ -134,7 +141,8 @@ struct ClassifierState {
     {
         for (void *p : { (void *)ev_reads, (void *)ev_members, (void *)ev_events, (void *)svev_members, (void *)svev_events, (void *)svev_ws,
                          (void *)rr_records, (void *)rr_summaries, (void *)cl_cands, (void *)cl_sv_cands, (void *)cl_counts, (void *)cl_sv_counts,
-                         (void *)li_members, (void *)li_positions, (void *)int_members, (void *)int_calls })
+                         (void *)li_members, (void *)li_positions, (void *)int_members, (void *)int_calls, (void *)dd_members, (void *)dd_cands,
+                         (void *)dd_cons })
             if (p) (void)hipFree(p);
         *this = ClassifierState();
     }
@@ -176,6 +184,7 @@ struct pg_device_batch {
     bool soa_uploaded = false;
     long long exact_n = -1;            // host copy of the counter; -1: not read back (the exact kernel is launched regardless)
     bool searched = false;             // close end + far end have run on the batch: its output records and run pool hold a result
+    bool close_searched = false;       // the close end has run on the batch (alone, or as part of a search): the close fields of its records hold a result
     ClassifierState cls;               // the device classifier's tables and lists (null / false: none built)
 };
 

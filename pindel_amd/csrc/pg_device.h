@@ -607,6 +607,72 @@ int pg_int_gather_launch(const struct PgIntArgs *a, void *stream);
 int pg_int_sort_pass_launch(const struct PgIntArgs *a, const struct PgIntRec *src, struct PgIntRec *dst, uint32_t n_mem, int pass, void *stream);
 // head flags, members, calls over the sorted records; fills info->n_calls.  n_mem > 0
 int pg_int_tables_launch(const struct PgIntArgs *a, const struct PgIntRec *sorted, uint32_t n_mem, void *stream);
+// Dispersed-duplication breakpoint tables and consensus (pg_dd_tables.hip): the reads of the caller's segments that pass
+// the DD test, compacted in ascending read index, ordered by (seg, pos) with stable counting passes; the keys with enough support
+// become candidates, one wave per candidate votes its consensus, and the containment kernel runs over the packed pool.
+enum { PG_KERNEL_DD_TABLES = 13 };    // ... continued: the launch-log id of pg_device_batch_dd
+#define PG_DD_KEY_WORDS 2             // w[0] = seg, w[1] = pos
+#define PG_DD_SORT_PASSES 8           // one per key byte, least significant first: pos (4), seg (4)
+#define PG_DD_MIN_CONSENSUS 15u       // MIN_CONSENSUS_LENGTH, src/search_MEI.cpp:38
+#define PG_DD_WAVES 4u                // candidates per workgroup of the consensus and pool kernels (one wave each)
+struct PgDdRec { uint32_t w[4]; };    // one DD read: seg, pos, read, close_len | rc_flag << 16
+struct PgDdAux {                      // one member as the consensus kernel reads it
+    uint64_t base;                    // offset in seq of the first byte of the read's post-state
+    uint32_t len;                     // the post-state's length
+    uint32_t u_rc;                    // u = len - close_len | rc_flag << 16
+};
+struct PgDdInfo {                     // what the host reads back
+    uint32_t n_dd;                    // DD reads
+    uint32_t n_keys, n_mem, n_cands;  // distinct (seg, pos); members and candidates kept
+    uint32_t cons_bytes, max_cons, n_tested;
+    uint32_t key_or[PG_DD_KEY_WORDS], key_and[PG_DD_KEY_WORDS];   // over the compacted records' key words: a byte equal in both is constant
+};
+struct PgDdArgs {
+    const PgOutRec *out;
+    const uint8_t *seq;
+    const uint64_t *seq_off;
+    const uint8_t *strand;
+    const uint32_t *seg_first;        // n_seg + 1, device memory
+    const uint8_t *seg_strand;        // n_seg, device memory
+    uint32_t n, n_seg;
+    int32_t chr_id, min_bp_support, min_map_distance;
+    uint32_t chr_size;                // the padded length of chr_id
+    uint32_t slot;                    // bytes per candidate of `slots`: the longest read of the batch
+    pg_dd_member *members;            // info.n_mem
+    pg_dd_cand *cands;                // info.n_cands
+    uint8_t *cons;                    // info.cons_bytes
+    struct PgDdRec *rec_a, *rec_b;    // n each
+    struct PgDdAux *aux;              // n
+    uint8_t *flag, *keep, *keep_head; // n each
+    uint32_t *rank, *blk;             // n; n / PG_EV_BLOCK + 2 -- of flag
+    uint32_t *rank_m, *blk_m;         // ... of keep
+    uint32_t *rank_c, *blk_c;         // ... of keep_head
+    uint32_t *cfirst;                 // n + 1
+    uint32_t *digit_cnt;              // 256 x (n / PG_EV_BLOCK + 2) + 1
+    uint8_t *slots;                   // info.n_cands x slot: the accepted columns per candidate
+    uint32_t *cons_off;               // info.n_cands + 1: the lengths, then their scan
+    // the containment kernel's items, one per candidate (an untested one has a query of no bytes and a window of none)
+    uint64_t *q_off;                  // info.n_cands + 1
+    int32_t *q_chr;                   // info.n_cands
+    uint64_t *q_ws;
+    uint32_t *q_wl;
+    uint8_t *q_out;                   // 2 x info.n_cands
+    struct PgDdInfo *info;
+};
+// the DD reads flagged and compacted into rec_b (ascending read index); info->n_dd and the key masks are then valid.  n > 0
+int pg_ddt_gather_launch(const struct PgDdArgs *a, void *stream);
+// one stable counting pass over key byte `pass` of src[0 .. n_dd) into dst
+int pg_ddt_sort_pass_launch(const struct PgDdArgs *a, const struct PgDdRec *src, struct PgDdRec *dst, uint32_t n_dd, int pass, void *stream);
+// head flags, firsts and counts over the sorted records, the keys with enough support flagged; fills info->n_keys / n_mem / n_cands.  n_dd > 0
+int pg_ddt_keys_launch(const struct PgDdArgs *a, const struct PgDdRec *sorted, uint32_t n_dd, void *stream);
+// members, candidates (without the consensus fields) and the members' aux records.  n_dd > 0, members / cands / aux allocated
+int pg_ddt_tables_launch(const struct PgDdArgs *a, const struct PgDdRec *sorted, uint32_t n_dd, void *stream);
+// one wave per candidate: the consensus into its slot, cons_len, flags and window; then the scan of the lengths.  n_cands > 0
+int pg_ddt_consensus_launch(const struct PgDdArgs *a, uint32_t n_cands, void *stream);
+// the pool packed from the slots, cons_off and the containment items.  n_cands > 0
+int pg_ddt_pool_launch(const struct PgDdArgs *a, uint32_t n_cands, void *stream);
+// PG_DD_CONTAINED from the containment kernel's output
+int pg_ddt_verdict_launch(const struct PgDdArgs *a, uint32_t n_cands, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -703,6 +703,88 @@ def int_write_from_tables(out_prefix, names, chr_names, far_names, seqs, junctio
         raise ValueError("pgh_int_write_from_tables: " + (L.pgh_last_error() or b"").decode())
 
 
+# pg_dd_member, pg_dd_cand, pg_dd_sizes and the flags: one copy, the binding's (importing it loads no library)
+from .binding import DD_CAND_DTYPE, DD_CONTAINED, DD_MEMBER_DTYPE, DD_TESTED, DdSizes  # noqa: E402
+
+
+def _seg_arrays(seg_first, seg_strand):
+    strand = np.frombuffer(seg_strand.encode() if isinstance(seg_strand, str) else bytes(seg_strand), dtype=np.uint8)
+    first = np.ascontiguousarray(seg_first, dtype=np.uint32)
+    assert not strand.size or first.size == strand.size + 1, "seg_first has n_seg + 1 entries"
+    return first, strand
+
+
+def dd_tables_from_close(seq, seq_off, anchor_strand, has, rc_flag, last_abs, last_len, seg_first, seg_strand, chr_id, chrom, mm,
+                         min_bp_support=3, min_map_distance=8000):
+    """The dispersed-duplication breakpoint tables on the host (pgh_dd_tables_from_close): the reference Engine.dd_tables
+    is compared with, byte for byte.  The reads as handed to the search; per read whether it has a close end, its rc flag,
+    UP_Close.back()'s AbsLoc (close_last) and LengthStr (close_max); the segments and parameters of pg_dd_window; chrom: the padded
+    bases of chr_id (bytes), mm: g_maxMismatch (the containment test runs on the host).  Returns a dict: members (DD_MEMBER_DTYPE),
+    cands (DD_CAND_DTYPE), cons (bytes)."""
+    L = lib()
+    n = len(seq_off) - 1
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    strand = np.ascontiguousarray(anchor_strand, dtype=np.uint8)
+    has = np.ascontiguousarray(has, dtype=np.uint8)
+    rc_flag = np.ascontiguousarray(rc_flag, dtype=np.uint8)
+    last_abs = np.ascontiguousarray(last_abs, dtype=np.uint32)
+    last_len = np.ascontiguousarray(last_len, dtype=np.uint16)
+    first, sstrand = _seg_arrays(seg_first, seg_strand)
+    chrom = np.frombuffer(bytes(chrom), dtype=np.uint8)
+    mm = np.ascontiguousarray(mm[:500], dtype=np.uint32)
+    assert len(strand) == n and len(has) == n and len(rc_flag) == n and len(last_abs) == n and len(last_len) == n and mm.size == 500
+    members = np.zeros(max(n, 1), dtype=DD_MEMBER_DTYPE)
+    cands = np.zeros(max(n, 1), dtype=DD_CAND_DTYPE)
+    cons = np.zeros(max(int(seq.size), 1), dtype=np.uint8)        # (a consensus is no longer than its longest member)
+    sizes = DdSizes()
+    vp = C.c_void_p
+    L.pgh_dd_tables_from_close.argtypes = [C.c_uint32] + [vp] * 9 + [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint64, vp, vp, vp, vp,
+                                                                     C.c_uint64, vp]
+    rc = L.pgh_dd_tables_from_close(n, seq.ctypes.data if seq.size else None, seq_off.ctypes.data, strand.ctypes.data, has.ctypes.data,
+                                    rc_flag.ctypes.data, last_abs.ctypes.data, last_len.ctypes.data, first.ctypes.data if first.size else None,
+                                    sstrand.ctypes.data if sstrand.size else None, int(sstrand.size), int(chr_id), int(min_bp_support),
+                                    int(min_map_distance), chrom.ctypes.data if chrom.size else None, int(chrom.size), mm.ctypes.data,
+                                    members.ctypes.data, cands.ctypes.data, cons.ctypes.data, int(cons.size), C.addressof(sizes))
+    if rc:
+        raise ValueError("pgh_dd_tables_from_close: " + (L.pgh_last_error() or b"").decode())
+    return dict(members=members[:int(sizes.members)], cands=cands[:int(sizes.cands)], cons=cons[:int(sizes.cons_bytes)].tobytes())
+
+
+def dd_cands_from_tables(names, seqs, anchor_strand, n_seg, members, cands, cons, sample="S", spacer=100000):
+    """Test hook (pgh_dd_cands_from_tables): the single consumer of the DD breakpoint tables on tables made by hand.  Per split read its
+    name, bytes as ingested and anchor strand; the tables.  Returns the consumer's candidates in its order as a list of
+    (seg, bio_bp, tested, contained, consensus, [(name, sample, sequence, mapped, unmapped), ...])."""
+    L = lib()
+    n = len(seqs)
+    assert len(names) == n and len(anchor_strand) == n
+    seq = np.frombuffer(b"".join(seqs), dtype=np.uint8) if n else np.zeros(0, dtype=np.uint8)
+    seq_off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.uint64)
+    strand = np.ascontiguousarray(anchor_strand, dtype=np.uint8)
+    members = np.ascontiguousarray(members, dtype=DD_MEMBER_DTYPE)
+    cands = np.ascontiguousarray(cands, dtype=DD_CAND_DTYPE)
+    cons = np.frombuffer(bytes(cons), dtype=np.uint8)
+    sizes = DdSizes(int(members.size), int(cands.size), int(cons.size))
+    nm = (C.c_char_p * max(n, 1))(*[s.encode() if isinstance(s, str) else bytes(s) for s in names])
+    text = C.create_string_buffer(1 << 20)
+    vp = C.c_void_p
+    L.pgh_dd_cands_from_tables.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_char_p, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_char_p, C.c_uint64]
+    rc = L.pgh_dd_cands_from_tables(int(spacer), n, C.cast(nm, vp), sample.encode(), seq.ctypes.data if seq.size else None, seq_off.ctypes.data,
+                                    strand.ctypes.data if n else None, int(n_seg), members.ctypes.data if members.size else None,
+                                    cands.ctypes.data if cands.size else None, cons.ctypes.data if cons.size else None, C.addressof(sizes),
+                                    text, 1 << 20)
+    if rc:
+        raise ValueError("pgh_dd_cands_from_tables: " + (L.pgh_last_error() or b"").decode())
+    out = []
+    for line in text.value.decode("latin-1").split("\n"):
+        f = line.split("\t")
+        if f[0] == "C":
+            out.append((int(f[1]), int(f[2]), f[3] == "1", f[4] == "1", f[5], []))
+        elif f[0] == "R":
+            out[-1][5].append(tuple(f[1:6]))
+    return out
+
+
 def last_report_windows():
     """Windows of the last call_from_points(report_reads=True) that Caller::process_window_tables wrote from records and summaries."""
     return int(lib().pgh_last_report_windows())

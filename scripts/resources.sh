@@ -4,7 +4,7 @@
 lib=$(readlink -f "${1:-$(dirname "$0")/../pindel_amd/libpindel_pg.so}")
 tmp=$(mktemp -d); cp "$lib" "$tmp/lib.so"; cd "$tmp" || exit 1
 /opt/rocm/lib/llvm/bin/llvm-objdump --offloading lib.so > /dev/null 2>&1
-# (one code object per HIP source of the library: the search kernels, -q, the hint tables, the device-buffer entries)
+# (one code object per HIP source of the library: the search kernels, -q and its breakpoint tables, the hint tables, the device-buffer entries, the classifier parts)
 ls lib.so.*gfx950* > /dev/null 2>&1 || { echo "no gfx950 code object in $lib"; exit 1; }
 for co in lib.so.*gfx950*; do /opt/rocm/lib/llvm/bin/llvm-readelf --notes "$co"; done > notes.txt
 python3 - <<'PY'
