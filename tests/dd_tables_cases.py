@@ -136,6 +136,47 @@ def counted_candidates(biol, n_cands, seed=0):
     return pl
 
 
+def dd_read_totals(biol, k, seed=0):
+    """Exactly k DD reads beside reads that are none: keys of three members each, half of them in a '+' segment and half in a '-'
+    segment over the same breakpoints, appended in a shuffled order of position (the sort has work to do); the k % 3 reads left over
+    form one key below the support at the highest position of the '-' segment, so that every DD record in front of it is a member
+    and sorted record m is member m: key 85 holds records 255, 256 and 257, key 170 records 510 to 512, key 256 begins at 768.
+    The reads that are none can be no DD reads whatever the search finds for them: groups of the other strand inside either
+    segment, and a group behind the last segment."""
+    pl = Plan(biol, seed)
+    keys = k // 3
+    per_seg = [(keys + 1) // 2, keys // 2]
+    for s, strand in enumerate((b"+", b"-")):
+        other = b"-" if strand == b"+" else b"+"
+        order = pl.rng.permutation(per_seg[s])
+        for j, g in enumerate(order):
+            pl.group(strand, 1500 + 110 * int(g), 3)
+            if j % 40 == 7:
+                pl.group(other, 1500 + 110 * int(g), 3)              # the other strand at the same breakpoint: no DD reads
+        if s == 1 and k % 3:
+            pl.group(strand, 1500 + 110 * per_seg[1], k % 3)         # below min_bp_support 3: DD reads that are no members
+        pl.group(other, 1555, 3)
+        pl.end_segment(strand)
+    pl.group(b"+", 1500, 3)                                           # outside every segment
+    return pl
+
+
+def assert_dd_read_totals(t, every, k, block=256):
+    """What dd_read_totals(biol, k) is meant to hold, on the statement's tables at min_bp_support 3 (t) and 1 (every: each DD read is
+    a member there, so its member count is the DD-read count)"""
+    assert len(every["members"]) == k and len(t["members"]) == k - k % 3
+    c = t["cands"]
+    assert len(c) == k // 3 and (c["n_reads"] == 3).all() and set(c["seg"].tolist()) == {0, 1}
+    # the members are the first k - k % 3 DD records in sorted order: the same reads in the same places
+    assert every["members"]["read"][:len(t["members"])].tolist() == t["members"]["read"].tolist()
+    pos = c["pos"].astype(np.int64) + (c["seg"].astype(np.int64) << 32)
+    assert (np.diff(pos) > 0).all()
+    if k > block + 1:
+        across = c[(c["first"] < block) & (c["first"] + c["n_reads"] > block)]
+        assert len(across) == 1 and int(across[0]["first"]) == block - 1          # records 255, 256 and 257
+        assert (c["first"] % block == 0).sum() >= 2                               # ... and a key that begins a block
+
+
 def one_big_candidate(biol, n_members, seed=0):
     """one candidate of n_members members whose walks shrink (n falls along the columns), beside a small one at the same position in
     a segment of the other strand"""

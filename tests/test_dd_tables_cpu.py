@@ -1,6 +1,7 @@
 """The dispersed-duplication breakpoint tables without a GPU: the header, the exports and the layouts; the host
 statement hostlib.dd_tables_from_close against the literal restatement of tests/dd_tables_restated.py on a hand-made batch that
-holds every edge of the contract and on random batches; and the one consumer on hand-made tables."""
+holds every edge of the contract and on random batches; the DD-read totals of tests/dd_tables_cases.py through the oracle's close end
+and the statement; and the one consumer on hand-made tables."""
 import os
 import re
 
@@ -10,7 +11,9 @@ import pytest
 from oracle import pyoracle
 from pindel_amd import binding, hostlib
 from tests import dd_restated
+from tests import dd_tables_cases as dc
 from tests import dd_tables_restated as R
+from tests.parity import run_oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _COMP = bytes.maketrans(b"ACGTN", b"TGCAN")
@@ -245,6 +248,29 @@ def test_random_batches(seed):
     assert int(got["cands"]["n_reads"].sum()) == len(got["members"])
     if n >= 100:
         assert len(got["cands"]) >= 2 and (got["cands"]["flags"] & 1).any()
+
+
+# ------------------------------------------------------------------------------------------------ the plans of the GPU test
+def oracle_close_ends(chroms, batch):
+    """per read: has a close end, rc_flag, UP_Close.back()'s AbsLoc and LengthStr -- from the CPU oracle's close end"""
+    r = run_oracle({}, chroms, batch, do_far=False)
+    cnt = r["close_cnt"].astype(np.int64)
+    last = r["close_pts"][np.arange(batch.n), np.maximum(cnt - 1, 0)]
+    has = (cnt > 0).astype(np.uint8)
+    return has, r["rc_flag"], np.where(has, last["abs_loc"], 0).astype(np.uint32), np.where(has, last["length"], 0).astype(np.uint16)
+
+
+@pytest.mark.parametrize("k", [255, 256, 257, 1024, 1025])
+def test_dd_read_totals_plan(k):
+    """tests/dd_tables_cases.py dd_read_totals through the oracle's close end and the statement alone: the plan holds what
+    tests/test_gpu_dd_tables.py asserts of it on the device's close ends"""
+    chroms, biol = dc.reference()
+    batch, first, strand = dc.dd_read_totals(biol, k, seed=k).batch()
+    has, rc, la, ll = oracle_close_ends(chroms, batch)
+    tables = [hostlib.dd_tables_from_close(batch.seq, batch.seq_off, batch.anchor_strand, has, rc, la, ll, first, strand, 0, chroms[0][1], MM,
+                                           support, 400) for support in (3, 1)]
+    dc.assert_dd_read_totals(tables[0], tables[1], k)
+    assert batch.n > k + 12 and int(first[-1]) < batch.n
 
 
 # ------------------------------------------------------------------------------------------------ the consumer

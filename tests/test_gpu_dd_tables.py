@@ -134,6 +134,19 @@ def test_candidate_counts(world, k):
         c.close()
 
 
+@pytest.mark.parametrize("k", [255, 256, 257, 1024, 1025])
+def test_dd_read_totals(world, k):
+    """k DD reads beside reads that are none: the compaction, the sort and the head flags at one block of DD records, at its edge and
+    beyond it (dd_key_of reads blk[m / PG_EV_BLOCK]); from 258 reads on one key's members are the sorted records 255, 256 and 257"""
+    c = Case(world, dc.dd_read_totals(world["biol"], k, seed=k))
+    try:
+        t = c.check(f"{k} DD reads")
+        dc.assert_dd_read_totals(t, c.statement(support=1), k)
+        c.check(f"{k} DD reads, min_bp_support 1", support=1)
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("m", [63, 64, 65, 130])
 def test_one_candidate_of_many_members(world, m):
     c = Case(world, dc.one_big_candidate(world["biol"], m, seed=m))
